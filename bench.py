@@ -8,11 +8,22 @@ deq -> clip -> lin -> apply_rf -> alpha -> hal -> blend inference, batch 16 of
 initialisers, non-trivial BatchNorm statistics).  One "step" = one pass of
 the hot path over one batch, inputs already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per
 GPU); inference shards over the batch axis with no data-path collective
 ("weak" scaling: every rank processes its own batch).
+
+A plain run times the headline leg only.  --full adds the other legs: the
+exact-fp32 kernels, the Dequantization-Net alone, the HBM-bound kernels, the
+Refinement-Net, the per-launch roofline, the CPU baseline with its oracle
+check, joint training and fine-tuning (the --no-* / --*-steps options select
+among them).  --dump-outputs DIR writes the HDR images of the last timed step
+(rank 0) as DIR/hdr.npy, float32; inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.  Compare with a
+tolerance: on two HIP streams (the default) one run in three returned the first
+image of the batch up to 5e-6 (of a maximum of 1.9) off the other two, while
+runs on one stream (--streams 1) were bit-identical.
 """
 import argparse
 import importlib
@@ -30,6 +41,7 @@ if ROOT not in sys.path:
 
 F32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_{32x32x2,16x16x4}_f32 dense peak
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 / fp16 MFMA peak (the 5 PF headline figure includes 2:1 sparsity)
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: array bytes in all (the files stay under 64 MB)
 TRAFFIC_FILE = next((f for f in ("r03_traffic.json", "r02_traffic.json", "r01_traffic.json") if os.path.exists(os.path.join(ROOT, "profiles", f))), "r01_traffic.json")
 
 
@@ -56,7 +68,22 @@ def parse_args():
     ap.add_argument("--finetune-batch", type=int, default=4)       # finetune_real_dataset.py:25
     ap.add_argument("--finetune-size", type=int, default=1024)
     ap.add_argument("--finetune-prec", default="fp32,fp16", help="comma list of the fine-tuning precisions to time")
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the headline one (off: the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output to DIR/<name>.npy")
     return ap.parse_args()
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy in float32 for each tensor; one larger than its share of DUMP_BYTES is cut to a fixed, seeded sample of
+    its elements (the same flat positions on every run with the same arguments)"""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() * 4 > budget:
+            idx = torch.randint(0, a.numel(), (budget // 4,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(directory, name + ".npy"), a.cpu().numpy())
 
 
 def randomise_bn(model, gen):
@@ -341,6 +368,8 @@ def main():
     assert bool(torch.isfinite(out).all())
     if rank == 0:
         progress("inference leg done: %.2f ms/step" % (dt / args.steps * 1e3))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"hdr": out})
     n_gpus = world
     ms_per_step = dt / args.steps * 1e3
     value = args.batch * n_gpus * args.steps / dt
@@ -364,7 +393,7 @@ def main():
                    "per_gpu_batch": args.batch, "hip_streams_per_gpu": args.streams,
                    "parallelism": "batch-sharded x%d, no collective" % n_gpus},
     }
-    if rank == 0 and n_gpus == 1 and not args.exact_fp32 and not args.no_roofline:      # (--no-roofline = the lean runs under the profiler)
+    if args.full and rank == 0 and n_gpus == 1 and not args.exact_fp32 and not args.no_roofline:      # (--no-roofline = the lean runs under the profiler)
         # the same leg with every layer on the exact-fp32 kernels (fp32 MFMA / FMA products only), and how far the two results are apart
         K.EXACT_FP32 = True
         try:
@@ -384,7 +413,7 @@ def main():
             K.EXACT_FP32 = False
 
     # ---- BASELINE configs[1]: Dequantization-Net only, batch 8 x 512 x 512 (informational; the headline stays configs[2]) ----
-    if not args.no_refinement:
+    if args.full and not args.no_refinement:
         x8 = ldr[:8].contiguous() if args.batch >= 8 else ldr
         with torch.no_grad():
             for _ in range(2):
@@ -402,7 +431,7 @@ def main():
 
     # ---- the HBM-bound kernels of the path against the HBM roofline (soft histogram standalone at B = 32,
     #      and the fused front end of the Linearization-Net as it runs inside the step) ----------
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         try:
             def hbm_rate(fn, nbytes, reps=10):
                 for _ in range(3):
@@ -428,7 +457,7 @@ def main():
             result["hbm_kernels_error"] = repr(exc)[:300]
 
     # ---- the same inference with the Refinement-Net appended ("report with and without") ----------
-    if not args.no_refinement:
+    if args.full and not args.no_refinement:
         torch.manual_seed(4321)
         ref_net = pkg.refinement_net.model()
         run_ref = pkg.pipeline.Inference(deq, lin, hal, ref_net, streams=args.streams)
@@ -451,7 +480,7 @@ def main():
         del out_ref, run_ref, ref_net
 
     # ---- roofline of the dominant kernel: per-launch HIP-event timing on the launch stream ----------
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         progress("roofline leg (per-launch HIP events)")
         try:
             records = []     # (kernel label, flops, e0, e1, description, nested)
@@ -654,7 +683,7 @@ def main():
     # ---- CPU baseline: the fp32 torch-CPU channels-last restatement of the same path ("port": TF2-CPU is
     #      not installable here), all host cores, 2 warm-ups, median of 5 runs, on a bounded sample of the workload (one image of
     #      the batch); the NumPy float32 oracle checks the GPU result of that image.  Rank 0, N = 1 only. ------------------------
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         try:
             from oracle import nets, torch_cpu  # checker / baseline only -- never on the product path
             table = np.load(os.path.join(ROOT, "singlehdr-tf2_amd", "data", "invemor_g0_hinv11.npy"))
@@ -700,7 +729,7 @@ def main():
 
     # ---- joint-training leg (BASELINE configs[3]): deq+lin+hal + VGG16 perceptual loss, fwd+bwd+Adam, batch 32 x
     #      256x256 per GPU, ONE RCCL all-reduce(SUM) of the flat fp32 gradient per step (weak scaling) ------------
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         if rank == 0:
             progress("joint-training leg")
         del out
@@ -787,7 +816,7 @@ def main():
 
     # ---- fine-tuning leg (BASELINE configs[4]): the chained deq->lin->hal->ref step of finetune_real_dataset.py on
     #      1024x1024 tiles, fp32 operands vs the fp16-MFMA-operand conv path (fp32 master weights / accumulation) ----
-    if args.finetune_steps > 0:
+    if args.full and args.finetune_steps > 0:
         tout = step = None
         torch.cuda.empty_cache()
         fg = torch.Generator().manual_seed(5 + rank)

@@ -180,3 +180,19 @@ def test_bench_rank0_only_legs_hold_no_collective():
             break
     else:
         raise AssertionError("fp16 roofline leg not found")
+
+
+def test_bench_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an output within the budget is written whole in float32; a larger one as the same seeded
+    sample of its elements on every run, within the budget."""
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    small, big = torch.rand((2, 8, 8, 3), dtype=torch.float64), torch.rand((4, 32, 32, 3))
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small})
+    got = np.load(str(tmp_path / "a" / "small.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big})
+    b, c = np.load(str(tmp_path / "b" / "big.npy")), np.load(str(tmp_path / "c" / "big.npy"))
+    assert b.dtype == np.float32 and b.nbytes <= 4096 and np.array_equal(b, c)
+    assert np.isin(b, big.numpy()).all()

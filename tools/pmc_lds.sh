@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pmc_lds
 mkdir -p $O
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 0 --finetune-steps 1 --finetune-prec fp16"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 0 --finetune-steps 1 --finetune-prec fp16"
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CU_CYCLES SQ_VALU_MFMA_BUSY_CYCLES --kernel-trace --output-format csv -d $O/p1 -- python3 $R/bench.py $ARGS > $O/p1.log 2>&1 || echo "pass 1 failed"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/p2 -- python3 $R/bench.py $ARGS > $O/p2.log 2>&1 || echo "pass 2 failed"
 cd $R && python3 - <<'PY'

@@ -7,7 +7,7 @@ R="$GRAFT_REPO_ROOT"
 O="$R/gpurun_out/$TAG"
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/train" -- python3 "$R/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 4 --finetune-steps 0 > "$O/train_line.json" 2> "$O/train.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/train" -- python3 "$R/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 4 --finetune-steps 0 > "$O/train_line.json" 2> "$O/train.err"
 cp "$(ls "$O"/train/*/*kernel_stats.csv | head -1)" "$O/train_kernel_stats.csv"
 rm -rf "$O/train"
 python3 - "$O/train_kernel_stats.csv" <<'PY'

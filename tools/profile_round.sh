@@ -7,10 +7,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-INF="--streams 1 --steps 5 --warmup 2 --no-cpu-baseline --no-refinement --train-steps 0 --finetune-steps 0"
+INF="--full --streams 1 --steps 5 --warmup 2 --no-cpu-baseline --no-refinement --train-steps 0 --finetune-steps 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/inf -- python3 $R/bench.py $INF > $O/bench_line.json 2> $O/inf.err
 echo "inference profile done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 4 --finetune-steps 0 > $O/train_line.json 2> $O/train.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/train -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-roofline --no-refinement --train-steps 4 --finetune-steps 0 > $O/train_line.json 2> $O/train.err
 echo "training profile done"
 PM="--streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --no-refinement --train-steps 0 --finetune-steps 0"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py $PM > /dev/null 2> $O/pmc_f.err
