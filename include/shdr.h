@@ -519,6 +519,26 @@ int shdr_rgbe_encode_f32(const float* x, uint8_t* y, int64_t npix, int reverse_c
  * files, :150).  Returns the number of bytes written to `out`, or -1 (see shdr_last_error) if `capacity` is less than
  * height * (4 + 4 * (width + width / 127 + 2)). */
 int64_t shdr_rgbe_rle_encode(const uint8_t* rgbe, int width, int height, uint8_t* out, int64_t capacity);
+/* The inverse, host side: `size` bytes of scanline data (after the resolution line) -> RGBE [height][width][4]; flat and
+ * adaptive-RLE scanlines, the pixel source of cv2.imread("*.hdr") (dataset.py:182).  Returns the number of bytes consumed,
+ * or -1 (see shdr_last_error) on truncated or corrupt data; never reads past `size` or writes past the image. */
+int64_t shdr_rgbe_rle_decode(const uint8_t* data, int64_t size, int width, int height, uint8_t* rgbe);
+
+/* ---- training-set patch sampler (dataset.py:141-252; cv2.resize with the default INTER_LINEAR, see csrc/dataset.hip) ---- */
+/* HDRDataset._hdr_read_resize (dataset.py:181-202): RGBE [H0][W0][4] -> float BGR [H][W][3] (Ward's decode without +0.5,
+ * channels reversed, clip(0, None)), resized by cv2's bilinear rule (half-pixel centres, replicated border). */
+int shdr_hdr_load_resize_f32(const uint8_t* rgbe, float* y, int H0, int W0, int H, int W, void* stream);
+/* np.mean of the 512 x 512 x 3 crop of PatchHDRDataset.__getitem__ (dataset.py:214-221, :268) for every (file, parity):
+ * means[2 f + p].  Images at arena + offsets[f], dims[f] = {H, W}, min(H, W) == 512.  partials: 2 * n_files * 64 floats.
+ * Deterministic (fixed-order fp32 tree). */
+int shdr_hdr_window_means_f32(const float* arena, const int64_t* offsets, const int32_t* dims, int n_files, float* partials,
+                              float* means, void* stream);
+/* PatchHDRDataset.__getitem__ (dataset.py:212-252) for N samples in one launch: y [N][P][P][3].  params [N][param_stride]
+ * int32 on the device: {idx, S, y0, x0, k, flip0, flip1}: crop of file idx / 2 and parity idx % 2, 0.5 x / (mean + 1e-6),
+ * linear resize 512 -> S x S, crop P x P at (y0, x0), np.rot90(k), flip(axis 0), flip(axis 1).  P % 16 == 0; the
+ * caller checks 0 <= idx < 2 n_files, P <= S, y0 + P <= S and x0 + P <= S (taps are clamped into the crop regardless). */
+int shdr_hdr_patch_sample_f32(const float* arena, const int64_t* offsets, const int32_t* dims, const float* means,
+                              const int32_t* params, int param_stride, int N, int n_files, int P, float* y, void* stream);
 
 /* ---- camera-pipeline simulator (joint_training.py:26-69 `_preprocessing`) ------------- */
 /* Philox4x32-10 block function (host): the counter-based generator the noise kernel uses; exported so that tests can

@@ -1706,3 +1706,53 @@ def flip_rot90(x, flip, rot, divisor=1.0):
     _lib.check(lib.shdr_flip_rot90_f32(_ptr(x), _ptr(y), _ptr(flip), _ptr(rot), n, h, c, float(divisor), _stream()),
                "shdr_flip_rot90_f32")
     return y
+
+
+# ---------------------------------------------------------------------------
+# training-set patch sampler (dataset.py:141-252), see csrc/dataset.hip
+# ---------------------------------------------------------------------------
+def hdr_load_resize(rgbe, out):
+    """RGBE bytes uint8 [H0, W0, 4] on the device -> float BGR, cv2-linear resized into `out` [H, W, 3] (a view of the arena)"""
+    lib = _lib.load()
+    rgbe = _chk(rgbe, "rgbe", torch.uint8)
+    out = _chk(out, "out")
+    if rgbe.dim() != 3 or rgbe.shape[2] != 4 or out.dim() != 3 or out.shape[2] != 3:
+        raise ValueError("hdr_load_resize: expected rgbe [H0, W0, 4] and out [H, W, 3]")
+    h0, w0, _ = rgbe.shape
+    h, w, _ = out.shape
+    _lib.check(lib.shdr_hdr_load_resize_f32(_ptr(rgbe), _ptr(out), h0, w0, h, w, _stream()), "shdr_hdr_load_resize_f32")
+    return out
+
+
+def hdr_window_means(arena, offsets, dims):
+    """np.mean of both 512 x 512 crops of every resident image: float32 [2 * n_files] (file f, parity p at 2 f + p)"""
+    lib = _lib.load()
+    arena = _chk(arena, "arena")
+    offsets = _chk(offsets, "offsets", torch.int64)
+    dims = _chk(dims, "dims", torch.int32)
+    n = offsets.numel()
+    if dims.numel() != 2 * n:
+        raise ValueError("hdr_window_means: dims must be [n_files, 2]")
+    partials = torch.empty(2 * n * 64, device=arena.device, dtype=torch.float32)
+    means = torch.empty(2 * n, device=arena.device, dtype=torch.float32)
+    _lib.check(lib.shdr_hdr_window_means_f32(_ptr(arena), _ptr(offsets), _ptr(dims), n, _ptr(partials), _ptr(means), _stream()),
+               "shdr_hdr_window_means_f32")
+    return means
+
+
+def hdr_patch_sample(arena, offsets, dims, means, params, P):
+    """one PatchHDRDataset.__getitem__ per row of `params` (int32 [N, >= 7] on the device: idx, S, y0, x0, k, flip0, flip1)
+    -> float32 [N, P, P, 3].  The caller validates the parameters (dataset.PatchHDRDataset.render does)."""
+    lib = _lib.load()
+    arena = _chk(arena, "arena")
+    offsets = _chk(offsets, "offsets", torch.int64)
+    dims = _chk(dims, "dims", torch.int32)
+    means = _chk(means, "means")
+    params = _chk(params, "params", torch.int32)
+    if params.dim() != 2 or params.shape[1] < 7:
+        raise ValueError("hdr_patch_sample: params must be int32 [N, >= 7]")
+    n = params.shape[0]
+    y = torch.empty((n, P, P, 3), device=arena.device, dtype=torch.float32)
+    _lib.check(lib.shdr_hdr_patch_sample_f32(_ptr(arena), _ptr(offsets), _ptr(dims), _ptr(means), _ptr(params), params.shape[1], n,
+                                             offsets.numel(), int(P), _ptr(y), _stream()), "shdr_hdr_patch_sample_f32")
+    return y

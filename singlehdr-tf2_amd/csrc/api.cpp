@@ -116,3 +116,57 @@ extern "C" int64_t shdr_rgbe_rle_encode(const uint8_t* rgbe, int width, int heig
   }
   return w;
 }
+
+// The inverse: every scanline is either flat (4 * width bytes) or, when 8 <= width <= 32767 and it starts with 2, 2 and
+// the width, four run-length coded components -- the rule cv2.imread("*.hdr") applies (dataset.py:182).  Every read is
+// checked against `size`, every write against the scanline.  Host only.
+extern "C" int64_t shdr_rgbe_rle_decode(const uint8_t* data, int64_t size, int width, int height, uint8_t* rgbe) {
+  if (!data || !rgbe || size < 0 || width <= 0 || height <= 0) {
+    shdr::set_error("rgbe_rle_decode: bad arguments");
+    return -1;
+  }
+  const bool rle_ok = width >= 8 && width <= 32767;
+  int64_t pos = 0;
+  for (int y = 0; y < height; ++y) {
+    uint8_t* line = rgbe + (int64_t)y * width * 4;
+    if (rle_ok && size - pos >= 4 && data[pos] == 2 && data[pos + 1] == 2 && ((int)data[pos + 2] << 8 | data[pos + 3]) == width) {
+      pos += 4;
+      for (int c = 0; c < 4; ++c) {
+        int x = 0;
+        while (x < width) {
+          if (pos >= size) {
+            shdr::set_error("rgbe_rle_decode: truncated data in scanline %d", y);
+            return -1;
+          }
+          const int n = data[pos];
+          if (n > 128) {                                    // a run of n - 128 copies of the next byte
+            const int run = n - 128;
+            if (pos + 1 >= size || x + run > width) {
+              shdr::set_error("rgbe_rle_decode: %s in scanline %d", pos + 1 >= size ? "truncated data" : "corrupt run", y);
+              return -1;
+            }
+            for (int i = 0; i < run; ++i) line[4 * (x + i) + c] = data[pos + 1];
+            x += run;
+            pos += 2;
+          } else {                                          // n literal bytes
+            if (pos + 1 + n > size || x + n > width) {
+              shdr::set_error("rgbe_rle_decode: %s in scanline %d", pos + 1 + n > size ? "truncated data" : "corrupt literal", y);
+              return -1;
+            }
+            for (int i = 0; i < n; ++i) line[4 * (x + i) + c] = data[pos + 1 + i];
+            x += n;
+            pos += 1 + n;
+          }
+        }
+      }
+    } else {
+      if (size - pos < 4 * (int64_t)width) {
+        shdr::set_error("rgbe_rle_decode: truncated data in flat scanline %d", y);
+        return -1;
+      }
+      for (int64_t i = 0; i < 4 * (int64_t)width; ++i) line[i] = data[pos + i];
+      pos += 4 * (int64_t)width;
+    }
+  }
+  return pos;
+}

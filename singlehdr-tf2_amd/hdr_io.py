@@ -63,10 +63,22 @@ def write_hdr(path, rgbe):
         f.write(rle_encode(rgbe))
 
 
-def read_hdr(path):
-    """Radiance picture file -> float32 RGB [H, W, 3] (flat and RLE scanlines, -Y +X orientation)"""
+def rle_decode(data, height, width):
+    """scanline bytes (flat or RLE) -> uint8 RGBE [height, width, 4] (libshdr host routine); ValueError on truncated or corrupt data"""
+    buf = np.frombuffer(data, dtype=np.uint8)
+    rgbe = np.empty((height, width, 4), dtype=np.uint8)
+    n = _lib.load().shdr_rgbe_rle_decode(ctypes.c_void_p(buf.ctypes.data), buf.size, width, height, ctypes.c_void_p(rgbe.ctypes.data))
+    if n < 0:
+        raise ValueError(_lib.load().shdr_last_error().decode())
+    return rgbe
+
+
+def read_rgbe(path):
+    """Radiance picture file -> its RGBE bytes uint8 [H, W, 4] (flat and RLE scanlines, -Y +X orientation)"""
     with open(path, "rb") as f:
         data = f.read()
+    if data.startswith(b"\x76\x2f\x31\x01"):
+        raise ValueError("%s: OpenEXR files are not supported (Radiance .hdr only)" % path)
     if not data.startswith(b"#?"):
         raise ValueError("%s: not a Radiance file" % path)
     end = data.index(b"\n\n")
@@ -77,30 +89,15 @@ def read_hdr(path):
     if not m:
         raise ValueError("%s: unsupported resolution line %r" % (path, data[end + 2:nl]))
     h, w = int(m.group(1)), int(m.group(2))
-    buf = np.frombuffer(data, dtype=np.uint8, offset=nl + 1)
-    rgbe = np.empty((h, w, 4), dtype=np.uint8)
-    pos = 0
-    for y in range(h):
-        if 8 <= w <= 32767 and buf[pos] == 2 and buf[pos + 1] == 2 and (int(buf[pos + 2]) << 8 | int(buf[pos + 3])) == w:
-            pos += 4
-            for c in range(4):
-                x = 0
-                while x < w:
-                    n = int(buf[pos])
-                    if n > 128:
-                        rgbe[y, x:x + n - 128, c] = buf[pos + 1]
-                        x += n - 128
-                        pos += 2
-                    else:
-                        rgbe[y, x:x + n, c] = buf[pos + 1:pos + 1 + n]
-                        x += n
-                        pos += 1 + n
-                if x != w:
-                    raise ValueError("%s: corrupt scanline %d" % (path, y))
-        else:
-            rgbe[y] = buf[pos:pos + 4 * w].reshape(w, 4)
-            pos += 4 * w
-    return rgbe_decode(rgbe)
+    try:
+        return rle_decode(memoryview(data)[nl + 1:], h, w)
+    except ValueError as exc:
+        raise ValueError("%s: %s" % (path, exc)) from None
+
+
+def read_hdr(path):
+    """Radiance picture file -> float32 RGB [H, W, 3] (flat and RLE scanlines, -Y +X orientation)"""
+    return rgbe_decode(read_rgbe(path))
 
 
 def rgbe_decode(rgbe):
