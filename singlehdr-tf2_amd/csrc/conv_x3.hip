@@ -59,6 +59,7 @@ struct X3G {
   static constexpr int PATCH_HALVES = PPIX * 32;              // one fp16 image of the patch
   static constexpr int LDS_BYTES = (2 * PATCH_HALVES + 2 * UNIT_HALVES) * 2;
   static constexpr int LDS_BYTES_UP = LDS_BYTES + LRPIX * 32 * 4;
+  static constexpr int RANGE_BYTES = 16;                       // + the waves' output maxima (x3_range_out), behind everything else
 };
 
 struct X3Args {
@@ -124,7 +125,7 @@ __device__ __forceinline__ void x3_split4(const f32x4 v, float xs, unsigned (&h)
     asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l[p]) : "v"(t1), "s"(k2048));
   }
 }
-// max |y| of a block -> the range slot: the waves' maxima meet in LDS (dead after the tap loop's last barrier) and ONE thread issues a
+// max |y| of a block -> the range slot: the waves' maxima meet in four LDS words of their own and ONE thread issues a
 // no-return atomicMax, and only when the block's maximum exceeds what the slot already holds.  Atomics execute at the memory side, one
 // after the other per address (measured ~4 ns each): one per WAVE cost the small layers of the U-Nets 15 - 35 us per launch, all of it
 // in the first round of blocks, which finish together and all still see the slot empty.
@@ -532,7 +533,11 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     }
   }
 #ifndef SHDR_ABL_NO_TAIL
-  if (a.yr && a.final) x3_range_out(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, reinterpret_cast<unsigned*>(xsm));      // (a pooled output is bounded by the same maximum)
+  // (a pooled output is bounded by the same maximum).  The waves' words have LDS of their own: without a barrier after the last chunk (the
+  // 1 x 1 form) wave 0 may still be reading patch pixel (0, 0) when another wave writes its maximum
+  if (a.yr && a.final)
+    x3_range_out(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen,
+                 reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + (UP ? G::LDS_BYTES_UP : G::LDS_BYTES)));
 #endif
 }
 
@@ -540,6 +545,203 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
 #undef patch_l
 #undef filt
 #undef lrs
+
+// ---- 1 x 1 layers: one split per chunk for up to 256 couts ---------------------------------------------------------------------------
+// A 1 x 1 layer runs ONE tap (48 MFMAs per wave) on every chunk it splits: conv_x3_kernel<false, 1, 1> with 64 couts per block fetched,
+// split and staged each 32-channel chunk once per 64-cout slice -- four times for Cout = 256 -- and was vector-issue bound (6.3 VALU
+// instructions per MFMA, 2.1 TB/s).  Here a block is BP = 128 CONSECUTIVE output pixels (no halo: any run of pixels is a patch) x NS
+// slices of 64 couts (NS = 4: 256 couts, NS = 2: 128); wave w takes slice w % NS and the 128 / (4 / NS) pixels of group w / NS
+// (MT1 = 2 NS 16-pixel rows: 128 accumulator registers at NS = 4).  Per chunk the block loads 16 KB of fp32 input, splits it ONCE into the
+// two fp16 images (four float4 per thread) and every wave consumes it: split VALU per MFMA 2 / NS of the 64-cout form.
+// The wave's filter fragments (wh, wl of its slice: 8 KB per chunk, the packed layout [Cout / 64][chunks][wh, wl][64][32] read as it is)
+// come straight from global memory (L2: every block of the layer reads the same filter) into registers one chunk ahead -- no LDS image,
+// no staging; the patch images are double-buffered (32 KB) and the raw input prefetched two chunks ahead in two register sets, so a
+// chunk takes ONE barrier.  Operands, chunk order, MFMA order per product (wh xh, ws xl, wl xh) and the epilogue are those of
+// conv_x3_kernel<false, 1, 1>: the results are bit-identical to it.
+constexpr int X1_BP = 128;
+template <int NS>
+__global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
+  constexpr int MT1 = 2 * NS, BP = X1_BP;
+  constexpr int PJ1 = BP * 8 / 256;                            // float4 pieces per thread and chunk (4)
+  constexpr int IMG = BP * 32;                                 // halves of one fp16 image of a chunk (8 KB)
+  static_assert(NS * (BP / (MT1 * 16)) == 4, "four waves: NS cout slices x pixel groups");
+  __shared__ __attribute__((aligned(16))) _Float16 x1sm[2 * 2 * IMG];       // [buffer][h, l][BP pixels][32], 16-byte slots swizzled by sx()
+  __shared__ unsigned x1rw[4];                                 // the waves' output maxima (x3_range_out)
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slice = wave % NS, grp = wave / NS;
+  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int pn = L % a.nblk_n, pm = L / a.nblk_n;
+  const int P0 = pm * BP, Ptot = a.N * a.H * a.W;
+
+  // ---- patch geometry (fixed per block): piece p = tid + 256 j -> (block pixel p >> 3, float4 p & 7 of the chunk) -------------------
+  int ppix[PJ1];                                               // input pixel of the piece's output pixel, -1: beyond the layer
+  const int pdst = (tid >> 3) * 32 + 8 * (((tid & 7) >> 1) ^ sx((tid >> 3) & 15)) + 4 * (tid & 1);      // + 32 * 32 j (same column)
+#pragma unroll
+  for (int j = 0; j < PJ1; ++j) {
+    const int P = P0 + (tid >> 3) + 32 * j;
+    ppix[j] = -1;
+    if (P < Ptot) {
+      const int ow = P % a.W, t = P / a.W;
+      const int oh = t % a.H, img = t / a.H;
+      const int ih = a.in_s * oh + a.bh, iw = a.in_s * ow + a.bw;
+      if ((unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win) ppix[j] = (img * a.Hin + ih) * a.Win + iw;
+    }
+  }
+  const int nch1 = a.C1 >> 5, nch = (a.C1 + a.C2) >> 5;
+  using Set0 = std::integral_constant<int, 0>;
+  using Set1 = std::integral_constant<int, 1>;
+  f32x4 pr_sets[2][PJ1];
+  auto load_patch = [&](int c, auto setc) __attribute__((always_inline)) {                    // chunk c -> register set setc
+    constexpr int S = decltype(setc)::value;
+    const bool second = c >= nch1;
+    const float* src = second ? a.x2 : a.x1;
+    const int Cs = second ? a.C2 : a.C1;
+    const int c0 = (second ? c - nch1 : c) << 5;
+#pragma unroll
+    for (int j = 0; j < PJ1; ++j) {
+      pr_sets[S][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (ppix[j] >= 0) pr_sets[S][j] = *reinterpret_cast<const f32x4*>(src + (size_t)(unsigned)ppix[j] * (unsigned)Cs + c0 + 4 * (tid & 7));
+    }
+  };
+  float xs = 1.0f, ixs = 1.0f;
+  auto store_patch = [&](int buf, auto setc) __attribute__((always_inline)) {                 // register set setc -> the two images of buffer buf
+    constexpr int S = decltype(setc)::value;
+#pragma unroll
+    for (int j = 0; j < PJ1; ++j) {
+      unsigned h[2], l[2];
+      x3_split4(pr_sets[S][j], xs, h, l);
+      *reinterpret_cast<uint2*>(x1sm + buf * 2 * IMG + pdst + 1024 * j) = make_uint2(h[0], h[1]);
+      *reinterpret_cast<uint2*>(x1sm + buf * 2 * IMG + IMG + pdst + 1024 * j) = make_uint2(l[0], l[1]);
+    }
+  };
+  // ---- filter fragments of the wave's slice, straight from the packed filter (lane: cout row ni * 16 + fi, channels 8 fg .. 8 fg + 7).
+  //      A chunk runs in two halves, couts ni = 0, 1 (fragments f0) and ni = 2, 3 (f1), over all MT1 pixel rows; each half's fragments
+  //      are loaded while the other half runs (32 registers instead of 64 for a whole chunk held one chunk ahead: 256 couts fit two waves
+  //      per SIMD without spilling), at the price of reading the patch images twice
+  const int fi = lane & 15, fg = lane >> 4;
+  const _Float16* wsl = a.wp + (size_t)(pn * NS + slice) * nch * UNIT_HALVES + fi * 32 + 8 * fg;
+  f16x8 f0h[2], f0l[2], f1h[2], f1l[2];
+  auto load_w = [&](int c, int half, f16x8 (&h)[2], f16x8 (&l)[2]) __attribute__((always_inline)) {
+    const _Float16* g = wsl + (size_t)c * UNIT_HALVES + half * 2 * 16 * 32;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      h[k] = *reinterpret_cast<const f16x8*>(g + k * 16 * 32);
+      l[k] = *reinterpret_cast<const f16x8*>(g + IMG_HALVES + k * 16 * 32);
+    }
+  };
+
+  f32x4 acc[MT1][NT];
+#pragma unroll
+  for (int mi = 0; mi < MT1; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const int pc = pcol(fi);
+  const int a_rd = (grp * MT1 * 16 + pc) * 32 + 8 * (fg ^ sx(pc));      // B operand: (pixel grp * MT1 * 16 + pc, channel group fg) + 16 mi pixels
+
+  // couts ni = 2 half, 2 half + 1 of chunk c (patch buffer buf) over all pixel rows of the wave
+  auto half_pass = [&](int buf, auto halfc, const f16x8 (&wh)[2], const f16x8 (&wl)[2]) __attribute__((always_inline)) {
+    constexpr int H = decltype(halfc)::value;
+    const int bo = buf * 2 * IMG + a_rd;
+    f16x8 ws[2], ph[2], pl[2];
+    auto read_a = [&](int mi, int slot) __attribute__((always_inline)) {
+      ph[slot] = *reinterpret_cast<const f16x8*>(x1sm + bo + mi * 16 * 32);
+      pl[slot] = *reinterpret_cast<const f16x8*>(x1sm + IMG + bo + mi * 16 * 32);
+    };
+    read_a(0, 0);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) ws[k] = wh[k] * (_Float16)(1.0f / 2048.0f);                // exact (as in conv_x3_kernel)
+#pragma unroll
+    for (int mi = 0; mi < MT1; ++mi) {
+      if (mi + 1 < MT1) read_a(mi + 1, (mi + 1) & 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) acc[mi][2 * H + k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[k], ph[mi & 1], acc[mi][2 * H + k], 0, 0, 0);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) acc[mi][2 * H + k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[k], pl[mi & 1], acc[mi][2 * H + k], 0, 0, 0);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) acc[mi][2 * H + k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[k], ph[mi & 1], acc[mi][2 * H + k], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  using Half0 = std::integral_constant<int, 0>;
+  using Half1 = std::integral_constant<int, 1>;
+
+  load_patch(0, Set0{});
+  if (nch > 1) load_patch(1, Set1{});
+  load_w(0, 0, f0h, f0l);
+  x3_range_scale(a.xr1, a.xr2, xs, ixs);                       // (behind the first loads: the slot is a dependent scalar load)
+  store_patch(0, Set0{});
+  if (nch > 2) load_patch(2, Set0{});
+  // chunk c: buffer c & 1 holds it; `nxt` = the register set of chunk c + 1 (split into the other buffer here, then refilled with c + 3)
+  auto chunk = [&](int c, auto nxt) __attribute__((always_inline)) {
+    __syncthreads();                                           // chunk c is in buffer c & 1; every wave is done with the other buffer (chunk c - 1)
+    load_w(c, 1, f1h, f1l);
+    if (c + 1 < nch) {
+      store_patch((c + 1) & 1, nxt);
+      if (c + 3 < nch) load_patch(c + 3, nxt);
+    }
+    half_pass(c & 1, Half0{}, f0h, f0l);
+    if (c + 1 < nch) load_w(c + 1, 0, f0h, f0l);
+    half_pass(c & 1, Half1{}, f1h, f1l);
+  };
+#pragma unroll 1
+  for (int c = 0; c < nch; c += 2) {
+    chunk(c, Set1{});
+    if (c + 1 < nch) chunk(c + 1, Set0{});
+  }
+
+  // ---- epilogue: conv_x3_kernel's, per 16-pixel row mi: lane = pixel P0 + grp * MT1 * 16 + 16 mi + pc x 4 consecutive couts ------------
+  const float inv_s = a.hdr[1] * ixs;
+  const unsigned yr_seen = a.yr ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  int ep0 = (pn * NS + slice) * BN;                            // first cout of the wave's slice
+  asm volatile("" : "+s"(ep0));                                // (loads below the chunk loop, not hoisted above it)
+  f32x4 bias_r[NT], scale_r[NT], shift_r[NT];
+#pragma unroll
+  for (int ni = 0; ni < NT; ++ni) {
+    const int cl = ni * 16 + 4 * fg;
+    bias_r[ni] = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    scale_r[ni] = a.scale ? *reinterpret_cast<const f32x4*>(a.scale + ep0 + cl) : (f32x4){1.f, 1.f, 1.f, 1.f};
+    shift_r[ni] = a.scale ? *reinterpret_cast<const f32x4*>(a.shift + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  const int Pw = P0 + grp * MT1 * 16 + pc;                     // the lane's pixel of row mi: Pw + 16 mi
+  float ym = 0.0f;
+  constexpr int EB = 4;                                        // rows per batch of residual loads (64 registers)
+#pragma unroll
+  for (int m0 = 0; m0 < MT1; m0 += EB) {
+    f32x4 res_r[EB][NT];
+    if (a.res) {
+#pragma unroll
+      for (int e = 0; e < EB; ++e)
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) {
+          const int P = Pw + 16 * (m0 + e);
+          res_r[e][ni] = P < Ptot ? *reinterpret_cast<const f32x4*>(a.res + (size_t)P * a.res_cs + ep0 + ni * 16 + 4 * fg) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+      const int P = Pw + 16 * (m0 + e);
+      if (P0 + grp * MT1 * 16 + 16 * (m0 + e) >= Ptot) continue;                               // wave-uniform
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni) {
+        f32x4 v = acc[m0 + e][ni] * inv_s;
+        asm("" : "+v"(v));                                     // rounded before the bias, as in conv_x3_kernel (its yin select keeps the two apart)
+        v += bias_r[ni];
+        shdr::act_apply4<0>(v, a.act1);
+        if (a.scale) v = v * scale_r[ni] + shift_r[ni];
+        if (a.res) v += res_r[e][ni];
+        shdr::act_apply4<0>(v, a.act2);
+        if (P < Ptot) {
+          *reinterpret_cast<f32x4*>(a.y + (size_t)P * a.Cout + ep0 + ni * 16 + 4 * fg) = v;
+          if (a.yr) ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[0])), fabsf(v[1])), fabsf(v[2])), fabsf(v[3]));
+        }
+      }
+    }
+  }
+  if (a.yr) x3_range_out(a.yr, ym, lane, wave, yr_seen, x1rw);
+}
 
 // ---- filter preparation ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void x3_absmax_kernel(const float* __restrict__ w, long n, unsigned* __restrict__ out) {
@@ -617,7 +819,7 @@ inline int64_t x3_phase_floats(const X3Phase& p, int Ct, int Cout) { return X3_H
 
 template <bool UP, int KH, int KW, bool MP = false>
 int launch_x3(const X3Args& a, hipStream_t st) {
-  constexpr int lds = UP ? X3G<KH, KW>::LDS_BYTES_UP : X3G<KH, KW>::LDS_BYTES;
+  constexpr int lds = (UP ? X3G<KH, KW>::LDS_BYTES_UP : X3G<KH, KW>::LDS_BYTES) + X3G<KH, KW>::RANGE_BYTES;
   static bool attr_done[shdr::kMaxDevices] = {};
   const int dev_slot = shdr::device_slot();
   if (!attr_done[dev_slot]) {
@@ -629,6 +831,21 @@ int launch_x3(const X3Args& a, hipStream_t st) {
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_x3_kernel<UP, KH, KW, MP>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return shdr::check_launch("conv_x3_kernel");
+}
+
+// conv_x3_1x1_kernel: 256 couts per block where Cout allows it, else 128 (Cout 64 and 32 keep conv_x3_kernel<false, 1, 1>: its block
+// already holds every cout of the layer and splits a chunk once)
+int launch_x3_1x1(const X3Args& a0, hipStream_t st) {
+  X3Args a = a0;
+  const long npix = (long)a.N * a.H * a.W;
+  const int ns = a.Cout % 256 == 0 ? 4 : 2;
+  a.nblk_m = (int)((npix + X1_BP - 1) / X1_BP);
+  a.nblk_n = a.Cout / (64 * ns);
+  const long nblk = (long)a.nblk_m * a.nblk_n;
+  if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
+  if (ns == 4) hipLaunchKernelGGL((conv_x3_1x1_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv_x3_1x1_kernel<2>), dim3((unsigned)nblk), dim3(256), 0, st, a);
+  return shdr::check_launch("conv_x3_1x1_kernel");
 }
 
 }  // namespace
@@ -808,7 +1025,12 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
     a.final = i == n - 1;
     int rc;
     if (ph[i].th == 3 && ph[i].tw == 3) rc = up ? launch_x3<true, 3, 3>(a, st) : launch_x3<false, 3, 3>(a, st);
-    else if (ph[i].th == 1 && ph[i].tw == 1) rc = launch_x3<false, 1, 1>(a, st);
+    else if (ph[i].th == 1 && ph[i].tw == 1) {
+      // the wide-block kernel takes 128- and 256-cout multiples with a plain output; a pooled or projected output (no network has one
+      // on a 1 x 1 layer), the narrow layers and SHDR_X3_1X1_SLICED=1 (A/B) run the 64-cout instantiation
+      const bool wide = d->Cout % 128 == 0 && y && !y_pool && !proj && !up && n == 1 && SHDR_ENV("SHDR_X3_1X1_SLICED") == nullptr;
+      rc = wide ? launch_x3_1x1(a, st) : launch_x3<false, 1, 1>(a, st);
+    }
     else if (ph[i].th == 4 && ph[i].tw == 4) rc = launch_x3<false, 4, 4>(a, st);
     else if (ph[i].th == 4 && ph[i].tw == 3) rc = launch_x3<false, 4, 3>(a, st);
     else if (ph[i].th == 3 && ph[i].tw == 4) rc = launch_x3<false, 3, 4>(a, st);
