@@ -7,6 +7,7 @@ no fallback path: CPU tensors or a missing library raise.
 """
 import collections
 import ctypes
+import math
 
 import torch
 
@@ -128,7 +129,12 @@ def _d(t):
 # The split-operand conv plans scale their input by a power of two taken from a RANGE SLOT: a device float holding an upper bound of
 # max |x| of the tensor.  The kernels that produce a tensor write its slot from their epilogue (`y_range`), bound-preserving ops
 # (pooling, bilinear resize, clip, channel reversal) hand their input's slot on, host-known bounds become constant slots, and a tensor
-# that arrives without one is measured by the library (one pass over it).  Slots travel as the attribute `_shdr_range` of the tensor.
+# that arrives without one is measured by the library (one pass over it).  A tensor's range travels as ONE record: the attributes
+# `_shdr_range` (slot), `_shdr_bound` (host bound) and `_shdr_range_ver` (the t._version both describe), written together by _set_range.
+#   R1  a read checks the version for both kinds: an in-place update (autograd accumulating a second gradient into a buffer) voids them.
+#   R2  a bound that is not finite is not recorded (the kernels read one as "scale 1, measure nothing").
+#   R3  raw-pointer writes bump no version: _conv2d_raw drops `out`'s record before any launch, then attaches the slot a kernel wrote.
+#   R4  fp32 add(a, b, relu=True) hands the sum's measured slot on (|relu(s)| <= |s|) instead of clip's infinite bound.
 _RANGE_SCOPES = []
 _CONST_SLOTS = {}
 
@@ -169,47 +175,43 @@ def _new_slot(device):
     return torch.zeros(1, device=device, dtype=torch.float32)
 
 
+def _record(t):
+    """(slot, bound) of t's range record if it still describes t (R1), else (None, None) -- also for t None"""
+    ver = getattr(t, "_shdr_range_ver", None)
+    return (t._shdr_range, t._shdr_bound) if ver is not None and ver == t._version else (None, None)
+
+
 def _range_of(t):
-    """the range slot of a tensor (1-element fp32 device tensor) or None; a host-known bound (`_shdr_bound`) becomes a constant slot"""
-    if t is None:
-        return None
-    r = getattr(t, "_shdr_range", None)
-    if r is not None:
-        # a slot describes the tensor as it was written: an in-place update since then (autograd accumulating a second gradient
-        # into the same buffer) voids it -- torch bumps the version counter on every in-place op
-        return r if getattr(t, "_shdr_range_ver", t._version) == t._version else None
-    b = getattr(t, "_shdr_bound", None)
-    if b is None:
-        return None
-    key = (t.device, float(b))
-    slot = _CONST_SLOTS.get(key)
+    """the range slot of a tensor (1-element fp32 device tensor) or None; a host-known bound becomes a constant slot"""
+    slot, b = _record(t)
+    if slot is not None or b is None:
+        return slot
+    slot = _CONST_SLOTS.get((t.device, b))
     if slot is None:
-        slot = _CONST_SLOTS[key] = torch.full((1,), float(b), device=t.device, dtype=torch.float32)
+        slot = _CONST_SLOTS[(t.device, b)] = torch.full((1,), b, device=t.device, dtype=torch.float32)
     return slot
 
 
-def _set_range(t, slot):
-    t._shdr_range = slot
-    t._shdr_range_ver = t._version
+def _bound_of(t):
+    """the host-known upper bound of max |t| or None"""
+    return _record(t)[1]
+
+
+def _set_range(t, slot, bound=None):
+    t._shdr_range, t._shdr_bound, t._shdr_range_ver = slot, bound, t._version
     return t
 
 
-def _carry_range(y, x, factor=None):
+def _carry_range(y, x):
     """y is bounded by x's bound (pooling, convex resampling, channel permutation, clipping of an already bounded tensor, the
     derivative of an activation applied to a gradient)"""
-    r = _range_of(x) if getattr(x, "_shdr_range", None) is not None else None
-    if r is not None:
-        _set_range(y, r)
-    b = getattr(x, "_shdr_bound", None)
-    if b is not None:
-        y._shdr_bound = b
-    return y
+    return _set_range(y, *_record(x))
 
 
 def set_bound(t, bound):
-    """declare a host-known upper bound of max |t| (e.g. an image in [0, 1])"""
-    t._shdr_bound = float(bound)
-    return t
+    """declare a host-known upper bound of max |t| (e.g. an image in [0, 1]); a non-finite one declares nothing (R2)"""
+    b = float(bound)
+    return _set_range(t, None, b if math.isfinite(b) else None)
 
 
 def absmax_slot(x):
@@ -335,6 +337,7 @@ def _conv2d_raw(x, w, bias, stride, x2, x2_scale, act1, scale, shift, residual, 
         _chk(out, "out")
         if tuple(out.shape) != (n, ho, wo, cout):
             raise ValueError("conv2d: bad out shape")
+        _set_range(out, None)          # R3: the kernels below write out through a raw pointer
     d.y_cstride = cout
     for t, nm, ln in ((bias, "bias", cout), (scale, "scale", cout), (shift, "shift", cout)):
         if t is not None and (_chk(_d(t), nm).numel() != ln):
@@ -616,10 +619,8 @@ def lin_frontend(img, channels=96, dtype=None):
     y = torch.empty((n, h, w, channels), device=img.device, dtype=dtype)
     fn = "shdr_lin_frontend_fwd_f16" if dtype == HALF else "shdr_lin_frontend_fwd_f32"
     _lib.check(getattr(lib, fn)(_ptr(img), _ptr(y), n, h, w, channels, _stream()), fn)
-    b = getattr(img_in, "_shdr_bound", None)
-    if b is not None:                  # image: b, sobel: sum |coefficient| = 8 times b, soft-histogram channels: [0, 1]
-        set_bound(y, max(1.0, 8.0 * b))
-    return y
+    b = _bound_of(img_in)              # image: b, sobel: sum |coefficient| = 8 times b, soft-histogram channels: [0, 1]
+    return y if b is None else set_bound(y, max(1.0, 8.0 * b))
 
 
 def invcrf_decode(feat, wfc, bfc, table):
@@ -707,10 +708,8 @@ def vgg_preprocess(x, out_channels=3, dtype=torch.float32):
     y = torch.empty(tuple(x.shape[:-1]) + (out_channels,), device=x.device, dtype=torch.float32)
     _lib.check(lib.shdr_vgg_preprocess_fwd_f32(_ptr(x), _ptr(y), npix, out_channels, _stream()),
                "shdr_vgg_preprocess_fwd_f32")
-    b = getattr(x_in, "_shdr_bound", None)
-    if b is not None:
-        set_bound(y, 255.0 * b + 124.0)     # x * 255 - mean, |mean| < 124
-    return y
+    b = _bound_of(x_in)
+    return y if b is None else set_bound(y, 255.0 * b + 124.0)     # x * 255 - mean, |mean| < 124
 
 
 def reverse3(x):
@@ -761,10 +760,8 @@ def pack3(srcs, out_channels=None, dtype=torch.float32):
                                       _stream()), "shdr_pack3_fwd_f32")
     if n == 1:                               # a channel-padded copy: the same range
         return _carry_range(y, srcs_in[0])
-    bounds = [getattr(t, "_shdr_bound", None) for t in srcs_in]
-    if all(b is not None for b in bounds):   # (device-side slots of several sources are not merged: measured by the consumer)
-        set_bound(y, max(bounds))
-    return y
+    bounds = [_bound_of(t) for t in srcs_in]      # (device-side slots of several sources are not merged: measured by the consumer)
+    return y if None in bounds else set_bound(y, max(bounds))
 
 
 # ---------------------------------------------------------------------------
@@ -976,7 +973,8 @@ def add(a, b, relu=False):
         _lib.check(lib.shdr_add_f16(_ptr(a), _ptr(b), _ptr(y), a.numel(), int(bool(relu)), _stream()), "shdr_add_f16")
         return y
     if relu:
-        return clip(add(a, b), 0.0, float("inf"))
+        s = add(a, b)
+        return _carry_range(clip(s, 0.0, float("inf")), s)     # R4
     a, b = _chk(_d(a), "a"), _chk(_d(b), "b")
     if a.shape != b.shape:
         raise ValueError("add: shape mismatch")

@@ -443,8 +443,8 @@ def test_split_operand_forward_is_range_safe(shdr, case, known_range, monkeypatc
                 K.absmax_slot(x2d)
         y = K.conv2d(xd, dev(wt), dev(b * bias_mag), x2=x2d, act1=K.ACT_LRELU)
         if not exact:                           # ... and the slot this launch wrote for its consumer holds max |y|
-            assert hasattr(y, "_shdr_range")
-            got, want = float(y._shdr_range), float(y[torch.isfinite(y)].abs().max())
+            assert K._range_of(y) is not None
+            got, want = float(K._range_of(y)), float(y[torch.isfinite(y)].abs().max())
             assert got == want or not np.isfinite(got), (got, want)
         monkeypatch.setattr(K, "EXACT_FP32", False)
         return host(y)
@@ -487,25 +487,50 @@ def test_split_operand_range_slots_travel_with_the_tensors(shdr, monkeypatch):
     w2 = dev(f32(rng.normal(size=(3, 3, 64, 64)) / 24)).requires_grad_(True)
     with torch.no_grad(), K.range_scope():
         y1, p1 = K.conv2d_avgpool2(x, w1, None, act1=K.ACT_RELU)
-        assert y1._shdr_range is p1._shdr_range and float(y1._shdr_range) == float(y1.abs().max())
+        assert K._range_of(y1) is K._range_of(p1) and float(K._range_of(y1)) == float(y1.abs().max())
         up = K.resize2x(K.maxpool2(p1))
-        assert up._shdr_range is p1._shdr_range
+        assert K._range_of(up) is K._range_of(p1)
         y2 = K.conv2d(up, w2)
         c = K.clip(y2, 0.0, 1.0)
-        assert c._shdr_bound == 1.0 and float(K._range_of(c)) == 1.0
+        assert K._bound_of(c) == 1.0 and float(K._range_of(c)) == 1.0
         # the exact-fp32 MFMA / direct kernels track their output range too (their consumer may be a split-operand layer)
         w3 = dev(f32(rng.normal(size=(1, 1, 64, 96)) / 8)).requires_grad_(True)       # (96 couts: not a split-operand layer)
         assert K.conv2d_plan(tuple(y2.shape), tuple(w3.shape)) == "mfma"
         res96 = dev(f32(rng.normal(size=tuple(y2.shape[:3]) + (96,))))
         for kw in (dict(), dict(act1=K.ACT_RELU, residual=res96, act2=K.ACT_RELU)):
             y3 = K.conv2d(y2, w3, **kw)
-            assert float(y3._shdr_range) == float(y3.abs().max())
+            assert float(K._range_of(y3)) == float(y3.abs().max())
         w4 = dev(f32(rng.normal(size=(1, 1, 64, 3)))).requires_grad_(True)
         assert K.conv2d_plan(tuple(y2.shape), tuple(w4.shape)) == "direct"
         y4 = K.conv2d(y2, w4)
-        assert float(y4._shdr_range) == float(y4.abs().max())
+        assert float(K._range_of(y4)) == float(y4.abs().max())
         plain = K.conv2d(up.clone(), w2)              # no slot on the clone: measured below the ABI (possibly another power of two)
         assert bool(torch.isfinite(y2).all()) and float((plain - y2).abs().max()) <= 1e-6 * float(y2.abs().max())
+
+        def split_conv_as_exact(t):
+            assert K.conv2d_plan(tuple(t.shape), tuple(w2.shape)) == "x3"
+            ys = K.conv2d(t, w2)
+            monkeypatch.setattr(K, "EXACT_FP32", True)
+            ye = K.conv2d(t, w2)
+            monkeypatch.setattr(K, "EXACT_FP32", False)
+            assert bool(torch.isfinite(ys).all()) and float((ys - ye).abs().max()) <= 5e-6 * float(ye.abs().max())
+
+        # records that no longer describe the tensor are not read: an in-place update voids a host bound (bound 1 would scale
+        # values up to 1e4 by 2^10, past the fp16 range) ...
+        x = K.clip(dev(f32(rng.normal(size=(2, 64, 64, 64)))), 0.0, 1.0)
+        x.mul_(1e4)
+        assert K._range_of(x) is None
+        split_conv_as_exact(x)
+        # ... and a convolution into `out=` replaces the slot of out's old contents (raw-pointer writes bump no version)
+        buf = dev(f32(rng.normal(size=(2, 64, 64, 64)) * 1e-3))
+        K.absmax_slot(buf)
+        K.conv2d(dev(f32(rng.normal(size=(2, 64, 64, 64)) * 1e4)), w2, algo=K.ALGO_MFMA, out=buf)
+        assert float(buf.abs().max()) > 1e3
+        split_conv_as_exact(buf)
+        # fp32 relu(a + b) hands the measured slot of the sum on (an infinite clip bound would switch the consumer's scaling off)
+        a, b = dev(f32(rng.normal(size=(2, 16, 16, 32)) * 3.0)), dev(f32(rng.normal(size=(2, 16, 16, 32)) * 3.0))
+        s = K.add(a, b, relu=True)
+        assert np.isfinite(float(K._range_of(s))) and float(K._range_of(s)) >= float(s.abs().max()) > 0.0
 
 
 def test_backward_elementwise_kernels_track_their_output_range(shdr):
@@ -516,23 +541,23 @@ def test_backward_elementwise_kernels_track_their_output_range(shdr):
     with torch.no_grad(), K.range_scope():
         a, b = dev(f32(rng.normal(size=(2, 16, 16, 32)) * 1e-6)), dev(f32(rng.normal(size=(2, 16, 16, 32)) * 1e-6))
         s = K.add(a, b)
-        assert torch.equal(s, a + b) and float(s._shdr_range) == float(s.abs().max())
+        assert torch.equal(s, a + b) and float(K._range_of(s)) == float(s.abs().max())
         x = dev(f32(rng.normal(size=(2, 16, 16, 32))))
         mean, var = K.bn_stats(x)
         gamma, beta = dev(f32(rng.normal(size=32))), dev(f32(rng.normal(size=32)))
         y = K.bn_train_apply(x, mean, var, gamma, beta, 1e-3, True)
         dx, _, _ = K.bn_bwd(s, x, y, mean, var, gamma, 1e-3)
-        assert float(dx._shdr_range) == float(dx.abs().max()) > 0.0
+        assert float(K._range_of(dx)) == float(dx.abs().max()) > 0.0
         dx1, _, _ = K.bn_bwd(s[..., :3].contiguous(), x[..., :3].contiguous(), None, mean[:3].contiguous(), var[:3].contiguous(),
                              gamma[:3].contiguous(), 1e-3)            # the scalar kernel (C % 4 != 0)
-        assert float(dx1._shdr_range) == float(dx1.abs().max()) > 0.0
+        assert float(K._range_of(dx1)) == float(dx1.abs().max()) > 0.0
         big = dev(f32(rng.normal(size=(2, 32, 32, 32)) * 3e4))
         r = K.resize2x_bwd(big, (2, 16, 16, 32))
-        assert float(r._shdr_range) == float(r.abs().max()) > float(big.abs().max())      # up to nine weighted taps add up
+        assert float(K._range_of(r)) == float(r.abs().max()) > float(big.abs().max())      # up to nine weighted taps add up
         K.absmax_slot(big)
         for g in (K.avgpool2_bwd(big, (2, 64, 64, 32)), K.maxpool2_bwd(dev(f32(rng.normal(size=(2, 64, 64, 32)))), big),
                   K.upsample_zero2(big, (2, 64, 64, 32))):
-            assert g._shdr_range is big._shdr_range and float(g.abs().max()) <= float(big._shdr_range)
+            assert K._range_of(g) is K._range_of(big) and float(g.abs().max()) <= float(K._range_of(big))
 
 
 def test_projected_output_of_the_split_operand_kernel(shdr, monkeypatch):
@@ -551,7 +576,7 @@ def test_projected_output_of_the_split_operand_kernel(shdr, monkeypatch):
         pj, pp = K.conv2d_maxpool2(x, w, b, act1=K.ACT_RELU, proj=proj)
         want = torch.einsum("nhwc,jc->nhwj", y.double(), proj.double())
         assert torch.equal(pp, yp) and float((pj.double() - want).abs().max()) <= 1e-5 * float(want.abs().max())
-        assert float(pp._shdr_range) >= float(pp.abs().max())
+        assert float(K._range_of(pp)) >= float(pp.abs().max())
         lo = dev(f32(rng.normal(size=(2, 16, 24, 64))))
         yu = K.conv2d_up2(lo, w, b, act1=K.ACT_RELU, scale=sc, shift=sh, act2=K.ACT_RELU)
         pu = K.conv2d_up2(lo, w, b, act1=K.ACT_RELU, scale=sc, shift=sh, act2=K.ACT_RELU, proj=proj)
@@ -678,7 +703,7 @@ def test_conv2d_x3_thirty_two_couts(shdr, monkeypatch):
     assert K.conv2d_plan((n, h, w, 64), wt.shape) == "x3"
     y = K.conv2d(dev(x), dev(wt), dev(b), act1=K.ACT_LRELU)
     assert tuple(y.shape) == (n, h, w, 32) and rel_err(host(y), oracle_conv(x, wt, b, act1=2)) <= TOL
-    assert float(y._shdr_range) == float(y.abs().max())
+    assert float(K._range_of(y)) == float(y.abs().max())
     xa, xb = f32(rng.normal(size=(n, h, w, 32))), f32(rng.normal(size=(n, h, w, 32)))
     assert K.conv2d_plan((n, h, w, 32), wt.shape, c2=32) == "x3"
     y2 = K.conv2d(dev(xa), dev(wt), dev(b), x2=dev(xb), act1=K.ACT_LRELU)
@@ -709,7 +734,7 @@ def test_conv2d_x3_residual_joins(shdr, monkeypatch):
         assert K.conv2d_plan((n, h, w, cin), wt.shape, has_residual=True) == "x3"
         y = K.conv2d(dev(x), dev(wt), None, scale=dev(sc), shift=dev(sh), residual=dev(res), act2=K.ACT_RELU)
         ref = np.maximum(oracle_conv(x, wt) * sc + sh + res[..., :cout], 0.0)
-        assert rel_err(host(y), ref) <= TOL and float(y._shdr_range) == float(y.abs().max())
+        assert rel_err(host(y), ref) <= TOL and float(K._range_of(y)) == float(y.abs().max())
         monkeypatch.setenv("SHDR_NO_X3_RESIDUAL", "1")
         assert K.conv2d_plan((n, h, w, cin), wt.shape, has_residual=True) != "x3"
         y_exact = K.conv2d(dev(x), dev(wt), None, scale=dev(sc), shift=dev(sh), residual=dev(res), act2=K.ACT_RELU)

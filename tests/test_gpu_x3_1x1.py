@@ -51,7 +51,7 @@ def _run(K, shape, tensors, act1=None):
         y = K.conv2d(xi, wt, b, stride=stride, x2=x2i, x2_scale=x2s, act1=K.ACT_RELU if act1 is None else act1, scale=sc, shift=sh, residual=res,
                      act2=K.ACT_LRELU if has_res else K.ACT_NONE)
     torch.cuda.synchronize()
-    slot = getattr(y, "_shdr_range", None)
+    slot = K._range_of(y)
     assert slot is not None
     return y.cpu(), slot.cpu().view(torch.int32).clone()
 

@@ -196,3 +196,40 @@ def test_bench_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path, monkey
     b, c = np.load(str(tmp_path / "b" / "big.npy")), np.load(str(tmp_path / "c" / "big.npy"))
     assert b.dtype == np.float32 and b.nbytes <= 4096 and np.array_equal(b, c)
     assert np.isin(b, big.numpy()).all()
+
+
+def test_range_record_is_read_only_while_it_describes_the_tensor(shdr):
+    """_ops "range slots" R1: a slot or host bound is read (and handed on) only at the version of the tensor it was recorded for.
+    CPU tensors: a constant slot is a host tensor, nothing is launched."""
+    K = shdr._ops
+    x = torch.rand(2, 4, 4, 3)
+    K.set_bound(x, 1.0)
+    assert K._bound_of(x) == 1.0 and float(K._range_of(x)) == 1.0
+    assert K._bound_of(K._carry_range(torch.empty(2, 4, 4, 3), x)) == 1.0
+    x.mul_(1000.0)                                  # max |x| is now far above the recorded bound
+    assert K._range_of(x) is None and K._bound_of(x) is None
+    stale = K._carry_range(torch.empty(2, 4, 4, 3), x)
+    assert K._range_of(stale) is None and K._bound_of(stale) is None
+    slot = torch.zeros(1)
+    K._set_range(x, slot)
+    assert K._range_of(x) is slot and K._bound_of(x) is None
+    assert K._range_of(K._carry_range(torch.empty(2, 4, 4, 3), x)) is slot
+    x.add_(1.0)
+    assert K._range_of(x) is None and K._range_of(K._carry_range(torch.empty(2, 4, 4, 3), x)) is None
+
+
+def test_range_record_keeps_no_infinite_bound(shdr):
+    """R2: a non-finite bound is no bound (the kernels would read it as "scale 1, measure nothing")"""
+    K = shdr._ops
+    for b in (float("inf"), float("nan")):
+        t = K.set_bound(torch.rand(3), b)
+        assert K._range_of(t) is None and K._bound_of(t) is None
+
+
+def test_range_slot_survives_fork_aliases(shdr):
+    K = shdr._ops
+    x = torch.rand(2, 4, 4, 8, requires_grad=True)
+    slot = torch.zeros(1)
+    K._set_range(x, slot)
+    aliases = K.fork(x, 3)
+    assert len(aliases) == 3 and all(t is not x and K._range_of(t) is slot for t in aliases)
