@@ -540,6 +540,28 @@ int shdr_hdr_window_means_f32(const float* arena, const int64_t* offsets, const 
 int shdr_hdr_patch_sample_f32(const float* arena, const int64_t* offsets, const int32_t* dims, const float* means,
                               const int32_t* params, int param_stride, int N, int n_files, int P, float* y, void* stream);
 
+/* ---- OpenEXR training files (exr.py; single-part scanline, NONE / RLE / ZIPS / ZIP, see csrc/exr.hip) -------------- */
+#define SHDR_EXR_HALF   1   /* OpenEXR pixel types (UINT = 0 is not a colour type here) */
+#define SHDR_EXR_FLOAT  2
+/* Host side: OpenEXR's signed-count RLE (a count byte c < 0 as int8: -c literal bytes follow; otherwise the next byte
+ * repeated c + 1 times) of `size` bytes -> `out`.  Returns the number of bytes written, or -1 (see shdr_last_error) when a
+ * run or literal overruns the input or `capacity`; never reads past `size` or writes past `capacity`.  The output is still
+ * interleaved and delta-coded (shdr_exr_unpredict_u8 undoes both). */
+int64_t shdr_exr_rle_decode(const uint8_t* data, int64_t size, uint8_t* out, int64_t capacity);
+/* Chunks [chunk_off[c], chunk_off[c + 1]) of `payload` (size bytes, c < n_chunks; chunk_off int64 [n_chunks + 1] and coded
+ * uint8 [n_chunks] on the device): coded chunks get the RLE / ZIP predictor and the byte interleave undone, the others are
+ * copied; `out` has the payload's layout.  One workgroup per chunk, deterministic.  Offsets are clamped into [0, size]. */
+int shdr_exr_unpredict_u8(const uint8_t* payload, uint8_t* out, int64_t size, const int64_t* chunk_off, const uint8_t* coded,
+                          int n_chunks, void* stream);
+/* Planar scanline bytes (size bytes; row r at chunk_off[r / lines] + (r % lines) * row_bytes, n_chunks = ceil(H0 / lines))
+ * -> float [H][W][3]: output channel i is the run at byte chan_off[i] of each scanline, of type chan_type[i]
+ * (SHDR_EXR_HALF / SHDR_EXR_FLOAT; chan_off and chan_type are 3-entry HOST arrays).  clip != 0 applies np.clip(x, 0, None)
+ * to the source samples (NaN and +inf pass).  Resized by the rule of shdr_hdr_load_resize_f32 with the same arithmetic;
+ * H == H0 and W == W0 is an exact copy.  Sample reads are clamped into the buffer. */
+int shdr_exr_load_resize_f32(const uint8_t* planes, int64_t size, const int64_t* chunk_off, int n_chunks, int lines,
+                             int64_t row_bytes, const int64_t* chan_off, const int32_t* chan_type, int H0, int W0, float* y,
+                             int H, int W, int clip, void* stream);
+
 /* ---- camera-pipeline simulator (joint_training.py:26-69 `_preprocessing`) ------------- */
 /* Philox4x32-10 block function (host): the counter-based generator the noise kernel uses; exported so that tests can
  * check the published known-answer vectors. */

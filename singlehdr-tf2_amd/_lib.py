@@ -47,6 +47,10 @@ SIGNATURES = {
     "shdr_hdr_load_resize_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "shdr_hdr_window_means_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "shdr_hdr_patch_sample_f32": (c_int, [c_ptr] * 5 + [c_int] * 4 + [c_ptr, c_ptr]),
+    "shdr_exr_rle_decode": (c_i64, [c_ptr, c_i64, c_ptr, c_i64]),
+    "shdr_exr_unpredict_u8": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr]),
+    "shdr_exr_load_resize_f32": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_int, c_i64, c_ptr, c_ptr, c_int, c_int, c_ptr, c_int, c_int,
+                                         c_int, c_ptr]),
     "shdr_philox4x32_10": (c_int, [c_ptr, c_ptr, c_ptr]),
     "shdr_camera_expose_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, ctypes.c_uint64, c_ptr]),
     "shdr_jpeg_round_trip_f32": (c_int, [c_ptr] * 6 + [c_int, c_int, c_int, c_ptr]),

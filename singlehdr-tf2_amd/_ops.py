@@ -1754,3 +1754,41 @@ def hdr_patch_sample(arena, offsets, dims, means, params, P):
     _lib.check(lib.shdr_hdr_patch_sample_f32(_ptr(arena), _ptr(offsets), _ptr(dims), _ptr(means), _ptr(params), params.shape[1], n,
                                              offsets.numel(), int(P), _ptr(y), _stream()), "shdr_hdr_patch_sample_f32")
     return y
+
+
+# ---------------------------------------------------------------------------
+# OpenEXR training files (exr.py), see csrc/exr.hip
+# ---------------------------------------------------------------------------
+def exr_unpredict(payload, offsets, coded):
+    """uint8 chunk bytes on the device (chunk c at [offsets[c], offsets[c + 1]), int64 [n + 1]) -> the scanline bytes: the
+    RLE / ZIP predictor and byte interleave undone where coded[c] (uint8 [n]) is set, copied elsewhere"""
+    lib = _lib.load()
+    payload = _chk(payload, "payload", torch.uint8)
+    offsets = _chk(offsets, "offsets", torch.int64)
+    coded = _chk(coded, "coded", torch.uint8)
+    n = coded.numel()
+    if payload.dim() != 1 or offsets.numel() != n + 1:
+        raise ValueError("exr_unpredict: expected payload [size], offsets [n_chunks + 1] and coded [n_chunks]")
+    out = torch.empty_like(payload)
+    _lib.check(lib.shdr_exr_unpredict_u8(_ptr(payload), _ptr(out), payload.numel(), _ptr(offsets), _ptr(coded), n, _stream()),
+               "shdr_exr_unpredict_u8")
+    return out
+
+
+def exr_load_resize(planes, offsets, lines, row_bytes, chan_off, chan_type, h0, w0, out, clip=False):
+    """planar OpenEXR scanlines on the device (of exr_unpredict) -> float32, cv2-linear resized into `out` [H, W, 3]; output
+    channel i is the run at byte chan_off[i] of each scanline, of type chan_type[i] (1 HALF, 2 FLOAT); clip: np.clip(x, 0, None)
+    before the resize"""
+    lib = _lib.load()
+    planes = _chk(planes, "planes", torch.uint8)
+    offsets = _chk(offsets, "offsets", torch.int64)
+    out = _chk(out, "out")
+    if planes.dim() != 1 or out.dim() != 3 or out.shape[2] != 3 or len(chan_off) != 3 or len(chan_type) != 3:
+        raise ValueError("exr_load_resize: expected planes [size], out [H, W, 3] and three channels")
+    h, w, _ = out.shape
+    off = (ctypes.c_int64 * 3)(*[int(v) for v in chan_off])
+    typ = (ctypes.c_int32 * 3)(*[int(v) for v in chan_type])
+    _lib.check(lib.shdr_exr_load_resize_f32(_ptr(planes), planes.numel(), _ptr(offsets), offsets.numel() - 1, int(lines),
+                                            int(row_bytes), off, typ, int(h0), int(w0), _ptr(out), h, w, int(bool(clip)),
+                                            _stream()), "shdr_exr_load_resize_f32")
+    return out

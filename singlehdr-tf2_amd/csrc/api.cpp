@@ -1,6 +1,7 @@
 // libshdr: error state and version (host only).
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "shdr_internal.h"
 
@@ -169,4 +170,39 @@ extern "C" int64_t shdr_rgbe_rle_decode(const uint8_t* data, int64_t size, int w
     }
   }
   return pos;
+}
+
+// OpenEXR's RLE (exr.py): a signed count byte c; c < 0 -> -c literal bytes follow, otherwise the next byte repeated c + 1
+// times.  Every read is checked against `size`, every write against `capacity`.  Host only.
+extern "C" int64_t shdr_exr_rle_decode(const uint8_t* data, int64_t size, uint8_t* out, int64_t capacity) {
+  if (!data || !out || size < 0 || capacity < 0) {
+    shdr::set_error("exr_rle_decode: bad arguments");
+    return -1;
+  }
+  int64_t pos = 0, w = 0;
+  while (pos < size) {
+    const int c = (int8_t)data[pos++];
+    if (c < 0) {                                          // -c literal bytes
+      const int64_t n = -c;
+      if (n > size - pos || n > capacity - w) {
+        shdr::set_error("exr_rle_decode: literal of %lld bytes at input byte %lld overruns the %s", (long long)n,
+                        (long long)pos - 1, n > size - pos ? "input" : "output");
+        return -1;
+      }
+      memcpy(out + w, data + pos, (size_t)n);
+      pos += n;
+      w += n;
+    } else {                                              // a run of c + 1 copies of the next byte
+      const int64_t n = (int64_t)c + 1;
+      if (pos >= size || n > capacity - w) {
+        shdr::set_error("exr_rle_decode: run of %lld bytes at input byte %lld overruns the %s", (long long)n, (long long)pos - 1,
+                        pos >= size ? "input" : "output");
+        return -1;
+      }
+      memset(out + w, data[pos], (size_t)n);
+      pos += 1;
+      w += n;
+    }
+  }
+  return w;
 }

@@ -11,44 +11,23 @@
 // fast path (a 2 x 2 average); the bilinear weights are then (0.5, 0.5), the same value up to the order of the sums.
 // Compiled with -ffp-contract=off: every product and sum is rounded where numpy / OpenCV round it.
 #include "shdr_internal.h"
+#include "linear_resize.h"
 
 namespace {
+
+using shdr::linear::Taps;
+using shdr::linear::bilinear3;
+using shdr::linear::linear_taps;
 
 constexpr int kWin = 512;          // PatchHDRDataset's crop side (dataset.py:216-219)
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// one axis of cv2's bilinear map: taps s0, s1 (inside [0, n)) and the weight of s1
-struct Taps {
-  int s0, s1;
-  float f;
-};
-
-__device__ __forceinline__ Taps linear_taps(int d, double scale, int n, bool clamp_weight) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (clamp_weight) {                              // horizontal rule: the edge tap takes the whole weight
-    if (s < 0) { s = 0; f = 0.0f; }
-    if (s >= n - 1) { s = n - 1; f = 0.0f; }
-  }
-  Taps t;
-  t.s0 = min(max(s, 0), n - 1);                    // vertical rule: clamp the rows, keep the weights
-  t.s1 = min(max(s + 1, 0), n - 1);
-  t.f = f;
-  return t;
-}
 
 // Ward's RGBE -> float, as hdr_io.rgbe_decode: byte * 2^(e - 136), e == 0 -> 0; channel c of the result is the file's 2 - c
 // (cv2.imread's BGR; the [:,:,::-1] and np.flip(hdr, -1) of dataset.py:183-184 cancel), clip(0, None) (:185) is the identity
 __device__ __forceinline__ float3 rgbe_bgr(uchar4 p) {
   const float sc = p.w == 0 ? 0.0f : ldexpf(1.0f, (int)p.w - 136);
   return make_float3((float)p.z * sc, (float)p.y * sc, (float)p.x * sc);
-}
-
-__device__ __forceinline__ float3 lerp3(float3 a, float3 b, float f) {
-  const float g = 1.0f - f;
-  return make_float3(a.x * g + b.x * f, a.y * g + b.y * f, a.z * g + b.z * f);
 }
 
 // (a) load: one thread per output pixel; the four taps are decoded from the RGBE bytes (4 B per source pixel read, no
@@ -58,12 +37,7 @@ __global__ __launch_bounds__(256) void hdr_load_resize_kernel(const uchar4* __re
   const long total = (long)H * W;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long)gridDim.x * 256) {
     const int oy = (int)(p / W), ox = (int)(p - (long)oy * W);
-    const Taps ty = linear_taps(oy, sy, H0, false), tx = linear_taps(ox, sx, W0, true);
-    const uchar4* r0 = src + (long)ty.s0 * W0;
-    const uchar4* r1 = src + (long)ty.s1 * W0;
-    const float3 h0 = lerp3(rgbe_bgr(r0[tx.s0]), rgbe_bgr(r0[tx.s1]), tx.f);
-    const float3 h1 = lerp3(rgbe_bgr(r1[tx.s0]), rgbe_bgr(r1[tx.s1]), tx.f);
-    const float3 v = lerp3(h0, h1, ty.f);
+    const float3 v = bilinear3(oy, ox, H0, W0, sy, sx, [&](int r, int c) { return rgbe_bgr(src[(long)r * W0 + c]); });
     y[3 * p] = v.x;
     y[3 * p + 1] = v.y;
     y[3 * p + 2] = v.z;

@@ -4,9 +4,11 @@
     reader = RandDatasetReader(get_train_dataset(hdr_dir), 32)
     hdr, crf, invcrf, t = reader.read_batch_data()                     # device tensors [b,256,256,3], [b,1024], [b,1024], [b]
 
-Each Radiance file is read once when the dataset is built: the RLE scanlines are decoded on the host (libshdr, a bounded
+Each file is read once when the dataset is built.  Radiance files: the RLE scanlines are decoded on the host (libshdr, a bounded
 thread pool), the RGBE bytes go to the device and one kernel decodes, reverses the channels to cv2's BGR and resizes the short
-side to 512 into a resident arena; a second computes the mean of every 512 x 512 crop.  A batch is then one launch of the
+side to 512 into a resident arena.  OpenEXR files (exr.py): the host inflates or run-length decodes the chunks in the same
+pool, the device undoes OpenEXR's byte predictor and one kernel converts HALF / FLOAT, clips at 0 (:185), orders the channels
+BGR and resizes into the same arena.  A second kernel computes the mean of every 512 x 512 crop.  A batch is then one launch of the
 patch sampler (csrc/dataset.hip): crop, normalise, resize to S x S, 256 crop, rot90 and the two flips of
 PatchHDRDataset.__getitem__ (dataset.py:212-252), for every sample at once.  The CRF / exposure tables (:19-54) are host
 numpy, built once.
@@ -27,7 +29,11 @@ Deliberate differences from the reference:
     distributions are the reference's.
   * RandDatasetReader(dataset, batch_size, seed=0, rank=0).read_batch_data() returns device tensors, not lists of numpy
     arrays, and starts no worker processes.  It is draw() followed by PatchHDRDataset.render() and the CRF / t gathers.
-  * Only Radiance files (FORMAT=32-bit_rle_rgbe, -Y h +X w) are read; OpenEXR raises ValueError.
+  * Radiance files (FORMAT=32-bit_rle_rgbe, -Y h +X w) and OpenEXR files are read, chosen by their magic bytes.  Of OpenEXR,
+    single-part scanline files with NO_COMPRESSION, RLE, ZIPS or ZIP compression and HALF / FLOAT R, G, B channels (exr.py);
+    PIZ, PXR24, B44(A), DWAA / DWAB, tiled, deep, multi-part and luminance / chroma files raise ValueError.  Alpha and other
+    extra channels are ignored: cv2.imread(path, IMREAD_UNCHANGED) would return 4 channels, which the reference's network
+    cannot take.  The file list without a .pkl is the sorted *.hdr and *.exr files.
 """
 import concurrent.futures
 import glob
@@ -41,9 +47,11 @@ import torch
 
 try:
     from . import _ops as K
+    from . import exr
     from . import hdr_io
 except ImportError:
     import _ops as K
+    import exr
     import hdr_io
 
 CURR_PATH_PREFIX = os.path.dirname(os.path.abspath(__file__))
@@ -194,6 +202,13 @@ def _load_pkl(name):
         return pickle.load(f)
 
 
+def _source_shape(item):
+    """(h, w) of an item of HDRDataset"""
+    if isinstance(item, exr.Payload):
+        return item.header.height, item.header.width
+    return item.shape[:2]
+
+
 def resized_shape(h, w):
     """HDRDataset._hdr_read_resize (:188-191): short side to 512 with Python's round()"""
     ratio = max(WINDOW / h, WINDOW / w)
@@ -252,7 +267,8 @@ class ParamSampler:
 
 
 class HDRDataset(Dataset):
-    """the file list; items are the RGBE bytes of each file (the pixels are converted on the device, see PatchHDRDataset)"""
+    """the file list; items are the RGBE bytes of a Radiance file or the exr.Payload of an OpenEXR one (the pixels are
+    converted on the device, see PatchHDRDataset)"""
 
     def __init__(self, hdr_prefix, hdr_posfix_list, is_training):
         self._hdr_prefix = hdr_prefix
@@ -263,7 +279,8 @@ class HDRDataset(Dataset):
         return os.path.join(self._hdr_prefix, self._hdr_posfix_list[idx])
 
     def __getitem__(self, idx):
-        return hdr_io.read_rgbe(self.path(idx))
+        path = self.path(idx)
+        return exr.read_payload(path) if exr.is_exr(path) else hdr_io.read_rgbe(path)
 
     def __len__(self):
         return len(self._hdr_posfix_list)
@@ -295,16 +312,20 @@ class PatchHDRDataset(Dataset):
         if n == 0:
             raise ValueError("PatchHDRDataset: empty file list")
         t0 = time.perf_counter()
-        with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_LOAD_THREADS, n)) as pool:     # ctypes drops the GIL
-            rgbe = list(pool.map(self._hdr_dataset.__getitem__, range(n)))
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_LOAD_THREADS, n)) as pool:     # ctypes, zlib drop the GIL
+            items = list(pool.map(self._hdr_dataset.__getitem__, range(n)))
         t1 = time.perf_counter()
-        shapes = [resized_shape(*r.shape[:2]) for r in rgbe]
+        shapes = [resized_shape(*_source_shape(r)) for r in items]
         sizes = [h * w * 3 for h, w in shapes]
         offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         self.arena = torch.empty(int(sum(sizes)), device=self.device, dtype=torch.float32)
-        for i, (r, (h, w)) in enumerate(zip(rgbe, shapes)):
-            src = torch.from_numpy(r).to(self.device)
-            K.hdr_load_resize(src, self.arena[offsets[i]:offsets[i] + sizes[i]].view(h, w, 3))
+        for i, (r, (h, w)) in enumerate(zip(items, shapes)):
+            out = self.arena[offsets[i]:offsets[i] + sizes[i]].view(h, w, 3)
+            if isinstance(r, exr.Payload):
+                planes, chunk_offsets = exr.upload(r, self.device)
+                exr.load_resize(r, planes, chunk_offsets, out, "BGR", clip=True)
+            else:
+                K.hdr_load_resize(torch.from_numpy(r).to(self.device), out)
         self.shapes = shapes
         self.offsets = torch.from_numpy(offsets).to(self.device)
         self.dims = torch.tensor(shapes, dtype=torch.int32).to(self.device)
@@ -359,9 +380,10 @@ def _posfix_list(hdr_prefix, posfix_list, pkl_name):
     if posfix_list is None:
         posfix_list = _load_pkl(pkl_name)
     if posfix_list is None:
-        posfix_list = sorted(os.path.relpath(p, hdr_prefix) for p in glob.glob(os.path.join(hdr_prefix, "*.hdr")))
+        posfix_list = sorted(os.path.relpath(p, hdr_prefix) for ext in ("*.hdr", "*.exr")
+                             for p in glob.glob(os.path.join(hdr_prefix, ext)))
         if not posfix_list:
-            raise FileNotFoundError("no %s.pkl next to %s and no *.hdr under %s" % (pkl_name, __file__, hdr_prefix))
+            raise FileNotFoundError("no %s.pkl next to %s and no *.hdr or *.exr under %s" % (pkl_name, __file__, hdr_prefix))
     return list(posfix_list)
 
 

@@ -1,0 +1,282 @@
+"""OpenEXR training files: the counterpart of hdr_io.read_rgbe / read_hdr for the HDR collections the reference reads with
+cv2.imread(path, cv2.IMREAD_UNCHANGED) (dataset.py:181-186).
+
+    hdr = read_exr("scene.exr")                  # float32 RGB [H, W, 3] on the device, the file's values (no clipping)
+
+Scope, restated from OpenEXR 2.x's published file layout (no OpenEXR library is used):
+  * magic 76 2f 31 01, version 2, single-part scanline images (the long-names flag 0x400 is allowed; tiled 0x200, deep 0x800
+    and multi-part 0x1000 files are refused);
+  * compression NO_COMPRESSION (0), RLE (1), ZIPS (2) and ZIP (3); PIZ, PXR24, B44, B44A, DWAA and DWAB are refused by name;
+  * channels R, G and B, each HALF or FLOAT; other channels (A, Z, ...) of any type are skipped but occupy their bytes; every
+    channel has x / y sampling 1;
+  * any dataWindow (the image is the data window, as in OpenCV's decoder), line order INCREASING_Y or DECREASING_Y.
+
+Layout: after the header comes a table of one uint64 file offset per chunk, indexed by increasing y whatever the line order.
+A chunk is int32 y (its first scanline), int32 size, then the data of 1 scanline (NONE, RLE, ZIPS) or 16 (ZIP; the last chunk
+may hold fewer).  A scanline holds, channel by channel in name-sorted order, `width` samples (HALF 2 bytes, FLOAT / UINT 4,
+little-endian).  RLE and ZIP(S) both interleave the chunk's bytes (even bytes first, then odd) and delta-code them
+(d[i] = t[i] - t[i-1] + 128) before compressing; a chunk whose stored size equals its decoded size is stored raw.
+
+Split of the work: the host reads and checks the bytes and inflates (zlib, which drops the GIL) or run-length decodes
+(libshdr's shdr_exr_rle_decode, via ctypes, which drops it too) every chunk; the device undoes the predictor and the
+interleave (shdr_exr_unpredict_u8) and converts / resizes straight from the planar scanlines (shdr_exr_load_resize_f32,
+csrc/exr.hip).  Every refusal is a ValueError naming the file and the reason.
+"""
+import collections
+import ctypes
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+try:
+    from . import _lib
+    from . import _ops as K
+except ImportError:
+    import _lib
+    import _ops as K
+
+MAGIC = b"\x76\x2f\x31\x01"
+UINT, HALF, FLOAT = 0, 1, 2
+SAMPLE_BYTES = {UINT: 4, HALF: 2, FLOAT: 4}
+NO_COMPRESSION, RLE_COMPRESSION, ZIPS_COMPRESSION, ZIP_COMPRESSION = 0, 1, 2, 3
+COMPRESSION_NAMES = ("NO_COMPRESSION", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB")
+LINES_PER_CHUNK = {NO_COMPRESSION: 1, RLE_COMPRESSION: 1, ZIPS_COMPRESSION: 1, ZIP_COMPRESSION: 16}
+INCREASING_Y, DECREASING_Y = 0, 1
+FLAG_TILED, FLAG_LONG_NAMES, FLAG_DEEP, FLAG_MULTIPART = 0x200, 0x400, 0x800, 0x1000
+MAX_SIDE = 1 << 20                 # a larger data window is refused as absurd
+MAX_PIXELS = 1 << 28
+
+Channel = collections.namedtuple("Channel", "name type offset")      # offset: byte offset of the channel's run in a scanline
+Header = collections.namedtuple("Header", "data_window width height channels compression line_order lines row_bytes n_chunks "
+                                          "table_offset")
+Payload = collections.namedtuple("Payload", "header data offsets coded")
+"""data: uint8 [offsets[-1]], the chunks in increasing-y order; offsets: int64 [n_chunks + 1], chunk c at
+data[offsets[c]:offsets[c + 1]] (min(lines, rows left) * row_bytes bytes); coded: uint8 [n_chunks], 1 where the predictor and
+the interleave are still to be undone (0 for raw chunks and NO_COMPRESSION)"""
+
+
+def is_exr(path):
+    with open(path, "rb") as f:
+        return f.read(4) == MAGIC
+
+
+def _fail(path, reason):
+    return ValueError("%s: %s" % (path, reason))
+
+
+def _cstr(data, pos, max_len, path, what):
+    end = data.find(b"\0", pos, pos + max_len + 1)
+    if end < 0:
+        raise _fail(path, "truncated header" if data.find(b"\0", pos) < 0 else "%s longer than %d bytes" % (what, max_len))
+    return data[pos:end], end + 1
+
+
+def _unpack(fmt, data, pos, path):
+    n = struct.calcsize(fmt)
+    if pos + n > len(data):
+        raise _fail(path, "truncated header")
+    return struct.unpack_from(fmt, data, pos)
+
+
+def _parse_chlist(value, path, max_name):
+    chans, pos = [], 0
+    while True:
+        if pos >= len(value):
+            raise _fail(path, "truncated channel list")
+        if value[pos] == 0:
+            break
+        name, pos = _cstr(value, pos, max_name, path, "channel name")
+        if pos + 16 > len(value):
+            raise _fail(path, "truncated channel list")
+        ptype, _, xs, ys = struct.unpack_from("<iB3xii", value, pos)
+        pos += 16
+        if ptype not in SAMPLE_BYTES:
+            raise _fail(path, "channel %r has unknown pixel type %d" % (name.decode("latin-1"), ptype))
+        if xs != 1 or ys != 1:
+            raise _fail(path, "channel %r has sampling %d x %d (only 1 is supported)" % (name.decode("latin-1"), xs, ys))
+        chans.append((name, ptype))
+    return chans
+
+
+def _parse_header(data, path):
+    if len(data) < 8:
+        raise _fail(path, "truncated header")
+    if data[:4] != MAGIC:
+        raise _fail(path, "not an OpenEXR file")
+    version, = struct.unpack_from("<I", data, 4)
+    if version & 0xFF != 2:
+        raise _fail(path, "OpenEXR version %d (only 2 is supported)" % (version & 0xFF))
+    for flag, what in ((FLAG_TILED, "tiled"), (FLAG_DEEP, "deep"), (FLAG_MULTIPART, "multi-part")):
+        if version & flag:
+            raise _fail(path, "%s OpenEXR files are not supported (single-part scanline only)" % what)
+    if version & ~0xFF & ~FLAG_LONG_NAMES:
+        raise _fail(path, "unknown version flags 0x%x" % (version & ~0xFF))
+    max_name = 255 if version & FLAG_LONG_NAMES else 31
+    attrs, pos = {}, 8
+    while True:
+        if pos >= len(data):
+            raise _fail(path, "truncated header")
+        if data[pos] == 0:
+            pos += 1
+            break
+        name, pos = _cstr(data, pos, max_name, path, "attribute name")
+        atype, pos = _cstr(data, pos, max_name, path, "attribute type")
+        size, = _unpack("<i", data, pos, path)
+        pos += 4
+        if size < 0 or pos + size > len(data):
+            raise _fail(path, "truncated header")
+        attrs[name] = (atype, data[pos:pos + size])
+        pos += size
+
+    def attr(name, atype, size=None):
+        if name not in attrs:
+            raise _fail(path, "missing header attribute %r" % name.decode())
+        t, v = attrs[name]
+        if t != atype or (size is not None and len(v) != size):
+            raise _fail(path, "header attribute %r has type %r, size %d" % (name.decode(), t.decode("latin-1"), len(v)))
+        return v
+
+    if b"type" in attrs and attrs[b"type"][1].rstrip(b"\0") != b"scanlineimage":
+        raise _fail(path, "part type %r is not supported (scanline images only)" % attrs[b"type"][1].decode("latin-1"))
+    comp = attr(b"compression", b"compression", 1)[0]
+    if comp not in LINES_PER_CHUNK:
+        name = COMPRESSION_NAMES[comp] if comp < len(COMPRESSION_NAMES) else "unknown (%d)" % comp
+        raise _fail(path, "%s compression is not supported (NO_COMPRESSION, RLE, ZIPS and ZIP are)" % name)
+    order = attr(b"lineOrder", b"lineOrder", 1)[0]
+    if order not in (INCREASING_Y, DECREASING_Y):
+        raise _fail(path, "line order %d is not supported (INCREASING_Y or DECREASING_Y)" % order)
+    xmin, ymin, xmax, ymax = struct.unpack("<iiii", attr(b"dataWindow", b"box2i", 16))
+    width, height = xmax - xmin + 1, ymax - ymin + 1
+    if width <= 0 or height <= 0 or width > MAX_SIDE or height > MAX_SIDE or width * height > MAX_PIXELS:
+        raise _fail(path, "data window (%d, %d) - (%d, %d) is empty or absurd" % (xmin, ymin, xmax, ymax))
+    chans = sorted(_parse_chlist(attr(b"channels", b"chlist"), path, max_name))     # the layout's order, whatever the list's
+    names = [n for n, _ in chans]
+    if len(set(names)) != len(names):
+        raise _fail(path, "duplicate channel names")
+    for need in (b"R", b"G", b"B"):
+        if need not in names:
+            raise _fail(path, "no %s channel (RGB images only; luminance / chroma files are not supported)" % need.decode())
+    channels, off = [], 0
+    for n, t in chans:
+        if n in (b"R", b"G", b"B") and t == UINT:
+            raise _fail(path, "channel %s is UINT (colour channels must be HALF or FLOAT)" % n.decode())
+        channels.append(Channel(n.decode("latin-1"), t, off))
+        off += SAMPLE_BYTES[t] * width
+    lines = LINES_PER_CHUNK[comp]
+    n_chunks = -(-height // lines)
+    if pos + 8 * n_chunks > len(data):
+        raise _fail(path, "truncated offset table")
+    return Header((xmin, ymin, xmax, ymax), width, height, tuple(channels), comp, order, lines, off, n_chunks, pos)
+
+
+def read_header(path):
+    """the data window, the channel list (name, type, byte offset in a scanline; layout order), compression, line order, lines
+    per chunk, scanline bytes and chunk count of an OpenEXR file; ValueError (naming the file) on anything out of scope"""
+    with open(path, "rb") as f:
+        data = f.read()
+    return _parse_header(data, path)
+
+
+def _rle_decode(src, size, dst, capacity):
+    lib = _lib.load()
+    n = lib.shdr_exr_rle_decode(ctypes.c_void_p(src), size, ctypes.c_void_p(dst), capacity)
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return n
+
+
+def rle_decode(data, capacity):
+    """OpenEXR RLE bytes -> the decoded bytes (at most `capacity`; libshdr host routine); ValueError on an overrun"""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.empty(max(int(capacity), 1), dtype=np.uint8)
+    n = _rle_decode(src.ctypes.data, src.size, out.ctypes.data, int(capacity))
+    return out[:n].tobytes()
+
+
+def read_payload(path):
+    """the file's chunks decoded on the host (inflated / run-length decoded, predictor and interleave NOT undone): a Payload"""
+    with open(path, "rb") as f:
+        data = f.read()
+    hdr = _parse_header(data, path)
+    n, lines, row_bytes = hdr.n_chunks, hdr.lines, hdr.row_bytes
+    table = np.frombuffer(data, dtype="<u8", count=n, offset=hdr.table_offset).astype(np.uint64)
+    table_end = hdr.table_offset + 8 * n
+    rows = np.minimum(lines, hdr.height - np.arange(n, dtype=np.int64) * lines)
+    offsets = np.concatenate([[0], np.cumsum(rows * row_bytes)]).astype(np.int64)
+    out = np.empty(int(offsets[-1]), dtype=np.uint8)
+    coded = np.zeros(n, dtype=np.uint8)
+    src = np.frombuffer(data, dtype=np.uint8)
+    ymin = hdr.data_window[1]
+    for c in range(n):
+        o = int(table[c])
+        if o < table_end or o > len(data) - 8:
+            raise _fail(path, "chunk %d: offset %d lies outside the file's chunk data" % (c, o))
+        y, size = struct.unpack_from("<ii", data, o)
+        if y != ymin + c * lines:
+            raise _fail(path, "chunk %d: y is %d, its table slot implies %d" % (c, y, ymin + c * lines))
+        if size < 0 or size > len(data) - o - 8:
+            raise _fail(path, "chunk %d: size %d runs past the end of the file" % (c, size))
+        lo, hi = int(offsets[c]), int(offsets[c + 1])
+        want = hi - lo
+        raw = src[o + 8:o + 8 + size]
+        if size == want:                                                 # stored raw (compression would not shrink it)
+            out[lo:hi] = raw
+            continue
+        if size > want or hdr.compression == NO_COMPRESSION:
+            raise _fail(path, "chunk %d: %d bytes stored, its %d scanlines hold %d" % (c, size, int(rows[c]), want))
+        if hdr.compression == RLE_COMPRESSION:
+            try:
+                got = _rle_decode(raw.ctypes.data, size, out[lo:hi].ctypes.data, want)
+            except ValueError as exc:
+                raise _fail(path, "chunk %d: %s" % (c, exc)) from None
+        else:
+            d = zlib.decompressobj()
+            try:
+                buf = d.decompress(data[o + 8:o + 8 + size], want + 1)
+            except zlib.error as exc:
+                raise _fail(path, "chunk %d: zlib error: %s" % (c, exc)) from None
+            if len(buf) == want and not d.eof:
+                raise _fail(path, "chunk %d: zlib error: incomplete or overlong stream" % c)
+            got = len(buf)
+            if got == want:
+                out[lo:hi] = np.frombuffer(buf, dtype=np.uint8)
+        if got != want:
+            raise _fail(path, "chunk %d: decodes to %s bytes, its %d scanlines hold %d" % (
+                c, got if got <= want else "more than %d" % want, int(rows[c]), want))
+        coded[c] = 1
+    return Payload(hdr, out, offsets, coded)
+
+
+def channel_table(header, order="RGB"):
+    """(byte offsets, types) of the channels named by `order` ("RGB", or "BGR" for the training arena)"""
+    by_name = {ch.name: ch for ch in header.channels}
+    return [by_name[c].offset for c in order], [by_name[c].type for c in order]
+
+
+def upload(payload, device):
+    """the payload on the device with the predictor undone: (planar scanline bytes, chunk offsets) as uint8 / int64 tensors"""
+    data = torch.from_numpy(payload.data).to(device)
+    offsets = torch.from_numpy(payload.offsets).to(device)
+    if not payload.coded.any():
+        return data, offsets
+    coded = torch.from_numpy(payload.coded).to(device)
+    return K.exr_unpredict(data, offsets, coded), offsets
+
+
+def load_resize(payload, planes, offsets, out, order="RGB", clip=False):
+    """the payload's image (of upload()) converted to float32 in channel order `order` and resized into out [H, W, 3]"""
+    hdr = payload.header
+    chan_off, chan_type = channel_table(hdr, order)
+    return K.exr_load_resize(planes, offsets, hdr.lines, hdr.row_bytes, chan_off, chan_type, hdr.height, hdr.width, out, clip)
+
+
+def read_exr(path, device=None):
+    """OpenEXR file -> float32 RGB [H, W, 3] on the device (the data window; the file's values, HALF converted exactly, no
+    clipping): the EXR counterpart of hdr_io.read_hdr"""
+    payload = read_payload(path)
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    planes, offsets = upload(payload, device)
+    out = torch.empty((payload.header.height, payload.header.width, 3), device=device, dtype=torch.float32)
+    return load_resize(payload, planes, offsets, out, "RGB", clip=False)
