@@ -598,6 +598,17 @@ int shdr_conv2d_pack_filter_f16(const float* w, void* wp, int KH, int KW, int C1
  * fp32 [N,Ho,Wo,cout_valid] when y_is_f32 (the 3-channel heads); scale / shift / residual / act2 of the desc are not used. */
 int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y,
                         int y_is_f32, void* stream);
+/* Inference form: y = act2(affine(act1(conv(concat[x1, x2], wp) + bias)) + residual), affine(v) = v * scale[co] + shift[co] -- the
+ * epilogue of shdr_conv2d_fwd_f32 on fp16 feature maps, accumulation and epilogue in fp32, one rounding to fp16.  Replaces, with
+ * training=False and the folded inference BatchNormalization: the conv -> BN -> relu of hallucination_net.py:163-165, the `up` blocks'
+ * conv -> relu -> BN -> relu (:86-89), the composed s1 -> conv2 -> norm2 -> relu tail (:179-185), the heads tanh(out(x)) + input
+ * (dequantization_net.py:62-63) and relu(input[..., 0:3] + out(x)) (refinement_net.py:63-66).
+ * scale / shift: fp32 per output channel or NULL (identity); residual: NULL, or fp32 (residual_is_f32) / fp16 [N,Ho,Wo,d->res_cstride]
+ * read at channel co; act2 = d->act2.  y as shdr_conv2d_fwd_f16 (fp16 [N,Ho,Wo,Cout], or fp32 [N,Ho,Wo,cout_valid]).  tanh (act1 or
+ * act2) on an fp16 output is refused (SHDR_E_SHAPE).  Without scale, shift, residual and act2 this IS shdr_conv2d_fwd_f16. */
+int shdr_conv2d_fwd_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                              const float* scale, const float* shift, const void* residual, int residual_is_f32, void* y, int y_is_f32,
+                              void* stream);
 /* dw[kh][kw][ci_off + ci][co] += scale * sum_p x[p + tap][ci] * dz[p][co]  (fp32, accumulated with atomics; the caller zeroes dw).
  * x = source `which` of the forward conv `d` (d->C1 / d->C2 = channels per pixel of the fp16 tensors, possibly zero-padded),
  * dz fp16 with dz_channels per pixel; dw = [KH,KW,c1_rows + c2_rows, d->Cout], of which the first cout_valid columns are written. */

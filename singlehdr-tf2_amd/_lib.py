@@ -159,6 +159,7 @@ SIGNATURES = {
     "shdr_conv2d_packed_filter_elems_f16": (c_i64, [c_int] * 5),
     "shdr_conv2d_pack_filter_f16": (c_int, [c_ptr, c_ptr] + [c_int] * 5 + [c_f32, c_ptr]),
     "shdr_conv2d_fwd_f16": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 5 + [c_int, c_ptr]),
+    "shdr_conv2d_fwd_fused_f16": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 7 + [c_int, c_ptr, c_int, c_ptr]),
     "shdr_conv2d_wgrad_f16": (c_int, [ctypes.POINTER(ConvDesc), c_ptr, c_int, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     "shdr_conv2d_patch_ok_f16": (c_int, [ctypes.POINTER(ConvDesc)]),
     "shdr_conv2d_fwd_patch_f16": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 5 + [c_int, c_ptr]),

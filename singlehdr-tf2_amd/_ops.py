@@ -233,13 +233,17 @@ def conv2d(x, w, bias=None, stride=1, x2=None, x2_scale=1.0, act1=ACT_NONE, scal
     that a narrow head runs on the MFMA tile); only the first `cout_valid` channels are stored.
     `pad=(top, left)` / `out_hw=(Ho, Wo)` override the SAME rule (used by the strided dgrad)."""
     if _is_h(x):
-        if scale is not None or shift is not None or residual is not None or act2 != ACT_NONE or pad is not None or out is not None \
-                or w_batch_stride or algo != ALGO_AUTO:
-            raise NotImplementedError("conv2d: the native-fp16 path takes bias + act1 only (training-mode layers)")
-        if _needs_grad(x, x2, w, bias):
+        fused = scale is not None or shift is not None or residual is not None or act2 != ACT_NONE
+        if pad is not None or out is not None or w_batch_stride or algo != ALGO_AUTO:
+            raise NotImplementedError("conv2d: the native-fp16 path takes no pad / out / w_batch_stride / algo")
+        if _needs_grad(x, x2, w, bias, scale, shift, residual):
+            if fused:
+                raise NotImplementedError("conv2d: the native-fp16 path takes bias + act1 only on a gradient tape (training-mode layers)")
             return AUTOGRAD.conv2d_h(x, w, bias, stride, x2, x2_scale, act1, cout_valid)
+        # tape-free: the inference epilogue (folded BatchNorm, residual, act2) fused into the fp16 kernels (shdr_conv2d_fwd_fused_f16)
         return conv2d_h(x, pack_filter_h(w, x.shape[3], 0 if x2 is None else x2.shape[3], x2_scale), bias, tuple(w.shape[:2]),
-                        w.shape[3], stride=stride, x2=x2, act1=act1, cout_valid=cout_valid)
+                        w.shape[3], stride=stride, x2=x2, act1=act1, cout_valid=cout_valid, scale=scale, shift=shift,
+                        residual=residual, act2=act2)
     if algo == ALGO_AUTO:
         algo = _AUTO_ALGO[PRECISION]
     fused = scale is not None or shift is not None or residual is not None or act2 != ACT_NONE
@@ -1424,9 +1428,15 @@ def _conv_desc_h(x_shape, c2, khw, cout_gemm, stride, cout_valid, pad=None, out_
     return d
 
 
-def conv2d_h(x, wp, bias, khw, cout_gemm, stride=1, x2=None, act1=ACT_NONE, cout_valid=None, pad=None, out_hw=None):
+FUSED_F16_CALLS = [0]           # convolutions run through shdr_conv2d_fwd_fused_f16 (diagnostic / tests: the fp16 inference path ran)
+
+
+def conv2d_h(x, wp, bias, khw, cout_gemm, stride=1, x2=None, act1=ACT_NONE, cout_valid=None, pad=None, out_hw=None, scale=None,
+             shift=None, residual=None, act2=ACT_NONE):
     """y = act1(conv(concat[x, x2], wp) + bias) on fp16 feature maps, `wp` from pack_filter_h.  The output is fp16
-    [N,Ho,Wo,cout_gemm], or fp32 [N,Ho,Wo,cout_valid] for a narrow head (cout_valid < cout_gemm: image-like tensors stay fp32)."""
+    [N,Ho,Wo,cout_gemm], or fp32 [N,Ho,Wo,cout_valid] for a narrow head (cout_valid < cout_gemm: image-like tensors stay fp32).
+    Inference epilogue (no gradient): y = act2(act1(...) * scale + shift + residual), scale / shift fp32 per output channel,
+    residual fp32 or fp16 [N,Ho,Wo,>= stored channels] -- one kernel (shdr_conv2d_fwd_fused_f16)."""
     lib = _lib.load()
     x = _chkh(_d(x), "x")
     c2 = 0
@@ -1441,8 +1451,25 @@ def conv2d_h(x, wp, bias, khw, cout_gemm, stride=1, x2=None, act1=ACT_NONE, cout
     if bias is not None and _chk(_d(bias), "bias").numel() < (cout_valid if head else cout_gemm):
         raise ValueError("conv2d_h: bias too short")
     y = torch.empty((x.shape[0], d.Ho, d.Wo, cout_valid if head else cout_gemm), device=x.device, dtype=torch.float32 if head else HALF)
-    _lib.check(lib.shdr_conv2d_fwd_f16(ctypes.byref(d), _ptr(x), _ptr(x2), _ptr(wp), _ptr(_d(bias)), _ptr(y), int(head), _stream()),
-               "shdr_conv2d_fwd_f16")
+    if scale is None and shift is None and residual is None and act2 == ACT_NONE:
+        _lib.check(lib.shdr_conv2d_fwd_f16(ctypes.byref(d), _ptr(x), _ptr(x2), _ptr(wp), _ptr(_d(bias)), _ptr(y), int(head), _stream()),
+                   "shdr_conv2d_fwd_f16")
+        return y
+    nch = y.shape[3]
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v is not None and _chk(_d(v), name).numel() < nch:
+            raise ValueError("conv2d_h: %s too short (%d < %d channels)" % (name, v.numel(), nch))
+    res = None
+    if residual is not None:
+        res = _chk(_d(residual), "residual", HALF if _is_h(residual) else torch.float32)
+        if tuple(res.shape[:3]) != (x.shape[0], d.Ho, d.Wo) or res.shape[3] < nch:
+            raise ValueError("conv2d_h: residual shape %s incompatible with output %s" % (tuple(res.shape), tuple(y.shape)))
+        d.res_cstride = res.shape[3]
+    d.act2 = act2
+    _lib.check(lib.shdr_conv2d_fwd_fused_f16(ctypes.byref(d), _ptr(x), _ptr(x2), _ptr(wp), _ptr(_d(bias)), _ptr(_d(scale)),
+                                             _ptr(_d(shift)), _ptr(res), int(res is not None and res.dtype == torch.float32), _ptr(y),
+                                             int(head), _stream()), "shdr_conv2d_fwd_fused_f16")
+    FUSED_F16_CALLS[0] += 1
     return y
 
 

@@ -15,7 +15,8 @@
 //   pipeline    KC chunks per stage, two stages in LDS: fragments of the whole stage -> registers, DMA of the next stage,
 //               MFMAs, one barrier per stage.
 //   epilogue    bias + activation in fp32 -> fp16 through LDS -> 16-byte row-contiguous stores; or fp32 output with
-//               cout_valid < Cout for the 3-channel heads (image-like tensors stay fp32).
+//               cout_valid < Cout for the 3-channel heads (image-like tensors stay fp32).  The FUSED instantiations add the
+//               inference epilogue of shdr_conv2d_fwd_fused_f16 (folded BatchNorm, residual, act2); the training ones do not see it.
 // The same kernel is the input gradient (dgrad): it runs on dZ with the flipped / transposed filter.
 // Replaces tf.keras.layers.Conv2D forward and GradientTape.gradient w.r.t. its input in finetune_real_dataset.py:144-178.
 #include <hip/hip_fp16.h>
@@ -47,6 +48,12 @@ struct ConvHArgs {
   int tiles_x, tiles_y, nblk_m, nblk_n;
   int act1, cout_valid;
 };
+// the inference instantiations (shdr_conv2d_fwd_fused_f16) take the fused epilogue on top; the training ones keep ConvHArgs
+struct ConvHFusedArgs : ConvHArgs {
+  shdr::FusedEpiF16 f;
+};
+template <bool FUSED>
+using ConvHArgsT = std::conditional_t<FUSED, ConvHFusedArgs, ConvHArgs>;
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
@@ -84,8 +91,8 @@ __global__ __launch_bounds__(256) void conv_pack_filter_f16_kernel(const float* 
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool FAST, int KC>
-__global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgs a) {
+template <int BM, int BN, int WM, int WN, bool FAST, int KC, bool FUSED>
+__global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED> a) {
   static_assert(WM * WN == 4, "4 waves per block");
   constexpr int TH = BM / 16;                      // pixel tile = TH rows x 16 columns
   constexpr int MT = BM / WM / 16, NT = BN / WN / 16;
@@ -258,6 +265,24 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgs a) {
       const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
       if (oh >= a.Ho || ow >= a.Wo) continue;
       const size_t pix = ((size_t)img * a.Ho + oh) * a.Wo + ow;
+      if constexpr (FUSED) {                                   // bias, act1 (tanh: the deq head), affine, residual, act2 per 4 couts
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) {
+          const int co = n0 + wn * NT * 16 + ni * 16 + 4 * fg;
+          if (co >= a.cout_valid) continue;
+          const int nv = a.cout_valid - co;
+          f32x4 v = acc[mi][ni];
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (a.bias && e < nv) v[e] += a.bias[co + e];
+          shdr::act_apply4<1>(v, a.act1);
+          shdr::fused_epi4_f16<1>(v, co, pix, nv, true, a.f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (e < nv) a.y32[pix * a.cout_valid + co + e] = v[e];
+        }
+        continue;
+      }
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
@@ -277,6 +302,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgs a) {
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
     const int r = wm * MT * 16 + mi * 16 + fi;
+    [[maybe_unused]] const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
 #pragma unroll
     for (int ni = 0; ni < NT; ++ni) {
       const int cl = wn * NT * 16 + ni * 16 + 4 * fg;
@@ -286,8 +312,16 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgs a) {
         v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
       }
       f16x4 h;
+      if constexpr (FUSED) {                                   // (no tanh on fp16 outputs here: shdr_conv2d_fwd_fused_f16 declines it)
+        shdr::act_apply4<0>(v, a.act1);
+        const bool in = oh < a.Ho && ow < a.Wo;
+        shdr::fused_epi4_f16<0>(v, n0 + cl, in ? ((size_t)img * a.Ho + oh) * a.Wo + ow : 0, 4, in, a.f);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) h[e] = (_Float16)shdr::act_apply(v[e], a.act1);
+        for (int e = 0; e < 4; ++e) h[e] = (_Float16)v[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = (_Float16)shdr::act_apply(v[e], a.act1);
+      }
       *reinterpret_cast<f16x4*>(stage + r * RS + cl) = h;
     }
   }
@@ -303,8 +337,9 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgs a) {
   }
 }
 
-template <int BM, int BN, int WM, int WN, bool FAST, int KC>
-int launch_f16(ConvHArgs& a, hipStream_t st) {
+template <int BM, int BN, int WM, int WN, bool FAST, int KC, class A>
+int launch_f16(A& a, hipStream_t st) {
+  constexpr bool FUSED = std::is_same_v<A, ConvHFusedArgs>;
   constexpr int TH = BM / 16;
   a.tiles_x = (a.Wo + 15) / 16;
   a.tiles_y = (a.Ho + TH - 1) / TH;
@@ -315,19 +350,19 @@ int launch_f16(ConvHArgs& a, hipStream_t st) {
   static bool attr_done[shdr::kMaxDevices] = {};
   const int dev_slot = shdr::device_slot();
   if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, WM, WN, FAST, KC>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, WM, WN, FAST, KC, FUSED>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     attr_done[dev_slot] = true;
   }
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk <= 0 || nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_f16: grid of %ld blocks", nblk);
-  hipLaunchKernelGGL((conv_f16_kernel<BM, BN, WM, WN, FAST, KC>), dim3((unsigned)nblk), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv_f16_kernel<BM, BN, WM, WN, FAST, KC, FUSED>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return shdr::check_launch("conv_f16_kernel");
 }
 
-template <int BM, int BN, int WM, int WN>
-int launch_f16_k(ConvHArgs& a, hipStream_t st) {
+template <int BM, int BN, int WM, int WN, class A>
+int launch_f16_k(A& a, hipStream_t st) {
   // two chunks per stage unless the layer has a single chunk per tap-walk that short (1x1 layers with 32 channels)
   if (a.fast) return a.nchunks >= 2 ? launch_f16<BM, BN, WM, WN, true, 2>(a, st) : launch_f16<BM, BN, WM, WN, true, 1>(a, st);
   return a.nchunks >= 2 ? launch_f16<BM, BN, WM, WN, false, 2>(a, st) : launch_f16<BM, BN, WM, WN, false, 1>(a, st);
@@ -340,6 +375,15 @@ extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* 
 extern "C" int shdr_conv2d_w3_ok_f16(const shdr_conv2d_desc* d);
 extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y,
                                       void* stream);
+
+// the fused inference forms of the two specialised kernels (shdr_conv2d_fwd_fused_f16 dispatches to them when their predicate takes
+// every fused option of the call; the general kernel runs the layer otherwise)
+extern "C" int shdr_conv2d_patch_fused_ok_f16(const shdr_conv2d_desc* d, int y_is_f32);
+extern "C" int shdr_conv2d_fwd_patch_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                               const shdr::FusedEpiF16* f, void* y, void* stream);
+extern "C" int shdr_conv2d_w3_fused_ok_f16(const shdr_conv2d_desc* d, int has_residual);
+extern "C" int shdr_conv2d_fwd_w3_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                            const shdr::FusedEpiF16* f, void* y, void* stream);
 
 inline bool f16_fast(int C1, int C2) { return ((C1 + C2) % 32 == 0) && (C2 == 0 || C1 % 32 == 0); }
 inline int f16_nchunks(int ntaps, int C1, int C2) {
@@ -366,8 +410,10 @@ extern "C" int shdr_conv2d_pack_filter_f16(const float* w, void* wp, int KH, int
   return shdr::check_launch("conv_pack_filter_f16");
 }
 
-extern "C" int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
-                                   void* y, int y_is_f32, void* stream) {
+namespace {
+// the checks and kernel arguments shared by shdr_conv2d_fwd_f16 and shdr_conv2d_fwd_fused_f16
+int f16_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, int y_is_f32,
+              ConvHArgs& a) {
   SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_f16: null desc/x1/wp/y");
   SHDR_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C1 > 0 && d->C2 >= 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 &&
                    d->stride > 0 && d->Ho > 0 && d->Wo > 0,
@@ -388,7 +434,7 @@ extern "C" int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, co
   SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) &&
                    (!bias || shdr::aligned16(bias)),
                SHDR_E_ALIGN, "conv2d_f16: tensors must be 16-byte aligned");
-  ConvHArgs a{};
+  a = ConvHArgs{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2);
   a.wp = reinterpret_cast<const _Float16*>(wp);
@@ -404,12 +450,52 @@ extern "C" int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, co
   a.nchunks = f16_nchunks(a.ntaps, a.C1, a.C2);
   a.act1 = d->act1;
   a.cout_valid = cout_valid;
+  return SHDR_OK;
+}
+}  // namespace
+
+extern "C" int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                   void* y, int y_is_f32, void* stream) {
+  ConvHArgs a;
+  if (int e = f16_setup(d, x1, x2, wp, bias, y, y_is_f32, a)) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // narrow full-resolution layers (<= 32 channels per tap, 16 / 32 couts): raw patch + resident filter in LDS (conv_f16_patch.hip)
   if (shdr_conv2d_patch_ok_f16(d) && (y_is_f32 || d->act1 != SHDR_ACT_TANH) && SHDR_ENV("SHDR_NO_PATCH") == nullptr)
     return shdr_conv2d_fwd_patch_f16(d, x1, x2, wp, bias, y, y_is_f32, stream);
   // wide 3x3 layers: raw patch per 32-channel chunk instead of nine im2col stagings (conv_f16_w3.hip)
   if (!y_is_f32 && shdr_conv2d_w3_ok_f16(d) && SHDR_ENV("SHDR_NO_W3") == nullptr) return shdr_conv2d_fwd_w3_f16(d, x1, x2, wp, bias, y, stream);
+  if (a.Cout % 128 == 0) return launch_f16_k<128, 128, 2, 2>(a, st);
+  if (a.Cout % 64 == 0) return launch_f16_k<256, 64, 4, 1>(a, st);
+  if (a.Cout % 32 == 0) return launch_f16_k<256, 32, 4, 1>(a, st);
+  return launch_f16_k<256, 16, 4, 1>(a, st);
+}
+
+extern "C" int shdr_conv2d_fwd_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                         const float* scale, const float* shift, const void* residual, int residual_is_f32, void* y,
+                                         int y_is_f32, void* stream) {
+  if (!scale && !shift && !residual && (!d || d->act2 == SHDR_ACT_NONE))      // nothing fused: the training entry, unchanged
+    return shdr_conv2d_fwd_f16(d, x1, x2, wp, bias, y, y_is_f32, stream);
+  ConvHFusedArgs a;
+  if (int e = f16_setup(d, x1, x2, wp, bias, y, y_is_f32, a)) return e;
+  SHDR_REQUIRE(y_is_f32 || (d->act1 != SHDR_ACT_TANH && d->act2 != SHDR_ACT_TANH), SHDR_E_SHAPE,
+               "conv2d_fused_f16: tanh is compiled into the fp32-output (head) epilogue only");
+  const int nch = y_is_f32 ? a.cout_valid : d->Cout;           // channels the epilogue computes per pixel
+  SHDR_REQUIRE(!residual || d->res_cstride >= nch, SHDR_E_SHAPE, "conv2d_fused_f16: res_cstride %d < %d output channels",
+               d->res_cstride, nch);
+  SHDR_REQUIRE(!residual || (long)d->N * d->Ho * d->Wo * d->res_cstride < (1L << 32), SHDR_E_SHAPE,
+               "conv2d_fused_f16: residual with more than 2^32 elements");
+  a.f.scale = scale;
+  a.f.shift = shift;
+  a.f.res = residual;
+  a.f.res_f32 = residual_is_f32 ? 1 : 0;
+  a.f.res_cstride = residual ? d->res_cstride : 0;
+  a.f.act2 = d->act2;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // the same kernel families as shdr_conv2d_fwd_f16, each only where its fused form takes every option of the call
+  if (shdr_conv2d_patch_fused_ok_f16(d, y_is_f32) && SHDR_ENV("SHDR_NO_PATCH") == nullptr)
+    return shdr_conv2d_fwd_patch_fused_f16(d, x1, x2, wp, bias, &a.f, y, stream);
+  if (!y_is_f32 && shdr_conv2d_w3_fused_ok_f16(d, residual != nullptr) && SHDR_ENV("SHDR_NO_W3") == nullptr)
+    return shdr_conv2d_fwd_w3_fused_f16(d, x1, x2, wp, bias, &a.f, y, stream);
   if (a.Cout % 128 == 0) return launch_f16_k<128, 128, 2, 2>(a, st);
   if (a.Cout % 64 == 0) return launch_f16_k<256, 64, 4, 1>(a, st);
   if (a.Cout % 32 == 0) return launch_f16_k<256, 32, 4, 1>(a, st);

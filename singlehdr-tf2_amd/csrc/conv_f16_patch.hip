@@ -11,6 +11,8 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "shdr_internal.h"
 
 namespace {
@@ -32,6 +34,12 @@ struct PatchArgs {
   float* y32;
   int N, H, W, Cout, tiles_x, tiles_y, ntiles, act1, cout_valid;
 };
+// the inference instantiations (fp32 heads with the fused epilogue: shdr_conv2d_fwd_patch_fused_f16); the training ones keep PatchArgs
+struct PatchFusedArgs : PatchArgs {
+  shdr::FusedEpiF16 f;
+};
+template <bool FUSED>
+using PatchArgsT = std::conditional_t<FUSED, PatchFusedArgs, PatchArgs>;
 
 __host__ __device__ inline int pswz(int row) { return (-(row >> 2)) & 3; }
 
@@ -54,8 +62,8 @@ struct PG {
   static constexpr int LDS_HALVES = FILT_HALVES + 2 * PATCH_HALVES > STAGE_HALVES ? FILT_HALVES + 2 * PATCH_HALVES : STAGE_HALVES;
 };
 
-template <int KK, int CT, int NT, bool TWO>
-__global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgs a) {
+template <int KK, int CT, int NT, bool TWO, bool FUSED>
+__global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FUSED> a) {
   using G = PG<KK, CT, NT, TWO>;
   constexpr int MT = 4;                                        // wave w owns tile rows 4w .. 4w+3
   constexpr int PAD = (KK - 1) / 2;
@@ -209,12 +217,13 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgs a) 
       for (int ni = 0; ni < NT; ++ni) {
         const int co = ni * 16 + 4 * fg;
         f32x4 v = acc[mi][ni];
-        if (a.y32) {                                             // the fp32 heads (tanh lives here only: shdr_internal.h act_apply4)
+        if (FUSED || a.y32) {                                    // the fp32 heads (tanh lives here only: shdr_internal.h act_apply4)
           if (co >= a.cout_valid) continue;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (a.bias && co + e < a.cout_valid) v[e] += a.bias[co + e];
           shdr::act_apply4<1>(v, a.act1);
+          if constexpr (FUSED) shdr::fused_epi4_f16<1>(v, co, pix, a.cout_valid - co, true, a.f);   // affine, residual, act2
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             if (co + e < a.cout_valid) a.y32[pix * a.cout_valid + co + e] = v[e];
@@ -233,9 +242,10 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgs a) 
   }
 }
 
-template <int KK, int CT, int NT, bool TWO>
-int launch_patch(PatchArgs& a, hipStream_t st) {
+template <int KK, int CT, int NT, bool TWO, class A>
+int launch_patch(A& a, hipStream_t st) {
   using G = PG<KK, CT, NT, TWO>;
+  constexpr bool FUSED = std::is_same_v<A, PatchFusedArgs>;
   constexpr int lds = G::LDS_HALVES * 2;
   if constexpr (lds > 160 * 1024) {
     return shdr::fail(SHDR_E_SHAPE, "conv2d_patch_f16: filter + patches (%d bytes) do not fit the LDS", lds);
@@ -244,23 +254,23 @@ int launch_patch(PatchArgs& a, hipStream_t st) {
   static bool attr_done[shdr::kMaxDevices] = {};
   static int occ[shdr::kMaxDevices] = {};
   if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO>), 256, lds);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>), 256, lds);
     occ[dev_slot] = (e != hipSuccess || nb < 1) ? 1 : (nb > 4 ? 4 : nb);
     attr_done[dev_slot] = true;
   }
   long grid = 256L * occ[dev_slot];
   if (grid > a.ntiles) grid = a.ntiles;
-  hipLaunchKernelGGL((conv_f16_patch_kernel<KK, CT, NT, TWO>), dim3((unsigned)grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>), dim3((unsigned)grid), dim3(256), lds, st, a);
   return shdr::check_launch("conv_f16_patch_kernel");
   }
 }
 
-template <int KK, int NT>
-int dispatch_ct(PatchArgs& a, int C1, int C2, hipStream_t st) {
+template <int KK, int NT, class A>
+int dispatch_ct(A& a, int C1, int C2, hipStream_t st) {
   if (C2 == 16 && C1 == 16) return launch_patch<KK, 32, NT, true>(a, st);
   if (C1 == 8) return launch_patch<KK, 8, NT, false>(a, st);
   if (C1 == 16) return launch_patch<KK, 16, NT, false>(a, st);
@@ -282,8 +292,10 @@ extern "C" int shdr_conv2d_patch_ok_f16(const shdr_conv2d_desc* d) {
   return filt + 2 * patch <= 150 * 1024 ? 1 : 0;
 }
 
-extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
-                                         void* y, int y_is_f32, void* stream) {
+namespace {
+// the checks and kernel arguments shared by shdr_conv2d_fwd_patch_f16 and shdr_conv2d_fwd_patch_fused_f16
+int patch_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, int y_is_f32,
+                PatchArgs& a) {
   SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_patch_f16: null desc/x1/wp/y");
   SHDR_REQUIRE(shdr_conv2d_patch_ok_f16(d), SHDR_E_SHAPE, "conv2d_patch_f16: layer shape not taken by the patch kernel");
   SHDR_REQUIRE(y_is_f32 || d->act1 != SHDR_ACT_TANH, SHDR_E_SHAPE, "conv2d_patch_f16: tanh is compiled into the fp32-output (head) path only");
@@ -293,7 +305,7 @@ extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* 
   SHDR_REQUIRE((long)d->N * d->H * d->W * 32 < (1L << 32), SHDR_E_SHAPE, "conv2d_patch_f16: tensor too large");
   SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) && (!bias || shdr::aligned16(bias)),
                SHDR_E_ALIGN, "conv2d_patch_f16: tensors must be 16-byte aligned");
-  PatchArgs a{};
+  a = PatchArgs{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2);
   a.wp = reinterpret_cast<const _Float16*>(wp);
@@ -306,6 +318,14 @@ extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* 
   a.ntiles = a.N * a.tiles_x * a.tiles_y;
   a.act1 = d->act1;
   a.cout_valid = cout_valid;
+  return SHDR_OK;
+}
+}  // namespace
+
+extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                         void* y, int y_is_f32, void* stream) {
+  PatchArgs a;
+  if (int e = patch_setup(d, x1, x2, wp, bias, y, y_is_f32, a)) return e;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->Cout == 16) {
     if (d->KH == 3) return dispatch_ct<3, 1>(a, d->C1, d->C2, st);
@@ -315,4 +335,21 @@ extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* 
   if (d->KH == 3) return dispatch_ct<3, 2>(a, d->C1, d->C2, st);
   if (d->KH == 5) return dispatch_ct<5, 2>(a, d->C1, d->C2, st);
   return dispatch_ct<7, 2>(a, d->C1, d->C2, st);
+}
+
+// the fused inference epilogue (shdr_conv2d_fwd_fused_f16) is compiled for the 3x3 heads only: fp32 output, 16 couts of which the first
+// cout_valid are stored -- the deq / ref heads (dequantization_net.py:62-63, refinement_net.py:63-66); every other layer with fused options
+// goes to the general kernel
+extern "C" int shdr_conv2d_patch_fused_ok_f16(const shdr_conv2d_desc* d, int y_is_f32) {
+  return y_is_f32 && d && d->Cout == 16 && d->KH == 3 && shdr_conv2d_patch_ok_f16(d) ? 1 : 0;
+}
+
+extern "C" int shdr_conv2d_fwd_patch_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                               const shdr::FusedEpiF16* f, void* y, void* stream) {
+  SHDR_REQUIRE(f, SHDR_E_NULL, "conv2d_patch_fused_f16: null epilogue");
+  SHDR_REQUIRE(shdr_conv2d_patch_fused_ok_f16(d, 1), SHDR_E_SHAPE, "conv2d_patch_fused_f16: layer not taken by the fused head kernel");
+  PatchFusedArgs a;
+  if (int e = patch_setup(d, x1, x2, wp, bias, y, 1, a)) return e;
+  a.f = *f;
+  return dispatch_ct<3, 1>(a, d->C1, d->C2, reinterpret_cast<hipStream_t>(stream));
 }

@@ -10,6 +10,8 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "shdr_internal.h"
 
 namespace {
@@ -30,6 +32,12 @@ struct W3Args {
   _Float16* y;
   int N, H, W, C1, C2, Cout, tiles_x, tiles_y, nblk_m, nblk_n, act1;
 };
+// the inference instantiation (folded BatchNorm + second activation: shdr_conv2d_fwd_w3_fused_f16); the training one keeps W3Args
+struct W3FusedArgs : W3Args {
+  shdr::FusedEpiF16 f;
+};
+template <bool FUSED>
+using W3ArgsT = std::conditional_t<FUSED, W3FusedArgs, W3Args>;
 
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
@@ -50,7 +58,8 @@ constexpr int FJ = 3;                                          // filter DMA ins
 constexpr int FILT_HALVES = 3 * BN * 32;
 constexpr int W3_LDS_BYTES = (2 * PATCH_HALVES + 2 * FILT_HALVES) * 2;
 
-__global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3Args a) {
+template <bool FUSED>
+__global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED> a) {
   extern __shared__ __attribute__((aligned(16))) _Float16 wsm[];
   _Float16* patch = wsm;                                       // [2][PATCH_HALVES]
   _Float16* filt = wsm + 2 * PATCH_HALVES;                     // [2][FILT_HALVES]
@@ -170,6 +179,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3Args a) {
         v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
       }
       shdr::act_apply4<0>(v, a.act1);                      // (no tanh here: shdr_conv2d_w3_ok_f16; shdr_internal.h act_apply4)
+      if constexpr (FUSED) shdr::fused_epi4_f16<0>(v, n0 + cl, 0, 4, false, a.f);   // affine, act2 (no residual: w3_fused_ok)
       f16x4 h;
 #pragma unroll
       for (int e = 0; e < 4; ++e) h[e] = (_Float16)v[e];
@@ -202,15 +212,16 @@ extern "C" int shdr_conv2d_w3_ok_f16(const shdr_conv2d_desc* d) {
   return blocks >= min_blocks ? 1 : 0;
 }
 
-extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y,
-                                      void* stream) {
+namespace {
+// the checks and kernel arguments shared by shdr_conv2d_fwd_w3_f16 and shdr_conv2d_fwd_w3_fused_f16
+int w3_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, W3Args& a) {
   SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_w3_f16: null desc/x1/wp/y");
   SHDR_REQUIRE(shdr_conv2d_w3_ok_f16(d), SHDR_E_SHAPE, "conv2d_w3_f16: layer shape not taken by this kernel");
   SHDR_REQUIRE((d->C2 == 0) == (x2 == nullptr), SHDR_E_NULL, "conv2d_w3_f16: x2 must be given iff C2 > 0");
   SHDR_REQUIRE((long)d->N * d->H * d->W * (d->C1 > d->C2 ? d->C1 : d->C2) < (1L << 32), SHDR_E_SHAPE, "conv2d_w3_f16: tensor too large");
   SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) && (!bias || shdr::aligned16(bias)),
                SHDR_E_ALIGN, "conv2d_w3_f16: tensors must be 16-byte aligned");
-  W3Args a{};
+  a = W3Args{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2 ? x2 : x1);
   a.wp = reinterpret_cast<const _Float16*>(wp);
@@ -222,15 +233,44 @@ extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1,
   a.nblk_m = a.N * a.tiles_x * a.tiles_y;
   a.nblk_n = a.Cout / 64;
   a.act1 = d->act1;
+  return SHDR_OK;
+}
+
+template <bool FUSED>
+int w3_launch(const W3ArgsT<FUSED>& a, hipStream_t st) {
   static bool attr_done[shdr::kMaxDevices] = {};
   const int dev_slot = shdr::device_slot();
   if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_w3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_w3_kernel<FUSED>), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
     if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     attr_done[dev_slot] = true;
   }
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_w3_f16: grid of %ld blocks", nblk);
-  hipLaunchKernelGGL(conv_f16_w3_kernel, dim3((unsigned)nblk), dim3(256), W3_LDS_BYTES, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(conv_f16_w3_kernel<FUSED>, dim3((unsigned)nblk), dim3(256), W3_LDS_BYTES, st, a);
   return shdr::check_launch("conv_f16_w3_kernel");
+}
+}  // namespace
+
+extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y,
+                                      void* stream) {
+  W3Args a;
+  if (int e = w3_setup(d, x1, x2, wp, bias, y, a)) return e;
+  return w3_launch<false>(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the fused form takes the folded BatchNorm (scale / shift) and act2 of the Hallucination-Net's `up` blocks (hallucination_net.py:86-89); a
+// residual is declined (the general kernel takes it)
+extern "C" int shdr_conv2d_w3_fused_ok_f16(const shdr_conv2d_desc* d, int has_residual) {
+  return !has_residual && d && d->act2 != SHDR_ACT_TANH && shdr_conv2d_w3_ok_f16(d) ? 1 : 0;
+}
+
+extern "C" int shdr_conv2d_fwd_w3_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
+                                            const shdr::FusedEpiF16* f, void* y, void* stream) {
+  SHDR_REQUIRE(f, SHDR_E_NULL, "conv2d_w3_fused_f16: null epilogue");
+  SHDR_REQUIRE(shdr_conv2d_w3_fused_ok_f16(d, f->res != nullptr), SHDR_E_SHAPE, "conv2d_w3_fused_f16: layer or option not taken by this kernel");
+  W3FusedArgs a;
+  if (int e = w3_setup(d, x1, x2, wp, bias, y, a)) return e;
+  a.f = *f;
+  return w3_launch<true>(a, reinterpret_cast<hipStream_t>(stream));
 }

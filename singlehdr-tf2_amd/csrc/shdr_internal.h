@@ -186,4 +186,31 @@ __device__ __forceinline__ void act_apply4(V4& v, int act) {
   }
 }
 
+// The fused inference epilogue of the fp16 forward kernels (shdr_conv2d_fwd_fused_f16), applied after bias + act1:
+//   v = act2(v * scale[co] + shift[co] + residual[pix * res_cstride + co])    (scale / shift / residual NULL -> skipped)
+// Compiled only into the FUSED instantiations of conv_f16.hip, conv_f16_patch.hip and conv_f16_w3.hip: the training instantiations
+// never see it.  Four consecutive couts co .. co + 3 of one output pixel; only the first nvalid of them exist (the 3-channel heads),
+// and the residual is read only where res_ok (a pixel inside the output).
+struct FusedEpiF16 {
+  const float* scale;
+  const float* shift;
+  const void* res;         // fp32 or fp16 [N, Ho, Wo, res_cstride]
+  int res_f32, res_cstride, act2;
+};
+
+template <int TANH, class V4>
+__device__ __forceinline__ void fused_epi4_f16(V4& v, int co, size_t pix, int nvalid, bool res_ok, const FusedEpiF16& f) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e >= nvalid) break;
+    if (f.scale) v[e] *= f.scale[co + e];
+    if (f.shift) v[e] += f.shift[co + e];
+    if (f.res && res_ok) {
+      const size_t i = pix * (size_t)f.res_cstride + (size_t)(co + e);
+      v[e] += f.res_f32 ? static_cast<const float*>(f.res)[i] : (float)static_cast<const _Float16*>(f.res)[i];
+    }
+  }
+  act_apply4<TANH>(v, f.act2);
+}
+
 }  // namespace shdr

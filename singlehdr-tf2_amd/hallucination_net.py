@@ -126,8 +126,10 @@ class model(Layer):
         input_layer, il = K.fork(input_layer)        # the 3-channel BGR image of the last skip layer and the padded encoder input
         bgr = K.vgg_preprocess(input_layer)          # x*255, RGB->BGR, - mean  (:149-153)
         tail, d1_projected = None, False
-        if K.native_fp16() and train:                # BASELINE configs[4]: fp16 feature maps (16 channels: the input gradient of
-            x, d1 = self.d1(K.vgg_preprocess(il, 16, K.HALF))    # the first conv runs on the 16-channel MFMA tile)
+        # native fp16 for fine-tuning (BASELINE configs[4]) and for tape-free inference (the folded BatchNorm, the `up` blocks and the
+        # composed tail run as fused fp16 epilogues: shdr_conv2d_fwd_fused_f16); inference on a tape (frozen statistics) stays fp32
+        if K.native_fp16() and (train or not taping(input_layer, self.conv1.kernel, self.norm1.gamma)):
+            x, d1 = self.d1(K.vgg_preprocess(il, 16, K.HALF))    # fp16 feature maps, 16 channels: the 16-channel MFMA tile
         else:
             # tape-free fp32 inference: the tail (below) uses d1's skip tensor only through a 64 -> 3 linear map, formed in the epilogue
             # of d1.conv2 where its planned kernel can do that -- the 64-channel full-resolution skip tensor is then never written

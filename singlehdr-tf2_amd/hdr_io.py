@@ -107,7 +107,9 @@ def rgbe_decode(rgbe):
 
 
 class HdrReconstructor:
-    """LDR file -> HDR file with the reference tool's geometry (resize to 64x, 32-pixel symmetric pad, crop, resize back)."""
+    """LDR file -> HDR file with the reference tool's geometry (resize to 64x, 32-pixel symmetric pad, crop, resize back).
+    `inference` is any `pipeline.Inference` / `GraphedInference`, e.g. `Inference(deq, lin, hal, ref, precision="fp16")` for the
+    native-fp16 inference mode."""
 
     def __init__(self, inference, padding=PADDING, multiple=MULTIPLE):
         self.inference, self.padding, self.multiple = inference, padding, multiple

@@ -17,18 +17,32 @@ except ImportError:
 THRESHOLD = 0.12  # test_real_refinement.py:28
 
 
-class Inference:
-    """Callable equivalent of the reference's `inference(ldr)` tf.function."""
+PRECISIONS = ("fp32", "fp16")
 
-    def __init__(self, deq, lin, hal, ref=None, threshold=THRESHOLD, streams=1):
+
+class Inference:
+    """Callable equivalent of the reference's `inference(ldr)` tf.function.
+
+    precision="fp32" (default): the parity path (<= 1e-4 of the float64 oracle).
+    precision="fp16": the Dequantization-, Hallucination- and Refinement-Net run NATIVE fp16 -- fp16 feature maps in HBM, one fp16
+    MFMA per product, fp32 accumulation, the inference epilogues (folded BatchNorm, residual heads, second activation) fused into the
+    fp16 kernels (shdr_conv2d_fwd_fused_f16); the 3-channel images between the nets stay fp32.  The Linearization-Net stays on the fp32
+    path: its output is the inverse CRF that every later stage is computed from, and it is about a sixth of the step.  The precision
+    is scoped to the call (`_ops.PRECISION` is restored afterwards).  fp16 overflow is not clamped: a feature map beyond the fp16
+    range (|x| > 65504) leaves the output non-finite."""
+
+    def __init__(self, deq, lin, hal, ref=None, threshold=THRESHOLD, streams=1, precision="fp32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %s, got %r" % (PRECISIONS, precision))
         self._deq, self._lin, self._hal, self._ref = deq, lin, hal, ref
         self.threshold = threshold
+        self.precision = precision
         # streams > 1: the batch is cut into that many slices, each run on its own HIP stream -- images are
         # independent, and one slice's small / low-occupancy kernels overlap with another's large ones
         self._streams = [torch.cuda.Stream() for _ in range(streams)] if streams > 1 else None
 
     def __call__(self, ldr, return_intermediates=False):
-        with torch.no_grad():
+        with torch.no_grad(), K.precision(self.precision):
             if self._streams is None or return_intermediates or ldr.shape[0] < len(self._streams):
                 return self._run(ldr, return_intermediates)
             main = torch.cuda.current_stream()
@@ -51,13 +65,17 @@ class Inference:
     def _run_scoped(self, ldr, return_intermediates):
         pred_deq = self._deq(ldr, training=False)
         C_pred = K.clip(pred_deq, 0.0, 1.0)
-        pred_invcrf = self._lin(C_pred, training=False)
+        with K.precision("fp32"):          # the inverse CRF stays on the fp32 path in every mode
+            pred_invcrf = self._lin(C_pred, training=False)
         B_pred = tf_utils.apply_rf(C_pred, pred_invcrf)
         bgr_hal_res = self._hal(B_pred, training=False)
         # alpha = clamp((max_c B - 1 + thr)/thr); A = B + alpha * rgb2bgr(hal)   (:98-105), one kernel
         A_pred = K.alpha_blend(B_pred, bgr_hal_res, self.threshold)
         out = A_pred
-        if self._ref is not None:
+        if self._ref is not None and K.native_fp16():
+            # fp16 feature maps: [A, B, C, 0...] on two 16-byte channel groups (as FinetuneStep)
+            out = self._ref(K.pack3([A_pred, B_pred, C_pred], 16, K.HALF), training=False)
+        elif self._ref is not None:
             # tf.concat([A,B,C],-1) (:108), zero-padded to 12 channels for the MFMA tile
             out = self._ref(K.pack3([A_pred, B_pred, C_pred], 12), training=False)
         if return_intermediates:
@@ -79,9 +97,9 @@ class GraphedInference:
     The returned tensor IS the graph's static output buffer: the next call with the same input shape overwrites it in place
     (`.clone()` it to keep a result across calls, or pass `copy_output=True`)."""
 
-    def __init__(self, deq, lin, hal, ref=None, threshold=THRESHOLD, copy_output=False):
+    def __init__(self, deq, lin, hal, ref=None, threshold=THRESHOLD, copy_output=False, precision="fp32"):
         self._copy_output = copy_output
-        self._eager = Inference(deq, lin, hal, ref, threshold)
+        self._eager = Inference(deq, lin, hal, ref, threshold, precision=precision)     # (precision: see Inference)
         self._graphs = {}
 
     def reset(self):
