@@ -424,13 +424,13 @@ __global__ __launch_bounds__(256) void gap_h_kernel(const hf* __restrict__ x, fl
   for (int j = 0; j < 8; ++j) part[g][q][j] = s.v[j];
   __syncthreads();
   if (g == 0 && c0 < C) {
-    const float inv = 1.0f / (float)HW;
+    const float hw = (float)HW;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float t = 0.f;
 #pragma unroll
       for (int i = 0; i < 16; ++i) t += part[i][q][j];
-      y[n * C + c0 + j] = t * inv;
+      y[n * C + c0 + j] = t / hw;       // one correctly rounded division per output (sum * (1 / HW) rounds twice: up to 1.5 ulp, seen at HW = 63)
     }
   }
 }
@@ -945,6 +945,7 @@ extern "C" int shdr_bn_stats_f16(const void* x, double* ws, float* mean, float* 
   SHDR_REQUIRE(x && ws && mean && var, SHDR_E_NULL, "bn_stats_f16: null pointer");
   SHDR_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), SHDR_E_NULL, "bn_stats_f16: moving stats come in pairs");
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_stats_f16: bad shape (C %% 8 == 0)");
+  SHDR_REQUIRE(shdr::aligned16(x), SHDR_E_ALIGN, "bn_stats_f16: x must be 16-byte aligned");
   hipStream_t st = S(stream);
   launch_bn_reduce_h(st, H_(x), nullptr, nullptr, nullptr, ws, (long)npix, C, 0);
   hipLaunchKernelGGL(bn_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var, (long)npix, C, momentum);
@@ -954,6 +955,7 @@ extern "C" int shdr_bn_train_apply_f16(const void* x, const float* mean, const f
                                        int64_t npix, int C, float eps, int relu, void* stream) {
   SHDR_REQUIRE(x && mean && var && gamma && beta && y, SHDR_E_NULL, "bn_train_apply_f16: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_train_apply_f16: bad shape (C %% 8 == 0)");
+  SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(y), SHDR_E_ALIGN, "bn_train_apply_f16: x and y must be 16-byte aligned");
   const long nvec = (long)npix * (C / 8);
   hipLaunchKernelGGL(bn_apply_h_kernel, dim3(octet_grid(nvec, C / 8, 2048)), dim3(256), 0, S(stream), H_(x), (HP) nullptr, (HP) nullptr, mean, var,
                      gamma, beta, (const double*)nullptr, HM_(y), nvec, (long)npix, C, eps, relu, 0);
@@ -963,6 +965,8 @@ extern "C" int shdr_bn_bwd_f16(const void* dy, const void* x, const void* y_relu
                                double* ws, float* dgamma, float* dbeta, void* dx, int64_t npix, int C, float eps, void* stream) {
   SHDR_REQUIRE(dy && x && mean && var && gamma && ws && dgamma && dbeta && dx, SHDR_E_NULL, "bn_bwd_f16: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_bwd_f16: bad shape (C %% 8 == 0)");
+  SHDR_REQUIRE(shdr::aligned16(dy) && shdr::aligned16(x) && (!y_relu || shdr::aligned16(y_relu)) && shdr::aligned16(dx) && shdr::aligned16(mean),
+               SHDR_E_ALIGN, "bn_bwd_f16: dy, x, y_relu, dx and mean (read as float4) must be 16-byte aligned");
   hipStream_t st = S(stream);
   launch_bn_reduce_h(st, H_(dy), H_(x), H_(y_relu), mean, ws, (long)npix, C, 1);
   hipLaunchKernelGGL(bn_bwd_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
