@@ -583,6 +583,30 @@ int shdr_jpeg_round_trip_f32(const float* ldr, const int32_t* quality, float* jp
 int shdr_flip_rot90_f32(const float* x, float* y, const int32_t* flip, const int32_t* rot, int N, int S, int C,
                         float divisor, void* stream);
 
+/* ---- HDR-Real image folders resident on the device (convert_to_tf_record.py:50-86, finetune_real_dataset.py:43-61; SURVEY.md
+ *      section 8f rank 4).  Every HDR_gt / LDR_in pair lies once in two flat arenas, LDR as uint8 RGB and HDR as float32 RGB, both
+ *      [arena_pixels, 3], addressed by ONE table:
+ *        images  int64 [n_images, 3]   (first pixel of the image in both arenas, H, W)
+ *        patches int32 [n_patches, 3]  (image, h1, w1): top-left corner of a size x size patch
+ *        samples int32 [b, 3]          (patch, flip 0 / 1, rot 0 .. 4; 4 is 0: int(u * 4 + 0.5) of finetune_real_dataset.py:58)
+ *      The kernels trust their tables, so the library checks them first: every table is passed twice, `*_host` in host memory, which
+ *      the call validates before anything is launched, and the caller's device copy of the same bytes, which the kernel reads.  A patch
+ *      that leaves its image, an image that leaves the arenas, an index out of a table, a flip or rot out of range, size <= 0 and
+ *      b <= 0 are refused with SHDR_E_SHAPE, a NULL pointer with SHDR_E_NULL.  The stats call checks every patch, the gather call the
+ *      patches its samples name.  Nothing is allocated and nothing is copied by the library. ---- */
+/* count[p] = pixels of LDR patch p whose grey value r*0.299f + g*0.587f + b*0.114f (fp32, left to right, every product and sum
+ * rounded) is >= 249 or <= 6 (convert_to_tf_record.py:54-55); mean[p] = (float)(sum of HDR patch p in float64 / (size*size*3)).
+ * One workgroup per patch, a fixed reduction tree, no atomics: the same data give the same bits. */
+int shdr_pair_patch_stats(const uint8_t* ldr, const float* hdr, int64_t arena_pixels, const int64_t* images_host,
+                          const int64_t* images, int n_images, const int32_t* patches_host, const int32_t* patches, int n_patches,
+                          int size, int32_t* count, float* mean, void* stream);
+/* out_ldr[n] = rot90(flip_left_right(LDR patch) if flip else LDR patch, rot) / 255.0f and
+ * out_hdr[n] = rot90(flip(HDR patch), rot) / (1e-6f + mean[patch]) * 0.5f, both float32 [b, size, size, 3], in one launch. */
+int shdr_pair_patch_gather_f32(const uint8_t* ldr, const float* hdr, int64_t arena_pixels, const int64_t* images_host,
+                               const int64_t* images, int n_images, const int32_t* patches_host, const int32_t* patches,
+                               int n_patches, const float* mean, const int32_t* samples_host, const int32_t* samples, int b, int size,
+                               float* out_ldr, float* out_hdr, void* stream);
+
 
 /* ---- native-fp16 activation path: BASELINE configs[4] ("finetune_real_dataset.py with Refinement-Net, 1024x1024 tiles,
  *      fp16 MFMA conv path").  Feature maps are NHWC fp16 (`void*` = _Float16 / IEEE binary16) with C % 8 == 0, image-like

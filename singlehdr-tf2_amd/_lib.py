@@ -55,6 +55,9 @@ SIGNATURES = {
     "shdr_camera_expose_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, ctypes.c_uint64, c_ptr]),
     "shdr_jpeg_round_trip_f32": (c_int, [c_ptr] * 6 + [c_int, c_int, c_int, c_ptr]),
     "shdr_flip_rot90_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_f32, c_ptr]),
+    "shdr_pair_patch_stats": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "shdr_pair_patch_gather_f32": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int,
+                                           c_int, c_ptr, c_ptr, c_ptr]),
     "shdr_conv2d_winograd_fused_f32": (c_int, [c_ptr] * 6 + [c_int] * 7 + [c_ptr]),
     "shdr_conv2d_winograd_fused2_f32": (c_int, [c_ptr] * 8 + [c_int] * 8 + [c_ptr]),
     "shdr_conv2d_winograd_fused_up2_f32": (c_int, [c_ptr] * 6 + [c_int] * 7 + [c_ptr]),

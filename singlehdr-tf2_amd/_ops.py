@@ -9,6 +9,7 @@ import collections
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 try:
@@ -1819,3 +1820,76 @@ def exr_load_resize(planes, offsets, lines, row_bytes, chan_off, chan_type, h0, 
                                             int(row_bytes), off, typ, int(h0), int(w0), _ptr(out), h, w, int(bool(clip)),
                                             _stream()), "shdr_exr_load_resize_f32")
     return out
+
+
+# ---------------------------------------------------------------------------
+# HDR-Real image folders (hdr_real.py), see csrc/hdr_real.hip
+# ---------------------------------------------------------------------------
+def _host_table(a, name, dtype):
+    """a host table [n, 3] as the C ABI wants it: contiguous, of the given dtype (values that do not fit are refused, not wrapped)"""
+    arr = np.ascontiguousarray(a)
+    if arr.ndim != 2 or arr.shape[1] != 3 or arr.dtype.kind not in "iu":
+        raise ValueError("%s: expected an integer table [n, 3]" % name)
+    if arr.dtype == dtype:
+        return arr
+    out = arr.astype(dtype)
+    if not np.array_equal(out, arr):
+        raise ValueError("%s: values do not fit %s" % (name, np.dtype(dtype).name))
+    return out
+
+
+def _pair_tables(ldr, hdr, images, images_dev, patches, patches_dev, what):
+    ldr = _chk(ldr, "ldr", torch.uint8)
+    hdr = _chk(hdr, "hdr")
+    if ldr.numel() != hdr.numel() or ldr.numel() % 3:
+        raise ValueError("%s: the arenas must hold the same pixels, [arena_pixels, 3] each" % what)
+    images, patches = _host_table(images, "images", np.int64), _host_table(patches, "patches", np.int32)
+    images_dev = _chk(images_dev, "images_dev", torch.int64)
+    patches_dev = _chk(patches_dev, "patches_dev", torch.int32)
+    if tuple(images_dev.shape) != images.shape or tuple(patches_dev.shape) != patches.shape:
+        raise ValueError("%s: a device table is not the shape of its host table" % what)
+    return ldr, hdr, images, images_dev, patches, patches_dev
+
+
+def _hptr(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def pair_patch_stats(ldr, hdr, images, images_dev, patches, patches_dev, size):
+    """(count int32 [n_patches], mean float32 [n_patches]) of every size x size patch of the resident pairs: the extreme-pixel
+    count of convert_to_tf_record.py:54-55 and the float64-summed HDR mean.  ldr uint8 / hdr float32 arenas [arena_pixels, 3];
+    images int64 [n, 3] (first pixel, H, W), patches int32 [p, 3] (image, h1, w1): host arrays, which libshdr validates before it
+    launches, and their device copies, which the kernel reads (include/shdr.h)."""
+    lib = _lib.load()
+    ldr, hdr, images, images_dev, patches, patches_dev = _pair_tables(ldr, hdr, images, images_dev, patches, patches_dev,
+                                                                      "pair_patch_stats")
+    n = patches.shape[0]
+    count = torch.empty(n, device=hdr.device, dtype=torch.int32)
+    mean = torch.empty(n, device=hdr.device, dtype=torch.float32)
+    _lib.check(lib.shdr_pair_patch_stats(_ptr(ldr), _ptr(hdr), ldr.numel() // 3, _hptr(images), _ptr(images_dev), images.shape[0],
+                                         _hptr(patches), _ptr(patches_dev), n, int(size), _ptr(count), _ptr(mean), _stream()),
+               "shdr_pair_patch_stats")
+    return count, mean
+
+
+def pair_patch_gather(ldr, hdr, images, images_dev, patches, patches_dev, mean, samples, size):
+    """(ref_LDR, ref_HDR) float32 [b, size, size, 3] for samples int32 [b, 3] (patch, flip, rot) -- a host array: it is validated by
+    libshdr, copied to the device through pinned memory here, and one launch crops, flips, rotates and normalises both patches
+    (LDR / 255, HDR / (1e-6 + mean[patch]) * 0.5)."""
+    lib = _lib.load()
+    ldr, hdr, images, images_dev, patches, patches_dev = _pair_tables(ldr, hdr, images, images_dev, patches, patches_dev,
+                                                                      "pair_patch_gather")
+    mean = _chk(mean, "mean")
+    if mean.numel() != patches.shape[0]:
+        raise ValueError("pair_patch_gather: one mean per patch")
+    samples = _host_table(samples, "samples", np.int32)
+    b = samples.shape[0]
+    samples_dev = torch.from_numpy(samples).pin_memory().to(hdr.device, non_blocking=True) if b else None
+    shape = (b, int(size), int(size), 3) if b > 0 and size > 0 else (0,)
+    out_ldr = torch.empty(shape, device=hdr.device, dtype=torch.float32)
+    out_hdr = torch.empty(shape, device=hdr.device, dtype=torch.float32)
+    _lib.check(lib.shdr_pair_patch_gather_f32(_ptr(ldr), _ptr(hdr), ldr.numel() // 3, _hptr(images), _ptr(images_dev), images.shape[0],
+                                              _hptr(patches), _ptr(patches_dev), patches.shape[0], _ptr(mean), _hptr(samples),
+                                              None if samples_dev is None else _ptr(samples_dev), b, int(size), _ptr(out_ldr),
+                                              _ptr(out_hdr), _stream()), "shdr_pair_patch_gather_f32")
+    return out_ldr, out_hdr

@@ -44,6 +44,7 @@ SOURCES = {
     "camera.hip": ["-ffp-contract=off"],
     "dataset.hip": ["-ffp-contract=off"],
     "exr.hip": ["-ffp-contract=off"],
+    "hdr_real.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]
