@@ -688,6 +688,39 @@ int shdr_bn_bwd_f16(const void* dy, const void* x, const void* y_relu, const flo
 int shdr_lin_frontend_fwd_f16(const float* img, void* y, int N, int H, int W, int y_channels, void* stream);
 int shdr_lin_frontend_bwd_f16(const float* img, const void* dF, float* dimg, int N, int H, int W, int y_channels, void* stream);
 
+/* ---- validation metrics (csrc/metrics.hip): PSNR-L, PSNR-mu, SSIM-mu and the fine-tuning loss of an HDR estimate against its
+ *      ground truth, per image, on the device.  pred, gt: fp32 [N,H,W,3], H >= 11 and W >= 11 (one 11x11 SSIM window).  With
+ *        s_p, s_g = float32(0.5 / (1e-6 + mean(image)))  (normalise != 0: the mean normalisation of finetune_real_dataset.py:47,173)
+ *                   or 1 (normalise == 0),
+ *        p = max(s_p * pred, 0),  g = max(s_g * gt, 0),  peak = max(g),
+ *        T(x) = log(1 + mu * min(x / peak, 1)) / log(1 + mu),  logc(x) = log(1 + 10 x) / log(11)
+ *      the outputs are, per image and in float64,
+ *        mse_l = mean((p - g)^2) / peak^2,  mse_mu = mean((T(p) - T(g))^2),  l1_logc = mean|logc(p) - logc(g)|,
+ *        ssim_mu = SSIM (Wang et al. 2004) of T(p) against T(g) per channel: 11x11 Gaussian window of sigma 1.5 with weights summing
+ *                  to 1, the (H-10)(W-10) valid windows only, weighted population variances, C1 = 1e-4, C2 = 9e-4, mean over
+ *                  windows and channels.
+ *      peak == 0 (an all-black gt) is not special-cased: the results are the IEEE ones (NaN / inf).
+ *      Every reduction has two stages: a grid that depends on the shape alone writes float64 partial sums into `workspace`
+ *      (shdr_metrics_workspace_bytes(N, H, W) bytes, owned by the caller, 8-byte aligned), one block per image adds them in a fixed
+ *      order.  No floating-point atomics: the same inputs give the same bits.  NULL pointer -> SHDR_E_NULL; H < 11, W < 11 or
+ *      N <= 0 -> SHDR_E_SHAPE.  Asynchronous on `stream`, nothing is allocated. ---- */
+int64_t shdr_metrics_workspace_bytes(int N, int H, int W);
+/* scale_pred[n], scale_gt[n] (the float32 values s_p, s_g, stored as float64) and peak[n] = max(g) (exact: the product of two
+ * float32 numbers in float64) */
+int shdr_pair_moments_f32(const float* pred, const float* gt, int N, int H, int W, int normalise, double* scale_pred,
+                          double* scale_gt, double* peak, void* workspace, void* stream);
+/* the four metrics, from the scales and peaks of shdr_pair_moments_f32 (device arrays [N]).  One block per tile of
+ * SHDR_METRICS_TILE_H x SHDR_METRICS_TILE_W windows. */
+#define SHDR_METRICS_TILE_H 16
+#define SHDR_METRICS_TILE_W 32
+int shdr_hdr_metrics_f32(const float* pred, const float* gt, int N, int H, int W, float mu, const double* scale_pred,
+                         const double* scale_gt, const double* peak, double* mse_l, double* mse_mu, double* l1_logc,
+                         double* ssim_mu, void* workspace, void* stream);
+/* 8-bit preview: y = round(255 * T(max(scale[n] * x, 0))^(1/2.2)) with peak[n] in T; scale == NULL -> 1.  uint8 [N,H,W,3];
+ * reverse_channels != 0 reads the pixel as BGR (as shdr_rgbe_encode_f32). */
+int shdr_tonemap_u8_f32(const float* x, const double* scale, const double* peak, uint8_t* y, int N, int H, int W, float mu,
+                        int reverse_channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

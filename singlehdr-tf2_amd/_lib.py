@@ -194,6 +194,10 @@ SIGNATURES = {
     "shdr_lin_frontend_fwd_f16": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "shdr_lin_frontend_bwd_f16": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "shdr_adam_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_ptr]),
+    "shdr_metrics_workspace_bytes": (c_i64, [c_int, c_int, c_int]),
+    "shdr_pair_moments_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int] + [c_ptr] * 5),
+    "shdr_hdr_metrics_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_f32] + [c_ptr] * 9),
+    "shdr_tonemap_u8_f32": (c_int, [c_ptr] * 4 + [c_int] * 3 + [c_f32, c_int, c_ptr]),
 }
 
 _lib = None

@@ -1893,3 +1893,77 @@ def pair_patch_gather(ldr, hdr, images, images_dev, patches, patches_dev, mean, 
                                               None if samples_dev is None else _ptr(samples_dev), b, int(size), _ptr(out_ldr),
                                               _ptr(out_hdr), _stream()), "shdr_pair_patch_gather_f32")
     return out_ldr, out_hdr
+
+
+# ---------------------------------------------------------------------------
+# validation metrics (csrc/metrics.hip; the public layer is metrics.py)
+# ---------------------------------------------------------------------------
+METRICS_TILE = (16, 32)        # SSIM windows per block of shdr_hdr_metrics_f32 (SHDR_METRICS_TILE_H x _W, include/shdr.h)
+
+
+def _pair(pred, gt, what):
+    pred, gt = _chk(_d(pred), "pred"), _chk(_d(gt), "gt")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape != gt.shape:
+        raise ValueError("%s: pred and gt must both be [N, H, W, 3], got %s and %s" % (what, tuple(pred.shape), tuple(gt.shape)))
+    if pred.device != gt.device:
+        raise ValueError("%s: pred and gt are on different devices" % what)
+    return pred, gt
+
+
+def _metrics_ws(lib, n, h, w, device, what):
+    nbytes = lib.shdr_metrics_workspace_bytes(n, h, w)
+    if nbytes < 0:
+        _lib.check(int(nbytes), what)
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def pair_moments(pred, gt, normalise=True):
+    """(scale_pred, scale_gt, peak), float64 [N]: the mean-normalisation scales 0.5 / (1e-6 + mean) of both images (1 without
+    `normalise`) and the peak max(max(scale_gt * gt, 0)) of the ground truth"""
+    lib = _lib.load()
+    pred, gt = _pair(pred, gt, "pair_moments")
+    n, h, w, _ = pred.shape
+    ws = _metrics_ws(lib, n, h, w, pred.device, "shdr_pair_moments_f32")
+    out = torch.empty((3, n), device=pred.device, dtype=torch.float64)
+    _lib.check(lib.shdr_pair_moments_f32(_ptr(pred), _ptr(gt), n, h, w, int(bool(normalise)), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                         _ptr(ws), _stream()), "shdr_pair_moments_f32")
+    return out[0], out[1], out[2]
+
+
+def hdr_metrics(pred, gt, normalise=True, mu=5000.0):
+    """Per-image quality of an HDR estimate, float64 device tensors [N] (definitions: include/shdr.h "validation metrics"):
+    mse_l, mse_mu, l1_logc, ssim_mu, peak, scale_pred, scale_gt.  Two stream-ordered launches, no host synchronisation; the same
+    inputs give the same bits.  An all-black gt (peak 0) gives the IEEE results (NaN / inf)."""
+    lib = _lib.load()
+    pred, gt = _pair(pred, gt, "hdr_metrics")
+    n, h, w, _ = pred.shape
+    ws = _metrics_ws(lib, n, h, w, pred.device, "shdr_hdr_metrics_f32")
+    out = torch.empty((7, n), device=pred.device, dtype=torch.float64)
+    sp, sg, peak = out[4], out[5], out[6]
+    _lib.check(lib.shdr_pair_moments_f32(_ptr(pred), _ptr(gt), n, h, w, int(bool(normalise)), _ptr(sp), _ptr(sg), _ptr(peak), _ptr(ws),
+                                         _stream()), "shdr_pair_moments_f32")
+    _lib.check(lib.shdr_hdr_metrics_f32(_ptr(pred), _ptr(gt), n, h, w, float(mu), _ptr(sp), _ptr(sg), _ptr(peak), _ptr(out[0]),
+                                        _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(ws), _stream()), "shdr_hdr_metrics_f32")
+    return dict(mse_l=out[0], mse_mu=out[1], l1_logc=out[2], ssim_mu=out[3], peak=peak, scale_pred=sp, scale_gt=sg)
+
+
+def tonemap_u8(x, peak=None, reverse_channels=False, mu=5000.0):
+    """float [N, H, W, 3] (or [H, W, 3]) -> uint8 of the same shape: round(255 * T(max(x, 0))^(1/2.2)) with the tone curve T of
+    hdr_metrics.  peak: float64 device tensor with one value per image; None -> the image's maximum."""
+    lib = _lib.load()
+    x = _chk(_d(x), "x")
+    shape = tuple(x.shape)
+    x4 = x if x.dim() == 4 else x[None]
+    if x4.dim() != 4 or x4.shape[-1] != 3:
+        raise ValueError("tonemap_u8: expected [N, H, W, 3] or [H, W, 3], got %s" % (shape,))
+    n, h, w, _ = x4.shape
+    if peak is None:
+        peak = pair_moments(x4, x4, normalise=False)[2]
+    else:
+        peak = _chk(peak, "peak", torch.float64).reshape(-1)
+        if peak.numel() != n:
+            raise ValueError("tonemap_u8: one peak per image")
+    y = torch.empty(shape, device=x.device, dtype=torch.uint8)
+    _lib.check(lib.shdr_tonemap_u8_f32(_ptr(x4), None, _ptr(peak), _ptr(y), n, h, w, float(mu), int(reverse_channels), _stream()),
+               "shdr_tonemap_u8_f32")
+    return y

@@ -106,6 +106,16 @@ def rgbe_decode(rgbe):
     return rgbe[..., :3].astype(np.float32) * scale[..., None]
 
 
+def write_preview(path, hdr_tensor, peak=None, reverse_channels=False):
+    """8-bit preview of an HDR image: float32 [H, W, 3] on the device -> K.tonemap_u8 (mu-law tone curve up to `peak`, default the
+    image's maximum, then a 2.2 gamma) -> an image file through PIL (the format follows the extension; PNG is lossless)"""
+    from PIL import Image
+    if hdr_tensor.dim() != 3:
+        raise ValueError("write_preview: expected one image [H, W, 3], got %s" % (tuple(hdr_tensor.shape),))
+    u8 = K.tonemap_u8(hdr_tensor.contiguous(), peak, reverse_channels)
+    Image.fromarray(u8.cpu().numpy(), "RGB").save(path)
+
+
 class HdrReconstructor:
     """LDR file -> HDR file with the reference tool's geometry (resize to 64x, 32-pixel symmetric pad, crop, resize back).
     `inference` is any `pipeline.Inference` / `GraphedInference`, e.g. `Inference(deq, lin, hal, ref, precision="fp16")` for the
@@ -116,6 +126,11 @@ class HdrReconstructor:
 
     def reconstruct(self, rgb_u8):
         """uint8 RGB [H, W, 3] (host) -> RGBE bytes uint8 [H, W, 4] (host) of the HDR estimate, RGB order"""
+        return K.rgbe_encode(self.reconstruct_device(rgb_u8), reverse_channels=True).cpu().numpy()
+
+    def reconstruct_device(self, rgb_u8):
+        """uint8 RGB [H, W, 3] (host) -> the HDR estimate float32 [H, W, 3] on the device, in the NETWORK's channel order: the
+        file's blue first (encode or preview it with reverse_channels=True)"""
         rgb_u8 = np.array(rgb_u8, dtype=np.uint8)               # contiguous, writable (torch.from_numpy)
         h, w, _ = rgb_u8.shape
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -134,10 +149,14 @@ class HdrReconstructor:
             y = K.resize_cubic(y, (h, w))                                                         # :146-147
         # :144 flips the channels, :150 flips them back and cv2 stores its BGR argument as RGB: the net's channel 0 is the
         # file's blue, i.e. the network output is read as BGR
-        return K.rgbe_encode(y[0], reverse_channels=True).cpu().numpy()
+        return y[0]
 
-    def reconstruct_file(self, ldr_path, hdr_path):
-        write_hdr(hdr_path, self.reconstruct(read_ldr(ldr_path)))
+    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None):
+        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support"""
+        y = self.reconstruct_device(read_ldr(ldr_path))
+        write_hdr(hdr_path, K.rgbe_encode(y, reverse_channels=True).cpu().numpy())
+        if preview_path is not None:
+            write_preview(preview_path, y, reverse_channels=True)
 
     def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True):
         """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths"""

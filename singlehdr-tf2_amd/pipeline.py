@@ -9,9 +9,10 @@ import torch
 
 try:
     from . import _ops as K
-    from . import tf_utils
+    from . import metrics, tf_utils
 except ImportError:
     import _ops as K
+    import metrics
     import tf_utils
 
 THRESHOLD = 0.12  # test_real_refinement.py:28
@@ -126,6 +127,30 @@ class GraphedInference:
         static_in.copy_(ldr)
         graph.replay()
         return static_out.clone() if self._copy_output else static_out
+
+
+class Evaluate:
+    """Validation loop: run `inference` (an `Inference` or `GraphedInference`, either precision) on LDR batches and score the HDR
+    estimates against their ground truth with a `metrics.Evaluator` -- the consumer of `dataset.get_vali_dataset` patches (fed
+    through `camera`), of an `hdr_real.HdrRealFolder` built with augment=False and of `tfrecord.HdrRealDataset`.  Nothing here
+    synchronises with the host until `run` / `evaluator.result()` reads the accumulated state."""
+
+    def __init__(self, inference, evaluator=None):
+        self.inference = inference
+        self.evaluator = metrics.Evaluator() if evaluator is None else evaluator
+
+    def __call__(self, ldr, hdr):
+        """updates the evaluator with one batch and returns the HDR estimate"""
+        with torch.no_grad():
+            pred = self.inference(ldr)
+            self.evaluator.update(pred, hdr)
+        return pred
+
+    def run(self, batches):
+        """batches: an iterable of (ldr, hdr) device tensors [N, H, W, 3]; returns evaluator.result()"""
+        for ldr, hdr in batches:
+            self(ldr, hdr)
+        return self.evaluator.result()
 
 
 class FlatParams:
