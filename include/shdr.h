@@ -721,6 +721,85 @@ int shdr_hdr_metrics_f32(const float* pred, const float* gt, int N, int H, int W
 int shdr_tonemap_u8_f32(const float* x, const double* scale, const double* peak, uint8_t* y, int N, int H, int W, float mu,
                         int reverse_channels, void* stream);
 
+/* ---- baseline-JPEG file decoder (csrc/jpeg.hip): a BATCH of files of different sizes, layouts and tables -> quantised
+ *      coefficients and uint8 RGB, bit for bit libjpeg's default decode (islow IDCT, fancy upsampling).  The host parses the
+ *      markers, removes the FF 00 stuffing and cuts the scan at its RSTn markers (jpeg.py); the device decodes the Huffman stream
+ *      with the self-synchronising scheme of Weissenberger & Schmidt (2018): every restart segment is cut into subsequences of
+ *      `subseq_bits` bits, one thread each, 256 per workgroup; a workgroup lies inside ONE image.
+ *
+ *      data       device bytes: the unstuffed segments, each starting on a 4-byte boundary (padding content is irrelevant)
+ *      tables     device bytes: per image SHDR_JPEG_TABLE_BYTES at image.table_off (a multiple of 4): four quantisation tables
+ *                 (64 uint16 each, natural order), then four Huffman tables of SHDR_JPEG_HUFF_BYTES: uint16 look[512] (the next
+ *                 9 bits -> code length << 8 | symbol, 0 when the code is longer), int32 maxcode[17] (largest code of length l,
+ *                 -1: none), int32 valoff[17] (index of the first symbol of length l minus its first code), uint8 symbols[256]
+ *      images     one shdr_jpeg_image per file; segs: SHDR_JPEG_SEG_FIELDS int32 per restart segment; sub_seg: per subsequence
+ *                 slot its segment, or -1 for the unused slots at the end of an image's last workgroup.  Each table is passed as
+ *                 a host array, which is validated, and as the device copy of that very array, which the kernels read.
+ *      coef       device int16 [n_blocks][64], natural order, DC prediction undone; an image's blocks start at image.blk_off,
+ *                 component c at comp[c].blk_off, raster order over its bw x bh blocks
+ *      out        device uint8: image i is [height, width, 3] RGB at image.out_off (grey: R = G = B)
+ *      errors     device int32 [n_images]: 0 or the SHDR_JPEG_E_* of the first subsequence of the image that failed; such an image's
+ *                 coefficients and pixels are unspecified, other images are not affected
+ *      workspace  shdr_jpeg_workspace_bytes(n_sub, n_blocks, plane_bytes) bytes, 16-byte aligned, owned by the caller
+ *      Whatever the bytes of `data`, no read leaves a segment and no write leaves an image's blocks.  No atomics: the same input
+ *      gives the same bits.  The calls wait on `stream` once per synchronisation pass after the first two (a pass flag comes back
+ *      to the host); they allocate nothing.  The number of launches is 9 (11 with pixels) plus one per pass. ---- */
+#define SHDR_JPEG_HUFF_BYTES 1416
+#define SHDR_JPEG_TABLE_BYTES (512 + 4 * SHDR_JPEG_HUFF_BYTES)
+#define SHDR_JPEG_E_CODE 1      /* a bit pattern that is no code word of the table, or a decoder state that cannot occur */
+#define SHDR_JPEG_E_BITS 2      /* the segment ends before its blocks are complete */
+#define SHDR_JPEG_E_OVERRUN 3   /* a run of zeros leaves the block */
+typedef struct shdr_jpeg_component {
+  int32_t h, v;                 /* sampling factors: luma 1x1, 2x1 or 2x2, chroma 1x1 (a grey image: 1x1); anything else is refused */
+  int32_t tq, dc_slot, ac_slot; /* its quantisation table and Huffman tables (0..3) in the image's table block */
+  int32_t bw, bh;               /* blocks per row / column of the padded plane: mcus_x * h, mcus_y * v */
+  int32_t blk_off;              /* first block, relative to image.blk_off: the blocks of the components before it */
+  int32_t plane_off;            /* its plane in the workspace, relative to image.plane_off: 64 bytes per block before it */
+  int32_t cw, ch;               /* libjpeg's downsampled size: ceil(width * h / hmax), ceil(height * v / vmax) */
+} shdr_jpeg_component;
+typedef struct shdr_jpeg_image {
+  int64_t blk_off;              /* first block of the image in `coef` (strictly increasing over the images) */
+  int64_t plane_off;            /* first byte of its component planes (in total 64 bytes per block) */
+  int64_t out_off;              /* first byte of its pixels in `out` */
+  int64_t table_off;            /* first byte of its tables in `tables` */
+  int32_t width, height, ncomp; /* ncomp: 1 or 3 */
+  int32_t mcus_x, mcus_y, blocks_per_mcu, restart_interval;       /* restart_interval in MCUs, 0: none */
+  int32_t first_wg, n_wg;       /* its workgroups: subsequence slots first_wg * 256 .. (first_wg + n_wg) * 256 */
+  int32_t reserved, reserved2;
+  shdr_jpeg_component comp[3];
+} shdr_jpeg_image;
+#define SHDR_JPEG_SEG_FIELDS 6
+#define SHDR_JPEG_SEG_DWORD 0        /* offset of the segment in `data`, in 4-byte units */
+#define SHDR_JPEG_SEG_BITS 1         /* its length in bits (the unstuffed bytes * 8) */
+#define SHDR_JPEG_SEG_FIRST_SUB 2    /* its first subsequence slot; it has max(1, ceil(bits / subseq_bits)) consecutive ones */
+#define SHDR_JPEG_SEG_FIRST_BLOCK 3  /* its first block in the image's scan order (MCU by MCU, component by component) */
+#define SHDR_JPEG_SEG_BLOCKS 4       /* the blocks it must hold */
+#define SHDR_JPEG_SEG_IMAGE 5
+#define SHDR_JPEG_STAGES 6
+typedef struct shdr_jpeg_batch {
+  const uint8_t* data;
+  const uint8_t* tables;
+  const shdr_jpeg_image* images;     /* host */
+  const shdr_jpeg_image* images_dev;
+  const int32_t* segs;               /* host */
+  const int32_t* segs_dev;
+  const int32_t* sub_seg;            /* host */
+  const int32_t* sub_seg_dev;
+  int32_t* passes;                   /* host, may be NULL: receives the number of synchronisation passes launched */
+  float* stage_ms;                   /* host, may be NULL: receives SHDR_JPEG_STAGES device-event times in ms (the call then
+                                      * waits for its last kernel): clearing the workspace, the synchronisation passes (with the
+                                      * host's waits between them), block scan + write pass, DC scan + DC, IDCT, upsample + colour;
+                                      * the last two are 0 from shdr_jpeg_entropy_decode */
+  int64_t data_bytes, table_bytes, n_sub, n_blocks, plane_bytes, out_bytes;
+  int32_t n_images, n_segs, subseq_bits, reserved;       /* subseq_bits: 256, 512, 1024 or 2048 */
+} shdr_jpeg_batch;
+int64_t shdr_jpeg_workspace_bytes(int64_t n_sub, int64_t n_blocks, int64_t plane_bytes);      /* -1 on bad sizes */
+int shdr_jpeg_entropy_decode(const shdr_jpeg_batch* batch, int16_t* coef, int32_t* errors, void* workspace, void* stream);
+int shdr_jpeg_decode_u8(const shdr_jpeg_batch* batch, int16_t* coef, uint8_t* out, int32_t* errors, void* workspace, void* stream);
+/* measurement: per subsequence slot the round (pass * 258 + iteration inside the workgroup; 0: never) in which its end state last
+ * changed during the decode that last used `workspace`, copied to the host array rounds [n_sub]; waits on `stream` */
+int shdr_jpeg_sync_rounds(const void* workspace, int64_t n_sub, int64_t n_blocks, int64_t plane_bytes, int32_t* rounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,10 @@ SIGNATURES = {
     "shdr_pair_moments_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int] + [c_ptr] * 5),
     "shdr_hdr_metrics_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_f32] + [c_ptr] * 9),
     "shdr_tonemap_u8_f32": (c_int, [c_ptr] * 4 + [c_int] * 3 + [c_f32, c_int, c_ptr]),
+    "shdr_jpeg_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "shdr_jpeg_entropy_decode": (c_int, [c_ptr] * 5),
+    "shdr_jpeg_decode_u8": (c_int, [c_ptr] * 6),
+    "shdr_jpeg_sync_rounds": (c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
 }
 
 _lib = None

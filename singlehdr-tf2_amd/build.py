@@ -46,6 +46,7 @@ SOURCES = {
     "dataset.hip": ["-ffp-contract=off"],
     "exr.hip": ["-ffp-contract=off"],
     "hdr_real.hip": ["-ffp-contract=off"],
+    "jpeg.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]
@@ -68,7 +69,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
+    headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []
     for src, extra in SOURCES.items():

@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off: the float steps (noise chain, grey conversion) round exactly like the fp32 restatement
 // in oracle/camera.py.
 #include "shdr_internal.h"
+#include "jpeg_int.h"
 
 namespace {
 
@@ -59,60 +60,8 @@ __global__ __launch_bounds__(256) void camera_expose_kernel(const float* __restr
   }
 }
 
-// ---------------------------------------------------------------- libjpeg integer arithmetic
-constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270;
-constexpr int F_0_899976223 = 7373, F_1_175875602 = 9633, F_1_501321110 = 12299, F_1_847759065 = 15137;
-constexpr int F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995, F_3_072711026 = 25172;
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// 1-D forward pass over d[0..7*stride]
-__device__ __forceinline__ void fdct_1d(int* d, int stride, bool first) {
-  const int a0 = d[0], a1 = d[stride], a2 = d[2 * stride], a3 = d[3 * stride], a4 = d[4 * stride], a5 = d[5 * stride],
-            a6 = d[6 * stride], a7 = d[7 * stride];
-  int t0 = a0 + a7, t7 = a0 - a7, t1 = a1 + a6, t6 = a1 - a6, t2 = a2 + a5, t5 = a2 - a5, t3 = a3 + a4, t4 = a3 - a4;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  const int sh = first ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS;
-  d[0] = first ? (t10 + t11) << PASS1_BITS : descale(t10 + t11, PASS1_BITS);
-  d[4 * stride] = first ? (t10 - t11) << PASS1_BITS : descale(t10 - t11, PASS1_BITS);
-  int z1 = (t12 + t13) * F_0_541196100;
-  d[2 * stride] = descale(z1 + t13 * F_0_765366865, sh);
-  d[6 * stride] = descale(z1 - t12 * F_1_847759065, sh);
-  z1 = t4 + t7;
-  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-  const int z5 = (z3 + z4) * F_1_175875602;
-  t4 *= F_0_298631336; t5 *= F_2_053119869; t6 *= F_3_072711026; t7 *= F_1_501321110;
-  z1 *= -F_0_899976223; z2 *= -F_2_562915447;
-  z3 = z3 * -F_1_961570560 + z5;
-  z4 = z4 * -F_0_390180644 + z5;
-  d[7 * stride] = descale(t4 + z1 + z3, sh);
-  d[5 * stride] = descale(t5 + z2 + z4, sh);
-  d[3 * stride] = descale(t6 + z2 + z3, sh);
-  d[stride] = descale(t7 + z1 + z4, sh);
-}
-
-__device__ __forceinline__ void idct_1d(int* d, int stride, bool first) {
-  int z2 = d[2 * stride], z3 = d[6 * stride];
-  int z1 = (z2 + z3) * F_0_541196100;
-  int t2 = z1 - z3 * F_1_847759065, t3 = z1 + z2 * F_0_765366865;
-  int t0 = (d[0] + d[4 * stride]) << CONST_BITS, t1 = (d[0] - d[4 * stride]) << CONST_BITS;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-  t0 = d[7 * stride]; t1 = d[5 * stride]; t2 = d[3 * stride]; t3 = d[stride];
-  z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
-  int z4 = t1 + t3;
-  const int z5 = (z3 + z4) * F_1_175875602;
-  t0 *= F_0_298631336; t1 *= F_2_053119869; t2 *= F_3_072711026; t3 *= F_1_501321110;
-  z1 *= -F_0_899976223; z2 *= -F_2_562915447;
-  z3 = z3 * -F_1_961570560 + z5;
-  z4 = z4 * -F_0_390180644 + z5;
-  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-  const int sh = first ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS + 3;
-  d[0] = descale(t10 + t3, sh); d[7 * stride] = descale(t10 - t3, sh);
-  d[stride] = descale(t11 + t2, sh); d[6 * stride] = descale(t11 - t2, sh);
-  d[2 * stride] = descale(t12 + t1, sh); d[5 * stride] = descale(t12 - t1, sh);
-  d[3 * stride] = descale(t13 + t0, sh); d[4 * stride] = descale(t13 - t0, sh);
-}
+// ---------------------------------------------------------------- libjpeg integer arithmetic (jpeg_int.h)
+using namespace shdr::jpegint;
 
 // ITU T.81 Annex K tables (natural order)
 __constant__ uint8_t kLumaQ[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
@@ -201,16 +150,6 @@ __global__ __launch_bounds__(64) void jpeg_mcu_kernel(const float* __restrict__ 
   }
 }
 
-__device__ __forceinline__ int fancy_up(const uint8_t* __restrict__ p, int ch, int cw, int y, int x) {
-  // output sample (y, x) of the 2x upsampled plane: near row / far row, near column / far column, weights 9:3:3:1
-  const int cy = y >> 1, cx = x >> 1;
-  const int fy = min(max(cy + ((y & 1) ? 1 : -1), 0), ch - 1);
-  const int fx = min(max(cx + ((x & 1) ? 1 : -1), 0), cw - 1);
-  const int this_col = 3 * p[cy * cw + cx] + p[fy * cw + cx];
-  const int far_col = 3 * p[cy * cw + fx] + p[fy * cw + fx];
-  return (3 * this_col + far_col + ((x & 1) ? 7 : 8)) >> 4;
-}
-
 // one thread per pixel; counts[n][0] = #grey >= 249, counts[n][1] = #grey <= 6
 __global__ __launch_bounds__(256) void jpeg_finish_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cbp,
                                                           const uint8_t* __restrict__ crp, float* __restrict__ out,
@@ -224,14 +163,9 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(const uint8_t* __restr
   for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
     const int y = p / W, x = p - y * W;
     const int yy = yp[(size_t)n * npix + p];
-    const int u = fancy_up(cb, ch, cw, y, x) - 128, v = fancy_up(cr, ch, cw, y, x) - 128;
-    const int half = 1 << 15;
-    int r = yy + ((91881 * v + half) >> 16);                       // FIX(1.40200)
-    int g = yy + ((-22554 * u + half - 46802 * v) >> 16);          // FIX(0.34414), FIX(0.71414)
-    int b = yy + ((116130 * u + half) >> 16);                      // FIX(1.77200)
-    r = r < 0 ? 0 : (r > 255 ? 255 : r);
-    g = g < 0 ? 0 : (g > 255 ? 255 : g);
-    b = b < 0 ? 0 : (b > 255 ? 255 : b);
+    const int u = fancy_up_h2v2(cb, cw, ch, cw, y, x) - 128, v = fancy_up_h2v2(cr, cw, ch, cw, y, x) - 128;
+    int r, g, b;
+    ycc_to_rgb(yy, u, v, r, g, b);
     float* o = out + ((size_t)n * npix + p) * 3;
     o[0] = (float)r / 255.0f; o[1] = (float)g / 255.0f; o[2] = (float)b / 255.0f;     // tf.cast(jpeg, float32) / 255   (:52)
     // tf.image.rgb_to_grayscale on uint8: u8 * (1/255) -> dot (0.2989, 0.5870, 0.1140) -> saturate_cast(x * 255.5)

@@ -129,12 +129,18 @@ class HdrReconstructor:
         return K.rgbe_encode(self.reconstruct_device(rgb_u8), reverse_channels=True).cpu().numpy()
 
     def reconstruct_device(self, rgb_u8):
-        """uint8 RGB [H, W, 3] (host) -> the HDR estimate float32 [H, W, 3] on the device, in the NETWORK's channel order: the
-        file's blue first (encode or preview it with reverse_channels=True)"""
-        rgb_u8 = np.array(rgb_u8, dtype=np.uint8)               # contiguous, writable (torch.from_numpy)
-        h, w, _ = rgb_u8.shape
-        dev = torch.device("cuda", torch.cuda.current_device())
-        x = K.u8_to_unit(torch.from_numpy(rgb_u8).to(dev, non_blocking=True), False)[None]        # RGB in [0,1]  (:125)
+        """uint8 RGB [H, W, 3] (host array, or a uint8 device tensor such as jpeg.decode returns: no host round trip) -> the HDR
+        estimate float32 [H, W, 3] on the device, in the NETWORK's channel order: the file's blue first (encode or preview it with
+        reverse_channels=True)"""
+        if isinstance(rgb_u8, torch.Tensor):
+            if rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or not rgb_u8.is_cuda:
+                raise ValueError("reconstruct_device: a tensor input must be uint8 [H, W, 3] on the device")
+            u8 = rgb_u8.contiguous()
+        else:
+            rgb_u8 = np.array(rgb_u8, dtype=np.uint8)           # contiguous, writable (torch.from_numpy)
+            u8 = torch.from_numpy(rgb_u8).to(torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+        h, w, _ = u8.shape
+        x = K.u8_to_unit(u8, False)[None]                                                         # RGB in [0,1]  (:125)
         m = self.multiple
         rh, rw = -(-h // m) * m, -(-w // m) * m
         if (rh, rw) != (h, w):
@@ -151,21 +157,32 @@ class HdrReconstructor:
         # file's blue, i.e. the network output is read as BGR
         return y[0]
 
-    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None):
-        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support"""
-        y = self.reconstruct_device(read_ldr(ldr_path))
+    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil"):
+        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
+        decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
+        (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope)"""
+        if decoder not in ("pil", "device"):
+            raise ValueError("reconstruct_file: decoder must be 'pil' or 'device', got %r" % (decoder,))
+        if decoder == "device":
+            try:
+                from . import jpeg
+            except ImportError:
+                import jpeg
+            y = self.reconstruct_device(jpeg.read_ldr_device(ldr_path))
+        else:
+            y = self.reconstruct_device(read_ldr(ldr_path))
         write_hdr(hdr_path, K.rgbe_encode(y, reverse_channels=True).cpu().numpy())
         if preview_path is not None:
             write_preview(preview_path, y, reverse_channels=True)
 
-    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True):
-        """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths"""
+    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil"):
+        """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder: as reconstruct_file"""
         os.makedirs(output_dir, exist_ok=True)
         written = []
         for path in sorted(glob.glob(os.path.join(dataset_dir, pattern))):
             start = time.perf_counter()
             out = os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + ".hdr")          # :148-149
-            self.reconstruct_file(path, out)
+            self.reconstruct_file(path, out, decoder=decoder)
             written.append(out)
             if verbose:
                 print("Spends time : %s seconds" % (time.perf_counter() - start))

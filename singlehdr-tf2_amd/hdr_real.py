@@ -33,11 +33,13 @@ try:
     from . import _ops as K
     from . import exr
     from . import hdr_io
+    from . import jpeg
     from . import tfrecord
 except ImportError:
     import _ops as K
     import exr
     import hdr_io
+    import jpeg
     import tfrecord
 
 SIZE = 256                     # patch_size   (convert_to_tf_record.py:12)
@@ -91,10 +93,14 @@ class HdrRealFolder:
     iter(folder)     one epoch: a seeded permutation of the kept patches (the same on every rank), of which rank r takes the
                      elements r::world_size, in batches of batch_size (the last one may be short: drop_remainder=False)
     Flips are u0 < 0.5 and rots int(u1 * 4 + 0.5) of float32 uniforms, as tfrecord.HdrRealDataset draws them: rot 4 occurs and is
-    rot 0.  augment=False gives flip 0 and rot 0."""
+    rot 0.  augment=False gives flip 0 and rot 0.
+    jpeg_decoder="device" decodes all LDR files in ONE jpeg.decode batch whose output arena IS ldr_arena (the same bytes as "pil",
+    hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch)."""
 
     def __init__(self, dirpath, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1, batch_size=BATCH_SIZE,
-                 augment=True):
+                 augment=True, jpeg_decoder="pil"):
+        if jpeg_decoder not in ("pil", "device"):
+            raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil' or 'device', got %r" % (jpeg_decoder,))
         hdr_paths = sorted(p for ext in ("*.hdr", "*.exr") for p in glob.glob(os.path.join(dirpath, "HDR_gt", ext)))
         ldr_paths = sorted(glob.glob(os.path.join(dirpath, "LDR_in", "*.jpg")))
         if len(hdr_paths) != len(ldr_paths):
@@ -103,10 +109,44 @@ class HdrRealFolder:
         if not hdr_paths:
             raise FileNotFoundError("HdrRealFolder: no HDR_gt/*.hdr (or *.exr) + LDR_in/*.jpg under %s" % dirpath)
         t0 = time.perf_counter()
-        ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        ldr_arena = None
+        if jpeg_decoder == "device":
+            ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device)
+        else:
+            ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
         hdr = [exr.read_payload(p) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
         self.files = list(zip(hdr_paths, ldr_paths))
-        self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0)
+        self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0, ldr_arena)
+
+    @staticmethod
+    def _decode_ldr_on_device(paths, device):
+        """(uint8 [H, W, 3] device views per file, the flat arena they lie in).  Every baseline JPEG of the folder is decoded in ONE
+        jpeg batch; when all files are such and stored upright, the batch's output arena is returned as it is.  Files outside the
+        decoder's scope (progressive, CMYK, ...) are read by PIL and uploaded, files with an EXIF Orientation are turned, and the
+        arena is then assembled from the pieces: still one batch, whatever the number of files."""
+        in_scope = []
+        for i, p in enumerate(paths):
+            try:
+                with open(p, "rb") as f:
+                    jpeg.device_tables(jpeg.parse(f.read()))
+                in_scope.append(i)
+            except jpeg.Unsupported:
+                pass
+        images = [None] * len(paths)
+        if in_scope:
+            d = jpeg.Decoded([paths[i] for i in in_scope], device)
+            d.check()
+            if len(in_scope) == len(paths) and all(h.orientation == 1 for h in d.plan.headers):
+                return [d.image(i) for i in range(len(paths))], d.out
+            for k, i in enumerate(in_scope):
+                images[i] = jpeg.apply_orientation(d.image(k), d.plan.headers[k].orientation)
+        for i, p in enumerate(paths):
+            if images[i] is None:
+                images[i] = torch.from_numpy(hdr_io.read_ldr(p)).to(device)
+        arena = torch.cat([a.reshape(-1) for a in images])
+        sizes = np.cumsum([0] + [a.numel() for a in images])
+        return [arena[sizes[i]:sizes[i + 1]].view(a.shape) for i, a in enumerate(images)], arena
 
     @classmethod
     def from_arrays(cls, ldr_list, hdr_list, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1,
@@ -134,7 +174,7 @@ class HdrRealFolder:
             return item.header.height, item.header.width
         return tuple(item.shape[:2])
 
-    def _setup(self, ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, host_seconds):
+    def _setup(self, ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, host_seconds, ldr_arena=None):
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.size, self.stride, self.batch_size, self.augment = int(size), int(stride), int(batch_size), bool(augment)
         self.rank, self.world_size = int(rank), int(world_size)
@@ -153,7 +193,10 @@ class HdrRealFolder:
         total = int(sum(pixels))
         self.shapes = shapes
         self.images = np.ascontiguousarray(np.column_stack([offsets, np.asarray(shapes, dtype=np.int64).reshape(-1, 2)]), dtype=np.int64)
-        self.ldr_arena = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in ldr])).to(self.device)
+        if ldr_arena is not None:                                  # decoded on the device, already flat in file order
+            self.ldr_arena = ldr_arena
+        else:
+            self.ldr_arena = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in ldr])).to(self.device)
         self.hdr_arena = torch.empty(total * 3, device=self.device, dtype=torch.float32)
         for i, (item, (h, w)) in enumerate(zip(hdr, shapes)):
             out = self.hdr_arena[3 * offsets[i]:3 * (offsets[i] + h * w)].view(h, w, 3)
