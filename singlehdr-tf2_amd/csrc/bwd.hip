@@ -284,12 +284,12 @@ __global__ __launch_bounds__(256) void resize2x_bwd_kernel(const float* __restri
 __global__ __launch_bounds__(256) void gap_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
                                                       long total_q, int HW, int C) {
   const int Q = C >> 2;
-  const float inv = 1.0f / (float)HW;
+  const float hw = (float)HW;           // dy / HW, one rounding (dy * (1 / HW) rounds twice)
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total_q; e += (long)gridDim.x * 256) {
     const int q = (int)(e % Q);
     const long n = e / ((long)Q * HW);
     float4 g = ld4(dy + n * C + 4 * q);
-    g.x *= inv; g.y *= inv; g.z *= inv; g.w *= inv;
+    g.x /= hw; g.y /= hw; g.z /= hw; g.w /= hw;
     st4(dx + e * 4, g);
   }
 }
@@ -664,6 +664,10 @@ __global__ __launch_bounds__(256) void apply_rf_bwd_kernel(const float* __restri
   const float* xb = x + (long)b * n_per_batch;
   const float* gb = dy + (long)b * n_per_batch;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_per_batch; i += (long)gridDim.x * 256) {
+    // the forward's weights (crf.hip: contraction off): y1 - yv and yv - y0 of the ROUNDED product.  Contracted into fma(-km1, x, y1)
+    // they were taken from the unrounded one while the floor came from the rounded one: on a table knot the weights were
+    // (1 - d, -d) instead of (1, 0)
+#pragma clang fp contract(off)
     const float yv = km1 * xb[i];
     const float y0 = floorf(yv), y1 = y0 + 1.0f;
     const int i0 = min(max((int)y0, 0), K - 1), i1 = min(max((int)y1, 0), K - 1);
@@ -699,10 +703,10 @@ __global__ __launch_bounds__(256) void diff_loss_bwd_kernel(const float* __restr
                                                             const float* __restrict__ g, float* __restrict__ da,
                                                             long n_per, int B, int mode, int accumulate) {
   const long total = n_per * B;
-  const float inv = 1.0f / (float)n_per;
+  const float np = (float)n_per;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const float d = a[i] - bb[i];
-    const float gb = g[i / n_per] * inv;
+    const float gb = g[i / n_per] / np;          // the per-sample scale g / n, one rounding (g * (1 / n) rounds twice)
     const float v = mode ? (d > 0.f ? gb : (d < 0.f ? -gb : 0.f)) : 2.0f * d * gb;
     da[i] = accumulate ? da[i] + v : v;
   }
@@ -894,7 +898,8 @@ extern "C" int shdr_avgpool2_bwd_f32(const float* dy, float* dx, int N, int H, i
 }
 extern "C" int shdr_maxpool2_bwd_f32(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = nhwc4("maxpool2_bwd", x, dx, N, H, W, C)) return rc;
-  SHDR_REQUIRE(dy && shdr::aligned16(dy), SHDR_E_NULL, "maxpool2_bwd: dy null or unaligned");
+  SHDR_REQUIRE(dy, SHDR_E_NULL, "maxpool2_bwd: dy is null");
+  SHDR_REQUIRE(shdr::aligned16(dy), SHDR_E_ALIGN, "maxpool2_bwd: dy must be 16-byte aligned");
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_bwd: H, W must be even");
   hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
                      S(stream), x, dy, dx, N, H, W, C);
@@ -903,8 +908,8 @@ extern "C" int shdr_maxpool2_bwd_f32(const float* x, const float* dy, float* dx,
 extern "C" int shdr_maxpool3s2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int H, int W, int C,
                                        void* stream) {
   if (int rc = nhwc4("maxpool3s2_bwd", x, dx, N, H, W, C)) return rc;
-  SHDR_REQUIRE(dy && shdr::aligned16(dy), SHDR_E_NULL, "maxpool3s2_bwd: dy null or unaligned");
-  SHDR_REQUIRE(y && shdr::aligned16(y), SHDR_E_NULL, "maxpool3s2_bwd: y (the pooled output) null or unaligned");
+  SHDR_REQUIRE(dy && y, SHDR_E_NULL, "maxpool3s2_bwd: dy or y (the pooled output) is null");
+  SHDR_REQUIRE(shdr::aligned16(dy) && shdr::aligned16(y), SHDR_E_ALIGN, "maxpool3s2_bwd: dy and y must be 16-byte aligned");
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);

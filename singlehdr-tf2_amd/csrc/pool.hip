@@ -166,8 +166,8 @@ __global__ __launch_bounds__(256) void gap_kernel(const float* __restrict__ x, f
     float4 t = part[0][q];
 #pragma unroll
     for (int i = 1; i < 16; ++i) t = add4(t, part[i][q]);
-    const float inv = 1.0f / (float)HW;
-    st4(y + n * C + c0, make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv));
+    const float hw = (float)HW;         // one correctly rounded division per output (sum * (1 / HW) rounds twice: 1.41 ulp at HW = 63)
+    st4(y + n * C + c0, make_float4(t.x / hw, t.y / hw, t.z / hw, t.w / hw));
   }
 }
 
