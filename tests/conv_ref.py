@@ -1,0 +1,138 @@
+"""float64 NumPy statement of the three convolution operations of the native-fp16 path, with the conventions of `shdr_conv2d_desc`
+(include/shdr.h): NHWC tensors, HWIO filters, cross-correlation, TF 'SAME' padding (the extra cell goes to the bottom / right, so a
+stride-2 layer is padded asymmetrically), two sources concatenated along the channels with the second one scaled by `x2_scale`.
+
+It calls nothing of the product.  tests/test_conv_ref.py pins it to oracle.ops.conv2d and to float64 autograd;
+tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element.
+"""
+import numpy as np
+
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
+LRELU_SLOPE = np.float32(0.1)              # the fp32 constant of the kernels (shdr::act_apply: v * 0.1f)
+
+
+def same_pad(size, k, stride):
+    """(output size, padding before) of TF 'SAME'"""
+    out = -(-size // stride)
+    return out, max((out - 1) * stride + k - size, 0) // 2
+
+
+def _geometry(h, w, kh, kw, stride, pad, out_hw):
+    ho, pt = same_pad(h, kh, stride)
+    wo, pl = same_pad(w, kw, stride)
+    if pad is not None:
+        pt, pl = pad
+    if out_hw is not None:
+        ho, wo = out_hw
+    return ho, wo, pt, pl
+
+
+def _padded(x, kh, kw, stride, ho, wo, pt, pl):
+    """x zero-padded so that output (oh, ow) and tap (a, b) read xp[:, oh * stride + a, ow * stride + b]"""
+    n, h, w, c = x.shape
+    pb = max((ho - 1) * stride + kh - pt - h, 0)
+    pr = max((wo - 1) * stride + kw - pl - w, 0)
+    return np.pad(x, ((0, 0), (pt, pb), (pl, pr), (0, 0)))
+
+
+def _sources(x, x2, x2_scale):
+    x = np.asarray(x, dtype=np.float64)
+    if x2 is None:
+        return x
+    return np.concatenate([x, np.asarray(x2, dtype=np.float64) * float(x2_scale)], axis=-1)
+
+
+def conv2d(x, x2, w, bias, stride, x2_scale, pad=None, out_hw=None):
+    """z[n, oh, ow, co] = bias[co] + sum_{a, b, c} xin[n, oh * stride - pad_t + a, ow * stride - pad_l + b, c] * w[a, b, c, co],
+    xin = concat[x, x2_scale * x2]; cells outside the input are zero.  `pad` = (pad_t, pad_l) and `out_hw` = (Ho, Wo) replace the
+    'SAME' values, as `_ops.conv2d_h` takes them (the polyphase input gradient)."""
+    xin = _sources(x, x2, x2_scale)
+    w = np.asarray(w, dtype=np.float64)
+    n, h, wd, c = xin.shape
+    kh, kw, cin, cout = w.shape
+    assert cin == c, (xin.shape, w.shape)
+    ho, wo, pt, pl = _geometry(h, wd, kh, kw, stride, pad, out_hw)
+    xp = _padded(xin, kh, kw, stride, ho, wo, pt, pl)
+    z = np.zeros((n, ho, wo, cout))
+    for a in range(kh):
+        for b in range(kw):
+            z += xp[:, a:a + (ho - 1) * stride + 1:stride, b:b + (wo - 1) * stride + 1:stride] @ w[a, b]
+    if bias is not None:
+        z += np.asarray(bias, dtype=np.float64)[:cout]
+    return z
+
+
+def dgrad(dz, w, x_shape, c_begin, c_count, scale, stride):
+    """gradient of sum(z * dz) w.r.t. ONE source of the 'SAME' forward conv: the source owns filter rows [c_begin, c_begin + c_count)
+    and enters the conv multiplied by `scale`.  dz may carry more channels per pixel than the filter has columns (a zero-padded head):
+    the extra ones carry no gradient."""
+    dz = np.asarray(dz, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    n, h, wd, c = x_shape
+    assert c == c_count
+    kh, kw, _, cout = w.shape
+    ho, wo, pt, pl = _geometry(h, wd, kh, kw, stride, None, None)
+    assert dz.shape[:3] == (n, ho, wo) and dz.shape[3] >= cout, (dz.shape, (n, ho, wo, cout))
+    dz = dz[..., :cout]
+    dxp = np.zeros_like(_padded(np.zeros((n, h, wd, c)), kh, kw, stride, ho, wo, pt, pl))
+    for a in range(kh):
+        for b in range(kw):
+            dxp[:, a:a + (ho - 1) * stride + 1:stride, b:b + (wo - 1) * stride + 1:stride] += dz @ w[a, b, c_begin:c_begin + c_count].T
+    return float(scale) * dxp[:, pt:pt + h, pl:pl + wd]
+
+
+def wgrad(x, x2, dz, w_shape, stride, x2_scale, cout_valid):
+    """gradient of sum(z * dz) w.r.t. the filter [kh, kw, C1 + C2, Cout]: rows [0, C1) from x, rows [C1, C1 + C2) from x2 (times
+    x2_scale); columns >= cout_valid are zero (dz channels beyond them are ignored)."""
+    dz = np.asarray(dz, dtype=np.float64)
+    kh, kw, cin, cout = w_shape
+    dw = np.zeros((kh, kw, cin, cout))
+    cv = cout if cout_valid is None else cout_valid
+    row = 0
+    for src, s in ((x, 1.0), (x2, float(x2_scale))):
+        if src is None:
+            continue
+        src = np.asarray(src, dtype=np.float64)
+        n, h, wd, c = src.shape
+        ho, wo, pt, pl = _geometry(h, wd, kh, kw, stride, None, None)
+        assert dz.shape[:3] == (n, ho, wo), (dz.shape, (n, ho, wo))
+        xp = _padded(src, kh, kw, stride, ho, wo, pt, pl)
+        for a in range(kh):
+            for b in range(kw):
+                patch = xp[:, a:a + (ho - 1) * stride + 1:stride, b:b + (wo - 1) * stride + 1:stride]
+                dw[a, b, row:row + c, :cv] = s * np.tensordot(patch, dz[..., :cv], axes=([0, 1, 2], [0, 1, 2]))
+        row += c
+    assert row == cin, (row, cin)
+    return dw
+
+
+def _act32(v, act):
+    if act == ACT_RELU:
+        return np.maximum(v, np.float32(0.0))
+    if act == ACT_LRELU:
+        return np.where(v >= 0, v, v * LRELU_SLOPE).astype(np.float32)          # ONE fp32 product with the kernel's constant
+    if act == ACT_TANH:
+        return np.tanh(v.astype(np.float64)).astype(np.float32)                  # (the one step that is not exact: see the GPU test)
+    return v
+
+
+def epilogue(z, act1, scale=None, shift=None, residual=None, act2=ACT_NONE):
+    """the inference epilogue of shdr_conv2d_fwd_fused_f16 after the fp32 accumulator + bias `z`, in the kernel's order
+    (shdr::fused_epi4_f16): act1, * scale[co], + shift[co], + residual, act2.  Every step is fp32 and rounded once; the result is the fp32
+    value that is stored (fp32 heads) or cast to fp16 (`to_f16`).  With scale a power of two the product is exact, so a compiler that
+    contracts `v * scale + shift` into one FMA computes the same value."""
+    v = np.asarray(z, dtype=np.float64).astype(np.float32)
+    c = v.shape[-1]
+    v = _act32(v, act1)
+    if scale is not None:
+        v = (v * np.asarray(scale, dtype=np.float32)[:c]).astype(np.float32)
+    if shift is not None:
+        v = (v + np.asarray(shift, dtype=np.float32)[:c]).astype(np.float32)
+    if residual is not None:
+        v = (v + np.asarray(residual)[..., :c].astype(np.float32)).astype(np.float32)
+    return _act32(v, act2)
+
+
+def to_f16(v):
+    """round to nearest even, ONE rounding from the float64 value (2049 -> 2048, 2051 -> 2052)"""
+    return np.asarray(v, dtype=np.float64).astype(np.float16)
