@@ -524,6 +524,27 @@ int64_t shdr_rgbe_rle_encode(const uint8_t* rgbe, int width, int height, uint8_t
  * or -1 (see shdr_last_error) on truncated or corrupt data; never reads past `size` or writes past the image. */
 int64_t shdr_rgbe_rle_decode(const uint8_t* data, int64_t size, int width, int height, uint8_t* rgbe);
 
+/* The same encoder on the device (csrc/hdr_rle.hip), for a BATCH of RGBE images of different sizes in one call: the bytes of
+ * image i are exactly what shdr_rgbe_rle_encode writes for it (adaptive RLE for 8 <= W <= 32767, flat lines outside).
+ *      rgbe        device bytes, 4-byte aligned: the images' [H][W][4] pixels back to back (a same-size batch [N][H][W][4] out of
+ *                  shdr_rgbe_encode_f32 is already in this layout)
+ *      shapes      int32 [n_images][2] = (H, W), as a host array, which is validated, and as the device copy of that very array
+ *                  (shapes_dev), which the kernels read
+ *      out         device bytes: the images' coded scanlines back to back; out_capacity must be at least the out_bytes of
+ *                  shdr_rgbe_rle_encode_batch_sizes (the host routine's bound, 4 + 4 * (W + W / 127 + 2) per coded line)
+ *      offsets     device int64 [n_images + 1]: image i is out[offsets[i] .. offsets[i + 1])
+ *      workspace   workspace_bytes of shdr_rgbe_rle_encode_batch_sizes, 16-byte aligned, owned by the caller
+ * Four stream-ordered launches (first rows, coded sizes per row and component, an exclusive scan over all rows, the write pass), no
+ * atomics -- the same input gives the same bytes -- no host wait and no allocation.  Arguments are checked before anything is
+ * launched.  The _timed form also fills stage_ms [SHDR_RLE_STAGES] with the device-event times of the four launches and then waits
+ * for the last one (measurement only). */
+#define SHDR_RLE_STAGES 4
+int shdr_rgbe_rle_encode_batch_sizes(const int32_t* shapes, int n_images, int64_t* out_bytes, int64_t* workspace_bytes);
+int shdr_rgbe_rle_encode_batch(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shapes_dev, int n_images, uint8_t* out,
+                               int64_t out_capacity, int64_t* offsets, void* workspace, void* stream);
+int shdr_rgbe_rle_encode_batch_timed(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shapes_dev, int n_images, uint8_t* out,
+                                     int64_t out_capacity, int64_t* offsets, void* workspace, void* stream, float* stage_ms);
+
 /* ---- training-set patch sampler (dataset.py:141-252; cv2.resize with the default INTER_LINEAR, see csrc/dataset.hip) ---- */
 /* HDRDataset._hdr_read_resize (dataset.py:181-202): RGBE [H0][W0][4] -> float BGR [H][W][3] (Ward's decode without +0.5,
  * channels reversed, clip(0, None)), resized by cv2's bilinear rule (half-pixel centres, replicated border). */

@@ -44,6 +44,9 @@ SIGNATURES = {
     "shdr_rgbe_encode_f32": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr]),
     "shdr_rgbe_rle_encode": (c_i64, [c_ptr, c_int, c_int, c_ptr, c_i64]),
     "shdr_rgbe_rle_decode": (c_i64, [c_ptr, c_i64, c_int, c_int, c_ptr]),
+    "shdr_rgbe_rle_encode_batch_sizes": (c_int, [c_ptr, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "shdr_rgbe_rle_encode_batch": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    "shdr_rgbe_rle_encode_batch_timed": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "shdr_hdr_load_resize_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "shdr_hdr_window_means_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "shdr_hdr_patch_sample_f32": (c_int, [c_ptr] * 5 + [c_int] * 4 + [c_ptr, c_ptr]),

@@ -1684,6 +1684,58 @@ def rgbe_encode(x, reverse_channels=False):
     return y
 
 
+def _rle_batch(rgbe, what):
+    """(flat uint8 pixels, host shape table int32 [n, 2]) of `rgbe`: one [H, W, 4] or [N, H, W, 4] tensor (used as it is, no copy) or a
+    list of [H, W, 4] tensors of different sizes (packed back to back on the device)"""
+    def chk(t):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 4):
+            raise TypeError("%s: expected uint8 RGBE device tensors [H, W, 4] or [N, H, W, 4] (see rgbe_encode)" % what)
+        if t.numel() == 0:
+            raise ValueError("%s: an image has no pixels: %s" % (what, tuple(t.shape)))
+        return t.contiguous()
+    if isinstance(rgbe, (list, tuple)):
+        if not rgbe:
+            raise ValueError("%s: no images" % what)
+        imgs = [chk(t) for t in rgbe]
+        if any(t.dim() != 3 for t in imgs):
+            raise TypeError("%s: a list holds single images [H, W, 4]" % what)
+        shapes = np.array([t.shape[:2] for t in imgs], dtype=np.int32)
+        flat = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([t.reshape(-1) for t in imgs])
+        return flat, shapes
+    t = chk(rgbe)
+    n = 1 if t.dim() == 3 else t.shape[0]
+    return t.reshape(-1), np.tile(np.array(t.shape[-3:-1], dtype=np.int32), (n, 1))
+
+
+def rgbe_rle_encode(rgbe, capacity=None, stage_ms=None):
+    """Radiance scanline bytes of RGBE images, coded on the device (csrc/hdr_rle.hip): byte for byte what the host routine
+    shdr_rgbe_rle_encode (hdr_io.rle_encode) writes.  rgbe: uint8 device tensor [H, W, 4] or [N, H, W, 4] (the layout rgbe_encode
+    returns: no copy), or a list of [H, W, 4] tensors of different sizes.  Returns (bytes uint8 [capacity], offsets int64 [N + 1]) on
+    the device: image i is bytes[offsets[i]:offsets[i + 1]].  Stream-ordered, no host wait.  capacity: size of the output buffer
+    (default and minimum: the host routine's bound); stage_ms: a list that receives the four launches' device times (measurement: the
+    call then waits)."""
+    lib = _lib.load()
+    flat, shapes = _rle_batch(rgbe, "rgbe_rle_encode")
+    n = shapes.shape[0]
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_rgbe_rle_encode_batch_sizes(_hptr(shapes), n, ctypes.byref(out_b), ctypes.byref(ws_b)),
+               "shdr_rgbe_rle_encode_batch_sizes")
+    dev = flat.device
+    cap = out_b.value if capacity is None else int(capacity)
+    out = torch.empty(max(cap, 1), device=dev, dtype=torch.uint8)
+    offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    shapes_dev = torch.from_numpy(shapes).to(dev)
+    args = (_ptr(flat), _hptr(shapes), _ptr(shapes_dev), n, _ptr(out), cap, _ptr(offsets), _ptr(ws), _stream())
+    if stage_ms is None:
+        _lib.check(lib.shdr_rgbe_rle_encode_batch(*args), "shdr_rgbe_rle_encode_batch")
+    else:
+        ms = (ctypes.c_float * 4)()
+        _lib.check(lib.shdr_rgbe_rle_encode_batch_timed(*args, ms), "shdr_rgbe_rle_encode_batch_timed")
+        stage_ms[:] = list(ms)
+    return out, offsets
+
+
 # ---------------------------------------------------------------------------
 # camera-pipeline simulator (joint_training.py:26-69), see csrc/camera.hip
 # ---------------------------------------------------------------------------

@@ -41,6 +41,7 @@ SOURCES = {
     "crf.hip": [],
     "glue.hip": [],
     "imageio.hip": [],
+    "hdr_rle.hip": [],
     "metrics.hip": [],
     "camera.hip": ["-ffp-contract=off"],
     "dataset.hip": ["-ffp-contract=off"],

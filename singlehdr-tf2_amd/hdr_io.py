@@ -7,7 +7,9 @@ Per image the reference does: cv2.imread (BGR) -> flip to RGB, /255 -> cubic res
 symmetric pad by 32 -> `bgr2rgb` (a second flip: the networks see BGR-ordered data) -> inference ->
 flip, crop the pad, cubic resize back -> cv2.imwrite('.hdr') of the channel-reversed result.  Here only the JPEG
 decode (PIL) and the file write are host work; the uint8 image goes to the device once and RGBE bytes (4 B/pixel
-instead of 12) come back -- every step in between is a libshdr kernel (csrc/imageio.hip).
+instead of 12) come back -- every step in between is a libshdr kernel (csrc/imageio.hip).  With encoder="device" the scanline
+RLE runs on the device too (csrc/hdr_rle.hip, the host routine's bytes) and only the coded bytes come back; reconstruct_files
+does that for a whole list of files in one batched encode and one copy.
 cv2 is not installed in this image, so cv2's behaviour is restated: INTER_CUBIC = a -0.75 bicubic
 with replicated borders, '.hdr' = Radiance RGBE with adaptive scanline RLE and the `-Y h +X w` orientation.
 """
@@ -52,15 +54,45 @@ def rle_encode(rgbe):
     return out[:n].tobytes()
 
 
-def write_hdr(path, rgbe):
-    """Radiance picture file from RGBE bytes [H, W, 4]"""
-    rgbe = np.asarray(rgbe)
-    if rgbe.dtype != np.uint8 or rgbe.ndim != 3 or rgbe.shape[2] != 4:
-        raise ValueError("write_hdr: expected uint8 [H, W, 4] RGBE (see _ops.rgbe_encode)")
-    h, w, _ = rgbe.shape
+def rle_encode_device(rgbe):
+    """uint8 RGBE device tensor [H, W, 4] or [N, H, W, 4], or a list of [H, W, 4] tensors of different sizes -> a list of scanline-RLE
+    `bytes`, one per image: rle_encode's bytes, coded by the device kernels (K.rgbe_rle_encode) and brought back in ONE copy of the
+    coded bytes (after a 8 (N + 1)-byte copy of the offsets that says how many there are) -- the pixels stay on the device"""
+    data, offsets = K.rgbe_rle_encode(rgbe)
+    off = offsets.cpu().numpy()
+    blob = data[:int(off[-1])].cpu().numpy().tobytes()
+    return [blob[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
+
+
+def _check_encoder(encoder, what):
+    if encoder not in ("host", "device"):
+        raise ValueError("%s: encoder must be 'host' or 'device', got %r" % (what, encoder))
+
+
+def _write_scanlines(path, h, w, data):
     with open(path, "wb") as f:
         f.write(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n" % (h, w))
-        f.write(rle_encode(rgbe))
+        f.write(data)
+
+
+def write_hdr(path, rgbe, encoder="host"):
+    """Radiance picture file from RGBE bytes [H, W, 4]: a host array or a uint8 device tensor.  encoder: "host" codes the scanlines
+    with the libshdr host routine (a device tensor is copied to the host first), "device" with the device kernels (a host array is
+    uploaded first); the files are identical"""
+    _check_encoder(encoder, "write_hdr")
+    on_device = isinstance(rgbe, torch.Tensor)
+    if not on_device:
+        rgbe = np.asarray(rgbe)
+    if rgbe.dtype != (torch.uint8 if on_device else np.uint8) or rgbe.ndim != 3 or rgbe.shape[2] != 4:
+        raise ValueError("write_hdr: expected uint8 [H, W, 4] RGBE (see _ops.rgbe_encode)")
+    h, w, _ = rgbe.shape
+    if encoder == "device":
+        if not on_device:
+            rgbe = torch.from_numpy(np.ascontiguousarray(rgbe)).to(torch.device("cuda", torch.cuda.current_device()))
+        data = rle_encode_device(rgbe)[0]
+    else:
+        data = rle_encode(rgbe.cpu().numpy() if on_device else rgbe)
+    _write_scanlines(path, h, w, data)
 
 
 def rle_decode(data, height, width):
@@ -157,33 +189,68 @@ class HdrReconstructor:
         # file's blue, i.e. the network output is read as BGR
         return y[0]
 
-    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil"):
-        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
-        decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
-        (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope)"""
+    def _read_device(self, ldr_path, decoder, what):
         if decoder not in ("pil", "device"):
-            raise ValueError("reconstruct_file: decoder must be 'pil' or 'device', got %r" % (decoder,))
+            raise ValueError("%s: decoder must be 'pil' or 'device', got %r" % (what, decoder))
         if decoder == "device":
             try:
                 from . import jpeg
             except ImportError:
                 import jpeg
-            y = self.reconstruct_device(jpeg.read_ldr_device(ldr_path))
-        else:
-            y = self.reconstruct_device(read_ldr(ldr_path))
-        write_hdr(hdr_path, K.rgbe_encode(y, reverse_channels=True).cpu().numpy())
+            return self.reconstruct_device(jpeg.read_ldr_device(ldr_path))
+        return self.reconstruct_device(read_ldr(ldr_path))
+
+    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host"):
+        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
+        decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
+        (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope).
+        encoder: "host" copies the RGBE pixels back and codes the scanlines on the host; "device" codes them on the device and copies
+        the coded bytes (write_hdr: the same file)"""
+        _check_encoder(encoder, "reconstruct_file")
+        y = self._read_device(ldr_path, decoder, "reconstruct_file")
+        rgbe = K.rgbe_encode(y, reverse_channels=True)
+        write_hdr(hdr_path, rgbe if encoder == "device" else rgbe.cpu().numpy(), encoder=encoder)
         if preview_path is not None:
             write_preview(preview_path, y, reverse_channels=True)
 
-    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil"):
-        """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder: as reconstruct_file"""
+    def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host"):
+        """reconstruct_file for a list of files: geometry and inference per image as there, then ALL results of the call coded in one
+        batched scanline-RLE launch sequence and brought back in one copy (encoder="device"), then the files are written.
+        encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
+        4 B per pixel"""
+        _check_encoder(encoder, "reconstruct_files")
+        ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
+        if len(ldr_paths) != len(hdr_paths):
+            raise ValueError("reconstruct_files: %d inputs but %d outputs" % (len(ldr_paths), len(hdr_paths)))
+        if decoder not in ("pil", "device"):
+            raise ValueError("reconstruct_files: decoder must be 'pil' or 'device', got %r" % (decoder,))
+        if encoder == "host":
+            for src, dst in zip(ldr_paths, hdr_paths):
+                self.reconstruct_file(src, dst, decoder=decoder)
+            return
+        if not ldr_paths:
+            return
+        rgbe = [K.rgbe_encode(self._read_device(src, decoder, "reconstruct_files"), reverse_channels=True) for src in ldr_paths]
+        for dst, img, data in zip(hdr_paths, rgbe, rle_encode_device(rgbe)):
+            _write_scanlines(dst, img.shape[0], img.shape[1], data)
+
+    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil", encoder="host", group=16):
+        """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder, encoder: as reconstruct_file;
+        with encoder="device" the files go through reconstruct_files in groups of `group`"""
+        _check_encoder(encoder, "reconstruct_dir")
         os.makedirs(output_dir, exist_ok=True)
         written = []
-        for path in sorted(glob.glob(os.path.join(dataset_dir, pattern))):
+        paths = sorted(glob.glob(os.path.join(dataset_dir, pattern)))
+        step = max(int(group), 1) if encoder == "device" else 1
+        for i in range(0, len(paths), step):
             start = time.perf_counter()
-            out = os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + ".hdr")          # :148-149
-            self.reconstruct_file(path, out, decoder=decoder)
-            written.append(out)
+            part = paths[i:i + step]
+            outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + ".hdr") for path in part]        # :148-149
+            if encoder == "device":
+                self.reconstruct_files(part, outs, decoder=decoder, encoder="device")
+            else:
+                self.reconstruct_file(part[0], outs[0], decoder=decoder)
+            written.extend(outs)
             if verbose:
                 print("Spends time : %s seconds" % (time.perf_counter() - start))
         return written
