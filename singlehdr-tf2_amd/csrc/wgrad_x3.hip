@@ -289,6 +289,8 @@ extern "C" int shdr_x3_split_planes_f32(const float* x, int64_t n, const float* 
 // 1 if the split-operand weight gradient takes source `which` of the layer: whole 64-channel tiles on both sides
 extern "C" int shdr_conv2d_wgrad_x3_ok_f32(const shdr_conv2d_desc* d, int which) {
   if (!d || (which != 0 && !(which == 1 && d->C2 > 0))) return 0;
+  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C1 <= 0 || d->C2 < 0 || d->Cout <= 0) return 0;
+  if (d->KH <= 0 || d->KW <= 0 || d->stride <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
   const int Cx = which ? d->C2 : d->C1, cout = d->cout_valid > 0 ? d->cout_valid : d->Cout;
   // (a source whose channel count is not a multiple of the 64-channel tile -- the 96-channel front end of the Linearization-Net stem --
   //  has its last tile loaded with zeros beyond Cx and stored up to ci_valid)

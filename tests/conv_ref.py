@@ -3,7 +3,8 @@
 stride-2 layer is padded asymmetrically), two sources concatenated along the channels with the second one scaled by `x2_scale`.
 
 It calls nothing of the product.  tests/test_conv_ref.py pins it to oracle.ops.conv2d and to float64 autograd;
-tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element.
+tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element, and
+tests/test_gpu_wgrad_f32_exact.py the fp32 weight-gradient kernels (section 4.4).
 """
 import numpy as np
 
@@ -136,3 +137,58 @@ def epilogue(z, act1, scale=None, shift=None, residual=None, act2=ACT_NONE):
 def to_f16(v):
     """round to nearest even, ONE rounding from the float64 value (2049 -> 2048, 2051 -> 2052)"""
     return np.asarray(v, dtype=np.float64).astype(np.float16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the fp32 weight-gradient helpers (csrc/wgrad.hip, wgrad_x3.hip), for tests/test_gpu_wgrad_f32_exact.py (DESIGN.md section 4.4)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def bias_grad(dz):
+    """db[c] = sum over every pixel of dz[..., c]"""
+    dz = np.asarray(dz, dtype=np.float64)
+    return dz.reshape(-1, dz.shape[-1]).sum(axis=0)
+
+
+def filter_transform(w, c_begin, c_count, scale):
+    """wt[kh, kw, co, ci - c_begin] = scale * w[KH - 1 - kh, KW - 1 - kw, ci, co], ci in [c_begin, c_begin + c_count): the filter of the
+    input gradient written as a forward convolution on dz (include/shdr.h: shdr_filter_transform_f32)"""
+    w = np.asarray(w, dtype=np.float64)
+    assert 0 <= c_begin and 0 < c_count and c_begin + c_count <= w.shape[2]
+    return float(scale) * np.ascontiguousarray(w[::-1, ::-1, c_begin:c_begin + c_count, :].transpose(0, 1, 3, 2))
+
+
+def range_exponent(bound):
+    """T = 11 - (frexp exponent of the fp32 bound in a range slot): 2^T brings the bound to [2^10, 2^11).  0 for a slot that holds no
+    bound -- zero, infinity, a NaN pattern, or a word with the sign bit set (the kernel compares the slot's bits as an unsigned
+    number); clamped to +-126.  (No finite fp32 bound reaches the lower clamp: the largest one gives T = -117.)"""
+    b = int(np.asarray(bound, dtype=np.float32).view(np.uint32))
+    if b == 0 or b >= 0x7F800000:
+        return 0
+    _, ex = np.frexp(np.float64(np.float32(bound)))
+    return int(min(max(11 - int(ex), -126), 126))
+
+
+def split_planes(x, bound):
+    """(hi, lo) fp16 planes of an fp32 tensor as csrc/wgrad_x3.hip states them: hi = fp16(x 2^T), lo = fp16(fp32(x 2^T - hi) 2^11),
+    T = range_exponent(bound), every conversion round-to-nearest-even.  x 2^T is a power-of-two multiple of an fp32 number and
+    x 2^T - hi is the residual of a rounding: both are exact before their own single rounding, which is what float64 gives here.
+    The kernel forms both products as FMAs with a +0 addend; that shows in one place, the sign of a zero: a -0 input gives +0 planes
+    (-0 + +0 = +0), while a negative value that underflows to zero in fp16 stays -0.  The `+ 0.0` below are those addends."""
+    x = np.asarray(x, dtype=np.float32).astype(np.float64)
+    xs = np.ldexp(x, range_exponent(bound)) + 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = xs.astype(np.float16)
+        rest = (xs - hi.astype(np.float64)).astype(np.float32)
+        lo = (np.ldexp(rest.astype(np.float64), 11) + 0.0).astype(np.float16)
+    return hi, lo
+
+
+def wgrad_split(x, dz, khw, stride, x_bound, z_bound, x_scale=1.0):
+    """the split-operand weight gradient of ONE source (csrc/wgrad_x3.hip), [kh, kw, Cx, Cout] in float64:
+        x_scale 2^-(Tx + Tz) (sum Xh Zh + 2^-11 sum (Xl Zh + Xh Zl)),   X 2^Tx = Xh + Xl 2^-11,  dZ 2^Tz = Zh + Zl 2^-11
+    -- the Xl Zl 2^-22 term is dropped, as the kernel drops it."""
+    xh, xl = (p.astype(np.float64) for p in split_planes(x, x_bound))
+    zh, zl = (p.astype(np.float64) for p in split_planes(dz, z_bound))
+    shape = tuple(khw) + (xh.shape[3], zh.shape[3])
+    hi = wgrad(xh, None, zh, shape, stride, 1.0, None)
+    lo = wgrad(xl, None, zh, shape, stride, 1.0, None) + wgrad(xh, None, zl, shape, stride, 1.0, None)
+    return float(x_scale) * np.ldexp(hi + np.ldexp(lo, -11), -(range_exponent(x_bound) + range_exponent(z_bound)))

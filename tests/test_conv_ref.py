@@ -1,6 +1,8 @@
-"""tests/conv_ref.py (the float64 reference of tests/test_gpu_fp16_conv_exact.py) pinned at 1e-12 on random float64 inputs:
+"""tests/conv_ref.py (the float64 reference of tests/test_gpu_fp16_conv_exact.py and tests/test_gpu_wgrad_f32_exact.py) pinned at 1e-12 on
+random float64 inputs:
 conv2d to oracle.ops.conv2d, dgrad / wgrad to float64 autograd through tests/torch_ref.py::conv2d, the explicit pad / out_hw form to
-the polyphase decomposition of the stride-2 input gradient."""
+the polyphase decomposition of the stride-2 input gradient; the helpers of the fp32 weight-gradient tests (bias_grad, filter_transform,
+range_exponent, split_planes, wgrad_split) to their definitions."""
 import numpy as np
 import pytest
 import torch
@@ -133,3 +135,113 @@ def test_to_f16_rounds_once_to_nearest_even():
     np.testing.assert_array_equal(got.astype(np.float64), [2048.0, 2052.0, 2050.0, -2048.0, float(np.float16(0.1))])
     # one rounding: 2049 + 2^-20 lies above the tie and goes up, although its fp32 rounding (2049) would go down
     assert float(C.to_f16(2049.0 + 2.0 ** -20)) == 2050.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the helpers of the fp32 weight-gradient tests (tests/test_gpu_wgrad_f32_exact.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_bias_grad_is_the_pixel_sum():
+    dz = np.random.default_rng(3).normal(size=(2, 5, 7, 6))
+    close(C.bias_grad(dz), np.einsum("nhwc->c", dz))
+    close(C.bias_grad(dz[0, 0]), dz[0, 0].sum(0))
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if c[7] == 1], ids=[i for c, i in zip(CASES, IDS) if c[7] == 1])
+def test_filter_transform_then_conv2d_is_the_input_gradient(case):
+    """every source of the layer: c_begin > 0, c_count < Cin and the scale of the second source included"""
+    n, h, w, c1, c2, cout, k, stride, x2s = case
+    x, x2, wt, b, dz = operands(case)
+    close(C.filter_transform(wt, 0, c1, 1.0), filter_transform(wt, 0, c1, 1.0))
+    close(C.conv2d(dz, None, C.filter_transform(wt, 0, c1, 1.0), None, 1, 1.0), C.dgrad(dz, wt, x.shape, 0, c1, 1.0, 1))
+    if c2:
+        close(C.conv2d(dz, None, C.filter_transform(wt, c1, c2, x2s), None, 1, 1.0), C.dgrad(dz, wt, x2.shape, c1, c2, x2s, 1))
+
+
+def test_filter_transform_indices_on_a_non_square_filter():
+    w = np.arange(3 * 4 * 5 * 2, dtype=np.float64).reshape(3, 4, 5, 2)
+    wt = C.filter_transform(w, 1, 3, 0.5)
+    assert wt.shape == (3, 4, 2, 3)
+    for kh, kw, co, ci in ((0, 0, 0, 0), (2, 3, 1, 2), (1, 2, 1, 0), (0, 3, 0, 1)):
+        assert wt[kh, kw, co, ci] == 0.5 * w[2 - kh, 3 - kw, 1 + ci, co]
+
+
+def test_range_exponent():
+    f = np.float32
+    assert C.range_exponent(2.0) == 9 and C.range_exponent(1.0) == 10 and C.range_exponent(np.nextafter(f(1.0), f(0.0))) == 11
+    assert C.range_exponent(1024.0) == 0 and C.range_exponent(2047.9) == 0 and C.range_exponent(2048.0) == -1
+    for b in (2.0, 1.7, 3e-8, 6e4, 1e-30, 1e30):
+        assert 2.0 ** 10 <= float(f(b)) * 2.0 ** C.range_exponent(b) < 2.0 ** 11
+    # no bound in the slot
+    assert C.range_exponent(0.0) == 0 and C.range_exponent(np.inf) == 0 and C.range_exponent(np.nan) == 0
+    assert C.range_exponent(-0.0) == 0 and C.range_exponent(-3.0) == 0 and C.range_exponent(np.uint32(0x7FC5A5A5).view(f)) == 0
+    # clamps: denormal and tiny bounds; the largest finite bound stays above the lower one
+    assert C.range_exponent(np.uint32(1).view(f)) == 126 and C.range_exponent(2.0 ** -116) == 126 and C.range_exponent(2.0 ** -115) == 125
+    assert C.range_exponent(np.finfo(f).max) == -117
+
+
+def test_split_planes_recombine_within_the_documented_bound():
+    """|x 2^T - (hi + lo 2^-11)| <= 3 * 2^-22 |x 2^T| (csrc/wgrad_x3.hip) on random fp32 data over eight decades, the slot holding the
+    tensor's own maximum; both planes are fp16 numbers, and the high plane alone is the fp16 rounding of the scaled tensor"""
+    rng = np.random.default_rng(17)
+    x = (rng.normal(size=20000) * np.exp(4.0 * rng.normal(size=20000))).astype(np.float32)
+    for scale in (1.0, 3e-8, 2e4):
+        xs = (x * np.float32(scale)).astype(np.float32)
+        bound = np.abs(xs).max()
+        hi, lo = C.split_planes(xs, bound)
+        assert hi.dtype == np.float16 and lo.dtype == np.float16 and np.isfinite(hi).all() and np.isfinite(lo).all()
+        t = C.range_exponent(bound)
+        want = np.ldexp(xs.astype(np.float64), t)
+        assert float(np.abs(want).max()) < 2048.0
+        np.testing.assert_array_equal(hi, want.astype(np.float16))
+        err = np.abs(want - (hi.astype(np.float64) + np.ldexp(lo.astype(np.float64), -11)))
+        normal = np.abs(want) >= 2.0 ** -14                                # (below: fp16 denormals, absolute bound 2^-24 * 2^-11)
+        assert (err[normal] <= 3 * 2.0 ** -22 * np.abs(want[normal])).all()
+        assert (err[~normal] <= 2.0 ** -36).all()
+
+
+def test_split_planes_ties_zeros_and_empty_slots():
+    f = np.float32
+    # stated in the scaled domain (slot 1024 -> T = 0): ties go to the even neighbour, the rest keeps its sign
+    x = np.array([1024.5, 1025.5, 2.0 + 2.0 ** -11, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 0.0, -0.0, 2.0 ** -25, -1024.5,
+                  -2.0 ** -26, -2.0 ** -40], dtype=f)
+    hi, lo = C.split_planes(x, 1024.0)
+    np.testing.assert_array_equal(hi.astype(np.float64), [1024.0, 1026.0, 2.0, 1.0, 1.0 + 2.0 ** -9, 0.0, 0.0, 0.0, -1024.0, 0.0, 0.0])
+    np.testing.assert_array_equal(lo.astype(np.float64), [1024.0, -1024.0, 1.0, 1.0, -1.0, 0.0, 0.0, 2.0 ** -14, -1024.0, -2.0 ** -15, 0.0])
+    # signs of zeros, as the kernel's FMAs with a +0 addend leave them: a -0 input gives +0 planes; a negative value that underflows
+    # keeps its sign (hi of -2^-26; both planes of -2^-40)
+    assert not np.signbit(hi[[5, 6, 7]]).any() and not np.signbit(lo[[5, 6]]).any()
+    assert np.signbit(hi[[9, 10]]).all() and np.signbit(lo[10])
+    # a slot without a bound leaves the tensor unscaled
+    for empty in (0.0, np.inf, np.nan):
+        h2, l2 = C.split_planes(x, empty)
+        np.testing.assert_array_equal(h2.view(np.uint16), hi.view(np.uint16))
+        np.testing.assert_array_equal(l2.view(np.uint16), lo.view(np.uint16))
+    # scaling is exact: the planes of x 2^-9 under the slot 2.0 are the planes of x under 1024
+    h3, l3 = C.split_planes(np.ldexp(x, -9), 2.0)
+    np.testing.assert_array_equal(h3.view(np.uint16), hi.view(np.uint16))
+    np.testing.assert_array_equal(l3.view(np.uint16), lo.view(np.uint16))
+
+
+@pytest.mark.parametrize("low_plane_of", ["x", "dz"])
+@pytest.mark.parametrize("k,stride", [(3, 1), (7, 2), (1, 1)])
+def test_wgrad_split_is_exact_when_one_low_plane_is_empty(low_plane_of, k, stride):
+    """X 2^Tx = Xh + Xl 2^-11 with Zl = 0 (or the other way round): the dropped term Xl Zl is zero and the model IS the weight gradient"""
+    rng = np.random.default_rng(k * 5 + stride)
+    n, h, w, cx, cout = 2, 9, 11, 5, 4
+    kk = rng.choice([-2.0, 2.0], size=(n, h, w, cx))
+    jj = rng.integers(-1, 2, size=(n, h, w, cx)) * np.sign(kk) + (rng.integers(0, 2, size=(n, h, w, cx)) * np.sign(kk))
+    fine = np.ldexp(kk + np.ldexp(jj, -11), -7)                           # slot 8.0 -> T = 7
+    ho, wo = -(-h // stride), -(-w // stride)
+    if low_plane_of == "x":
+        x, dz, xb, zb = fine, rng.integers(-2, 3, size=(n, ho, wo, cout)).astype(np.float64), 8.0, 2.0
+    else:
+        x = rng.integers(-2, 3, size=(n, h, w, cx)).astype(np.float64)
+        dz = np.ldexp(rng.choice([-2.0, 2.0], size=(n, ho, wo, cout)) + np.ldexp(rng.integers(0, 2, size=(n, ho, wo, cout)), -11), -7)
+        xb, zb = 2.0, 8.0
+    hi, lo = C.split_planes(fine if low_plane_of == "x" else dz, 8.0)
+    assert lo.any(), "the fine operand must have a non-empty low plane"
+    eh, el = C.split_planes(dz if low_plane_of == "x" else x, 2.0)
+    assert not el.any()
+    want = C.wgrad(x, None, dz, (k, k, cx, cout), stride, 1.0, None)
+    np.testing.assert_array_equal(C.wgrad_split(x, dz, (k, k), stride, xb, zb), want)
+    np.testing.assert_array_equal(C.wgrad_split(x, dz, (k, k), stride, xb, zb, 2.0 ** -8), want * 2.0 ** -8)
