@@ -21,10 +21,14 @@
 // kernels do.  A launch without a slot (the low-level entry point only) runs unscaled.
 //
 // Kernel (the layout of conv_f16_w3.hip with fp32 tensors in HBM): block = 16 x 16 pixels x 64 couts, 4 waves; per 32-channel chunk
-// the raw 18 x 18 fp32 patch is loaded ONCE into registers (coalesced 128-byte lines, issued under the MFMAs of the previous
-// chunk), split, and written as two fp16 images of 64-byte rows (16-byte slot XOR-swizzled: conflict-free ds_read_b128); the three
-// two filter images stream through LDS per tap (8 KB, register-staged one tap ahead, double-buffered).  Per tap and wave: 16 operand
-// reads feed 48 MFMAs.  58 KB of LDS, two blocks per CU.
+// the raw 18 x 18 fp32 patch is loaded ONCE into registers (coalesced 128-byte lines), split, and written as two fp16 images of
+// 64-byte rows (16-byte slot XOR-swizzled: conflict-free ds_read_b128); the two filter images stream through LDS per tap (8 KB,
+// stored one tap ahead, double-buffered).  Per tap and wave: 16 operand reads feed 48 MFMAs.  58 KB of LDS, two blocks per CU.
+// The patch of chunk c + 1 is issued at the top of chunk c, BEHIND the filter unit that tap LOOK of the chunk needs; the filter units
+// are loaded LOOK taps ahead through a scalar base and waited for with counted vmcnt, so the patch flies under LOOK + 1 taps of MFMAs
+// before a wait can sit it out (template parameter LOOK below).  In the order of the first rounds (LOOK = 0) it did NOT land "under the
+// MFMAs of the previous chunk", as this comment used to say: the compiler's "s_waitcnt vmcnt(0)" in front of the first tap's filter
+// address arithmetic drained it before any MFMA of the chunk ran.
 // Fused around it: MaxPool2D(2) in the epilogue (the conv + max-pool pairs of hallucination_net.py:43-75 / vgg16.py:72-83: the 2 x 2
 // window is two accumulator rows of a lane and its neighbour lane) and tf.image.resize(x, 2x, BILINEAR) in the prologue (UP = true;
 // hallucination_net.py:86-88, dequantization_net.py:25-27): the block loads the 10 x 10 LOW-RES patch of a chunk (a quarter of the
@@ -165,12 +169,26 @@ __device__ __forceinline__ int pcol(int fi) { return fi < 4 ? fi : (fi >= 12 ? f
 // with the tap counts, the input offset and the sub-filter of each phase taken from the argument arrays; the partial sums stay in the
 // accumulators (the four-launch form wrote and re-read them three times: 3 x 2 x N Ho Wo Cout floats).  The patch geometry is that of the
 // 4 x 4 phase for every phase: a 3-tap dimension loads one row / column it does not use.
-template <bool UP, int KH, int KW, bool MP = false>
+// LOOK: issue order of the global loads (the arithmetic, and with it every output bit, is the same for all three).
+//   0  the order of the first rounds (SHDR_X3_LEGACY_PREFETCH=1): load_patch(c + 1) at the top of a chunk, filter unit u + 1 loaded after the
+//      barrier of tap u through a per-thread 64-bit address.  The compiler builds that address in the registers the previous filter load
+//      wrote and guards the arithmetic with "s_waitcnt vmcnt(0)": vmcnt retires in order, so the first tap of a chunk sat out the whole
+//      prefetch issued a few instructions earlier ("conv_x3: the prefetch was drained before the first tap").
+//   1, 2  a unit is a block-uniform 64-bit base in SGPRs plus ONE loop-invariant VGPR byte offset (no address arithmetic, no wait between a
+//      tap's barrier and its MFMAs), loaded LOOK taps ahead into fr[LOOK][FJ] by inline asm (outside the compiler's scoreboard), and the
+//      unit that tap u + LOOK needs is issued IN FRONT of the chunk's patch loads.  The wait in front of store_filt is counted:
+//      "vmcnt(loads issued after the unit)" leaves the later units and, in the first LOOK taps of a chunk, the patch loads in flight -- the
+//      patch flies for LOOK + 1 taps before a wait can sit it out.  Out-of-image pieces are zeros without a load, so the number of patch
+//      loads a WAVE issues is not static: pcnt counts the pieces with at least one lane inside the image (a lower bound of the loads
+//      issued, which is the safe side), the wait is coded for pcnt = PJ, PJ - 1 and PJ - 2 (interior tiles and plain edges) and falls
+//      back to sitting the patch out.
+template <bool UP, int KH, int KW, bool MP = false, int LOOK = 0>
 __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   using G = X3G<KH, KW>;
   constexpr int PWID = G::PWID, PPIX = G::PPIX, PJ = G::PJ, PATCH_HALVES = G::PATCH_HALVES, NTAPS = KH * KW;
   static_assert(!UP || (KH == 3 && KW == 3), "the up-sampling prologue belongs to the 3 x 3 stride-1 form");
   static_assert(!MP || (!UP && KH == 4 && KW == 4), "the phase loop is built on the 4 x 4 patch geometry");
+  static_assert(LOOK >= 0 && LOOK <= 2 && LOOK <= KW, "filter look-ahead: 0 (legacy order), 1 or 2 taps");
   extern __shared__ __attribute__((aligned(16))) _Float16 xsm[];
   // LDS regions as expressions of the __shared__ symbol (pointer VARIABLES captured by the lambdas below lost their address space: the
   // compiler kept them as 64-bit generic pointers in scratch and reloaded them inside the tap loop)
@@ -193,7 +211,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   // ---- patch geometry (fixed per block): piece p = tid + 256 j -> (patch pixel, float4 of the 32-channel chunk) ----------------
   int ppix[PJ];                                                // pixel index in the image tensor, -1: padding / beyond the patch
   int pdst[PJ];                                                // half offset of the 8-byte destination inside an image
+  int pcnt = 0;                                                // LOOK > 0: patch loads per chunk this wave is sure to issue (wave-uniform)
   auto patch_geometry = [&](int bh, int bw) __attribute__((always_inline)) {                  // (MP: once per phase)
+    if (LOOK > 0) pcnt = 0;
 #pragma unroll
     for (int j = 0; j < (UP ? 0 : PJ); ++j) {
       const int p = tid + 256 * j;
@@ -203,9 +223,11 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
       const bool ok = pix < PPIX && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
       ppix[j] = ok ? (img * a.Hin + ih) * a.Win + iw : -1;
       pdst[j] = pix < PPIX ? pix * 32 + 8 * ((q >> 1) ^ sx(px)) + 4 * (q & 1) : -1;
+      if (LOOK > 0) pcnt += __ballot(ppix[j] >= 0) != 0ull;
     }
   };
   if (!MP) patch_geometry(a.bh, a.bw);
+  if (LOOK > 0 && !MP && !UP) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
   // UP: low-res pieces of this thread: piece p = tid + 256 j -> (low-res patch pixel, float4)
   int lpix[LRJ];
   if (UP) {
@@ -216,7 +238,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
       const int ly = pix / LRW, lx = pix - ly * LRW;
       const int r = (oh0 >> 1) - 1 + ly, c = (ow0 >> 1) - 1 + lx;
       lpix[j] = (pix < LRPIX && (unsigned)r < (unsigned)a.Hl && (unsigned)c < (unsigned)a.Wl) ? (img * a.Hl + r) * a.Wl + c : -1;
+      if (LOOK > 0) pcnt += __ballot(lpix[j] >= 0) != 0ull;
     }
+    if (LOOK > 0) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
   }
   const int nch1 = a.C1 >> 5, nch = (a.C1 + a.C2) >> 5;
   int nunits = nch * NTAPS;                                    // (MP: per phase)
@@ -227,11 +251,21 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   using Set1 = std::integral_constant<int, DEPTH - 1>;
   f32x4 pr_sets[DEPTH][PJ];
 #define pr (pr_sets[0])                                        /* the UP paths and the single-set kernels */
-  auto load_lr = [&](int c) __attribute__((always_inline)) {                                  // UP: low-res chunk c -> the first LRJ registers
+  // LOOK > 0: the registers of a prefetch are zeroed IN FRONT of the filter unit issued before it (zero_patch): the compiler cannot tell
+  // that the set's previous loads were waited for (store_patch sits under another condition) and guards the first write with a full wait,
+  // which must not find that unit in flight
+  auto zero_patch = [&](auto setc) __attribute__((always_inline)) {
+    constexpr int S = decltype(setc)::value;
+#pragma unroll
+    for (int j = 0; j < (UP ? LRJ : PJ); ++j) pr_sets[S][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < (UP ? LRJ : PJ); ++j) asm volatile("" : "+v"(pr_sets[S][j]));
+  };
+  auto load_lr = [&](int c, bool zeroed) __attribute__((always_inline)) {                     // UP: low-res chunk c -> the first LRJ registers
 #pragma unroll
     for (int j = 0; j < LRJ; ++j) {
       const int q = (tid + 256 * j) & 7;
-      pr[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (!zeroed) pr[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (lpix[j] >= 0) pr[j] = *reinterpret_cast<const f32x4*>(a.x1 + (size_t)(unsigned)lpix[j] * (unsigned)a.C1 + (c << 5) + 4 * q);
     }
   };
@@ -282,9 +316,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
       if (j & 1) __builtin_amdgcn_sched_barrier(0);            // two pieces (32 registers of taps) in flight, not eleven: no spills
     }
   };
-  auto load_patch = [&](int c, auto setc) __attribute__((always_inline)) {                    // chunk c -> register set setc
+  auto load_patch = [&](int c, auto setc, bool zeroed = false) __attribute__((always_inline)) {      // chunk c -> register set setc
     constexpr int S = decltype(setc)::value;
-    if (UP) { load_lr(c); return; }
+    if (UP) { load_lr(c, zeroed); return; }
     const bool second = c >= nch1;
     const float* src = second ? a.x2 : a.x1;
     const int Cs = second ? a.C2 : a.C1;
@@ -292,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
 #pragma unroll
     for (int j = 0; j < PJ; ++j) {
       const int q = (tid + 256 * j) & 7;
-      pr_sets[S][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (!zeroed) pr_sets[S][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (ppix[j] >= 0) pr_sets[S][j] = *reinterpret_cast<const f32x4*>(src + (size_t)(unsigned)ppix[j] * (unsigned)Cs + c0 + 4 * q);
     }
   };
@@ -313,15 +347,53 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     const int im = p >> 8, co = (p & 255) >> 2, slot = p & 3;
     fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ f4(co));
   }
-  u32x4 fr[FJ];
-  auto load_filt = [&](int u) __attribute__((always_inline)) {
+  // LOOK = 2: units alternate between two register slots.  The slot of a unit has to be a compile-time constant (a slot chosen by a branch
+  // on the unit's parity left the compiler free to keep it in other registers on either side and to copy a load in flight), so the nine
+  // taps of a chunk are unrolled: the unit of tap k sits in slot k & 1.  Nine is odd: behind the last tap, where the chunk's loads are
+  // waited for anyway, the unit of the next chunk's tap 1 moves from slot 0 to slot 1.  (Three slots indexed by kw need no move and spill.)
+  constexpr int NFR = LOOK < 2 ? 1 : 2;
+  static_assert(LOOK < 2 || (!MP && KH == 3 && KW == 3), "LOOK = 2 is built for the nine-tap kernels");
+  u32x4 fr[NFR][FJ];
+#pragma unroll
+  for (int s = 0; s < NFR; ++s)
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) fr[s][j] = (u32x4){0u, 0u, 0u, 0u};
+  auto load_filt = [&](int u) __attribute__((always_inline)) {                                // LOOK = 0
     const u32x4* g = reinterpret_cast<const u32x4*>(wbase + (size_t)u * UNIT_HALVES);
 #pragma unroll
-    for (int j = 0; j < FJ; ++j) fr[j] = g[tid + 256 * j];
+    for (int j = 0; j < FJ; ++j) fr[0][j] = g[tid + 256 * j];
   };
-  auto store_filt = [&](int buf) __attribute__((always_inline)) {
+  // LOOK > 0: the thread's two pieces lie 4096 bytes apart -- past the 13-bit signed offset field, hence the offset register points between them.
+  // Always issued, past the last unit of the layer (MP: of the phase) the last unit again: the number of loads in flight stays static.
+  // (s: a constant once the kw loop is unrolled)
+  const unsigned foff = 16u * (unsigned)tid + 2048u;
+  auto issue_filt = [&](int u, int s) __attribute__((always_inline)) {
+    const _Float16* ub = wbase + (size_t)(u < nunits ? u : nunits - 1) * UNIT_HALVES;
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:-2048" : "+v"(fr[s][0]) : "v"(foff), "s"(ub) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "+v"(fr[s][1]) : "v"(foff), "s"(ub) : "memory");
+  };
+  constexpr int PJL = UP ? LRJ : PJ;                           // patch loads of a thread and chunk at most
+  constexpr int WB = (LOOK > 1 ? LOOK - 1 : 0) * FJ;                        // loads of the later units, always behind the one waited for
+#define X3_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory")
+  auto store_filt = [&](int v) __attribute__((always_inline)) {                               // LOOK = 0: unit v, waited for by the compiler
 #pragma unroll
-    for (int j = 0; j < FJ; ++j) *reinterpret_cast<u32x4*>(filt + buf * UNIT_HALVES + fdst[j]) = fr[j];
+    for (int j = 0; j < FJ; ++j) *reinterpret_cast<u32x4*>(filt + (v & 1) * UNIT_HALVES + fdst[j]) = fr[0][j];
+  };
+  // LOOK > 0: unit v (slot s) has landed = everything but the (LOOK - 1) FJ loads of the later units and the np patch loads issued after
+  // it (np < 0: the prologue, nothing was issued after it); then registers -> LDS buffer v & 1.  The counted wait names no register
+  // (under a branch, an asm that ties fr is given registers of its own, and the copy into them reads the load in flight); ONE fence
+  // behind the branches ties the slot, so that every use of it is ordered after the wait.
+  auto wait_store_filt = [&](int v, int s, int np, bool st) __attribute__((always_inline)) {
+    if (np < 0) X3_WAIT_VM(0);
+    else if (np >= PJL) X3_WAIT_VM(WB + PJL);
+    else if (np >= PJL - 1) X3_WAIT_VM(WB + PJL - 1);
+    else if (np >= PJL - 2) X3_WAIT_VM(WB + PJL - 2);
+    else X3_WAIT_VM(WB);
+    asm volatile("" : "+v"(fr[s][0]), "+v"(fr[s][1]) : : "memory");
+    if (st) {                                                  // (only the store is conditional: no asm that names fr under a branch)
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) *reinterpret_cast<u32x4*>(filt + (v & 1) * UNIT_HALVES + fdst[j]) = fr[s][j];
+    }
   };
 
   f32x4 acc[MT][NT];
@@ -350,61 +422,119 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     nunits = nch * kh_n * kw_n;
     wbase = a.pwp[phase] + (size_t)pn * nunits * UNIT_HALVES;
     patch_geometry(a.pbh[phase], a.pbw[phase]);
+    if (LOOK > 0) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
     if (phase > 0) __syncthreads();                            // every wave has read the last tap of the previous phase (patch and filter buffers)
   }
   load_patch(0, Set0{});
   if (DEPTH == 2 && nch > 1) load_patch(1, Set1{});
-  load_filt(0);
+  if (LOOK == 0) load_filt(0);
+  else issue_filt(0, 0);
   if (!MP || phase == 0) x3_range_scale(a.xr1, a.xr2, xs, ixs);
   if (UP) {
     park_lr();
     __syncthreads();
   }
   store_patch(Set0{});
-  store_filt(0);
+  if (LOOK == 0) store_filt(0);
+  else wait_store_filt(0, 0, -1, true);
+  if (LOOK == 2) issue_filt(1, 1);
   // one chunk: `cur` = the register set chunk c was loaded into (already split into LDS: free for chunk c + DEPTH), `nxt` = the set of chunk c + 1
   auto chunk = [&](int c, auto cur, auto nxt) __attribute__((always_inline)) {
-    if (c + DEPTH < nch) load_patch(c + DEPTH, cur);           // lands under the taps of this chunk (and, for the 1 x 1 layers, of the next)
-#pragma unroll 1
-    for (int kh = 0; kh < (MP ? kh_n : KH); ++kh) {
-#pragma unroll
-      for (int kw = 0; kw < KW; ++kw) {                        // unrolled: acol[kw] stays a register
-        if (MP && kw >= kw_n) continue;                        // (block-uniform)
-        const int u = MP ? (c * kh_n + kh) * kw_n + kw : c * NTAPS + kh * KW + kw;
-        __syncthreads();                                       // unit u (and, at the first tap, the patch) is in LDS; buffer (u + 1) & 1 is free
-        if (u + 1 < nunits) load_filt(u + 1);
-        const _Float16* F = filt + (u & 1) * UNIT_HALVES;
-        const int rowh = (wave * MT + kh) * PWID * 32;          // scalar: first patch row of this wave and tap
-        // A-operand reads run one pixel row ahead of the MFMAs that use them
-        f16x8 wh[NT], ws[NT], wl[NT], ph[2], pl[2];
-        auto read_a = [&](int mi, int slot) __attribute__((always_inline)) {
-          const int o = rowh + mi * PWID * 32 + acol[kw];
-          ph[slot] = *reinterpret_cast<const f16x8*>(patch_h + o);
-          pl[slot] = *reinterpret_cast<const f16x8*>(patch_l + o);
-        };
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) {
-          wh[ni] = *reinterpret_cast<const f16x8*>(F + b_rd[ni]);
-          wl[ni] = *reinterpret_cast<const f16x8*>(F + IMG_HALVES + b_rd[ni]);
-        }
-        read_a(0, 0);
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni) ws[ni] = wh[ni] * (_Float16)(1.0f / 2048.0f);      // exact (power of two; gradual underflow below |wh| = 2^-3 as in fp16 itself)
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi) {
-          if (mi + 1 < MT) read_a(mi + 1, (mi + 1) & 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0);
-#pragma unroll
-          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[ni], pl[mi & 1], acc[mi][ni], 0, 0, 0);
-#pragma unroll
-          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (u + 1 < nunits) store_filt((u + 1) & 1);           // read after the next barrier
-      }
+    const bool pf = c + DEPTH < nch;
+    if (LOOK > 0) {
+      // the unit of tap LOOK in FRONT of the patch loads: the waits of taps 0 .. LOOK - 1 are for units older than the patch
+      zero_patch(cur);                                         // (unconditionally: under "if (pf)" every patch load got the compiler's full wait instead)
+      __builtin_amdgcn_sched_barrier(0);
+      issue_filt((MP ? c * kh_n * kw_n : c * NTAPS) + LOOK, LOOK % NFR);      // (slot of tap 0 + LOOK)
+      __builtin_amdgcn_sched_barrier(0);
     }
+    if (pf) load_patch(c + DEPTH, cur, LOOK > 0);              // lands under the taps of this chunk (and, for the 1 x 1 layers, of the next)
+    if (LOOK > 0) __builtin_amdgcn_sched_barrier(0);
+    const int np = pf ? pcnt : 0;
+    // One tap, as a macro: the LOOK = 0 loop below is the loop of the first rounds, statement for statement (its code is the same), and the
+    // new order peels the first row of a chunk off the kh loop (FIRST): its first tap's look-ahead unit is already issued and its first
+    // LOOK waits leave the patch in flight -- as straight-line code, since a filter load or a wait that names fr under a branch on kh lets
+    // the compiler hold the slot in other registers on the two sides and copy a load in flight.
+    //   barrier: unit u (and, at the first tap, the patch) is in LDS; buffer (u + 1) & 1 is free
+    //   rowh: scalar, the first patch row of this wave and tap; the A-operand reads run one pixel row ahead of the MFMAs that use them
+    //   ws = wh 2^-11: exact (power of two; gradual underflow below |wh| = 2^-3 as in fp16 itself)
+    //   the unit stored at the end is read after the next barrier
+#define X3_SLOT(D) (NFR == 1 ? 0 : (kh * KW + kw + (D)) % NFR)  /* slot of the unit D taps on */
+#define X3_TAP(FIRST)                                                                                                          \
+  {                                                                                                                             \
+    if (MP && kw >= kw_n) continue;                                                                                            \
+    const int u = MP ? (c * kh_n + kh) * kw_n + kw : c * NTAPS + kh * KW + kw;                                                 \
+    __syncthreads();                                                                                                           \
+    if (LOOK == 0) {                                                                                                           \
+      if (u + 1 < nunits) load_filt(u + 1);                                                                                    \
+    } else if (!(FIRST) || kw > 0) {                                                                                            \
+      issue_filt(u + LOOK, X3_SLOT(LOOK));                                                                                     \
+    }                                                                                                                          \
+    const _Float16* F = filt + (u & 1) * UNIT_HALVES;                                                                          \
+    const int rowh = (wave * MT + kh) * PWID * 32;                                                                             \
+                                                                                                                               \
+    f16x8 wh[NT], ws[NT], wl[NT], ph[2], pl[2];                                                                                \
+    auto read_a = [&](int mi, int slot) __attribute__((always_inline)) {                                                       \
+      const int o = rowh + mi * PWID * 32 + acol[kw];                                                                          \
+      ph[slot] = *reinterpret_cast<const f16x8*>(patch_h + o);                                                                 \
+      pl[slot] = *reinterpret_cast<const f16x8*>(patch_l + o);                                                                 \
+    };                                                                                                                         \
+_Pragma("unroll")                                                                                                              \
+    for (int ni = 0; ni < NT; ++ni) {                                                                                          \
+      wh[ni] = *reinterpret_cast<const f16x8*>(F + b_rd[ni]);                                                                  \
+      wl[ni] = *reinterpret_cast<const f16x8*>(F + IMG_HALVES + b_rd[ni]);                                                     \
+    }                                                                                                                          \
+    read_a(0, 0);                                                                                                              \
+_Pragma("unroll")                                                                                                              \
+    for (int ni = 0; ni < NT; ++ni) ws[ni] = wh[ni] * (_Float16)(1.0f / 2048.0f);                                              \
+_Pragma("unroll")                                                                                                              \
+    for (int mi = 0; mi < MT; ++mi) {                                                                                          \
+      if (mi + 1 < MT) read_a(mi + 1, (mi + 1) & 1);                                                                           \
+      __builtin_amdgcn_sched_barrier(0);                                                                                       \
+_Pragma("unroll")                                                                                                              \
+      for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0); \
+_Pragma("unroll")                                                                                                              \
+      for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[ni], pl[mi & 1], acc[mi][ni], 0, 0, 0); \
+_Pragma("unroll")                                                                                                              \
+      for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0); \
+      __builtin_amdgcn_sched_barrier(0);                                                                                       \
+    }                                                                                                                          \
+    if (LOOK == 0) {                                                                                                           \
+      if (u + 1 < nunits) store_filt(u + 1);                                                                                   \
+    } else {                                                                                                                   \
+      wait_store_filt(u + 1, X3_SLOT(1), ((FIRST) && kw < LOOK) ? np : 0, u + 1 < nunits);                                       \
+    }                                                                                                                          \
+  }
+    if (LOOK == 0) {
+#pragma unroll 1
+      for (int kh = 0; kh < (MP ? kh_n : KH); ++kh) {
+#pragma unroll
+        for (int kw = 0; kw < KW; ++kw) X3_TAP(false)          // unrolled: acol[kw] stays a register
+      }
+    } else if (LOOK == 1) {
+      {
+        const int kh = 0;
+#pragma unroll
+        for (int kw = 0; kw < KW; ++kw) X3_TAP(true)
+      }
+#pragma unroll 1
+      for (int kh = 1; kh < (MP ? kh_n : KH); ++kh) {
+#pragma unroll
+        for (int kw = 0; kw < KW; ++kw) X3_TAP(false)
+      }
+    } else {
+#pragma unroll
+      for (int kh = 0; kh < KH; ++kh) {
+#pragma unroll
+        for (int kw = 0; kw < KW; ++kw) X3_TAP(kh == 0)
+      }
+      // every load of the chunk has landed (the patch is needed below): the unit of the next chunk's tap 1, issued into slot 0 at tap 8
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(fr[0][0]), "+v"(fr[0][1]) : : "memory");
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) fr[NFR - 1][j] = fr[0][j];
+    }
+#undef X3_TAP
+#undef X3_SLOT
     if (c + 1 < nch) {
       if (UP) {
         park_lr();                                             // the scratch was last read before the tap loop of this chunk
@@ -422,6 +552,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   }
   }                                                            // phase loop
 #undef pr
+#undef X3_WAIT_VM
 
   // ---- epilogue: y = act2(affine(act1(acc * 2^-S + bias))), 16-byte stores (lane = pixel x 4 consecutive couts); the 2 x 2 pooling
   //      window of the optional second output is two rows of this lane and of its neighbour lane -----------------------------------
@@ -817,20 +948,34 @@ int x3_phases(const shdr_conv2d_desc* d, X3Phase ph[4]) {
 }
 inline int64_t x3_phase_floats(const X3Phase& p, int Ct, int Cout) { return X3_HEADER_FLOATS + (int64_t)p.th * p.tw * Ct * ((Cout + 63) / 64 * 64); }    // two fp16 images
 
-template <bool UP, int KH, int KW, bool MP = false>
-int launch_x3(const X3Args& a, hipStream_t st) {
+template <bool UP, int KH, int KW, bool MP, int LOOK>
+int launch_x3_look(const X3Args& a, hipStream_t st) {
   constexpr int lds = (UP ? X3G<KH, KW>::LDS_BYTES_UP : X3G<KH, KW>::LDS_BYTES) + X3G<KH, KW>::RANGE_BYTES;
   static bool attr_done[shdr::kMaxDevices] = {};
   const int dev_slot = shdr::device_slot();
   if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<UP, KH, KW, MP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<UP, KH, KW, MP, LOOK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     attr_done[dev_slot] = true;
   }
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
-  hipLaunchKernelGGL((conv_x3_kernel<UP, KH, KW, MP>), dim3((unsigned)nblk), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv_x3_kernel<UP, KH, KW, MP, LOOK>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return shdr::check_launch("conv_x3_kernel");
+}
+// SHDR_X3_LEGACY_PREFETCH=1: the issue order of the first rounds (LOOK = 0), kept for same-box A/B runs and the bit-identity tests
+// (tests/test_gpu_x3_prefetch.py); it goes, with LOOK = 0, once a later round has confirmed the numbers of DESIGN.md section 6
+// (profiles/r05_bench_ab.txt).  SHDR_X3_LOOK=1|2: the filter look-ahead (A/B; default 2, the faster by wall time).
+template <bool UP, int KH, int KW, bool MP = false>
+int launch_x3(const X3Args& a, hipStream_t st) {
+  if (SHDR_ENV("SHDR_X3_LEGACY_PREFETCH")) return launch_x3_look<UP, KH, KW, MP, 0>(a, st);
+  int look = 2;
+  if (const char* e = SHDR_ENV("SHDR_X3_LOOK")) look = atoi(e);
+  // LOOK = 2 is built for the nine-tap kernels (3 x 3, with and without the up-sampling prologue): the stem is out of registers at
+  // LOOK = 1, a 1 x 1 chunk has no second tap, and the phase-launch forms of the stem run only under SHDR_X3_STEM_PHASE_LAUNCHES=1
+  constexpr bool look2 = KH == 3 && KW == 3 && !MP;
+  if (look >= 2 && look2) return launch_x3_look<UP, KH, KW, MP, look2 ? 2 : 1>(a, st);
+  return launch_x3_look<UP, KH, KW, MP, 1>(a, st);
 }
 
 // conv_x3_1x1_kernel: 256 couts per block where Cout allows it, else 128 (Cout 64 and 32 keep conv_x3_kernel<false, 1, 1>: its block
