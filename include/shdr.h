@@ -583,6 +583,67 @@ int shdr_exr_load_resize_f32(const uint8_t* planes, int64_t size, const int64_t*
                              int64_t row_bytes, const int64_t* chan_off, const int32_t* chan_type, int H0, int W0, float* y,
                              int H, int W, int clip, void* stream);
 
+/* ---- OpenEXR output (exr.py encode_exr / write_exr; csrc/exr_write.hip, csrc/deflate.hip) ------------------------------ */
+/* Huffman-only zlib stream of src[0 .. n), 1 <= n <= 2^30 (host): 78 01, one final dynamic-Huffman block of literals with a
+ * fixed-length header (csrc/deflate_huffman.h), the big-endian Adler-32.  zlib's inflate reads it.  Returns the stream's length,
+ * or -1 (see shdr_last_error) for bad arguments or when `capacity` is less than that length (nothing is written then).  The
+ * stream is written whatever its size; a caller that stores a chunk raw when coding does not shrink it (OpenEXR's rule)
+ * compares the returned length with n: the chunk counts as coded only if the stream is STRICTLY smaller. */
+int64_t shdr_deflate_huffman_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity);
+/* The code lengths of that stream (host): lengths[257], literals 0..255 and end-of-block; 0 for unused symbols, 1..15 for the
+ * others, Kraft sum exactly 1. */
+int shdr_deflate_huffman_lengths_host(const uint8_t* src, int64_t n, uint8_t* lengths);
+/* The same encoder on the device for a BATCH of chunks: chunk c is data[offsets[c] .. offsets[c + 1]).
+ *      data         device bytes
+ *      raw          device bytes with the same offsets, or NULL for `data`: what is stored for a chunk that is not coded
+ *      offsets      int64 [n_chunks + 1], offsets[0] = 0, as a host array, which is validated, and as the device copy of that
+ *                   very array (offsets_dev), which the kernels read (clamped into the data)
+ *      pad          bytes left untouched in front of every stored chunk (room for a caller's chunk header), 0 .. 4096
+ *      out          device bytes: per chunk `pad` bytes, then the stream of shdr_deflate_huffman_host if it is strictly smaller
+ *                   than the chunk, else the chunk's `raw` bytes; out_capacity at least the out_bytes of the _sizes call
+ *                   (the chunks' bytes + pad * n_chunks)
+ *      out_offsets  device int64 [n_chunks + 1]: chunk c is stored at out[out_offsets[c] + pad .. out_offsets[c + 1])
+ *      coded        device uint8 [n_chunks]: 1 where the stream was stored
+ *      workspace    workspace_bytes of the _sizes call, 16-byte aligned, owned by the caller
+ *      stage_ms     NULL, or float [SHDR_DEFLATE_STAGES] for the device-event times of the three launches (measurement only: the
+ *                   call then waits for the last one)
+ * Three stream-ordered launches (histogram + code lengths + Adler-32 per chunk, an exclusive scan of the stored sizes, the write
+ * pass in tiles of SHDR_DEFLATE_TILE symbols), no global atomics -- the same input gives the same bytes -- no host wait and no
+ * allocation.  Arguments are checked before anything is launched. */
+#define SHDR_DEFLATE_STAGES 3
+#define SHDR_DEFLATE_TILE 1024
+int shdr_deflate_huffman_batch_sizes(const int64_t* offsets, int n_chunks, int pad, int64_t* out_bytes, int64_t* workspace_bytes);
+int shdr_deflate_huffman_batch(const uint8_t* data, const uint8_t* raw, const int64_t* offsets, const int64_t* offsets_dev,
+                               int n_chunks, int pad, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, uint8_t* coded,
+                               void* workspace, void* stream, float* stage_ms);
+
+/* float32 images [H][W][3] -> OpenEXR scanline bytes, for a BATCH of images of different sizes in one launch.  A chunk is `lines`
+ * scanlines (1: NONE / ZIPS, 16: ZIP; the last chunk of an image may hold fewer); a scanline is W samples of B, then G, then R
+ * (the name-sorted order), HALF or FLOAT.  reverse_channels = 0: the pixel is R, G, B; != 0: it is B, G, R (the networks' order).
+ * HALF is round to nearest even with subnormals, overflow to +-inf and NaN kept (numpy's astype(float16)); saturate != 0 first
+ * turns finite values beyond +-65504 into +-65504.
+ *      pixels     device floats: the images back to back
+ *      shapes     int32 [n_images][2] = (H, W), host: validated
+ *      table_dev  device int64 [3][n_images + 1], the device copy of the `table` of shdr_exr_pack_sizes: row 0 the first chunk of
+ *                 image i, row 1 its first pixel, row 2 H_i * 2^32 + W_i (column n_images: the totals, and 0)
+ *      chunk_off  device int64 [n_chunks + 1]: chunk c is bytes [chunk_off[c], chunk_off[c + 1]) of planar / predicted
+ *      planar     device bytes [bytes]: the scanline bytes
+ *      predicted  NULL, or device bytes [bytes]: per chunk, the even bytes then the odd bytes, delta-coded
+ *                 (d[0] = t[0], d[i] = t[i] - t[i-1] + 128): what ZIP / ZIPS deflate
+ * shdr_exr_pack_sizes validates the shapes and returns the number of chunks and of bytes and, if the pointers are given, fills
+ * the HOST arrays table [3 * (n_images + 1)] and chunk_off [n_chunks + 1] that the caller uploads. */
+int shdr_exr_pack_sizes(const int32_t* shapes, int n_images, int pixel_type, int lines, int64_t* n_chunks, int64_t* bytes,
+                        int64_t* table, int64_t* chunk_off);
+int shdr_exr_pack_f32(const float* pixels, const int32_t* shapes, int n_images, int pixel_type, int lines, int reverse_channels,
+                      int saturate, const int64_t* table_dev, const int64_t* chunk_off, uint8_t* planar, uint8_t* predicted,
+                      void* stream);
+/* Chunk headers and offset tables of a batch of files whose chunks shdr_deflate_huffman_batch stored with pad = 8: writes
+ * int32 y, int32 size in front of every chunk at records[out_offsets[c]] and the uint64 file offset of chunk c to
+ * tables[8 c]: header_len[i] + 8 * (chunks of image i) + the chunk's distance from the image's first chunk.  table_dev as
+ * above; header_len: device int64 [n_images], the bytes of file i in front of its offset table. */
+int shdr_exr_finish_chunks(uint8_t* records, uint8_t* tables, const int64_t* out_offsets, const int64_t* table_dev,
+                           const int64_t* header_len, int n_images, int64_t n_chunks, int lines, void* stream);
+
 /* ---- camera-pipeline simulator (joint_training.py:26-69 `_preprocessing`) ------------- */
 /* Philox4x32-10 block function (host): the counter-based generator the noise kernel uses; exported so that tests can
  * check the published known-answer vectors. */

@@ -54,6 +54,13 @@ SIGNATURES = {
     "shdr_exr_unpredict_u8": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr]),
     "shdr_exr_load_resize_f32": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_int, c_i64, c_ptr, c_ptr, c_int, c_int, c_ptr, c_int, c_int,
                                          c_int, c_ptr]),
+    "shdr_deflate_huffman_host": (c_i64, [c_ptr, c_i64, c_ptr, c_i64]),
+    "shdr_deflate_huffman_lengths_host": (c_int, [c_ptr, c_i64, c_ptr]),
+    "shdr_deflate_huffman_batch_sizes": (c_int, [c_ptr, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "shdr_deflate_huffman_batch": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "shdr_exr_pack_sizes": (c_int, [c_ptr, c_int, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr]),
+    "shdr_exr_pack_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "shdr_exr_finish_chunks": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_ptr]),
     "shdr_philox4x32_10": (c_int, [c_ptr, c_ptr, c_ptr]),
     "shdr_camera_expose_f32": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, ctypes.c_uint64, c_ptr]),
     "shdr_jpeg_round_trip_f32": (c_int, [c_ptr] * 6 + [c_int, c_int, c_int, c_ptr]),

@@ -1875,6 +1875,153 @@ def exr_load_resize(planes, offsets, lines, row_bytes, chan_off, chan_type, h0, 
 
 
 # ---------------------------------------------------------------------------
+# OpenEXR output (exr.py encode_exr), see csrc/exr_write.hip and csrc/deflate.hip
+# ---------------------------------------------------------------------------
+DEFLATE_TILE = 1024          # SHDR_DEFLATE_TILE: symbols per tile of the device writer
+
+
+def deflate_huffman_host(chunk):
+    """Huffman-only zlib stream of a chunk of bytes (libshdr host routine; zlib.decompress reads it).  The stream is returned
+    whatever its size: a chunk counts as coded only if len(stream) < len(chunk)"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(chunk), dtype=np.uint8)
+    out = np.empty(2 * src.size + 512, dtype=np.uint8)                    # 1122 + 15 bits per symbol at the very most
+    n = lib.shdr_deflate_huffman_host(_hptr(src), src.size, _hptr(out), out.size)
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n].tobytes()
+
+
+def deflate_huffman_lengths_host(chunk):
+    """the 257 code lengths (literals, end-of-block) of deflate_huffman_host's stream: uint8 [257]"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(chunk), dtype=np.uint8)
+    out = np.empty(257, dtype=np.uint8)
+    rc = lib.shdr_deflate_huffman_lengths_host(_hptr(src), src.size, _hptr(out))
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out
+
+
+def deflate_huffman(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offsets_dev=None):
+    """Huffman-only zlib streams of a batch of chunks, coded on the device (csrc/deflate.hip): byte for byte what the host routine
+    shdr_deflate_huffman_host writes.  data: uint8 device tensor; offsets: int64 [n + 1] (host array or tensor), chunk c is
+    data[offsets[c]:offsets[c + 1]], at least 1 byte.  Returns (bytes, out_offsets int64 [n + 1], coded uint8 [n]) on the device:
+    chunk c is stored at bytes[front + out_offsets[c] + pad : front + out_offsets[c + 1]] -- its stream where coded[c], else (the
+    stream would not be strictly smaller) the chunk's bytes of `raw` (default: of `data`) as they are.  pad: bytes left free in front
+    of every stored chunk; front: bytes left free in front of all of them.  Stream-ordered, no host wait.  stage_ms: a list that
+    receives the three launches' device times (measurement: the call then waits); offsets_dev: the device copy of a host `offsets`,
+    if the caller has one."""
+    lib = _lib.load()
+    data = _chk(data, "data", torch.uint8)
+    if isinstance(offsets, torch.Tensor):
+        off_host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
+        off_dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
+    else:
+        off_host, off_dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
+        if off_dev is not None and _chk(off_dev, "offsets_dev", torch.int64).numel() != off_host.size:
+            raise ValueError("deflate_huffman: offsets_dev is not a copy of offsets")
+    if data.dim() != 1 or off_host.ndim != 1 or off_host.size < 2 or int(off_host[-1]) > data.numel():
+        raise ValueError("deflate_huffman: expected data [size] and offsets [n_chunks + 1] that end within it")
+    if raw is not None:
+        raw = _chk(raw, "raw", torch.uint8)
+        if raw.dim() != 1 or raw.numel() < int(off_host[-1]):
+            raise ValueError("deflate_huffman: raw must hold the chunks' bytes too")
+    n = off_host.size - 1
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_deflate_huffman_batch_sizes(_hptr(off_host), n, int(pad), ctypes.byref(out_b), ctypes.byref(ws_b)),
+               "shdr_deflate_huffman_batch_sizes")
+    dev = data.device
+    if off_dev is None:
+        off_dev = torch.from_numpy(off_host).to(dev)
+    front = int(front)
+    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
+    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    coded = torch.empty(n, device=dev, dtype=torch.uint8)
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    ms = (ctypes.c_float * 3)() if stage_ms is not None else None
+    _lib.check(lib.shdr_deflate_huffman_batch(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n,
+                                              int(pad), out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws),
+                                              _stream(), ms), "shdr_deflate_huffman_batch")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return out, out_offsets, coded
+
+
+EXR_HALF, EXR_FLOAT = 1, 2
+
+
+def _exr_batch(images, what):
+    """(flat float32 pixels, host shape table int32 [n, 2]) of `images`: one [H, W, 3] or [N, H, W, 3] tensor (used as it is, no copy)
+    or a list of [H, W, 3] tensors of different sizes (packed back to back on the device): the convention of _rle_batch"""
+    def chk(t):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise TypeError("%s: expected float32 device tensors [H, W, 3] or [N, H, W, 3]" % what)
+        if t.dtype != torch.float32 or t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise ValueError("%s: expected float32 images [H, W, 3] or [N, H, W, 3], got %s %s" % (what, t.dtype, tuple(t.shape)))
+        if t.numel() == 0:
+            raise ValueError("%s: an image has no pixels: %s" % (what, tuple(t.shape)))
+        return _d(t).contiguous()
+    if isinstance(images, (list, tuple)):
+        if not images:
+            raise ValueError("%s: no images" % what)
+        imgs = [chk(t) for t in images]
+        if any(t.dim() != 3 for t in imgs):
+            raise ValueError("%s: a list holds single images [H, W, 3]" % what)
+        shapes = np.array([t.shape[:2] for t in imgs], dtype=np.int32)
+        flat = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([t.reshape(-1) for t in imgs])
+        return flat, shapes
+    t = chk(images)
+    n = 1 if t.dim() == 3 else t.shape[0]
+    return t.reshape(-1), np.tile(np.array(t.shape[-3:-1], dtype=np.int32), (n, 1))
+
+
+ExrPacked = collections.namedtuple("ExrPacked", "planar predicted chunk_off chunk_off_dev table table_dev shapes lines")
+"""planar / predicted: uint8 device tensors [bytes] (predicted None unless asked for); chunk_off: host int64 [n_chunks + 1], chunk c is
+bytes [chunk_off[c], chunk_off[c + 1]) of both (chunk_off_dev: its device copy); table: host int64 [3, n_images + 1] (first chunk, first
+pixel, H * 2^32 + W of every image; table_dev: its device copy); shapes: host int32 [n_images, 2]; lines: scanlines per chunk"""
+
+
+def exr_pack(images, pixel_type=EXR_HALF, lines=16, reverse_channels=False, saturate=True, predict=True):
+    """float32 images -> OpenEXR scanline bytes on the device, one launch for the whole batch (csrc/exr_write.hip).  images: one
+    [H, W, 3], one [N, H, W, 3] or a list of [H, W, 3] device tensors.  Every chunk (`lines` scanlines: 16 for ZIP, 1 for ZIPS / NONE)
+    holds per scanline W samples of B, then G, then R, HALF (numpy's astype(float16); saturate: finite values beyond +-65504 become
+    +-65504 first) or FLOAT.  reverse_channels: channel 0 of the input is blue (the networks' order).  predict: also the interleaved,
+    delta-coded bytes of every chunk, which ZIP / ZIPS deflate.  Returns an ExrPacked."""
+    lib = _lib.load()
+    flat, shapes = _exr_batch(images, "exr_pack")
+    n = shapes.shape[0]
+    n_chunks, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    args = (_hptr(shapes), n, int(pixel_type), int(lines))
+    _lib.check(lib.shdr_exr_pack_sizes(*args, ctypes.byref(n_chunks), ctypes.byref(nbytes), None, None), "shdr_exr_pack_sizes")
+    tabs = np.empty(3 * (n + 1) + n_chunks.value + 1, dtype=np.int64)           # one array, one upload
+    table, chunk_off = tabs[:3 * (n + 1)], tabs[3 * (n + 1):]
+    _lib.check(lib.shdr_exr_pack_sizes(*args, None, None, _hptr(table), _hptr(chunk_off)), "shdr_exr_pack_sizes")
+    dev = flat.device
+    tabs_dev = torch.from_numpy(tabs).to(dev)
+    table_dev, chunk_off_dev = tabs_dev[:3 * (n + 1)], tabs_dev[3 * (n + 1):]
+    planar = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    predicted = torch.empty(nbytes.value, device=dev, dtype=torch.uint8) if predict else None
+    _lib.check(lib.shdr_exr_pack_f32(_ptr(flat), _hptr(shapes), n, int(pixel_type), int(lines), int(bool(reverse_channels)),
+                                     int(bool(saturate)), _ptr(table_dev), _ptr(chunk_off_dev), _ptr(planar),
+                                     _ptr(predicted) if predict else None, _stream()), "shdr_exr_pack_f32")
+    return ExrPacked(planar, predicted, chunk_off, chunk_off_dev, table.reshape(3, n + 1), table_dev, shapes, int(lines))
+
+
+def exr_finish_chunks(out, out_offsets, packed, header_len):
+    """chunk headers (int32 y, int32 size) and uint64 offset tables into `out` of deflate_huffman(..., pad=8, front=8 * n_chunks):
+    the tables of all images fill the front, image after image; header_len: the bytes of every file in front of its table"""
+    lib = _lib.load()
+    n, n_chunks = packed.shapes.shape[0], packed.chunk_off.size - 1
+    hl = torch.from_numpy(np.ascontiguousarray(header_len, dtype=np.int64)).to(out.device)
+    if hl.numel() != n or out.numel() < 8 * n_chunks or out_offsets.numel() != n_chunks + 1:
+        raise ValueError("exr_finish_chunks: the buffers do not belong to this batch")
+    _lib.check(lib.shdr_exr_finish_chunks(out.data_ptr() + 8 * n_chunks, _ptr(out), _ptr(out_offsets), _ptr(packed.table_dev), _ptr(hl), n,
+                                          n_chunks, packed.lines, _stream()), "shdr_exr_finish_chunks")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # HDR-Real image folders (hdr_real.py), see csrc/hdr_real.hip
 # ---------------------------------------------------------------------------
 def _host_table(a, name, dtype):

@@ -46,6 +46,8 @@ SOURCES = {
     "camera.hip": ["-ffp-contract=off"],
     "dataset.hip": ["-ffp-contract=off"],
     "exr.hip": ["-ffp-contract=off"],
+    "exr_write.hip": ["-ffp-contract=off"],
+    "deflate.hip": [],
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
 }
@@ -70,7 +72,8 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
+    headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
+               os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []
     for src, extra in SOURCES.items():

@@ -21,8 +21,17 @@ Split of the work: the host reads and checks the bytes and inflates (zlib, which
 (libshdr's shdr_exr_rle_decode, via ctypes, which drops it too) every chunk; the device undoes the predictor and the
 interleave (shdr_exr_unpredict_u8) and converts / resizes straight from the planar scanlines (shdr_exr_load_resize_f32,
 csrc/exr.hip).  Every refusal is a ValueError naming the file and the reason.
+
+Writing (encode_exr / write_exr) mirrors that split.  The device converts float32 to HALF or FLOAT, lays the samples out as planar
+scanlines (B, G, R) and applies the interleave and the delta predictor, all chunks of a batch of images in one launch
+(K.exr_pack, csrc/exr_write.hip).  With encoder="host" the predicted bytes come back and zlib.compress deflates every chunk in a
+bounded thread pool (full deflate, the better ratio); with encoder="device" a Huffman-only zlib encoder codes them on the device
+(K.deflate_huffman, csrc/deflate.hip), a last kernel writes the chunk headers and the offset tables, and everything that follows
+the file headers comes back in one copy.  Either way a chunk that does not get strictly smaller is stored raw.  Files are
+single-part scanline, channels B, G, R of one type, data window (0, 0) - (W - 1, H - 1), INCREASING_Y, NONE / ZIPS / ZIP.
 """
 import collections
+import concurrent.futures
 import ctypes
 import struct
 import zlib
@@ -280,3 +289,109 @@ def read_exr(path, device=None):
     planes, offsets = upload(payload, device)
     out = torch.empty((payload.header.height, payload.header.width, 3), device=device, dtype=torch.float32)
     return load_resize(payload, planes, offsets, out, "RGB", clip=False)
+
+
+# ---- writing ----------------------------------------------------------------------------------------------------------------
+PIXEL_TYPES = {"half": HALF, "float": FLOAT}
+WRITE_COMPRESSIONS = {"none": NO_COMPRESSION, "zips": ZIPS_COMPRESSION, "zip": ZIP_COMPRESSION}
+MAX_DEFLATE_THREADS = 16           # zlib drops the GIL; the bound of dataset.MAX_LOAD_THREADS
+
+
+def _attr(name, atype, value):
+    return name + b"\0" + atype + b"\0" + struct.pack("<i", len(value)) + value
+
+
+def file_header(height, width, pixel_type, compression):
+    """magic, version 2 and the eight attributes OpenEXR requires, in name order, for a B, G, R image of one pixel type"""
+    chlist = b"".join(n + b"\0" + struct.pack("<iB3xii", pixel_type, 0, 1, 1) for n in (b"B", b"G", b"R")) + b"\0"
+    box = struct.pack("<iiii", 0, 0, width - 1, height - 1)
+    return (MAGIC + struct.pack("<I", 2)
+            + _attr(b"channels", b"chlist", chlist)
+            + _attr(b"compression", b"compression", bytes([compression]))
+            + _attr(b"dataWindow", b"box2i", box)
+            + _attr(b"displayWindow", b"box2i", box)
+            + _attr(b"lineOrder", b"lineOrder", bytes([INCREASING_Y]))
+            + _attr(b"pixelAspectRatio", b"float", struct.pack("<f", 1.0))
+            + _attr(b"screenWindowCenter", b"v2f", struct.pack("<ff", 0.0, 0.0))
+            + _attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) + b"\0")
+
+
+def _write_options(what, pixel_type, compression, encoder):
+    if pixel_type not in PIXEL_TYPES:
+        raise ValueError("%s: pixel type %r is not supported ('half' or 'float')" % (what, pixel_type))
+    if compression not in WRITE_COMPRESSIONS:
+        raise ValueError("%s: %s compression is not supported ('none', 'zips' and 'zip' are)" % (
+            what, compression.upper() if isinstance(compression, str) else repr(compression)))
+    if encoder not in ("host", "device"):
+        raise ValueError("%s: encoder must be 'host' or 'device', got %r" % (what, encoder))
+    return PIXEL_TYPES[pixel_type], WRITE_COMPRESSIONS[compression]
+
+
+def _on_device(images, what):
+    def one(x):
+        if isinstance(x, np.ndarray):
+            if x.dtype != np.float32:
+                raise ValueError("%s: expected float32 images, got %s" % (what, x.dtype))
+            return torch.from_numpy(np.ascontiguousarray(x)).to(torch.device("cuda", torch.cuda.current_device()))
+        return x
+    return [one(x) for x in images] if isinstance(images, (list, tuple)) else one(images)
+
+
+def _assemble(header, lines, stored):
+    """one file: header, offset table, then per chunk int32 y, int32 size and the stored bytes"""
+    n = len(stored)
+    pos = len(header) + 8 * n
+    table, parts = [], []
+    for c, data in enumerate(stored):
+        table.append(pos)
+        parts.append(struct.pack("<ii", c * lines, len(data)))
+        parts.append(data)
+        pos += 8 + len(data)
+    return header + struct.pack("<%dQ" % n, *table) + b"".join(parts)
+
+
+def encode_exr(images, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False):
+    """float32 images -> a list of OpenEXR files as `bytes`, one per image.  images: one [H, W, 3], one [N, H, W, 3] or a list of
+    [H, W, 3] of different sizes, device tensors (float32 host arrays are uploaded).  pixel_type "half" (numpy's astype(float16);
+    saturate: finite values beyond +-65504 become +-65504 instead of inf) or "float"; compression "none", "zips" or "zip";
+    reverse_channels: channel 0 is blue (HdrReconstructor.reconstruct_device's order).  encoder: who deflates ZIP / ZIPS chunks --
+    "host": zlib.compress per chunk in a thread pool; "device": the Huffman-only encoder of csrc/deflate.hip (larger files, no host
+    deflate, one copy of the finished bytes).  The whole batch is packed, predicted and (device) coded in one call each."""
+    ptype, comp = _write_options("encode_exr", pixel_type, compression, encoder)
+    lines = LINES_PER_CHUNK[comp]
+    packed = K.exr_pack(_on_device(images, "encode_exr"), ptype, lines, reverse_channels, saturate, predict=comp != NO_COMPRESSION)
+    headers = [file_header(int(h), int(w), ptype, comp) for h, w in packed.shapes]
+    first, chunk_off = packed.table[0], packed.chunk_off
+    n_chunks = chunk_off.size - 1
+    if comp != NO_COMPRESSION and encoder == "device":
+        out, out_offsets, _ = K.deflate_huffman(packed.predicted, chunk_off, raw=packed.planar, pad=8, front=8 * n_chunks,
+                                                offsets_dev=packed.chunk_off_dev)
+        K.exr_finish_chunks(out, out_offsets, packed, [len(h) for h in headers])
+        off = out_offsets.cpu().numpy()
+        blob = memoryview(out[:8 * n_chunks + int(off[-1])].cpu().numpy())          # sliced without copies, joined once per file
+        return [b"".join((headers[i], blob[8 * int(first[i]):8 * int(first[i + 1])],
+                          blob[8 * n_chunks + int(off[first[i]]):8 * n_chunks + int(off[first[i + 1]])])) for i in range(len(headers))]
+    bounds = [(int(chunk_off[c]), int(chunk_off[c + 1])) for c in range(n_chunks)]
+    if comp == NO_COMPRESSION:
+        planar = packed.planar.cpu().numpy()
+        stored = [planar[a:b] for a, b in bounds]
+    else:
+        predicted = packed.predicted.cpu().numpy()
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_DEFLATE_THREADS, n_chunks)) as pool:
+            stored = list(pool.map(zlib.compress, [predicted[a:b] for a, b in bounds]))
+        planar = None
+        for c, (a, b) in enumerate(bounds):
+            if len(stored[c]) >= b - a:                                   # does not shrink: the scanline bytes as they are
+                if planar is None:
+                    planar = packed.planar.cpu().numpy()
+                stored[c] = planar[a:b]
+    return [_assemble(headers[i], lines, stored[int(first[i]):int(first[i + 1])]) for i in range(len(headers))]
+
+
+def write_exr(path, image, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False):
+    """one float32 image [H, W, 3] -> an OpenEXR file (encode_exr)"""
+    if getattr(image, "ndim", 0) != 3:
+        raise ValueError("write_exr: expected one image [H, W, 3], got shape %s" % (tuple(getattr(image, "shape", ())),))
+    data = encode_exr([image], pixel_type, compression, encoder, saturate, reverse_channels)[0]
+    with open(path, "wb") as f:
+        f.write(data)

@@ -9,7 +9,8 @@ flip, crop the pad, cubic resize back -> cv2.imwrite('.hdr') of the channel-reve
 decode (PIL) and the file write are host work; the uint8 image goes to the device once and RGBE bytes (4 B/pixel
 instead of 12) come back -- every step in between is a libshdr kernel (csrc/imageio.hip).  With encoder="device" the scanline
 RLE runs on the device too (csrc/hdr_rle.hip, the host routine's bytes) and only the coded bytes come back; reconstruct_files
-does that for a whole list of files in one batched encode and one copy.
+does that for a whole list of files in one batched encode and one copy.  output_format="exr" stores the float estimate as OpenEXR
+instead (exr.encode_exr: HALF or FLOAT, ZIP by default) -- RGBE keeps an 8-bit mantissa, about 1 % steps.
 cv2 is not installed in this image, so cv2's behaviour is restated: INTER_CUBIC = a -0.75 bicubic
 with replicated borders, '.hdr' = Radiance RGBE with adaptive scanline RLE and the `-Y h +X w` orientation.
 """
@@ -25,9 +26,11 @@ import torch
 try:
     from . import _lib
     from . import _ops as K
+    from . import exr
 except ImportError:
     import _lib
     import _ops as K
+    import exr
 
 PADDING = 32          # test_real_refinement.py:135
 MULTIPLE = 64         # :129-133
@@ -67,6 +70,19 @@ def rle_encode_device(rgbe):
 def _check_encoder(encoder, what):
     if encoder not in ("host", "device"):
         raise ValueError("%s: encoder must be 'host' or 'device', got %r" % (what, encoder))
+
+
+def _check_format(output_format, what):
+    if output_format not in ("hdr", "exr"):
+        raise ValueError("%s: output_format must be 'hdr' or 'exr', got %r" % (what, output_format))
+
+
+def _exr_options(encoder, exr_options):
+    """encode_exr's keyword arguments for the file loop: the estimate is in the networks' channel order"""
+    opts = dict(encoder=encoder)
+    opts.update(exr_options or {})
+    opts["reverse_channels"] = True
+    return opts
 
 
 def _write_scanlines(path, h, w, data):
@@ -200,30 +216,48 @@ class HdrReconstructor:
             return self.reconstruct_device(jpeg.read_ldr_device(ldr_path))
         return self.reconstruct_device(read_ldr(ldr_path))
 
-    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host"):
+    def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host", output_format="hdr",
+                         exr_options=None):
         """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
         decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
         (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope).
         encoder: "host" copies the RGBE pixels back and codes the scanlines on the host; "device" codes them on the device and copies
-        the coded bytes (write_hdr: the same file)"""
+        the coded bytes (write_hdr: the same file).
+        output_format: "hdr" writes a Radiance file; "exr" writes the float estimate as OpenEXR without the RGBE conversion
+        (exr.encode_exr with `exr_options`, a dict of its keyword arguments such as pixel_type or compression; `encoder` then says
+        who deflates)"""
         _check_encoder(encoder, "reconstruct_file")
+        _check_format(output_format, "reconstruct_file")
         y = self._read_device(ldr_path, decoder, "reconstruct_file")
-        rgbe = K.rgbe_encode(y, reverse_channels=True)
-        write_hdr(hdr_path, rgbe if encoder == "device" else rgbe.cpu().numpy(), encoder=encoder)
+        if output_format == "exr":
+            exr.write_exr(hdr_path, y, **_exr_options(encoder, exr_options))
+        else:
+            rgbe = K.rgbe_encode(y, reverse_channels=True)
+            write_hdr(hdr_path, rgbe if encoder == "device" else rgbe.cpu().numpy(), encoder=encoder)
         if preview_path is not None:
             write_preview(preview_path, y, reverse_channels=True)
 
-    def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host"):
+    def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host", output_format="hdr", exr_options=None):
         """reconstruct_file for a list of files: geometry and inference per image as there, then ALL results of the call coded in one
         batched scanline-RLE launch sequence and brought back in one copy (encoder="device"), then the files are written.
         encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
-        4 B per pixel"""
+        4 B per pixel.  output_format="exr": the float estimates of the whole list go through ONE exr.encode_exr call, whatever the
+        encoder"""
         _check_encoder(encoder, "reconstruct_files")
+        _check_format(output_format, "reconstruct_files")
         ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
         if len(ldr_paths) != len(hdr_paths):
             raise ValueError("reconstruct_files: %d inputs but %d outputs" % (len(ldr_paths), len(hdr_paths)))
         if decoder not in ("pil", "device"):
             raise ValueError("reconstruct_files: decoder must be 'pil' or 'device', got %r" % (decoder,))
+        if output_format == "exr":
+            if not ldr_paths:
+                return
+            ys = [self._read_device(src, decoder, "reconstruct_files") for src in ldr_paths]
+            for dst, data in zip(hdr_paths, exr.encode_exr(ys, **_exr_options(encoder, exr_options))):
+                with open(dst, "wb") as f:
+                    f.write(data)
+            return
         if encoder == "host":
             for src, dst in zip(ldr_paths, hdr_paths):
                 self.reconstruct_file(src, dst, decoder=decoder)
@@ -234,10 +268,14 @@ class HdrReconstructor:
         for dst, img, data in zip(hdr_paths, rgbe, rle_encode_device(rgbe)):
             _write_scanlines(dst, img.shape[0], img.shape[1], data)
 
-    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil", encoder="host", group=16):
+    def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil", encoder="host", group=16,
+                        output_format="hdr", exr_options=None):
         """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder, encoder: as reconstruct_file;
-        with encoder="device" the files go through reconstruct_files in groups of `group`"""
+        with encoder="device" the files go through reconstruct_files in groups of `group`.  output_format="exr" names the outputs
+        *.exr"""
         _check_encoder(encoder, "reconstruct_dir")
+        _check_format(output_format, "reconstruct_dir")
+        fmt = dict(output_format=output_format, exr_options=exr_options)
         os.makedirs(output_dir, exist_ok=True)
         written = []
         paths = sorted(glob.glob(os.path.join(dataset_dir, pattern)))
@@ -245,11 +283,11 @@ class HdrReconstructor:
         for i in range(0, len(paths), step):
             start = time.perf_counter()
             part = paths[i:i + step]
-            outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + ".hdr") for path in part]        # :148-149
+            outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + "." + output_format) for path in part]        # :148-149
             if encoder == "device":
-                self.reconstruct_files(part, outs, decoder=decoder, encoder="device")
+                self.reconstruct_files(part, outs, decoder=decoder, encoder="device", **fmt)
             else:
-                self.reconstruct_file(part[0], outs[0], decoder=decoder)
+                self.reconstruct_file(part[0], outs[0], decoder=decoder, **fmt)
             written.extend(outs)
             if verbose:
                 print("Spends time : %s seconds" % (time.perf_counter() - start))

@@ -1,0 +1,122 @@
+"""OpenEXR output: float HDR images on the device -> finished HALF / ZIP files on the host, with the chunks deflated by the host
+(zlib in a thread pool) and by the device (the Huffman-only encoder of csrc/deflate.hip), measured, not gated.
+
+    python tools/exr_write_bench.py [--out result.json]
+
+Inputs, made on the device: 16 x 512 x 512, 1 x 512 x 512 and 1 x 4096 x 3072 float images, a ramp with 2 % noise and a smooth variant
+of each.  One process, alternating windows (host route, device route, host, ...), the median of 5 windows each, wall time from a
+synchronised start to the files' bytes on the host:
+  host route    K.exr_pack -> copy of the predicted bytes -> zlib.compress per chunk (16 threads) -> assembly
+  device route  K.exr_pack -> K.deflate_huffman (three launches) -> K.exr_finish_chunks -> copy of the offsets and of the finished bytes
+and the parts of both, each from a synchronised start, plus the device-event times of the encoder's three launches.  Both routes'
+files are read back with exr.read_exr and compared with the HALF-rounded input before anything is timed."""
+import argparse
+import concurrent.futures
+import importlib
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+import zlib
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+shdr = importlib.import_module("singlehdr-tf2_amd")
+K, exr = shdr._ops, shdr.exr
+
+WINDOWS = 5
+STAGES = ("stats", "scan", "write")
+
+
+def content(n, h, w, noise, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    yy, xx = torch.meshgrid(torch.arange(h, device="cuda", dtype=torch.float32), torch.arange(w, device="cuda", dtype=torch.float32),
+                            indexing="ij")
+    imgs = []
+    for i in range(n):
+        base = torch.stack((1.0 + xx / w + yy / h + 0.1 * i, 0.5 + 0.25 * xx / w + 0.1 * yy / h, 2.0 + 3.0 * (xx + yy) / (h + w)), dim=-1)
+        if noise:
+            base = base * (1.0 + noise * torch.randn(base.shape, device="cuda", generator=g))
+        imgs.append(base)
+    return torch.stack(imgs).contiguous()
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def check(x, files):
+    want = x[0].half().float()
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "check.exr")
+        with open(path, "wb") as f:
+            f.write(files[0])
+        assert torch.equal(exr.read_exr(path), want), "the file does not read back as the HALF-rounded input"
+
+
+def measure(x):
+    n, h, w, _ = x.shape
+    host_files = exr.encode_exr(x, "half", "zip", "host")               # warm-up, and the bench measures encoders that are right
+    dev_files = exr.encode_exr(x, "half", "zip", "device")
+    check(x, host_files)
+    check(x, dev_files)
+    raw = 6 * n * h * w
+    host, dev = [], []
+    parts = {k: [] for k in ("pack", "predicted_copy", "host_deflate", "device_deflate", "finish", "finished_copy")}
+    stages = {k: [] for k in STAGES}
+    for _ in range(WINDOWS):
+        host.append(wall(lambda: exr.encode_exr(x, "half", "zip", "host")))
+        dev.append(wall(lambda: exr.encode_exr(x, "half", "zip", "device")))
+        box = {}
+        parts["pack"].append(wall(lambda: box.__setitem__("p", K.exr_pack(x, K.EXR_HALF, 16))))
+        p = box["p"]
+        n_chunks = p.chunk_off.size - 1
+        parts["predicted_copy"].append(wall(lambda: box.__setitem__("host", p.predicted.cpu().numpy())))
+        chunks = [box["host"][int(a):int(b)] for a, b in zip(p.chunk_off[:-1], p.chunk_off[1:])]
+        t0 = time.perf_counter()
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(exr.MAX_DEFLATE_THREADS, n_chunks)) as pool:
+            list(pool.map(zlib.compress, chunks))
+        parts["host_deflate"].append((time.perf_counter() - t0) * 1e3)
+        kw = dict(raw=p.planar, pad=8, front=8 * n_chunks, offsets_dev=p.chunk_off_dev)
+        parts["device_deflate"].append(wall(lambda: box.__setitem__("z", K.deflate_huffman(p.predicted, p.chunk_off, **kw))))
+        out, off, _ = box["z"]
+        parts["finish"].append(wall(lambda: K.exr_finish_chunks(out, off, p, [300] * n)))
+        parts["finished_copy"].append(wall(lambda: out[:8 * n_chunks + int(off.cpu()[-1])].cpu()))
+        ms = []
+        K.deflate_huffman(p.predicted, p.chunk_off, stage_ms=ms, **kw)
+        for k, v in zip(STAGES, ms):
+            stages[k].append(v)
+    med = statistics.median
+    return {"images": n, "height": h, "width": w, "raw_bytes": raw, "chunks": n_chunks,
+            "host_coded_over_raw": sum(len(f) for f in host_files) / raw, "device_coded_over_raw": sum(len(f) for f in dev_files) / raw,
+            "host_route_ms": med(host), "device_route_ms": med(dev), "parts_ms": {k: med(v) for k, v in parts.items()},
+            "stage_event_ms": {k: med(v) for k, v in stages.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    result = {}
+    for name, (n, h, w) in (("batch16_512", (16, 512, 512)), ("single_512", (1, 512, 512)), ("single_4096x3072", (1, 3072, 4096))):
+        for kind, noise in (("noisy", 0.02), ("smooth", 0.0)):
+            result["%s_%s" % (name, kind)] = measure(content(n, h, w, noise, seed=n + h))
+            print(name, kind, json.dumps(result["%s_%s" % (name, kind)]), flush=True)
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
