@@ -192,3 +192,122 @@ def wgrad_split(x, dz, khw, stride, x_bound, z_bound, x_scale=1.0):
     hi = wgrad(xh, None, zh, shape, stride, 1.0, None)
     lo = wgrad(xl, None, zh, shape, stride, 1.0, None) + wgrad(xh, None, zl, shape, stride, 1.0, None)
     return float(x_scale) * np.ldexp(hi + np.ldexp(lo, -11), -(range_exponent(x_bound) + range_exponent(z_bound)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the split-operand forward model (csrc/conv_x3.hip, conv_x3n.hip), for tests/test_gpu_conv_x3_exact.py
+# ---------------------------------------------------------------------------------------------------------------------------------
+def weight_exponent(w, x2_scale=1.0):
+    """S of x3_pack_kernel / x3n_pack_kernel: 14 - (frexp exponent of max(max |w| max(1, |x2_scale|), 1e-30)), the product formed in fp32;
+    clamped to +-100.  2^S brings the largest filter element to [2^13, 2^14)."""
+    f = np.float32
+    mx = f(np.abs(np.asarray(w, dtype=np.float32)).max(initial=f(0.0))) * max(f(1.0), abs(f(x2_scale)))
+    mx = max(f(mx), f(1e-30))
+    _, ex = np.frexp(np.float64(mx))
+    return int(min(max(14 - int(ex), -100), 100))
+
+
+def weight_planes(w, c1, x2_scale=1.0):
+    """(S, wh, ws, wl) of an HWIO filter as the pack kernels state them, the planes fp16 numbers held in float64:
+    v = fp32(w 2^S), rows >= c1 one more fp32 product with x2_scale; wh = fp16(v), wl = fp16(v - wh), ws = fp16(wh 2^-11) -- an fp16
+    product (v_pk_mul_f16), which underflows gradually below |wh| = 2^-3."""
+    w = np.asarray(w, dtype=np.float32)
+    s = weight_exponent(w, x2_scale)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.ldexp(w.astype(np.float64), s).astype(np.float32)
+        if c1 < w.shape[2]:
+            v[:, :, c1:] = (v[:, :, c1:].astype(np.float64) * np.float64(np.float32(x2_scale))).astype(np.float32)
+        v = v.astype(np.float64)
+        wh = v.astype(np.float16)
+        wl = (v - wh.astype(np.float64)).astype(np.float32).astype(np.float16)
+        ws = np.ldexp(wh.astype(np.float64), -11).astype(np.float16)
+    return s, wh.astype(np.float64), ws.astype(np.float64), wl.astype(np.float64)
+
+
+def common_lsb(*arrays):
+    """the largest power of two of which every element of every array is an integer multiple (elements: multiples of 2^-40 below
+    2^23; 1.0 for arrays without a non-zero element)"""
+    bits = 0
+    for a in arrays:
+        q = np.ldexp(np.abs(np.asarray(a, dtype=np.float64)), 40)
+        assert np.array_equal(q, np.rint(q)) and float(q.max(initial=0.0)) < 2.0 ** 63, "common_lsb: value off the 2^-40 grid"
+        bits |= int(np.bitwise_or.reduce(q.astype(np.uint64).reshape(-1), initial=np.uint64(0)))
+    return 1.0 if bits == 0 else float(bits & -bits) * 2.0 ** -40
+
+
+def conv_split(x, x2, w, bias, stride, x2_scale, x_bound, x2_bound=None, pad=None, out_hw=None):
+    """the split-operand convolution as conv_x3_kernel / conv_x3_1x1_kernel / conv_x3n_kernel compute it, in float64:
+        T = range_exponent(the larger of the two bounds)   (x3_range_scale: ONE scale for both sources)
+        (xh, xl) = split_planes(concat[x, x2], that bound)  (the second source enters UNSCALED: its scale lives in the filter planes)
+        acc = conv(xh, wh) + conv(xl, ws) + conv(xh, wl)    (three MFMAs into one fp32 accumulator; xl wl 2^-11 is dropped)
+        z   = acc 2^-(S + T) + bias
+    Returns (z, sum of |terms| per output, common lsb of the terms), the last two in units of the accumulator: where
+    sum / lsb < 2^24 the fp32 accumulator holds every partial sum exactly, in any order."""
+    c1 = np.asarray(x).shape[-1]
+    xin = _sources(x, x2, 1.0)
+    bits = lambda b: int(np.asarray(b, dtype=np.float32).view(np.uint32))      # the kernel compares the slots' bit patterns, unsigned
+    bound = x_bound if x2 is None or bits(x_bound) >= bits(x2_bound) else x2_bound
+    t = range_exponent(bound)
+    xh, xl = (p.astype(np.float64) for p in split_planes(xin, bound))
+    s, wh, ws, wl = weight_planes(w, c1, x2_scale if x2 is not None else 1.0)
+    kw = dict(stride=stride, x2_scale=1.0, pad=pad, out_hw=out_hw)
+    pairs = [(p, q) for p, q in ((xh, wh), (xl, ws), (xh, wl)) if p.any() and q.any()]          # (an empty plane contributes nothing)
+    acc, total = 0.0, 0.0
+    for p, q in pairs:
+        acc = acc + conv2d(p, None, q, None, **kw)
+        total = total + conv2d(np.abs(p), None, np.abs(q), None, **kw)
+    if not pairs:
+        acc = total = conv2d(xh, None, wh, None, **kw)
+    groups = [slice(0, c1)] + ([slice(c1, xin.shape[-1])] if x2 is not None else [])           # (the sources differ in scale: an lsb per source)
+    lsb = min([common_lsb(p[..., g]) * common_lsb(q[:, :, g]) for p, q in pairs for g in groups if p[..., g].any() and q[:, :, g].any()] or [1.0])
+    z = np.ldexp(acc, -(s + t))
+    if bias is not None:
+        z = z + np.asarray(bias, dtype=np.float64)[:z.shape[-1]]
+    return z, total, lsb
+
+
+def resize2x(x):
+    """tf.image.resize(x, 2x, BILINEAR) with half-pixel centres in the order of resize2x_kernel and of conv_x3_kernel's expand_store:
+    horizontal first, then vertical, each a + (b - a) w with w = 0.25 (odd output index: neighbours m, m + 1) or 0.75 (even: m - 1, m),
+    edges clamped.  Computed in the dtype of x: float64 for the pin against the oracle, float32 with one rounding per operation."""
+    x = np.asarray(x)
+    dt = x.dtype.type
+
+    def lerp(a, axis):
+        n = a.shape[axis]
+        i = np.arange(2 * n)
+        m = i >> 1
+        odd = (i & 1) == 1
+        ia = np.where(odd, m, np.maximum(m - 1, 0))
+        ib = np.where(odd, np.minimum(m + 1, n - 1), m)
+        wgt = np.where(odd, dt(0.25), dt(0.75)).astype(x.dtype)
+        shape = [1] * a.ndim
+        shape[axis] = 2 * n
+        va, vb = np.take(a, ia, axis=axis), np.take(a, ib, axis=axis)
+        return (va + ((vb - va).astype(x.dtype) * wgt.reshape(shape)).astype(x.dtype)).astype(x.dtype)
+    return lerp(lerp(x, 2), 1)
+
+
+def _windows(y):
+    y = np.asarray(y, dtype=np.float32)
+    assert y.shape[1] % 2 == 0 and y.shape[2] % 2 == 0
+    return y[:, 0::2, 0::2], y[:, 0::2, 1::2], y[:, 1::2, 0::2], y[:, 1::2, 1::2]
+
+
+def maxpool2(y):
+    """MaxPool2D(2) of an fp32 tensor"""
+    tl, tr, bl, br = _windows(y)
+    return np.maximum(np.maximum(tl, bl), np.maximum(tr, br))
+
+
+def avgpool2(y):
+    """AveragePooling2D(2) in fp32 as the kernels add: 0.25 ((top-left + top-right) + (bottom-left + bottom-right)), each step rounded"""
+    tl, tr, bl, br = _windows(y)
+    return (np.float32(0.25) * ((tl + tr).astype(np.float32) + (bl + br).astype(np.float32)).astype(np.float32)).astype(np.float32)
+
+
+def project(y, proj):
+    """(sum_c proj[j][c] y[..., c], sum_c |proj[j][c] y[..., c]|) in float64: the projected output of shdr_conv2d_fwd_x3_projected_f32"""
+    y = np.asarray(y, dtype=np.float64)
+    p = np.asarray(proj, dtype=np.float64)
+    return y @ p.T, np.abs(y) @ np.abs(p).T

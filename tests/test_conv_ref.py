@@ -245,3 +245,174 @@ def test_wgrad_split_is_exact_when_one_low_plane_is_empty(low_plane_of, k, strid
     want = C.wgrad(x, None, dz, (k, k, cx, cout), stride, 1.0, None)
     np.testing.assert_array_equal(C.wgrad_split(x, dz, (k, k), stride, xb, zb), want)
     np.testing.assert_array_equal(C.wgrad_split(x, dz, (k, k), stride, xb, zb, 2.0 ** -8), want * 2.0 ** -8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the split-operand forward model (tests/test_gpu_conv_x3_exact.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+import test_gpu_conv_x3_exact as X                                       # (no device is touched by importing it: the operand recipes live there)
+
+
+def test_weight_exponent_and_planes():
+    f = np.float32
+    assert C.weight_exponent(np.array([1.0])) == 13 and C.weight_exponent(np.array([0.999])) == 14 and C.weight_exponent(np.array([-2.0])) == 12
+    assert C.weight_exponent(np.array([1.0]), 2.0 ** -8) == 13 and C.weight_exponent(np.array([1.0]), -4.0) == 11       # max(1, |x2_scale|)
+    assert C.weight_exponent(np.zeros(3)) == 100 and C.weight_exponent(np.array([2.0 ** 120])) == -100 and C.weight_exponent(np.array([2.0 ** 100])) == -87
+    # wh + wl == v exactly for weights down to max |w| 2^-17: the low plane of such a weight is still on the fp16 grid (2^-24 at the
+    # bottom) when the weight carries 21 significant bits; a full fp32 weight (24 bits) is met to 2^-22 of itself
+    rng = np.random.default_rng(5)
+    w = (rng.normal(size=(3, 3, 8, 16)) * np.exp2(rng.integers(-15, 1, size=(3, 3, 8, 16)))).astype(np.float32)
+    w = np.clip(w, -1.5, 1.5)
+    w[0, 0, 0, 0] = 1.5
+    keep = np.abs(w) >= 1.5 * 2.0 ** -17
+    s, wh, ws, wl = C.weight_planes(w, 8)
+    v = np.ldexp(w.astype(np.float64), s)
+    assert s == 13 and keep.mean() > 0.9
+    assert (np.abs(wh + wl - v)[keep] <= 2.0 ** -22 * np.abs(v)[keep]).all()
+    m, e = np.frexp(w.astype(np.float64))
+    w21 = np.ldexp(np.rint(np.ldexp(m, 21)), e - 21)
+    w21[0, 0, 0, 0] = 1.5
+    s, wh, ws, wl = C.weight_planes(w21, 8)
+    v = np.ldexp(w21, s)
+    assert s == 13 and np.array_equal((wh + wl)[keep], v[keep]) and (wl != 0).mean() > 0.9
+    assert np.array_equal(wh, v.astype(np.float16).astype(np.float64))
+    # ws is an fp16 PRODUCT: exact down to |wh| = 2^-3, gradual underflow below
+    assert np.array_equal(ws[np.abs(wh) >= 0.125], np.ldexp(wh, -11)[np.abs(wh) >= 0.125])
+    _, wh2, ws2, _ = C.weight_planes(np.array([[[[1.0, 2.0 ** -13 * (2.0 ** -4 + 2.0 ** -14)]]]]), 1)
+    assert wh2[0, 0, 0, 1] == 2.0 ** -4 + 2.0 ** -14 and ws2[0, 0, 0, 1] == 2.0 ** -15                   # (2^-15 + 2^-25: a tie on the 2^-24 grid, to even)
+    # rows >= c1 take one more fp32 product with x2_scale
+    _, wh3, _, wl3 = C.weight_planes(np.ones((1, 1, 2, 1)), 1, 2.0 ** -8)
+    assert wh3[0, 0, 0, 0] == 8192.0 and wh3[0, 0, 1, 0] == 32.0 and not wl3.any()
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_conv_split_is_the_convolution_when_both_low_planes_are_empty(case):
+    n, h, w, c1, c2, cout, k, stride, x2s = case
+    rng = np.random.default_rng(h + w)
+    x, xb = X.int_x(rng, (n, h, w, c1))
+    # the recipe wants a power-of-two scale (the scaled second source must stay an integer tensor): the shared case with 1 / 255 runs at 0.5
+    x2s = x2s if np.frexp(x2s)[0] == 0.5 else 0.5
+    x2, x2b = (X.int_x(rng, (n, h, w, c2))[0] / x2s, 2.0 / x2s) if c2 else (None, None)
+    wt = X.int_w(rng, (k, k, c1 + c2, cout))
+    b = rng.integers(-3, 4, size=cout).astype(np.float64)
+    z, total, lsb = C.conv_split(x, x2, wt, b, stride, x2s, xb, x2b)
+    np.testing.assert_array_equal(z, C.conv2d(x, x2, wt, b, stride, x2s))
+    assert float(total.max()) / lsb <= 4 * k * k * (c1 + c2)
+    # the explicit pad / out_hw form is handed through
+    z2 = C.conv_split(x, x2, wt, b, 1, x2s, xb, x2b, pad=(0, 1), out_hw=(h, w))[0]
+    np.testing.assert_array_equal(z2, C.conv2d(x, x2, wt, b, 1, x2s, pad=(0, 1), out_hw=(h, w)))
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_conv_split_stays_inside_the_documented_bound_on_gaussian_inputs(case):
+    """|conv_split - conv2d| <= 3 * 2^-22 * sum |x| |w| (the bound written at the top of csrc/conv_x3.hip), bound = the measured range"""
+    n, h, w, c1, c2, cout, k, stride, x2s = case
+    x, x2, wt, b, _ = (None if a is None else a.astype(np.float32).astype(np.float64) for a in operands(case))
+    xb = float(np.abs(x).max())
+    x2b = float(np.abs(x2).max()) if c2 else None
+    z = C.conv_split(x, x2, wt, b, stride, x2s, xb, x2b)[0]
+    ref = C.conv2d(x, x2, wt, b, stride, x2s)
+    mag = C.conv2d(np.abs(x), None if x2 is None else np.abs(x2), np.abs(wt), None, stride, abs(x2s))
+    ratio = float((np.abs(z - ref) / (2.0 ** -22 * mag)).max())
+    assert ratio <= 3.0, ratio
+    assert ratio > 0.0, "the dropped term must show on Gaussian inputs"
+
+
+def test_operand_recipes_produce_the_planes_they_promise():
+    rng = np.random.default_rng(11)
+    shape = (2, 9, 11, 16)
+    # int: T = 9, xh = 512 x, xl empty; S = 13, wh = 8192 w, ws = 4 w, wl empty
+    x, xb = X.int_x(rng, shape)
+    assert xb == 2.0 and float(np.abs(x).max()) == 2.0 and C.range_exponent(xb) == 9
+    xh, xl = C.split_planes(x, xb)
+    assert np.array_equal(xh.astype(np.float64), 512.0 * x) and not xl.any()
+    w = X.int_w(rng, (3, 3, 16, 8))
+    s, wh, ws, wl = C.weight_planes(w, 16)
+    assert s == 13 and np.array_equal(wh, 8192.0 * w) and np.array_equal(ws, 4.0 * w) and not wl.any()
+    # fine-x: T = 7, xh = k, xl = j
+    x, xb, k, j = X.fine_x(rng, shape)
+    assert xb == 8.0 and C.range_exponent(xb) == 7 and j.any() and (np.abs(k) == 2).any()
+    xh, xl = C.split_planes(x, xb)
+    assert np.array_equal(xh.astype(np.float64), k) and np.array_equal(xl.astype(np.float64), j)
+    x, xb, k, j = X.fine_x(rng, shape, kmax=1)
+    assert float(np.abs(k).max()) == 1.0 and np.array_equal(C.split_planes(x, xb)[1].astype(np.float64), j)
+    # fine-w: S = 13, wh = 4096 q, ws = 2 q, wl = r -- also in the rows of a second source scaled by 2^-8 (there 16 q, q 2^-7, r 2^-8)
+    w, q, r = X.fine_w(rng, (3, 3, 16, 8))
+    assert r.any() and not r[q == 0].any() and w[0, 0, 0, 0] == 1.0
+    s, wh, ws, wl = C.weight_planes(w, 16)
+    assert s == 13 and np.array_equal(wh, 4096.0 * q) and np.array_equal(ws, 2.0 * q) and np.array_equal(wl, r)
+    s, wh, ws, wl = C.weight_planes(w, 8, 2.0 ** -8)
+    assert s == 13 and np.array_equal(wh[:, :, 8:], 16.0 * q[:, :, 8:]) and np.array_equal(wl[:, :, 8:], r[:, :, 8:] * 2.0 ** -8)
+    assert np.array_equal(ws[:, :, 8:], q[:, :, 8:] * 2.0 ** -7) and np.array_equal(wh[:, :, :8], 4096.0 * q[:, :, :8])
+    # a padded head: the columns beyond it are zero
+    assert not X.fine_w(rng, (3, 3, 16, 16), cols=3)[0][..., 3:].any() and not X.int_w(rng, (3, 3, 16, 16), cols=5)[..., 5:].any()
+
+
+def test_fine_x_and_fine_w_together_model_the_kernel_not_the_ideal():
+    """with both low planes non-empty the dropped xl wl 2^-11 term is non-zero: the reference differs from the true convolution on
+    nearly every output, by exactly that term"""
+    rng = np.random.default_rng(23)
+    x, xb, k, j = X.fine_x(rng, (1, 9, 11, 32))
+    w, q, r = X.fine_w(rng, (3, 3, 32, 16))
+    z, total, lsb = C.conv_split(x, None, w, None, 1, 1.0, xb)
+    ref = C.conv2d(x, None, w, None, 1, 1.0)
+    assert float(total.max()) / lsb < 2.0 ** 24
+    assert (z != ref).mean() > 0.9
+    dropped = np.ldexp(C.conv2d(j, None, r, None, 1, 1.0), -(11 + 13 + 7))
+    np.testing.assert_array_equal(ref - z, dropped)
+
+
+def test_resize2x_matches_the_oracle_and_is_exact_on_integers():
+    rng = np.random.default_rng(2)
+    for shape in ((1, 1, 3, 2), (2, 8, 8, 3), (1, 9, 11, 4), (1, 1, 1, 1)):
+        a = rng.normal(size=shape)
+        close(C.resize2x(a), ops.resize_bilinear_2x(a))
+        i = rng.integers(-2, 3, size=shape).astype(np.float64)
+        np.testing.assert_array_equal(C.resize2x(i.astype(np.float32)).astype(np.float64), C.resize2x(i))
+    # order and weights: horizontal first, a + (b - a) w with w in {0.25, 0.75}, edges clamped
+    row = np.array([0.0, 4.0, 8.0]).reshape(1, 1, 3, 1)
+    np.testing.assert_array_equal(C.resize2x(row)[0, 0, :, 0], [0.0, 1.0, 3.0, 5.0, 7.0, 8.0])
+    assert C.resize2x(row).shape == (1, 2, 6, 1)
+
+
+def test_pooled_and_projected_outputs():
+    f = np.float32
+    y = np.array([[1.0, -2.0, 3.0, 0.5], [4.0, 0.0, -1.0, 0.25]], dtype=f).reshape(1, 2, 4, 1)
+    np.testing.assert_array_equal(C.maxpool2(y)[0, 0, :, 0], [4.0, 3.0])
+    np.testing.assert_array_equal(C.avgpool2(y)[0, 0, :, 0], [0.75, 0.6875])
+    # the order of the sums: (tl + tr) + (bl + br), each rounded to fp32
+    big = np.array([[2.0 ** 24, 1.0], [1.0, -(2.0 ** 24)]], dtype=f).reshape(1, 2, 2, 1)
+    assert C.avgpool2(big)[0, 0, 0, 0] == f(0.25) * ((f(2.0 ** 24) + f(1.0)) + (f(1.0) + f(-(2.0 ** 24))))
+    y3 = np.arange(6, dtype=np.float64).reshape(1, 1, 2, 3)
+    proj = np.array([[1.0, 0.0, -1.0], [2.0, 2.0, 2.0], [0.0, 0.0, 0.0]])
+    yj, tj = C.project(y3, proj)
+    np.testing.assert_array_equal(yj[0, 0], [[-2.0, 6.0, 0.0], [-2.0, 24.0, 0.0]])
+    np.testing.assert_array_equal(tj[0, 0], [[2.0, 6.0, 0.0], [8.0, 24.0, 0.0]])
+    assert C.common_lsb(np.array([0.75, 2.0]), np.array([0.0])) == 0.25 and C.common_lsb(np.zeros(3)) == 1.0
+
+
+_ALL = X.X3_3X3 + X.X3_POOLED + X.X3_UP + X.X3_1X1 + X.X3_STEM + X.X3N + X.TANH
+
+
+@pytest.mark.parametrize("o", _ALL)
+def test_every_forward_case_meets_its_precondition_on_the_reference_alone(o):
+    r = X.reference(o)
+    assert r["worst"] < 1.0
+    if o["mode"] == "fxw":                                               # these cases show that the test models the kernel, not the ideal
+        xin = r["x"]
+        ideal = C.conv2d(xin, r["x2"], r["w"], None, o["stride"], o["x2s"])
+        split = C.conv_split(xin, r["x2"], r["w"], None, o["stride"], o["x2s"], r["xb"], r["x2b"])[0]
+        assert (ideal != split)[..., :r["cv"]].mean() > 0.5
+
+
+@pytest.mark.parametrize("o", X.DGRAD)
+def test_every_input_gradient_case_meets_its_precondition_on_the_reference_alone(o):
+    X.dgrad_reference(o)
+
+
+@pytest.mark.parametrize("o", X.X3N_BIG + X.X3N_BIG_OTHER)
+def test_every_1056_tile_case_meets_its_precondition_on_the_reference_alone(o):
+    """(the four 16 -> 16 forms share one float64 model: three of these cases cost an epilogue each)"""
+    assert (o["h"] // 16) * (o["w"] // 16) == 1056 and o["mode"] == "int"
+    r = X.big_reference(o) if o["c1"] == 16 and o["c2"] == 0 else X.reference(o)
+    assert r["worst"] < 1.0
