@@ -192,6 +192,8 @@ extern "C" int shdr_conv2d_prepare_filter_f32(const shdr_conv2d_desc* d, int has
 // ... and on the split-operand plan where the up-sampling pass is dear next to the convolution: the in-kernel expansion is repeated by
 // every 64-cout block of a tile, the resize2x pass costs 1 / Cout of the layer -- measured (tools/up2_bench.py, 16 x 512^2 step shapes):
 // 128 -> 64 2.70 -> 2.03 ms, 256 -> 128 2.13 -> 1.88, 512 -> 256 1.86 -> 1.79, 512 -> 512 0.91 -> 0.96: fused up to 256 couts
+// (re-measured with the 128-cout blocks, which expand a chunk once per 128 couts, tools/x3_wide_ab.py: 512 -> 512 at 32^2 x2 0.726 resize +
+// plain against 0.750 fused, at 16^2 x2 0.190 against 0.200 -- the limit stays)
 inline bool up2_in_kernel(const shdr_conv2d_desc* d, int plan) {
   if (d->C2 != 0) return false;
   if (plan == SHDR_PLAN_X3) return d->KH == 3 && d->stride == 1 && (d->Cout <= 256 || SHDR_ENV("SHDR_X3_UP_ALWAYS") != nullptr);

@@ -134,6 +134,8 @@ __device__ __forceinline__ void x3_split4(const f32x4 v, float xs, unsigned (&h)
 // after the other per address (measured ~4 ns each): one per WAVE cost the small layers of the U-Nets 15 - 35 us per launch, all of it
 // in the first round of blocks, which finish together and all still see the slot empty.
 // `seen` = the slot's value loaded at the START of the epilogue (the load's round trip to the memory side runs under the stores)
+// (NW = 8: the eight waves of conv_x3_wide_kernel, eight words)
+template <int NW = 4>
 __device__ __forceinline__ void x3_range_out(unsigned* slot, float m, int lane, int wave, unsigned seen, unsigned* lds) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
@@ -141,7 +143,12 @@ __device__ __forceinline__ void x3_range_out(unsigned* slot, float m, int lane, 
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (not __syncthreads(): that would also sit out the output stores)
   if (threadIdx.x == 0) {
     const unsigned b01 = lds[0] > lds[1] ? lds[0] : lds[1], b23 = lds[2] > lds[3] ? lds[2] : lds[3];
-    const unsigned b = b01 > b23 ? b01 : b23;                  // non-negative floats order like their bit patterns
+    unsigned b = b01 > b23 ? b01 : b23;                        // non-negative floats order like their bit patterns
+    if (NW == 8) {
+      const unsigned b45 = lds[4] > lds[5] ? lds[4] : lds[5], b67 = lds[6] > lds[7] ? lds[6] : lds[7];
+      const unsigned b47 = b45 > b67 ? b45 : b67;
+      b = b47 > b ? b47 : b;
+    }
 #ifndef SHDR_ABL_NO_RANGE_ATOMIC
     if (b > seen) atomicMax(slot, b);
 #endif
@@ -874,6 +881,417 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
   if (a.yr) x3_range_out(a.yr, ym, lane, wave, yr_seen, x1rw);
 }
 
+// ---- wide 3 x 3 layers: one split per chunk for 128 couts ---------------------------------------------------------------------------
+// conv_x3_kernel<false, 3, 3> fetches, splits and stages every 32-channel chunk of a tile once per 64-cout slice.  Here a block is the
+// same 16 x 16 pixels x TWO slices (128 couts), 512 threads, ONE block per CU at two waves per SIMD: wave w takes slice w >> 2 and the
+// pixel rows 4 (w & 3) .. + 3, and inside a tap does what a wave of conv_x3_kernel<false, 3, 3, false, 2> does -- the same fragment reads,
+// the same 48 MFMAs per tap in the same order per accumulator, the same epilogue with n0 = 128 pn + 64 slice: the results are
+// bit-identical to the sliced kernel.  Per chunk the 18 x 18 raw patch is loaded once by all 512 threads (6 float4 pieces per thread
+// instead of 11) and split once; the two fp16 images are DOUBLE-buffered (2 x 41 472 B, which one block per CU leaves room for), so
+// chunk c + 1 is split into the other buffer while the taps of chunk c run -- one piece between the MFMA groups of each of the taps
+// 3 .. 6 (the wait of tap 2 has sat the patch out: vmcnt retires in order and the unit of tap 4 was issued behind it), the last one
+// and the 32-thread remainder behind the wait that ends the chunk -- and the barrier + split phase between two chunks is gone: any time
+// after a chunk's first barrier every wave is done with the other buffer, and the first barrier of the next chunk publishes it.
+// Each 4-wave half stages its own slice's filter units (the packed layout read as it is, unit base wave-uniform in SGPRs) into its own
+// double buffer, in the issue order of LOOK = 2 moved one tap earlier: the fragments of a tap are read from LDS during the tap before
+// (see the prologue below).  115.7 KB of LDS.
+// UP (the bilinear 2x prologue): the block loads the 10 x 10 low-res patch of the next chunk (two float4 per thread), parks it in the
+// 12.5 KB scratch at the top of tap 3 (the barrier of tap 4 publishes it) and expands it to the 18 x 18 patch ONCE for both slices --
+// conv_x3_kernel<true, 3, 3>'s expansion, the arithmetic and order of resize2x_kernel -- a piece between the MFMA groups of each of the
+// taps 4 .. 7, the rest behind the chunk's last wait, into the other patch buffer.  128.5 KB of LDS.
+constexpr int XW_THREADS = 512, XW_BN = 128;
+constexpr long XW_UP_MIN_COUT = 128;                           // smallest Cout of an up-sampling layer on the 128-cout blocks (x3_forward)
+struct XWG {
+  using G = X3G<3, 3>;
+  static constexpr int PJ = (G::PPIX * 8 + XW_THREADS - 1) / XW_THREADS;     // float4 pieces per thread and chunk (6; the last: 32 threads)
+  static constexpr int RANGE_BYTES = 32;                       // the eight waves' output maxima
+  static constexpr int LR_BYTES = LRPIX * 32 * 4;              // UP: the low-res scratch
+  static constexpr int LDS_BYTES = (2 * 2 * G::PATCH_HALVES + 2 * 2 * UNIT_HALVES) * 2;
+};
+template <bool UP>
+__global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Args a) {
+  using G = X3G<3, 3>;
+  constexpr int KH = 3, KW = 3, PWID = G::PWID, PPIX = G::PPIX, PJ = XWG::PJ, PATCH_HALVES = G::PATCH_HALVES, NTAPS = 9;
+  static_assert((PJ - 1) * XW_THREADS < PPIX * 8 && PJ == 6, "every piece but the last is inside the patch for every thread");
+  extern __shared__ __attribute__((aligned(16))) _Float16 xsm[];
+#define patch_buf(B) (xsm + (B) * 2 * PATCH_HALVES)            /* [2 buffers][h, l][PATCH_HALVES] */
+#define filt (xsm + 4 * PATCH_HALVES)                          /* [2 slices][2 buffers][UNIT_HALVES] */
+#define lrs (reinterpret_cast<float*>(xsm + 4 * PATCH_HALVES + 4 * UNIT_HALVES))      /* UP: [LRPIX][32] fp32 */
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int slice = wave >> 2, wq = wave & 3;                  // cout slice of the wave, its group of four pixel rows
+  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int pn = L % a.nblk_n;
+  int pm = L / a.nblk_n;
+  const int tx = pm % a.tiles_x;
+  pm /= a.tiles_x;
+  const int ty = pm % a.tiles_y;
+  const int img = pm / a.tiles_y;
+  const int n0 = pn * XW_BN + slice * BN, oh0 = ty * 16, ow0 = tx * 16;
+
+  // ---- patch geometry (fixed per block): piece p = tid + 512 j -> (patch pixel, float4 of the 32-channel chunk) ------------------
+  // UP: the low-res 10 x 10 patch instead (PL = 2 pieces per thread), parked in LDS and expanded to the 18 x 18 patch ONCE per chunk for both
+  // slices with resize2x_kernel's arithmetic (conv_x3_kernel's expand_store, piece by piece)
+  constexpr int PL = UP ? (LRPIX * 8 + XW_THREADS - 1) / XW_THREADS : PJ;      // loaded pieces per thread and chunk
+  constexpr int T0 = UP ? 4 : 3;                               // first tap that carries a piece of the next chunk's patch
+  int ppix[PL], pdst[PJ];
+  int pcnt = 0;                                                // patch loads per chunk this wave is sure to issue (wave-uniform)
+  if (UP) {
+#pragma unroll
+    for (int j = 0; j < PL; ++j) {
+      const int p = tid + XW_THREADS * j;
+      const int pix = p >> 3;
+      const int ly = pix / LRW, lx = pix - ly * LRW;
+      const int r = (oh0 >> 1) - 1 + ly, c = (ow0 >> 1) - 1 + lx;
+      ppix[j] = (pix < LRPIX && (unsigned)r < (unsigned)a.Hl && (unsigned)c < (unsigned)a.Wl) ? (img * a.Hl + r) * a.Wl + c : -1;
+      pcnt += __ballot(ppix[j] >= 0) != 0ull;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < (UP ? 0 : PJ); ++j) {
+    const int p = tid + XW_THREADS * j;
+    const int pix = p >> 3, q = p & 7;
+    const int py = pix / PWID, px = pix - py * PWID;
+    const int ih = oh0 + py + a.bh, iw = ow0 + px + a.bw;
+    const bool ok = pix < PPIX && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
+    ppix[j] = ok ? (img * a.Hin + ih) * a.Win + iw : -1;
+    pdst[j] = pix < PPIX ? pix * 32 + 8 * ((q >> 1) ^ sx(px)) + 4 * (q & 1) : -1;
+    pcnt += __ballot(ppix[j] >= 0) != 0ull;
+  }
+  pcnt = __builtin_amdgcn_readfirstlane(pcnt);
+  const int nch1 = a.C1 >> 5, nch = (a.C1 + a.C2) >> 5;
+  const int nunits = nch * NTAPS;
+  f32x4 pr[PL];
+  auto zero_patch = [&]() __attribute__((always_inline)) {     // (in front of the filter unit issued before the prefetch: see conv_x3_kernel)
+#pragma unroll
+    for (int j = 0; j < PL; ++j) pr[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < PL; ++j) asm volatile("" : "+v"(pr[j]));
+  };
+  auto load_patch = [&](int c, bool zeroed) __attribute__((always_inline)) {
+    if (UP) {
+#pragma unroll
+      for (int j = 0; j < PL; ++j) {
+        const int q = (tid + XW_THREADS * j) & 7;
+        if (!zeroed) pr[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (ppix[j] >= 0) pr[j] = *reinterpret_cast<const f32x4*>(a.x1 + (size_t)(unsigned)ppix[j] * (unsigned)a.C1 + (c << 5) + 4 * q);
+      }
+      return;
+    }
+    const bool second = c >= nch1;
+    const float* src = second ? a.x2 : a.x1;
+    const int Cs = second ? a.C2 : a.C1;
+    const int c0 = (second ? c - nch1 : c) << 5;
+#pragma unroll
+    for (int j = 0; j < (UP ? 0 : PJ); ++j) {
+      const int q = (tid + XW_THREADS * j) & 7;
+      if (!zeroed) pr[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (ppix[j] >= 0) pr[j] = *reinterpret_cast<const f32x4*>(src + (size_t)(unsigned)ppix[j] * (unsigned)Cs + c0 + 4 * q);
+    }
+  };
+  float xs = 1.0f, ixs = 1.0f;
+  auto park_lr = [&]() __attribute__((always_inline)) {        // UP: registers -> LDS scratch [pixel][32]
+#pragma unroll
+    for (int j = 0; j < (UP ? PL : 0); ++j)
+      if (tid + XW_THREADS * j < LRPIX * 8) *reinterpret_cast<f32x4*>(lrs + 4 * (tid + XW_THREADS * j)) = pr[j];
+  };
+  // piece j of a chunk's 18 x 18 patch -> 8 bytes in each image of buffer buf: split from the register it was loaded into, or (UP)
+  // expanded from the scratch with the arithmetic and order of resize2x_kernel (horizontal first, then vertical) and split
+  auto split_store = [&](int buf, int j) __attribute__((always_inline)) {
+    f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int dst;
+    if (UP) {
+      const int r0 = (oh0 >> 1) - 1, c0 = (ow0 >> 1) - 1;
+      int t0 = tid;
+      asm volatile("" : "+v"(t0));                             // the geometry is computed HERE, not held in registers across the taps
+      const int p = t0 + XW_THREADS * j;
+      const int pix = p >> 3, q = p & 7;
+      if (pix >= PPIX) return;
+      const int py = pix / PWID, px = pix - py * PWID;
+      const int ih = oh0 - 1 + py, iw = ow0 - 1 + px;
+      if ((unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win) {
+        const int mr = ih >> 1, mc = iw >> 1;
+        const int ra = (ih & 1) ? mr : max(mr - 1, 0), rb = (ih & 1) ? min(mr + 1, a.Hl - 1) : mr;
+        const int ca = (iw & 1) ? mc : max(mc - 1, 0), cb2 = (iw & 1) ? min(mc + 1, a.Wl - 1) : mc;
+        const float* s00 = lrs + ((ra - r0) * LRW + (ca - c0)) * 32 + 4 * q;
+        const int dx = (cb2 - ca) * 32, dy = (rb - ra) * LRW * 32;
+        const float wx = (iw & 1) ? 0.25f : 0.75f, wy = (ih & 1) ? 0.25f : 0.75f;
+        const f32x4 q00 = *reinterpret_cast<const f32x4*>(s00), q01 = *reinterpret_cast<const f32x4*>(s00 + dx);
+        const f32x4 q10 = *reinterpret_cast<const f32x4*>(s00 + dy), q11 = *reinterpret_cast<const f32x4*>(s00 + dy + dx);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float t = q00[e] + (q01[e] - q00[e]) * wx;
+          const float u = q10[e] + (q11[e] - q10[e]) * wx;
+          v[e] = t + (u - t) * wy;
+        }
+      }
+      dst = pix * 32 + 8 * ((q >> 1) ^ sx(px)) + 4 * (q & 1);
+    } else {
+      if (j == PJ - 1 && pdst[j] < 0) return;
+      v = pr[UP ? 0 : j];
+      dst = pdst[j];
+    }
+    unsigned h[2], l[2];
+    x3_split4(v, xs, h, l);
+    *reinterpret_cast<uint2*>(patch_buf(buf) + dst) = make_uint2(h[0], h[1]);
+    *reinterpret_cast<uint2*>(patch_buf(buf) + PATCH_HALVES + dst) = make_uint2(l[0], l[1]);
+  };
+  // ---- filter units of the wave's slice: 8 KB per tap = 512 pieces of 16 bytes, two per thread of the 4-wave half -----------------
+  constexpr int FJ = 2;
+  const int ht = tid & 255;
+  const _Float16* wbase = a.wp + (size_t)(pn * 2 + slice) * nunits * UNIT_HALVES;
+#define fsl (filt + slice * 2 * UNIT_HALVES)                   /* the two unit buffers of the wave's slice */
+  int fdst[FJ];
+#pragma unroll
+  for (int j = 0; j < FJ; ++j) {
+    const int p = ht + 256 * j;
+    const int im = p >> 8, co = (p & 255) >> 2, slot = p & 3;
+    fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ f4(co));
+  }
+  u32x4 fr[2][FJ];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) fr[s][j] = (u32x4){0u, 0u, 0u, 0u};
+  const unsigned foff = 16u * (unsigned)ht + 2048u;
+  auto issue_filt = [&](int u, int s) __attribute__((always_inline)) {                        // (past the last unit the last unit again: a static load count)
+    const _Float16* ub = wbase + (size_t)(u < nunits ? u : nunits - 1) * UNIT_HALVES;
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:-2048" : "+v"(fr[s][0]) : "v"(foff), "s"(ub) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "+v"(fr[s][1]) : "v"(foff), "s"(ub) : "memory");
+  };
+  constexpr int WB = FJ;                                       // loads of the next unit, always behind the one waited for
+#define XW_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory")
+  // unit v (slot s) has landed = everything but the FJ loads of the unit behind it and the np patch loads issued after it (np < 0: the
+  // prologue); then registers -> the slice's LDS buffer v & 1.  (The wait names no register, one fence ties the slot: conv_x3_kernel.)
+  auto wait_store_filt = [&](int v, int s, int np, bool st) __attribute__((always_inline)) {
+    static_assert(PL <= 6, "the rungs below cover up to six patch loads per thread");
+    if (np < 0) XW_WAIT_VM(0);
+    else if (np >= 6) XW_WAIT_VM(WB + 6);
+    else if (np >= 5) XW_WAIT_VM(WB + 5);
+    else if (np >= 4) XW_WAIT_VM(WB + 4);
+    else if (np >= 3) XW_WAIT_VM(WB + 3);
+    else if (np >= 2) XW_WAIT_VM(WB + 2);
+    else if (np >= 1) XW_WAIT_VM(WB + 1);
+    else XW_WAIT_VM(WB);
+    asm volatile("" : "+v"(fr[s][0]), "+v"(fr[s][1]) : : "memory");
+    if (st) {
+#pragma unroll
+      for (int j = 0; j < FJ; ++j) *reinterpret_cast<u32x4*>(fsl + (v & 1) * UNIT_HALVES + fdst[j]) = fr[s][j];
+    }
+  };
+
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int fi = lane & 15, fg = lane >> 4;
+  int acol[KW], b_rd[NT];
+  const int pc = pcol(fi);
+#pragma unroll
+  for (int kw = 0; kw < KW; ++kw) acol[kw] = (pc + kw) * 32 + 8 * (fg ^ sx(pc + kw));
+#pragma unroll
+  for (int ni = 0; ni < NT; ++ni) {
+    const int row = ni * 16 + fi;
+    b_rd[ni] = row * 32 + 8 * (fg ^ f4(row));
+  }
+
+  static_assert(NT == MT, "one filter fragment pair of the next tap is read in front of each MFMA group");
+  load_patch(0, false);
+  issue_filt(0, 0);
+  issue_filt(1, 1);
+  x3_range_scale(a.xr1, a.xr2, xs, ixs);                       // (behind the first loads: the slot is a dependent scalar load)
+  if (UP) {
+    park_lr();
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < PJ; ++j) {
+    split_store(0, j);
+    if (UP && (j & 1)) __builtin_amdgcn_sched_barrier(0);      // two pieces' scratch reads in flight, not six
+  }
+  wait_store_filt(0, 0, -1, true);                             // units 0 and 1 -> the two buffers
+  wait_store_filt(1, 1, -1, true);
+  issue_filt(2, 0);
+  __syncthreads();
+  // The filter fragments of a tap are read ONE TAP AHEAD, a pair in front of each MFMA group of the tap before: all eight waves leave a
+  // tap's barrier together, and with the fragment reads behind it (80 KB per CU, 640 LDS cycles) no MFMA could issue until they were
+  // served -- the sliced kernel's second block per CU covers that phase, one block per CU has nobody to.  So unit u + 1 is in LDS at the
+  // barrier of tap u (stored at the end of tap u - 1, issued at the top of tap u - 2), and buffer u & 1, read during tap u - 1, is free.
+  f16x8 wh[NT], wl[NT];
+#pragma unroll
+  for (int ni = 0; ni < NT; ++ni) {
+    wh[ni] = *reinterpret_cast<const f16x8*>(fsl + b_rd[ni]);
+    wl[ni] = *reinterpret_cast<const f16x8*>(fsl + IMG_HALVES + b_rd[ni]);
+  }
+#pragma unroll 1
+  for (int c = 0; c < nch; ++c) {
+    const bool pf = c + 1 < nch;
+    const int cb = c & 1;                                      // patch buffer of this chunk; chunk c + 1 is split into cb ^ 1
+    zero_patch();
+    __builtin_amdgcn_sched_barrier(0);
+    issue_filt(c * NTAPS + 3, 1);                              // the unit of tap 3 in FRONT of the patch loads: the waits of taps 0, 1 leave the patch in flight
+    __builtin_amdgcn_sched_barrier(0);
+    if (pf) load_patch(c + 1, true);
+    __builtin_amdgcn_sched_barrier(0);
+    const int np = pf ? pcnt : 0;
+#pragma unroll
+    for (int kh = 0; kh < KH; ++kh) {
+#pragma unroll
+      for (int kw = 0; kw < KW; ++kw) {
+        const int t = kh * KW + kw;                            // the unit of tap t sits in register slot t & 1
+        const int u = c * NTAPS + t;
+        __syncthreads();                                       // unit u + 1 (and, at tap 0, the patch) is in LDS; filter buffer u & 1 is free
+        if (t == 3) {
+          // the compiler's own wait for the patch registers (a full one: it counts loads issued under branches no finer) HERE, where only
+          // the unit of tap 5 is in flight, a tap old -- between the MFMA groups it would also sit out the unit issued below
+#pragma unroll
+          for (int j = 0; j < PL; ++j) asm volatile("" : "+v"(pr[j]));
+          // UP: the low-res chunk into the scratch (last read by the expansion that ended the chunk before: every wave is past a barrier
+          // since), published by the barrier of tap 4
+          if (UP && pf) park_lr();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t > 0) issue_filt(u + 3, (t + 3) & 1);
+        const _Float16* F = fsl + ((u + 1) & 1) * UNIT_HALVES;  // the next tap's unit
+        const int rowh = (wq * MT + kh) * PWID * 32;
+
+        f16x8 ws[NT], nwh[NT], nwl[NT], ph[2], pl[2];
+        auto read_a = [&](int mi, int slot) __attribute__((always_inline)) {
+          const int o = rowh + mi * PWID * 32 + acol[kw];
+          ph[slot] = *reinterpret_cast<const f16x8*>(patch_buf(cb) + o);
+          pl[slot] = *reinterpret_cast<const f16x8*>(patch_buf(cb) + PATCH_HALVES + o);
+        };
+        read_a(0, 0);
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) ws[ni] = wh[ni] * (_Float16)(1.0f / 2048.0f);
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) {
+          if (mi + 1 < MT) read_a(mi + 1, (mi + 1) & 1);
+          nwh[mi] = *reinterpret_cast<const f16x8*>(F + b_rd[mi]);
+          nwl[mi] = *reinterpret_cast<const f16x8*>(F + IMG_HALVES + b_rd[mi]);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[ni], pl[mi & 1], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+          for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          // piece t - T0 of chunk c + 1 behind the second MFMA group of the taps 3 .. 6 (UP: 4 .. 7): it landed with the wait of tap 2
+          if (mi == 1 && t >= T0 && t - T0 < PJ - 2) {
+            if (pf) split_store(cb ^ 1, t - T0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        wait_store_filt(u + 2, t & 1, t < 2 ? np : 0, u + 2 < nunits);
+#pragma unroll
+        for (int ni = 0; ni < NT; ++ni) {
+          wh[ni] = nwh[ni];
+          wl[ni] = nwl[ni];
+        }
+      }
+    }
+    // every load of the chunk has landed: the unit of the next chunk's tap 2, issued into slot 1 at tap 8, moves to slot 0
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(fr[1][0]), "+v"(fr[1][1]) : : "memory");
+#pragma unroll
+    for (int j = 0; j < FJ; ++j) fr[0][j] = fr[1][j];
+    if (pf) {
+      split_store(cb ^ 1, PJ - 2);
+      split_store(cb ^ 1, PJ - 1);                             // (the 32 threads that have a sixth piece)
+    }
+  }
+#undef XW_WAIT_VM
+
+  // ---- epilogue: conv_x3_kernel's (without the projected output, which needs Cout = 64), on the wave's slice and rows --------------------------------------------
+  const float inv_s = a.hdr[1] * ixs;
+  const int ow = ow0 + pc;
+  const unsigned yr_seen = (a.yr && a.final) ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  int ep0 = n0;
+  asm volatile("" : "+s"(ep0));
+  f32x4 bias_r[NT], scale_r[NT], shift_r[NT];
+#pragma unroll
+  for (int ni = 0; ni < NT; ++ni) {
+    const int cl = ni * 16 + 4 * fg;
+    const bool cv = ep0 + cl < a.Cout;
+    bias_r[ni] = (a.bias && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.bias + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    scale_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.scale + ep0 + cl) : (f32x4){1.f, 1.f, 1.f, 1.f};
+    shift_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.shift + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  f32x4 yin_r[MT / 2][NT][2];
+  const float* addend = a.yin ? a.yin : (a.final ? a.res : nullptr);
+  if (addend) {
+    const int add_cs = a.yin ? a.Cout : a.res_cs;
+#pragma unroll
+    for (int mp = 0; mp < MT / 2; ++mp)
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int oh = oh0 + wq * MT + 2 * mp + r;
+          yin_r[mp][ni][r] = (oh < a.H && ow < a.W && ep0 + ni * 16 + 4 * fg < a.Cout)
+                                 ? *reinterpret_cast<const f32x4*>(addend + ((size_t)(img * a.H + oh) * a.W + ow) * add_cs + ep0 + ni * 16 + 4 * fg)
+                                 : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+  }
+  float ym = 0.0f;
+#pragma unroll
+  for (int mp = 0; mp < MT / 2; ++mp) {
+    const int oh = oh0 + wq * MT + 2 * mp;
+    if (oh >= a.H) continue;                                   // wave-uniform
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni) {
+      const int cl = ni * 16 + 4 * fg;
+      f32x4 v[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        v[r] = acc[2 * mp + r][ni] * inv_s;
+        const bool inside = oh + r < a.H && ow < a.W;
+        if (a.yin) v[r] += yin_r[mp][ni][r];
+        if (!a.final) {
+          if (inside) *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
+          continue;
+        }
+        v[r] += bias_r[ni];
+        shdr::act_apply4<0>(v[r], a.act1);
+        if (a.scale) v[r] = v[r] * scale_r[ni] + shift_r[ni];
+        if (a.res) v[r] += yin_r[mp][ni][r];
+        shdr::act_apply4<0>(v[r], a.act2);
+        if (a.y && oh + r < a.H && ow < a.W && n0 + cl < a.Cout)
+          *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
+#ifndef SHDR_ABL_NO_YM
+        if (a.yr && oh + r < a.H) ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[r][0])), fabsf(v[r][1])), fabsf(v[r][2])), fabsf(v[r][3]));
+#endif
+      }
+      if (a.yp && a.final) {
+        f32x4 m;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (a.pool_avg) {
+            const float t = v[0][e] + __shfl_xor(v[0][e], 1, 64), b = v[1][e] + __shfl_xor(v[1][e], 1, 64);
+            m[e] = 0.25f * (t + b);
+          } else {
+            m[e] = fmaxf(v[0][e], v[1][e]);
+            m[e] = fmaxf(m[e], __shfl_xor(m[e], 1, 64));
+          }
+        }
+        if (!(pc & 1) && ow < a.W && n0 + cl < a.Cout)
+          *reinterpret_cast<f32x4*>(a.yp + ((size_t)(img * (a.H >> 1) + (oh >> 1)) * (a.W >> 1) + (ow >> 1)) * a.Cout + n0 + cl) = m;
+      }
+    }
+  }
+#ifndef SHDR_ABL_NO_TAIL
+  if (a.yr && a.final)
+    x3_range_out<8>(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + XWG::LDS_BYTES + (UP ? XWG::LR_BYTES : 0)));
+#endif
+}
+#undef patch_buf
+#undef filt
+#undef fsl
+#undef lrs
+
 // ---- filter preparation ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void x3_absmax_kernel(const float* __restrict__ w, long n, unsigned* __restrict__ out) {
   float m = 0.f;
@@ -991,6 +1409,25 @@ int launch_x3_1x1(const X3Args& a0, hipStream_t st) {
   if (ns == 4) hipLaunchKernelGGL((conv_x3_1x1_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((conv_x3_1x1_kernel<2>), dim3((unsigned)nblk), dim3(256), 0, st, a);
   return shdr::check_launch("conv_x3_1x1_kernel");
+}
+
+// conv_x3_wide_kernel: 128 couts per block, half the blocks of the sliced grid
+template <bool UP>
+int launch_x3_wide(const X3Args& a0, hipStream_t st) {
+  X3Args a = a0;
+  a.nblk_n = a.Cout / XW_BN;
+  constexpr int lds = XWG::LDS_BYTES + (UP ? XWG::LR_BYTES : 0) + XWG::RANGE_BYTES;
+  static bool attr_done[shdr::kMaxDevices] = {};
+  const int dev_slot = shdr::device_slot();
+  if (!attr_done[dev_slot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_wide_kernel<UP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    attr_done[dev_slot] = true;
+  }
+  const long nblk = (long)a.nblk_m * a.nblk_n;
+  if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
+  hipLaunchKernelGGL((conv_x3_wide_kernel<UP>), dim3((unsigned)nblk), dim3(XW_THREADS), lds, st, a);
+  return shdr::check_launch("conv_x3_wide_kernel");
 }
 
 }  // namespace
@@ -1169,7 +1606,24 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
     a.yin = i > 0 ? y : nullptr;
     a.final = i == n - 1;
     int rc;
-    if (ph[i].th == 3 && ph[i].tw == 3) rc = up ? launch_x3<true, 3, 3>(a, st) : launch_x3<false, 3, 3>(a, st);
+    if (ph[i].th == 3 && ph[i].tw == 3) {
+      // the 128-cout blocks (conv_x3_wide_kernel<UP>) take the stride-1 layers with a multiple of 128 couts and at least 256 blocks: with
+      // the up-sampling prologue from 128 couts on, plain from 512 couts on; a projected output (Cout = 64) and SHDR_X3_SLICED=1 (A/B,
+      // tests/test_gpu_x3_wide.py) run the 64-cout kernel.  Measured (tools/x3_wide_ab.py, profiles/r06_x3_wide_layers_ab.txt; sliced / wide
+      // by the medians of five rounds, batch 16 and 8):
+      //   up-sampling, >= 256 blocks: 64^2 x2 512 -> 256 1.109 and 1.102, 128^2 x2 256 -> 128 1.089 and 1.088, 32^2 x2 256 -> 128 1.121 at
+      //   batch 16 -- the ranges apart everywhere (the expansion and the split run once per 128 couts, under the MFMAs);
+      //   plain, 512 couts: 64^2 1.018 - 1.020 and 1.029 - 1.033, 32^2 at batch 16 (256 blocks) 1.053, the ranges apart (an earlier session
+      //   on another box: 64^2 256 -> 512 at batch 16 1.017 with the ranges overlapping);
+      //   plain, 256 couts: 0.985 - 1.012 and 1.002 - 1.018, 128 couts: 0.980 - 1.039 and 0.960 - 0.994, ranges overlapping: they stay sliced;
+      //   128 blocks and fewer (half the CUs idle): 0.74 - 0.87, plain and up-sampling alike.
+      long wide_min_blocks = 256, wide_min_cout = up ? XW_UP_MIN_COUT : 512;
+      if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_BLOCKS")) wide_min_blocks = atol(e);
+      if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_COUT")) wide_min_cout = atol(e);
+      const bool wide = n == 1 && d->stride == 1 && d->Cout % XW_BN == 0 && d->Cout >= wide_min_cout && !proj &&
+                        (long)a.nblk_m * (d->Cout / XW_BN) >= wide_min_blocks && SHDR_ENV("SHDR_X3_SLICED") == nullptr;
+      rc = wide ? (up ? launch_x3_wide<true>(a, st) : launch_x3_wide<false>(a, st)) : up ? launch_x3<true, 3, 3>(a, st) : launch_x3<false, 3, 3>(a, st);
+    }
     else if (ph[i].th == 1 && ph[i].tw == 1) {
       // the wide-block kernel takes 128- and 256-cout multiples with a plain output; a pooled or projected output (no network has one
       // on a 1 x 1 layer), the narrow layers and SHDR_X3_1X1_SLICED=1 (A/B) run the 64-cout instantiation

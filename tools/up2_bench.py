@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Bilinear 2x + Conv2D 3x3 of the decoders' `up` blocks at the inference shapes (batch 16 x 512^2), fused prologue vs the two
-kernels:   python tools/up2_bench.py"""
+kernels:   python tools/up2_bench.py [BATCH]"""
 import importlib
 import os
 import sys
@@ -15,6 +15,9 @@ SHAPES = [  # n, low-res h, w, cin, cout
     (16, 16, 16, 512, 512), (16, 32, 32, 512, 512), (16, 64, 64, 512, 256), (16, 128, 128, 256, 128), (16, 256, 256, 128, 64),
     (16, 32, 32, 256, 128), (16, 64, 64, 128, 64), (16, 128, 128, 64, 32), (16, 256, 256, 32, 16),
 ]
+
+if len(sys.argv) > 1:
+    SHAPES = [(int(sys.argv[1]),) + tuple(sh[1:]) for sh in SHAPES]
 
 
 def timeit(fn, reps=10):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The wide 3x3 layers of the inference step (batch 16 x 512^2) on the split-operand fp16 kernel (plan "x3") vs the exact-fp32 plan
-(fused Winograd):   python tools/x3_bench.py"""
+(fused Winograd):   python tools/x3_bench.py [BATCH]"""
 import importlib
 import os
 import sys
@@ -23,6 +23,9 @@ SHAPES = [  # n, h, w, c1, c2, cout
     (16, 512, 512, 4, 0, 16, 7, 1), (16, 512, 512, 16, 0, 16, 7, 1), (16, 256, 256, 16, 0, 32, 5, 1), (16, 256, 256, 32, 0, 32, 5, 1),
     (16, 512, 512, 32, 0, 16, 3, 1), (16, 512, 512, 16, 16, 16, 3, 1), (16, 512, 512, 16, 0, 16, 3, 1),
 ]
+
+if len(sys.argv) > 1:                       # another batch size (the headline leg runs slices of 8 on two streams)
+    SHAPES = [(int(sys.argv[1]),) + tuple(sh[1:]) for sh in SHAPES]
 
 
 def timeit(fn, reps=10):

@@ -16,7 +16,7 @@ IFS=';' read -ra SETS <<< "${X3_PMC_SETS:-$DEFAULT_SETS}"       # X3_PMC_SETS="A
 for SET in "${SETS[@]}"; do
   i=$((i+1))
   # shellcheck disable=SC2086
-  rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$O/p$i" -- python3 "$R/tools/x3_one.py" "$HW" "$CIN" "$COUT" 16 "$KS" "$C2" > "$O/p$i.log" 2>&1 || echo "pass $i failed"
+  timeout -k 10 120 rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$O/p$i" -- python3 "$R/tools/x3_one.py" "$HW" "$CIN" "$COUT" 16 "$KS" "$C2" > "$O/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }
 done
 cd "$R" && python3 - "$O" "$TAG" <<'PY'
 import csv, glob, collections, sys
@@ -24,11 +24,11 @@ o, tag = sys.argv[1], sys.argv[2]
 tot = collections.defaultdict(float); n = collections.defaultdict(int); dur = []
 for f in glob.glob(o + "/p*/*/*counter_collection.csv"):
     for r in csv.DictReader(open(f)):
-        if "conv_x3_kernel" in r["Kernel_Name"]:
+        if "conv_x3_kernel" in r["Kernel_Name"] or "conv_x3_wide_kernel" in r["Kernel_Name"]:
             tot[r["Counter_Name"]] += float(r["Counter_Value"]); n[r["Counter_Name"]] += 1
 for f in glob.glob(o + "/p1/*/*kernel_trace.csv"):
     for r in csv.DictReader(open(f)):
-        if "conv_x3_kernel" in r["Kernel_Name"]:
+        if "conv_x3_kernel" in r["Kernel_Name"] or "conv_x3_wide_kernel" in r["Kernel_Name"]:
             dur.append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
 lines = ["layer %s (tools/x3_one.py), per launch" % tag]
 if dur:
