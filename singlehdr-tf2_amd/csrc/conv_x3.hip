@@ -26,9 +26,8 @@
 // stored one tap ahead, double-buffered).  Per tap and wave: 16 operand reads feed 48 MFMAs.  58 KB of LDS, two blocks per CU.
 // The patch of chunk c + 1 is issued at the top of chunk c, BEHIND the filter unit that tap LOOK of the chunk needs; the filter units
 // are loaded LOOK taps ahead through a scalar base and waited for with counted vmcnt, so the patch flies under LOOK + 1 taps of MFMAs
-// before a wait can sit it out (template parameter LOOK below).  In the order of the first rounds (LOOK = 0) it did NOT land "under the
-// MFMAs of the previous chunk", as this comment used to say: the compiler's "s_waitcnt vmcnt(0)" in front of the first tap's filter
-// address arithmetic drained it before any MFMA of the chunk ran.
+// before a wait can sit it out (template parameter LOOK below; the order it replaced, and why its prefetch never landed under the
+// MFMAs: DESIGN.md section 6).
 // Fused around it: MaxPool2D(2) in the epilogue (the conv + max-pool pairs of hallucination_net.py:43-75 / vgg16.py:72-83: the 2 x 2
 // window is two accumulator rows of a lane and its neighbour lane) and tf.image.resize(x, 2x, BILINEAR) in the prologue (UP = true;
 // hallucination_net.py:86-88, dequantization_net.py:25-27): the block loads the 10 x 10 LOW-RES patch of a chunk (a quarter of the
@@ -54,8 +53,8 @@ constexpr int IMG_HALVES = BN * 32;                            // one filter ima
 constexpr int UNIT_HALVES = 2 * IMG_HALVES;                    // wh, wl
 constexpr int LRW = 10, LRPIX = LRW * LRW;                     // low-res patch of the up-sampling prologue
 constexpr int LRJ = (LRPIX * 8 + 255) / 256;                   // float4 pieces per thread (4)
-// KH x KW taps over a 16 x 16 output tile: raw patch (16 + KH - 1) x (16 + KW - 1).  3 x 3 = the stride-1 layers; 4 x 4, 4 x 3, 3 x 4
-// (and 3 x 3) = the four phases of a 7 x 7 / stride-2 layer (see shdr_conv2d_fwd_x3_f32)
+// KH x KW taps over a 16 x 16 output tile: raw patch (16 + KH - 1) x (16 + KW - 1).  3 x 3 and 1 x 1 = the stride-1 layers; 4 x 4 = the
+// patch of the 7 x 7 / stride-2 layer, whose four phases run 4 x 4, 4 x 3, 3 x 4 and 3 x 3 taps on it (MP, see x3_forward)
 template <int KH, int KW>
 struct X3G {
   static constexpr int PH = 16 + KH - 1, PWID = 16 + KW - 1, PPIX = PH * PWID;
@@ -76,14 +75,12 @@ struct X3Args {
   const float* shift;
   float* y;                // [N,H,W,Cout] (or null when only the pooled tensor is wanted)
   float* yp;               // [N,H/2,W/2,Cout] = MaxPool2D(2)(y), or null
-  const float* yin;        // partial sums of earlier phases to add (same layout as y), or null
   const float* res;        // residual added between the affine and act2 (the ResNet joins of linearization_net.py:6-48), or null
   int res_cs;              // its channels per pixel
   int N, H, W, C1, C2, Cout, tiles_x, tiles_y, nblk_m, nblk_n, act1, act2;
   int Hl, Wl;              // UP: x1 is the low-res tensor [N,Hl,Wl,C1], H = 2 Hl, W = 2 Wl
   int Hin, Win;            // input tensor [N,Hin,Win,C]; tap (kh, kw) of output (oh, ow) reads input (in_s (oh + kh) + bh, in_s (ow + kw) + bw)
   int in_s, bh, bw;        // stride-1 3x3 SAME: in_s = 1, bh = bw = -1
-  int final;               // 0: store the raw partial sum (another phase follows), 1: the epilogue
   int pool_avg;            // yp = AveragePooling2D(2)(y) instead of MaxPool2D(2)(y)
   const unsigned* xr1;     // range slots of the two sources (bits of an upper bound of max |x|; null: no scaling)
   const unsigned* xr2;
@@ -155,6 +152,121 @@ __device__ __forceinline__ void x3_range_out(unsigned* slot, float m, int lane, 
   }
 }
 
+// ---- the tile epilogue of conv_x3_kernel (NW = 4 waves, PROJ) and conv_x3_wide_kernel (NW = 8; no projected output, which needs Cout = 64).
+// The wave holds acc[MT][NT] = the MT pixel rows from oh_row0 on x the 64 couts from n0 on; the lane's tile column is ow (pc in the tile: the
+// pcol permutation), its couts the quads 4 fg of each 16; ixs = 2^-T of the input scaling; range_lds = NW words of LDS for x3_range_out.
+template <int NW, bool PROJ>
+__device__ __forceinline__ void x3_tile_epilogue(const X3Args& a, f32x4 (&acc)[MT][NT], int img, int oh_row0, int ow, int pc, int fg, int n0, float ixs,
+                                                 int lane, int wave, unsigned* range_lds) {
+  // y = act2(affine(act1(acc * 2^-S + bias))), 16-byte stores (lane = pixel x 4 consecutive couts); the 2 x 2 pooling window of the
+  // optional second output is two rows of this lane and of its neighbour lane
+  const float inv_s = a.hdr[1] * ixs;
+  // bias / scale / shift of the lane's four cout quads are loaded ONCE, in front of the store loop: a load inside it is followed by
+  // "s_waitcnt vmcnt(0)", which also sits out the round trip of the output store issued just before it -- the stores of a block went
+  // out one at a time
+  // (the offsets pass through an opaque asm so that the loads are not hoisted above the tap loop, where their registers would be live
+  //  for the whole kernel)
+  const unsigned yr_seen = a.yr ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  int ep0 = n0;
+  asm volatile("" : "+s"(ep0));
+  f32x4 bias_r[NT], scale_r[NT], shift_r[NT];
+#pragma unroll
+  for (int ni = 0; ni < NT; ++ni) {
+    const int cl = ni * 16 + 4 * fg;
+    const bool cv = ep0 + cl < a.Cout;                           // (false only in the zero half of a 32-cout layer's slice: nothing loaded, nothing stored)
+    bias_r[ni] = (a.bias && cv) ? *reinterpret_cast<const f32x4*>(a.bias + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    scale_r[ni] = (a.scale && cv) ? *reinterpret_cast<const f32x4*>(a.scale + ep0 + cl) : (f32x4){1.f, 1.f, 1.f, 1.f};
+    shift_r[ni] = (a.scale && cv) ? *reinterpret_cast<const f32x4*>(a.shift + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // the residual, batched in front of the stores for the same reason
+  f32x4 res_r[MT / 2][NT][2];
+  if (a.res) {
+#pragma unroll
+    for (int mp = 0; mp < MT / 2; ++mp)
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int oh = oh_row0 + 2 * mp + r;
+          res_r[mp][ni][r] = (oh < a.H && ow < a.W && ep0 + ni * 16 + 4 * fg < a.Cout)
+                                 ? *reinterpret_cast<const f32x4*>(a.res + ((size_t)(img * a.H + oh) * a.W + ow) * a.res_cs + ep0 + ni * 16 + 4 * fg)
+                                 : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+  }
+  float ym = 0.0f;                                             // max |y| over this lane's stored values (a.yr)
+#pragma unroll
+  for (int mp = 0; mp < MT / 2; ++mp) {
+    const int oh = oh_row0 + 2 * mp;                           // even row of the pair (H even whenever yp is given)
+    if (oh >= a.H) continue;                                   // wave-uniform
+    float pj[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};      // a.proj: this lane's share (16 of the 64 couts) of the projected pixel, rows oh, oh + 1
+#pragma unroll
+    for (int ni = 0; ni < NT; ++ni) {
+      const int cl = ni * 16 + 4 * fg;
+      f32x4 v[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        v[r] = acc[2 * mp + r][ni] * inv_s;
+        asm("" : "+v"(v[r]));                                  // the product is rounded on its own: without the fence the compiler contracts it
+                                                               // with the bias into one FMA (other output bits; conv_x3_1x1_kernel has the same)
+        v[r] += bias_r[ni];
+        shdr::act_apply4<0>(v[r], a.act1);
+        if (a.scale) v[r] = v[r] * scale_r[ni] + shift_r[ni];
+        if (a.res) v[r] += res_r[mp][ni][r];
+        shdr::act_apply4<0>(v[r], a.act2);
+        if (a.y && oh + r < a.H && ow < a.W && n0 + cl < a.Cout)
+          *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
+        if (PROJ && a.proj) {
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(a.proj + j * 64 + cl);
+            pj[r][j] += v[r][0] * q[0] + v[r][1] * q[1] + v[r][2] * q[2] + v[r][3] * q[3];
+          }
+        }
+#ifndef SHDR_ABL_NO_YM
+        if (a.yr && oh + r < a.H) ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[r][0])), fabsf(v[r][1])), fabsf(v[r][2])), fabsf(v[r][3]));      // two v_max3_f32
+#endif
+      }
+      if (a.yp) {
+        f32x4 m;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (a.pool_avg) {                                    // (top-left + top-right) + (bottom-left + bottom-right), as pool.hip adds them
+            const float t = v[0][e] + __shfl_xor(v[0][e], 1, 64), b = v[1][e] + __shfl_xor(v[1][e], 1, 64);
+            m[e] = 0.25f * (t + b);
+          } else {
+            m[e] = fmaxf(v[0][e], v[1][e]);
+            m[e] = fmaxf(m[e], __shfl_xor(m[e], 1, 64));
+          }
+        }
+        if (!(pc & 1) && ow < a.W && n0 + cl < a.Cout)           // lanes fi and fi ^ 1 hold columns pc and pc ^ 1
+          *reinterpret_cast<f32x4*>(a.yp + ((size_t)(img * (a.H >> 1) + (oh >> 1)) * (a.W >> 1) + (ow >> 1)) * a.Cout + n0 + cl) = m;
+      }
+    }
+    if (PROJ && a.proj) {                                      // the four lane groups fg hold 16 couts each of the same pixel
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          float t = pj[r][j];
+          t += __shfl_xor(t, 16, 64);
+          t += __shfl_xor(t, 32, 64);
+          pj[r][j] = t;
+        }
+        if (fg == 0 && oh + r < a.H && ow < a.W) {
+          float* o = a.yproj + ((size_t)(img * a.H + oh + r) * a.W + ow) * 3;
+          o[0] = pj[r][0]; o[1] = pj[r][1]; o[2] = pj[r][2];
+        }
+      }
+    }
+  }
+#ifndef SHDR_ABL_NO_TAIL
+  // (a pooled output is bounded by the same maximum).  The waves' words have LDS of their own: without a barrier after the last chunk (the
+  // 1 x 1 form) wave 0 may still be reading patch pixel (0, 0) when another wave writes its maximum
+  if (a.yr)
+    x3_range_out<NW>(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, range_lds);
+#endif
+}
+
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
@@ -174,28 +286,26 @@ __device__ __forceinline__ int pcol(int fi) { return fi < 4 ? fi : (fi >= 12 ? f
 // parameter gradient differed from the exact-fp32 kernels' by 3e-5; scaled, by the run-to-run noise).
 // MP (with KH = KW = 4, the largest phase): the four parity phases of a 7x7 / stride-2 layer in ONE launch -- a phase loop around the chunk loop
 // with the tap counts, the input offset and the sub-filter of each phase taken from the argument arrays; the partial sums stay in the
-// accumulators (the four-launch form wrote and re-read them three times: 3 x 2 x N Ho Wo Cout floats).  The patch geometry is that of the
+// accumulators (the four-launch form of the first rounds, DESIGN.md section 4, wrote and re-read them three times).  The patch geometry is that of the
 // 4 x 4 phase for every phase: a 3-tap dimension loads one row / column it does not use.
-// LOOK: issue order of the global loads (the arithmetic, and with it every output bit, is the same for all three).
-//   0  the order of the first rounds (SHDR_X3_LEGACY_PREFETCH=1): load_patch(c + 1) at the top of a chunk, filter unit u + 1 loaded after the
-//      barrier of tap u through a per-thread 64-bit address.  The compiler builds that address in the registers the previous filter load
-//      wrote and guards the arithmetic with "s_waitcnt vmcnt(0)": vmcnt retires in order, so the first tap of a chunk sat out the whole
-//      prefetch issued a few instructions earlier ("conv_x3: the prefetch was drained before the first tap").
-//   1, 2  a unit is a block-uniform 64-bit base in SGPRs plus ONE loop-invariant VGPR byte offset (no address arithmetic, no wait between a
-//      tap's barrier and its MFMAs), loaded LOOK taps ahead into fr[LOOK][FJ] by inline asm (outside the compiler's scoreboard), and the
-//      unit that tap u + LOOK needs is issued IN FRONT of the chunk's patch loads.  The wait in front of store_filt is counted:
-//      "vmcnt(loads issued after the unit)" leaves the later units and, in the first LOOK taps of a chunk, the patch loads in flight -- the
-//      patch flies for LOOK + 1 taps before a wait can sit it out.  Out-of-image pieces are zeros without a load, so the number of patch
-//      loads a WAVE issues is not static: pcnt counts the pieces with at least one lane inside the image (a lower bound of the loads
-//      issued, which is the safe side), the wait is coded for pcnt = PJ, PJ - 1 and PJ - 2 (interior tiles and plain edges) and falls
-//      back to sitting the patch out.
-template <bool UP, int KH, int KW, bool MP = false, int LOOK = 0>
+// LOOK = 1, 2: how many taps ahead a filter unit is loaded (the arithmetic, and with it every output bit, is the same for both; the
+// history of the order, and of the one it replaced, is DESIGN.md section 6).  A unit is a block-uniform 64-bit base in SGPRs plus ONE
+// loop-invariant VGPR byte offset (no address arithmetic, no wait between a tap's barrier and its MFMAs), loaded LOOK taps ahead into
+// fr[LOOK][FJ] by inline asm (outside the compiler's scoreboard), and the unit that tap u + LOOK needs is issued IN FRONT of the chunk's
+// patch loads.  The wait in front of the store to LDS is counted: "vmcnt(loads issued after the unit)" leaves the later units and, in the
+// first LOOK taps of a chunk, the patch loads in flight -- the patch flies for LOOK + 1 taps before a wait can sit it out.  Out-of-image
+// pieces are zeros without a load, so the number of patch loads a WAVE issues is not static: pcnt counts the pieces with at least one
+// lane inside the image (a lower bound of the loads issued, which is the safe side), the wait is coded for pcnt = PJ, PJ - 1 and PJ - 2
+// (interior tiles and plain edges) and falls back to sitting the patch out.
+//   1  every form: the stem (out of registers at 2), the one-tap 1 x 1 form, and the nine-tap forms under SHDR_X3_LOOK=1
+//   2  the nine-tap forms by default: units alternate between two register slots, the taps of a chunk are unrolled (see NFR below)
+template <bool UP, int KH, int KW, bool MP = false, int LOOK = 1>
 __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   using G = X3G<KH, KW>;
   constexpr int PWID = G::PWID, PPIX = G::PPIX, PJ = G::PJ, PATCH_HALVES = G::PATCH_HALVES, NTAPS = KH * KW;
   static_assert(!UP || (KH == 3 && KW == 3), "the up-sampling prologue belongs to the 3 x 3 stride-1 form");
   static_assert(!MP || (!UP && KH == 4 && KW == 4), "the phase loop is built on the 4 x 4 patch geometry");
-  static_assert(LOOK >= 0 && LOOK <= 2 && LOOK <= KW, "filter look-ahead: 0 (legacy order), 1 or 2 taps");
+  static_assert(LOOK >= 1 && LOOK <= 2 && LOOK <= KW, "filter look-ahead: 1 or 2 taps");
   extern __shared__ __attribute__((aligned(16))) _Float16 xsm[];
   // LDS regions as expressions of the __shared__ symbol (pointer VARIABLES captured by the lambdas below lost their address space: the
   // compiler kept them as 64-bit generic pointers in scratch and reloaded them inside the tap loop)
@@ -218,9 +328,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   // ---- patch geometry (fixed per block): piece p = tid + 256 j -> (patch pixel, float4 of the 32-channel chunk) ----------------
   int ppix[PJ];                                                // pixel index in the image tensor, -1: padding / beyond the patch
   int pdst[PJ];                                                // half offset of the 8-byte destination inside an image
-  int pcnt = 0;                                                // LOOK > 0: patch loads per chunk this wave is sure to issue (wave-uniform)
+  int pcnt = 0;                                                // patch loads per chunk this wave is sure to issue (wave-uniform)
   auto patch_geometry = [&](int bh, int bw) __attribute__((always_inline)) {                  // (MP: once per phase)
-    if (LOOK > 0) pcnt = 0;
+    pcnt = 0;
 #pragma unroll
     for (int j = 0; j < (UP ? 0 : PJ); ++j) {
       const int p = tid + 256 * j;
@@ -230,11 +340,11 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
       const bool ok = pix < PPIX && (unsigned)ih < (unsigned)a.Hin && (unsigned)iw < (unsigned)a.Win;
       ppix[j] = ok ? (img * a.Hin + ih) * a.Win + iw : -1;
       pdst[j] = pix < PPIX ? pix * 32 + 8 * ((q >> 1) ^ sx(px)) + 4 * (q & 1) : -1;
-      if (LOOK > 0) pcnt += __ballot(ppix[j] >= 0) != 0ull;
+      pcnt += __ballot(ppix[j] >= 0) != 0ull;
     }
   };
   if (!MP) patch_geometry(a.bh, a.bw);
-  if (LOOK > 0 && !MP && !UP) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
+  if (!MP && !UP) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
   // UP: low-res pieces of this thread: piece p = tid + 256 j -> (low-res patch pixel, float4)
   int lpix[LRJ];
   if (UP) {
@@ -245,9 +355,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
       const int ly = pix / LRW, lx = pix - ly * LRW;
       const int r = (oh0 >> 1) - 1 + ly, c = (ow0 >> 1) - 1 + lx;
       lpix[j] = (pix < LRPIX && (unsigned)r < (unsigned)a.Hl && (unsigned)c < (unsigned)a.Wl) ? (img * a.Hl + r) * a.Wl + c : -1;
-      if (LOOK > 0) pcnt += __ballot(lpix[j] >= 0) != 0ull;
+      pcnt += __ballot(lpix[j] >= 0) != 0ull;
     }
-    if (LOOK > 0) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
+    pcnt = __builtin_amdgcn_readfirstlane(pcnt);
   }
   const int nch1 = a.C1 >> 5, nch = (a.C1 + a.C2) >> 5;
   int nunits = nch * NTAPS;                                    // (MP: per phase)
@@ -258,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   using Set1 = std::integral_constant<int, DEPTH - 1>;
   f32x4 pr_sets[DEPTH][PJ];
 #define pr (pr_sets[0])                                        /* the UP paths and the single-set kernels */
-  // LOOK > 0: the registers of a prefetch are zeroed IN FRONT of the filter unit issued before it (zero_patch): the compiler cannot tell
+  // The registers of a prefetch are zeroed IN FRONT of the filter unit issued before it (zero_patch): the compiler cannot tell
   // that the set's previous loads were waited for (store_patch sits under another condition) and guards the first write with a full wait,
   // which must not find that unit in flight
   auto zero_patch = [&](auto setc) __attribute__((always_inline)) {
@@ -365,12 +475,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   for (int s = 0; s < NFR; ++s)
 #pragma unroll
     for (int j = 0; j < FJ; ++j) fr[s][j] = (u32x4){0u, 0u, 0u, 0u};
-  auto load_filt = [&](int u) __attribute__((always_inline)) {                                // LOOK = 0
-    const u32x4* g = reinterpret_cast<const u32x4*>(wbase + (size_t)u * UNIT_HALVES);
-#pragma unroll
-    for (int j = 0; j < FJ; ++j) fr[0][j] = g[tid + 256 * j];
-  };
-  // LOOK > 0: the thread's two pieces lie 4096 bytes apart -- past the 13-bit signed offset field, hence the offset register points between them.
+  // The thread's two pieces lie 4096 bytes apart -- past the 13-bit signed offset field, hence the offset register points between them.
   // Always issued, past the last unit of the layer (MP: of the phase) the last unit again: the number of loads in flight stays static.
   // (s: a constant once the kw loop is unrolled)
   const unsigned foff = 16u * (unsigned)tid + 2048u;
@@ -380,13 +485,9 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     asm volatile("global_load_dwordx4 %0, %1, %2 offset:2048" : "+v"(fr[s][1]) : "v"(foff), "s"(ub) : "memory");
   };
   constexpr int PJL = UP ? LRJ : PJ;                           // patch loads of a thread and chunk at most
-  constexpr int WB = (LOOK > 1 ? LOOK - 1 : 0) * FJ;                        // loads of the later units, always behind the one waited for
+  constexpr int WB = (LOOK - 1) * FJ;                          // loads of the later units, always behind the one waited for
 #define X3_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory")
-  auto store_filt = [&](int v) __attribute__((always_inline)) {                               // LOOK = 0: unit v, waited for by the compiler
-#pragma unroll
-    for (int j = 0; j < FJ; ++j) *reinterpret_cast<u32x4*>(filt + (v & 1) * UNIT_HALVES + fdst[j]) = fr[0][j];
-  };
-  // LOOK > 0: unit v (slot s) has landed = everything but the (LOOK - 1) FJ loads of the later units and the np patch loads issued after
+  // Unit v (slot s) has landed = everything but the (LOOK - 1) FJ loads of the later units and the np patch loads issued after
   // it (np < 0: the prologue, nothing was issued after it); then registers -> LDS buffer v & 1.  The counted wait names no register
   // (under a branch, an asm that ties fr is given registers of its own, and the copy into them reads the load in flight); ONE fence
   // behind the branches ties the slot, so that every use of it is ordered after the wait.
@@ -429,39 +530,34 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     nunits = nch * kh_n * kw_n;
     wbase = a.pwp[phase] + (size_t)pn * nunits * UNIT_HALVES;
     patch_geometry(a.pbh[phase], a.pbw[phase]);
-    if (LOOK > 0) pcnt = __builtin_amdgcn_readfirstlane(pcnt);
+    pcnt = __builtin_amdgcn_readfirstlane(pcnt);
     if (phase > 0) __syncthreads();                            // every wave has read the last tap of the previous phase (patch and filter buffers)
   }
   load_patch(0, Set0{});
   if (DEPTH == 2 && nch > 1) load_patch(1, Set1{});
-  if (LOOK == 0) load_filt(0);
-  else issue_filt(0, 0);
+  issue_filt(0, 0);
   if (!MP || phase == 0) x3_range_scale(a.xr1, a.xr2, xs, ixs);
   if (UP) {
     park_lr();
     __syncthreads();
   }
   store_patch(Set0{});
-  if (LOOK == 0) store_filt(0);
-  else wait_store_filt(0, 0, -1, true);
+  wait_store_filt(0, 0, -1, true);
   if (LOOK == 2) issue_filt(1, 1);
   // one chunk: `cur` = the register set chunk c was loaded into (already split into LDS: free for chunk c + DEPTH), `nxt` = the set of chunk c + 1
   auto chunk = [&](int c, auto cur, auto nxt) __attribute__((always_inline)) {
     const bool pf = c + DEPTH < nch;
-    if (LOOK > 0) {
-      // the unit of tap LOOK in FRONT of the patch loads: the waits of taps 0 .. LOOK - 1 are for units older than the patch
-      zero_patch(cur);                                         // (unconditionally: under "if (pf)" every patch load got the compiler's full wait instead)
-      __builtin_amdgcn_sched_barrier(0);
-      issue_filt((MP ? c * kh_n * kw_n : c * NTAPS) + LOOK, LOOK % NFR);      // (slot of tap 0 + LOOK)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (pf) load_patch(c + DEPTH, cur, LOOK > 0);              // lands under the taps of this chunk (and, for the 1 x 1 layers, of the next)
-    if (LOOK > 0) __builtin_amdgcn_sched_barrier(0);
+    // the unit of tap LOOK in FRONT of the patch loads: the waits of taps 0 .. LOOK - 1 are for units older than the patch
+    zero_patch(cur);                                           // (unconditionally: under "if (pf)" every patch load got the compiler's full wait instead)
+    __builtin_amdgcn_sched_barrier(0);
+    issue_filt((MP ? c * kh_n * kw_n : c * NTAPS) + LOOK, LOOK % NFR);        // (slot of tap 0 + LOOK)
+    __builtin_amdgcn_sched_barrier(0);
+    if (pf) load_patch(c + DEPTH, cur, true);                  // lands under the taps of this chunk (and, for the 1 x 1 layers, of the next)
+    __builtin_amdgcn_sched_barrier(0);
     const int np = pf ? pcnt : 0;
-    // One tap, as a macro: the LOOK = 0 loop below is the loop of the first rounds, statement for statement (its code is the same), and the
-    // new order peels the first row of a chunk off the kh loop (FIRST): its first tap's look-ahead unit is already issued and its first
-    // LOOK waits leave the patch in flight -- as straight-line code, since a filter load or a wait that names fr under a branch on kh lets
-    // the compiler hold the slot in other registers on the two sides and copy a load in flight.
+    // One tap, as a macro: the first row of a chunk is peeled off the kh loop (FIRST): its first tap's look-ahead unit is already issued
+    // and its first LOOK waits leave the patch in flight -- as straight-line code, since a filter load or a wait that names fr under a
+    // branch on kh lets the compiler hold the slot in other registers on the two sides and copy a load in flight.
     //   barrier: unit u (and, at the first tap, the patch) is in LDS; buffer (u + 1) & 1 is free
     //   rowh: scalar, the first patch row of this wave and tap; the A-operand reads run one pixel row ahead of the MFMAs that use them
     //   ws = wh 2^-11: exact (power of two; gradual underflow below |wh| = 2^-3 as in fp16 itself)
@@ -472,11 +568,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
     if (MP && kw >= kw_n) continue;                                                                                            \
     const int u = MP ? (c * kh_n + kh) * kw_n + kw : c * NTAPS + kh * KW + kw;                                                 \
     __syncthreads();                                                                                                           \
-    if (LOOK == 0) {                                                                                                           \
-      if (u + 1 < nunits) load_filt(u + 1);                                                                                    \
-    } else if (!(FIRST) || kw > 0) {                                                                                            \
-      issue_filt(u + LOOK, X3_SLOT(LOOK));                                                                                     \
-    }                                                                                                                          \
+    if (!(FIRST) || kw > 0) issue_filt(u + LOOK, X3_SLOT(LOOK));                                                               \
     const _Float16* F = filt + (u & 1) * UNIT_HALVES;                                                                          \
     const int rowh = (wave * MT + kh) * PWID * 32;                                                                             \
                                                                                                                                \
@@ -506,23 +598,13 @@ _Pragma("unroll")                                                               
       for (int ni = 0; ni < NT; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[ni], ph[mi & 1], acc[mi][ni], 0, 0, 0); \
       __builtin_amdgcn_sched_barrier(0);                                                                                       \
     }                                                                                                                          \
-    if (LOOK == 0) {                                                                                                           \
-      if (u + 1 < nunits) store_filt(u + 1);                                                                                   \
-    } else {                                                                                                                   \
-      wait_store_filt(u + 1, X3_SLOT(1), ((FIRST) && kw < LOOK) ? np : 0, u + 1 < nunits);                                       \
-    }                                                                                                                          \
+    wait_store_filt(u + 1, X3_SLOT(1), ((FIRST) && kw < LOOK) ? np : 0, u + 1 < nunits);                                       \
   }
-    if (LOOK == 0) {
-#pragma unroll 1
-      for (int kh = 0; kh < (MP ? kh_n : KH); ++kh) {
-#pragma unroll
-        for (int kw = 0; kw < KW; ++kw) X3_TAP(false)          // unrolled: acol[kw] stays a register
-      }
-    } else if (LOOK == 1) {
+    if (LOOK == 1) {
       {
         const int kh = 0;
 #pragma unroll
-        for (int kw = 0; kw < KW; ++kw) X3_TAP(true)
+        for (int kw = 0; kw < KW; ++kw) X3_TAP(true)           // unrolled: acol[kw] stays a register
       }
 #pragma unroll 1
       for (int kh = 1; kh < (MP ? kh_n : KH); ++kh) {
@@ -561,122 +643,8 @@ _Pragma("unroll")                                                               
 #undef pr
 #undef X3_WAIT_VM
 
-  // ---- epilogue: y = act2(affine(act1(acc * 2^-S + bias))), 16-byte stores (lane = pixel x 4 consecutive couts); the 2 x 2 pooling
-  //      window of the optional second output is two rows of this lane and of its neighbour lane -----------------------------------
-  const float inv_s = a.hdr[1] * ixs;
-  const int ow = ow0 + pc;                                     // the lane's tile column (pcol permutation)
-  // bias / scale / shift of the lane's four cout quads are loaded ONCE, in front of the store loop: a load inside it is followed by
-  // "s_waitcnt vmcnt(0)", which also sits out the round trip of the output store issued just before it -- the stores of a block went
-  // out one at a time
-  // (the offsets pass through an opaque asm so that the loads are not hoisted above the tap loop, where their registers would be live
-  //  for the whole kernel)
-  const unsigned yr_seen = (a.yr && a.final) ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  int ep0 = n0;
-  asm volatile("" : "+s"(ep0));
-  f32x4 bias_r[NT], scale_r[NT], shift_r[NT];
-#pragma unroll
-  for (int ni = 0; ni < NT; ++ni) {
-    const int cl = ni * 16 + 4 * fg;
-    const bool cv = ep0 + cl < a.Cout;                           // (false only in the zero half of a 32-cout layer's slice: nothing loaded, nothing stored)
-    bias_r[ni] = (a.bias && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.bias + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    scale_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.scale + ep0 + cl) : (f32x4){1.f, 1.f, 1.f, 1.f};
-    shift_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.shift + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  // the partial sums of the earlier phases of a stride-2 layer (yin), batched in front of the stores for the same reason
-  // (the residual of a final launch travels in the same registers: a layer has partial sums OR a residual)
-  f32x4 yin_r[MT / 2][NT][2];
-  const float* addend = a.yin ? a.yin : (a.final ? a.res : nullptr);
-  if (addend) {
-    const int add_cs = a.yin ? a.Cout : a.res_cs;
-#pragma unroll
-    for (int mp = 0; mp < MT / 2; ++mp)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int oh = oh0 + wave * MT + 2 * mp + r;
-          yin_r[mp][ni][r] = (oh < a.H && ow < a.W && ep0 + ni * 16 + 4 * fg < a.Cout)
-                                 ? *reinterpret_cast<const f32x4*>(addend + ((size_t)(img * a.H + oh) * a.W + ow) * add_cs + ep0 + ni * 16 + 4 * fg)
-                                 : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-  }
-  float ym = 0.0f;                                             // max |y| over this lane's stored values (a.yr)
-#pragma unroll
-  for (int mp = 0; mp < MT / 2; ++mp) {
-    const int oh = oh0 + wave * MT + 2 * mp;                   // even row of the pair (H even whenever yp is given)
-    if (oh >= a.H) continue;                                   // wave-uniform
-    float pj[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};      // a.proj: this lane's share (16 of the 64 couts) of the projected pixel, rows oh, oh + 1
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) {
-      const int cl = ni * 16 + 4 * fg;
-      f32x4 v[2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        v[r] = acc[2 * mp + r][ni] * inv_s;
-        const bool inside = oh + r < a.H && ow < a.W;
-        if (a.yin) v[r] += yin_r[mp][ni][r];
-        if (!a.final) {
-          if (inside) *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
-          continue;
-        }
-        v[r] += bias_r[ni];
-        shdr::act_apply4<0>(v[r], a.act1);
-        if (a.scale) v[r] = v[r] * scale_r[ni] + shift_r[ni];
-        if (a.res) v[r] += yin_r[mp][ni][r];
-        shdr::act_apply4<0>(v[r], a.act2);
-        if (a.y && oh + r < a.H && ow < a.W && n0 + cl < a.Cout)
-          *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
-        if (a.proj) {
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            const f32x4 q = *reinterpret_cast<const f32x4*>(a.proj + j * 64 + cl);
-            pj[r][j] += v[r][0] * q[0] + v[r][1] * q[1] + v[r][2] * q[2] + v[r][3] * q[3];
-          }
-        }
-#ifndef SHDR_ABL_NO_YM
-        if (a.yr && oh + r < a.H) ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[r][0])), fabsf(v[r][1])), fabsf(v[r][2])), fabsf(v[r][3]));      // two v_max3_f32
-#endif
-      }
-      if (a.yp && a.final) {
-        f32x4 m;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (a.pool_avg) {                                    // (top-left + top-right) + (bottom-left + bottom-right), as pool.hip adds them
-            const float t = v[0][e] + __shfl_xor(v[0][e], 1, 64), b = v[1][e] + __shfl_xor(v[1][e], 1, 64);
-            m[e] = 0.25f * (t + b);
-          } else {
-            m[e] = fmaxf(v[0][e], v[1][e]);
-            m[e] = fmaxf(m[e], __shfl_xor(m[e], 1, 64));
-          }
-        }
-        if (!(pc & 1) && ow < a.W && n0 + cl < a.Cout)           // lanes fi and fi ^ 1 hold columns pc and pc ^ 1
-          *reinterpret_cast<f32x4*>(a.yp + ((size_t)(img * (a.H >> 1) + (oh >> 1)) * (a.W >> 1) + (ow >> 1)) * a.Cout + n0 + cl) = m;
-      }
-    }
-    if (a.proj && a.final) {                                   // the four lane groups fg hold 16 couts each of the same pixel
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          float t = pj[r][j];
-          t += __shfl_xor(t, 16, 64);
-          t += __shfl_xor(t, 32, 64);
-          pj[r][j] = t;
-        }
-        if (fg == 0 && oh + r < a.H && ow < a.W) {
-          float* o = a.yproj + ((size_t)(img * a.H + oh + r) * a.W + ow) * 3;
-          o[0] = pj[r][0]; o[1] = pj[r][1]; o[2] = pj[r][2];
-        }
-      }
-    }
-  }
-#ifndef SHDR_ABL_NO_TAIL
-  // (a pooled output is bounded by the same maximum).  The waves' words have LDS of their own: without a barrier after the last chunk (the
-  // 1 x 1 form) wave 0 may still be reading patch pixel (0, 0) when another wave writes its maximum
-  if (a.yr && a.final)
-    x3_range_out(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen,
-                 reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + (UP ? G::LDS_BYTES_UP : G::LDS_BYTES)));
-#endif
+  x3_tile_epilogue<4, true>(a, acc, img, oh0 + wave * MT, ow0 + pc, pc, fg, n0, ixs, lane, wave,
+                            reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + (UP ? G::LDS_BYTES_UP : G::LDS_BYTES)));
 }
 
 #undef patch_h
@@ -865,7 +833,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni) {
         f32x4 v = acc[m0 + e][ni] * inv_s;
-        asm("" : "+v"(v));                                     // rounded before the bias, as in conv_x3_kernel (its yin select keeps the two apart)
+        asm("" : "+v"(v));                                     // rounded before the bias, as in conv_x3_kernel: unfenced, the two contract into one FMA
         v += bias_r[ni];
         shdr::act_apply4<0>(v, a.act1);
         if (a.scale) v = v * scale_r[ni] + shift_r[ni];
@@ -1205,87 +1173,8 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
   }
 #undef XW_WAIT_VM
 
-  // ---- epilogue: conv_x3_kernel's (without the projected output, which needs Cout = 64), on the wave's slice and rows --------------------------------------------
-  const float inv_s = a.hdr[1] * ixs;
-  const int ow = ow0 + pc;
-  const unsigned yr_seen = (a.yr && a.final) ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  int ep0 = n0;
-  asm volatile("" : "+s"(ep0));
-  f32x4 bias_r[NT], scale_r[NT], shift_r[NT];
-#pragma unroll
-  for (int ni = 0; ni < NT; ++ni) {
-    const int cl = ni * 16 + 4 * fg;
-    const bool cv = ep0 + cl < a.Cout;
-    bias_r[ni] = (a.bias && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.bias + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    scale_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.scale + ep0 + cl) : (f32x4){1.f, 1.f, 1.f, 1.f};
-    shift_r[ni] = (a.scale && a.final && cv) ? *reinterpret_cast<const f32x4*>(a.shift + ep0 + cl) : (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
-  f32x4 yin_r[MT / 2][NT][2];
-  const float* addend = a.yin ? a.yin : (a.final ? a.res : nullptr);
-  if (addend) {
-    const int add_cs = a.yin ? a.Cout : a.res_cs;
-#pragma unroll
-    for (int mp = 0; mp < MT / 2; ++mp)
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int oh = oh0 + wq * MT + 2 * mp + r;
-          yin_r[mp][ni][r] = (oh < a.H && ow < a.W && ep0 + ni * 16 + 4 * fg < a.Cout)
-                                 ? *reinterpret_cast<const f32x4*>(addend + ((size_t)(img * a.H + oh) * a.W + ow) * add_cs + ep0 + ni * 16 + 4 * fg)
-                                 : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-  }
-  float ym = 0.0f;
-#pragma unroll
-  for (int mp = 0; mp < MT / 2; ++mp) {
-    const int oh = oh0 + wq * MT + 2 * mp;
-    if (oh >= a.H) continue;                                   // wave-uniform
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) {
-      const int cl = ni * 16 + 4 * fg;
-      f32x4 v[2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        v[r] = acc[2 * mp + r][ni] * inv_s;
-        const bool inside = oh + r < a.H && ow < a.W;
-        if (a.yin) v[r] += yin_r[mp][ni][r];
-        if (!a.final) {
-          if (inside) *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
-          continue;
-        }
-        v[r] += bias_r[ni];
-        shdr::act_apply4<0>(v[r], a.act1);
-        if (a.scale) v[r] = v[r] * scale_r[ni] + shift_r[ni];
-        if (a.res) v[r] += yin_r[mp][ni][r];
-        shdr::act_apply4<0>(v[r], a.act2);
-        if (a.y && oh + r < a.H && ow < a.W && n0 + cl < a.Cout)
-          *reinterpret_cast<f32x4*>(a.y + ((size_t)(img * a.H + oh + r) * a.W + ow) * a.Cout + n0 + cl) = v[r];
-#ifndef SHDR_ABL_NO_YM
-        if (a.yr && oh + r < a.H) ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[r][0])), fabsf(v[r][1])), fabsf(v[r][2])), fabsf(v[r][3]));
-#endif
-      }
-      if (a.yp && a.final) {
-        f32x4 m;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (a.pool_avg) {
-            const float t = v[0][e] + __shfl_xor(v[0][e], 1, 64), b = v[1][e] + __shfl_xor(v[1][e], 1, 64);
-            m[e] = 0.25f * (t + b);
-          } else {
-            m[e] = fmaxf(v[0][e], v[1][e]);
-            m[e] = fmaxf(m[e], __shfl_xor(m[e], 1, 64));
-          }
-        }
-        if (!(pc & 1) && ow < a.W && n0 + cl < a.Cout)
-          *reinterpret_cast<f32x4*>(a.yp + ((size_t)(img * (a.H >> 1) + (oh >> 1)) * (a.W >> 1) + (ow >> 1)) * a.Cout + n0 + cl) = m;
-      }
-    }
-  }
-#ifndef SHDR_ABL_NO_TAIL
-  if (a.yr && a.final)
-    x3_range_out<8>(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + XWG::LDS_BYTES + (UP ? XWG::LR_BYTES : 0)));
-#endif
+  x3_tile_epilogue<8, false>(a, acc, img, oh0 + wq * MT, ow0 + pc, pc, fg, n0, ixs, lane, wave,
+                             reinterpret_cast<unsigned*>(reinterpret_cast<char*>(xsm) + XWG::LDS_BYTES + (UP ? XWG::LR_BYTES : 0)));
 }
 #undef patch_buf
 #undef filt
@@ -1352,7 +1241,7 @@ namespace {
 struct X3Phase { int th, tw, p0, q0, step, bh, bw; };
 // 3 x 3 / stride 1: one "phase" (all nine taps).  7 x 7 / stride 2 (linearization_net.py:91): input pixels of one row / column parity
 // meet the filter taps of one parity only, so the layer is the sum of four stride-1 correlations of the parity-subsampled input with
-// the 4 x 4, 4 x 3, 3 x 4 and 3 x 3 sub-filters -- exactly the 49 taps, each phase one launch accumulating into y.
+// the 4 x 4, 4 x 3, 3 x 4 and 3 x 3 sub-filters -- exactly the 49 taps, the four phases of the MP kernel.
 int x3_phases(const shdr_conv2d_desc* d, X3Phase ph[4]) {
   if (d->stride == 1 || d->KH == 1) {
     // 3 x 3 (pad 1) or 1 x 1 (pad 0): all taps in one launch; the 1 x 1 / stride-2 layer reads input pixel (2 oh, 2 ow)
@@ -1381,16 +1270,13 @@ int launch_x3_look(const X3Args& a, hipStream_t st) {
   hipLaunchKernelGGL((conv_x3_kernel<UP, KH, KW, MP, LOOK>), dim3((unsigned)nblk), dim3(256), lds, st, a);
   return shdr::check_launch("conv_x3_kernel");
 }
-// SHDR_X3_LEGACY_PREFETCH=1: the issue order of the first rounds (LOOK = 0), kept for same-box A/B runs and the bit-identity tests
-// (tests/test_gpu_x3_prefetch.py); it goes, with LOOK = 0, once a later round has confirmed the numbers of DESIGN.md section 6
-// (profiles/r05_bench_ab.txt).  SHDR_X3_LOOK=1|2: the filter look-ahead (A/B; default 2, the faster by wall time).
+// SHDR_X3_LOOK=1|2: the filter look-ahead (A/B and the second arm of tests/test_gpu_x3_prefetch.py; default 2, the faster by wall time).
 template <bool UP, int KH, int KW, bool MP = false>
 int launch_x3(const X3Args& a, hipStream_t st) {
-  if (SHDR_ENV("SHDR_X3_LEGACY_PREFETCH")) return launch_x3_look<UP, KH, KW, MP, 0>(a, st);
   int look = 2;
   if (const char* e = SHDR_ENV("SHDR_X3_LOOK")) look = atoi(e);
   // LOOK = 2 is built for the nine-tap kernels (3 x 3, with and without the up-sampling prologue): the stem is out of registers at
-  // LOOK = 1, a 1 x 1 chunk has no second tap, and the phase-launch forms of the stem run only under SHDR_X3_STEM_PHASE_LAUNCHES=1
+  // LOOK = 1 and a 1 x 1 chunk has no second tap
   constexpr bool look2 = KH == 3 && KW == 3 && !MP;
   if (look >= 2 && look2) return launch_x3_look<UP, KH, KW, MP, look2 ? 2 : 1>(a, st);
   return launch_x3_look<UP, KH, KW, MP, 1>(a, st);
@@ -1577,14 +1463,15 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   X3Phase ph[4];
   const int n = x3_phases(d, ph);
-  SHDR_REQUIRE(n == 1 || y, SHDR_E_NULL, "conv2d_x3: the phases of a stride-2 layer accumulate in y");
   const int Ct = d->C1 + d->C2;
-  const float* pk = prepared;
-  if (n == 4 && SHDR_ENV("SHDR_X3_STEM_PHASE_LAUNCHES") == nullptr) {
+  a.hdr = prepared;
+  a.wp = reinterpret_cast<const _Float16*>(prepared + X3_HEADER_FLOATS);
+  if (rs && !x1_range) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + 2;      // the header-slot protocol (shdr_conv2d_x3_input_absmax_f32)
+  a.in_s = ph[0].step; a.bh = ph[0].bh; a.bw = ph[0].bw;
+  if (n == 4) {
     // the stride-2 stem in ONE launch: the phases' packed sub-filters share the scale 2^S (each header's maximum is taken over the whole
     // filter), the partial sums stay in registers
-    a.hdr = pk;
-    a.in_s = ph[0].step;
+    const float* pk = prepared;
     a.nphase = 4;
     for (int i = 0; i < 4; ++i) {
       SHDR_REQUIRE(ph[i].th <= 4 && ph[i].tw <= 4 && ph[i].step == ph[0].step, SHDR_E_SHAPE, "conv2d_x3: unexpected phase geometry");
@@ -1592,52 +1479,33 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
       a.pwp[i] = reinterpret_cast<const _Float16*>(pk + X3_HEADER_FLOATS);
       pk += x3_phase_floats(ph[i], Ct, d->Cout);
     }
-    a.wp = a.pwp[0];
-    a.yin = nullptr;
-    a.final = 1;
-    if (rs && !x1_range) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + 2;
     return launch_x3<false, 4, 4, true>(a, st);
   }
-  for (int i = 0; i < n; ++i) {
-    a.hdr = pk;
-    a.wp = reinterpret_cast<const _Float16*>(pk + X3_HEADER_FLOATS);
-    if (rs && !x1_range) a.xr1 = reinterpret_cast<const unsigned*>(pk) + 2;      // the header-slot protocol (shdr_conv2d_x3_input_absmax_f32)
-    a.in_s = ph[i].step; a.bh = ph[i].bh; a.bw = ph[i].bw;
-    a.yin = i > 0 ? y : nullptr;
-    a.final = i == n - 1;
-    int rc;
-    if (ph[i].th == 3 && ph[i].tw == 3) {
-      // the 128-cout blocks (conv_x3_wide_kernel<UP>) take the stride-1 layers with a multiple of 128 couts and at least 256 blocks: with
-      // the up-sampling prologue from 128 couts on, plain from 512 couts on; a projected output (Cout = 64) and SHDR_X3_SLICED=1 (A/B,
-      // tests/test_gpu_x3_wide.py) run the 64-cout kernel.  Measured (tools/x3_wide_ab.py, profiles/r06_x3_wide_layers_ab.txt; sliced / wide
-      // by the medians of five rounds, batch 16 and 8):
-      //   up-sampling, >= 256 blocks: 64^2 x2 512 -> 256 1.109 and 1.102, 128^2 x2 256 -> 128 1.089 and 1.088, 32^2 x2 256 -> 128 1.121 at
-      //   batch 16 -- the ranges apart everywhere (the expansion and the split run once per 128 couts, under the MFMAs);
-      //   plain, 512 couts: 64^2 1.018 - 1.020 and 1.029 - 1.033, 32^2 at batch 16 (256 blocks) 1.053, the ranges apart (an earlier session
-      //   on another box: 64^2 256 -> 512 at batch 16 1.017 with the ranges overlapping);
-      //   plain, 256 couts: 0.985 - 1.012 and 1.002 - 1.018, 128 couts: 0.980 - 1.039 and 0.960 - 0.994, ranges overlapping: they stay sliced;
-      //   128 blocks and fewer (half the CUs idle): 0.74 - 0.87, plain and up-sampling alike.
-      long wide_min_blocks = 256, wide_min_cout = up ? XW_UP_MIN_COUT : 512;
-      if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_BLOCKS")) wide_min_blocks = atol(e);
-      if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_COUT")) wide_min_cout = atol(e);
-      const bool wide = n == 1 && d->stride == 1 && d->Cout % XW_BN == 0 && d->Cout >= wide_min_cout && !proj &&
-                        (long)a.nblk_m * (d->Cout / XW_BN) >= wide_min_blocks && SHDR_ENV("SHDR_X3_SLICED") == nullptr;
-      rc = wide ? (up ? launch_x3_wide<true>(a, st) : launch_x3_wide<false>(a, st)) : up ? launch_x3<true, 3, 3>(a, st) : launch_x3<false, 3, 3>(a, st);
-    }
-    else if (ph[i].th == 1 && ph[i].tw == 1) {
-      // the wide-block kernel takes 128- and 256-cout multiples with a plain output; a pooled or projected output (no network has one
-      // on a 1 x 1 layer), the narrow layers and SHDR_X3_1X1_SLICED=1 (A/B) run the 64-cout instantiation
-      const bool wide = d->Cout % 128 == 0 && y && !y_pool && !proj && !up && n == 1 && SHDR_ENV("SHDR_X3_1X1_SLICED") == nullptr;
-      rc = wide ? launch_x3_1x1(a, st) : launch_x3<false, 1, 1>(a, st);
-    }
-    else if (ph[i].th == 4 && ph[i].tw == 4) rc = launch_x3<false, 4, 4>(a, st);
-    else if (ph[i].th == 4 && ph[i].tw == 3) rc = launch_x3<false, 4, 3>(a, st);
-    else if (ph[i].th == 3 && ph[i].tw == 4) rc = launch_x3<false, 3, 4>(a, st);
-    else rc = shdr::fail(SHDR_E_SHAPE, "conv2d_x3: no kernel for a %d x %d phase", ph[i].th, ph[i].tw);
-    if (rc) return rc;
-    pk += x3_phase_floats(ph[i], Ct, d->Cout);
+  if (ph[0].th == 3 && ph[0].tw == 3) {
+    // the 128-cout blocks (conv_x3_wide_kernel<UP>) take the stride-1 layers with a multiple of 128 couts and at least 256 blocks: with
+    // the up-sampling prologue from 128 couts on, plain from 512 couts on; a projected output (Cout = 64) and SHDR_X3_SLICED=1 (A/B,
+    // tests/test_gpu_x3_wide.py) run the 64-cout kernel.  Measured (tools/x3_wide_ab.py, profiles/r06_x3_wide_layers_ab.txt; sliced / wide
+    // by the medians of five rounds, batch 16 and 8):
+    //   up-sampling, >= 256 blocks: 64^2 x2 512 -> 256 1.109 and 1.102, 128^2 x2 256 -> 128 1.089 and 1.088, 32^2 x2 256 -> 128 1.121 at
+    //   batch 16 -- the ranges apart everywhere (the expansion and the split run once per 128 couts, under the MFMAs);
+    //   plain, 512 couts: 64^2 1.018 - 1.020 and 1.029 - 1.033, 32^2 at batch 16 (256 blocks) 1.053, the ranges apart (an earlier session
+    //   on another box: 64^2 256 -> 512 at batch 16 1.017 with the ranges overlapping);
+    //   plain, 256 couts: 0.985 - 1.012 and 1.002 - 1.018, 128 couts: 0.980 - 1.039 and 0.960 - 0.994, ranges overlapping: they stay sliced;
+    //   128 blocks and fewer (half the CUs idle): 0.74 - 0.87, plain and up-sampling alike.
+    long wide_min_blocks = 256, wide_min_cout = up ? XW_UP_MIN_COUT : 512;
+    if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_BLOCKS")) wide_min_blocks = atol(e);
+    if (const char* e = SHDR_ENV("SHDR_X3_WIDE_MIN_COUT")) wide_min_cout = atol(e);
+    const bool wide = d->stride == 1 && d->Cout % XW_BN == 0 && d->Cout >= wide_min_cout && !proj &&
+                      (long)a.nblk_m * (d->Cout / XW_BN) >= wide_min_blocks && SHDR_ENV("SHDR_X3_SLICED") == nullptr;
+    return wide ? (up ? launch_x3_wide<true>(a, st) : launch_x3_wide<false>(a, st)) : up ? launch_x3<true, 3, 3>(a, st) : launch_x3<false, 3, 3>(a, st);
   }
-  return SHDR_OK;
+  if (ph[0].th == 1 && ph[0].tw == 1) {
+    // the wide-block kernel takes 128- and 256-cout multiples with a plain output; a pooled or projected output (no network has one
+    // on a 1 x 1 layer), the narrow layers and SHDR_X3_1X1_SLICED=1 (A/B) run the 64-cout instantiation
+    const bool wide = d->Cout % 128 == 0 && y && !y_pool && !proj && !up && SHDR_ENV("SHDR_X3_1X1_SLICED") == nullptr;
+    return wide ? launch_x3_1x1(a, st) : launch_x3<false, 1, 1>(a, st);
+  }
+  return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: no kernel for a %d x %d layer", ph[0].th, ph[0].tw);
 }
 
 extern "C" int shdr_conv2d_fwd_x3_ranged_f32(const shdr_conv2d_desc* d, const float* x1, const float* x2, const float* prepared, const float* bias,

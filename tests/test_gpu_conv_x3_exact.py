@@ -211,9 +211,9 @@ def instance(o):
         return "conv_x3n_kernel<%d, %d, %d, %s, %s>" % (k, ct, cout // 16, "true" if c2 else "false", "true" if o.get("tanh") else "false")
     if o["plan"] != "x3":
         return "plan " + o["plan"]
-    look = 0 if "SHDR_X3_LEGACY_PREFETCH" in env else int(env.get("SHDR_X3_LOOK", 2))
+    look = int(env.get("SHDR_X3_LOOK", 2))
     if k == 7:
-        return "conv_x3_kernel<false, 4..3, 4..3> x 4 launches" if "SHDR_X3_STEM_PHASE_LAUNCHES" in env else "conv_x3_kernel<false, 4, 4, true, %d>" % min(look, 1)
+        return "conv_x3_kernel<false, 4, 4, true, 1>"
     if k == 1:
         wide = cout % 128 == 0 and not o.get("pool") and not o.get("proj") and "SHDR_X3_1X1_SLICED" not in env
         return "conv_x3_1x1_kernel<%d>" % (4 if cout % 256 == 0 else 2) if wide else "conv_x3_kernel<false, 1, 1, false, %d>" % min(look, 1)
@@ -378,11 +378,13 @@ X3_3X3 = [
     # Cout 32: one 64-cout slice, half of it zero columns that are neither biased nor stored
     case("x3_c64_32_1x17x15_fx_affine", "x3", 1, 17, 15, 64, 0, 32, 3, mode="fx", epi="affine", env=MB),
     case("x3_two_32_32_scaled_32_1x15x16_int_res", "x3", 1, 15, 16, 32, 32, 32, 3, epi="res", x2s=S8, env=MB),
-    # the issue orders of the global loads: LOOK 1 and the legacy order (LOOK 2 is the default above)
+    # the issue orders of the global loads: LOOK 1, and LOOK 2 (the default above) at two more shapes.  The "legacy" cases here and in
+    # X3_UP ran the load order of the first rounds until it was removed and run the default order now; they keep
+    # their names, which seed their operands
     case("x3_look1_c96_64_1x17x33_fxw", "x3", 1, 17, 33, 96, 0, 64, 3, mode="fxw", env=dict(MB, SHDR_X3_LOOK="1")),
     case("x3_look1_two_32_64_scaled_1x33x15_fw", "x3", 1, 33, 15, 32, 64, 64, 3, mode="fw", x2s=S8, env=dict(MB, SHDR_X3_LOOK="1")),
-    case("x3_legacy_c96_128_1x15x17_fxw_res", "x3", 1, 15, 17, 96, 0, 128, 3, mode="fxw", epi="res", env=dict(MB, SHDR_X3_LEGACY_PREFETCH="1")),
-    case("x3_legacy_c32_64_3x1x1_fx", "x3", 3, 1, 1, 32, 0, 64, 3, mode="fx", env=dict(MB, SHDR_X3_LEGACY_PREFETCH="1")),
+    case("x3_legacy_c96_128_1x15x17_fxw_res", "x3", 1, 15, 17, 96, 0, 128, 3, mode="fxw", epi="res", env=MB),
+    case("x3_legacy_c32_64_3x1x1_fx", "x3", 3, 1, 1, 32, 0, 64, 3, mode="fx", env=MB),
 ]
 
 
@@ -429,7 +431,7 @@ X3_UP = [
     case("x3_up_projected_c64_64_1x9x11_int_relu", "x3", 1, 9, 11, 64, 0, 64, 3, epi="relu", up=True, proj=True, env=MB),
     case("x3_up_projected_c32_64_1x8x8_fw", "x3", 1, 8, 8, 32, 0, 64, 3, mode="fw", keep=0.3, up=True, proj=True, env=MB),
     case("x3_up_look1_c64_64_1x9x11_fw", "x3", 1, 9, 11, 64, 0, 64, 3, mode="fw", keep=0.5, up=True, env=dict(MB, SHDR_X3_LOOK="1")),
-    case("x3_up_legacy_c64_64_1x8x8_fw", "x3", 1, 8, 8, 64, 0, 64, 3, mode="fw", keep=0.5, up=True, env=dict(MB, SHDR_X3_LEGACY_PREFETCH="1")),
+    case("x3_up_legacy_c64_64_1x8x8_fw", "x3", 1, 8, 8, 64, 0, 64, 3, mode="fw", keep=0.5, up=True, env=MB),
     case("x3_up_cout512_materialised_c32_1x9x11_fw", "x3", 1, 9, 11, 32, 0, 512, 3, mode="fw", up=True, env=MB),
     case("x3_up_cout512_in_kernel_c32_1x9x11_fw", "x3", 1, 9, 11, 32, 0, 512, 3, mode="fw", up=True, env=dict(MB, SHDR_X3_UP_ALWAYS="1")),
 ]
@@ -472,16 +474,15 @@ def test_x3_declines_1x1_with_k32_and_another_kernel_answers(K, lib, monkeypatch
     run_forward(K, lib, o, monkeypatch)
 
 
-# the 7 x 7 / 2 stem: the MP kernel (four phases in one launch) and the four phase launches <4, 4>, <4, 3>, <3, 4>, <3, 3> with the
-# partial sums travelling through y (`yin`).  K = 4704: int mode.
-PH = dict(MB, SHDR_X3_STEM_PHASE_LAUNCHES="1")
+# the 7 x 7 / 2 stem: the MP kernel (four phases of 4 x 4, 4 x 3, 3 x 4 and 3 x 3 taps in one launch).  K = 4704: int mode.  The
+# "stem_phases" cases ran the four-launch form until it was removed and run the MP kernel now; they keep their names, which seed their operands.
 X3_STEM = [
     case("stem_mp_96_64_1x17x16_relu", "x3", 1, 17, 16, 96, 0, 64, 7, stride=2, epi="relu", env=MB),
     case("stem_mp_96_128_1x32x32_affine", "x3", 1, 32, 32, 96, 0, 128, 7, stride=2, epi="affine", env=MB),
     case("stem_mp_96_64_3x33x35", "x3", 3, 33, 35, 96, 0, 64, 7, stride=2, env=MB),
-    case("stem_phases_96_64_1x17x16_affine", "x3", 1, 17, 16, 96, 0, 64, 7, stride=2, epi="affine", env=PH),
-    case("stem_phases_96_128_1x33x35_relu", "x3", 1, 33, 35, 96, 0, 128, 7, stride=2, epi="relu", env=PH),
-    case("stem_phases_32_64_1x32x32_lrelu", "x3", 1, 32, 32, 32, 0, 64, 7, stride=2, epi="lrelu", env=PH),
+    case("stem_phases_96_64_1x17x16_affine", "x3", 1, 17, 16, 96, 0, 64, 7, stride=2, epi="affine", env=MB),
+    case("stem_phases_96_128_1x33x35_relu", "x3", 1, 33, 35, 96, 0, 128, 7, stride=2, epi="relu", env=MB),
+    case("stem_phases_32_64_1x32x32_lrelu", "x3", 1, 32, 32, 32, 0, 64, 7, stride=2, epi="lrelu", env=MB),
 ]
 
 

@@ -107,21 +107,6 @@ def test_split_operand_switches(shdr, monkeypatch, var, shape):
     assert maxrel(got, ref) <= 5e-6, (var, plan)
 
 
-def test_stem_phase_launches_switch(shdr, monkeypatch):
-    """the 7x7 / stride-2 stem in one launch (partial sums of the four parity phases in registers) vs four launches accumulating in y:
-    the same products in the same order within a phase, the phases summed in another order"""
-    K = shdr._ops
-    monkeypatch.setenv("SHDR_X3_MIN_BLOCKS", "1")
-    for n, h, w in ((1, 64, 80), (2, 70, 46)):               # (ragged tiles, odd output sizes in the second case)
-        x, wt, b = _rand(n, h, w, 96, seed=30), _rand(7, 7, 96, 64, seed=31, scale=1.0 / (7 * 96 ** 0.5)), _rand(64, seed=32)
-        assert K.conv2d_plan((n, h, w, 96), tuple(wt.shape), stride=2) == "x3"
-        one = K.conv2d(x, wt, b, stride=2, act1=K.ACT_RELU)
-        monkeypatch.setenv("SHDR_X3_STEM_PHASE_LAUNCHES", "1")
-        four = K.conv2d(x, wt, b, stride=2, act1=K.ACT_RELU)
-        monkeypatch.delenv("SHDR_X3_STEM_PHASE_LAUNCHES")
-        assert maxrel(one, four) <= 2e-6
-
-
 def test_x3_up_always_switch_is_bit_identical(shdr, monkeypatch):
     """the bilinear prologue fused into the split kernel at 512 couts (the plan fuses it up to 256) = resize2x + the same kernel"""
     K = shdr._ops
