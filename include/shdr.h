@@ -185,6 +185,27 @@ int shdr_conv2d_fwd_prepared_projected_f32(const shdr_conv2d_desc* d, const floa
                                            float* y, float* y_pool, void* workspace, const float* x1_range, const float* x2_range,
                                            float* y_range, void* stream);
 
+/* The up-sampling 3x3 layers with the channel mix at LOW resolution (csrc/up2_lowres.hip; hallucination_net.py:77-91, inference):
+ * tf.image.resize(2x, BILINEAR) acts per channel, so conv3x3(resize2x(x)) = a 1x1 convolution Cin -> 9 Cout on the low-res image (one
+ * Cin x Cout matrix per tap: four times fewer MFMAs than the convolution on the up-sampled image) followed by a stencil pass that sums
+ * the nine tap planes with the bilinear weights (clamped indices; taps outside the up-sampled image left out) and applies the conv
+ * epilogue.  Same accuracy class as SHDR_PLAN_X3, other roundings: an OPT-IN form next to desc.prologue = SHDR_PROLOGUE_BILINEAR2X of
+ * shdr_conv2d_fwd_prepared_f32, whose descriptor `d` it takes (H, W: the up-sampled size).
+ * _ok: 1 if the layer is taken -- 3x3 / stride 1 / SAME, one source, even H and W, Cin % 32 == 0 and >= 64, Cout % 64 == 0, algo AUTO,
+ *      the low-res GEMM on the split-operand plan (SHDR_X3_MIN_BLOCKS applies to it); 0 under SHDR_NO_UP2_LOWRES=1.
+ * _filter_elems / _prepare_filter: floats of the prepared filter (16-byte aligned) and its preparation from the HWIO filter w
+ *      [3,3,Cin,Cout], once per filter version.
+ * _workspace_bytes: bytes the caller provides per forward call (the tap planes z [N,H/2,W/2,9 Cout (+ pad)], 256-byte aligned).
+ * _fwd: x the low-res tensor [N,H/2,W/2,Cin] -> y [N,H,W,Cout] = act2(affine(act1(conv + bias))); two launches on `stream`.
+ *      x_range / y_range: range slots as in shdr_conv2d_fwd_prepared_ranged_f32 (x_range NULL: measured). */
+int shdr_conv2d_up2_lowres_ok_f32(const shdr_conv2d_desc* d);
+int64_t shdr_conv2d_up2_lowres_filter_elems_f32(const shdr_conv2d_desc* d);
+int shdr_conv2d_up2_lowres_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream);
+int64_t shdr_conv2d_up2_lowres_workspace_bytes_f32(const shdr_conv2d_desc* d);
+int shdr_conv2d_fwd_up2_lowres_f32(const shdr_conv2d_desc* d, const float* x, const float* prepared, const float* bias,
+                                   const float* scale, const float* shift, float* y, void* workspace, const float* x_range,
+                                   float* y_range, void* stream);
+
 /*
  * Convolution backward (GradientTape.gradient through Conv2D: joint_training.py:185,
  * train.py:175,195,242, finetune_real_dataset.py:177).

@@ -263,13 +263,21 @@ def conv2d(x, w, bias=None, stride=1, x2=None, x2_scale=1.0, act1=ACT_NONE, scal
                        w_batch_stride, None)
 
 
-def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_NONE, proj=None):
+def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_NONE, proj=None, lowres=False):
     """Conv2D(SAME, stride 1)(tf.image.resize(x, 2x, BILINEAR)) with the conv2d epilogue -- the `up` blocks of
     hallucination_net.py:86-88 and dequantization_net.py:25-27.  Without a gradient tape the library fuses the resize into the
     convolution where the plan allows it (desc.prologue, csrc/conv_plan.hip); under a tape, and in the reduced-precision operand
     modes, it is the two recorded ops.
     proj [3, Cout]: the PROJECTED output sum_c proj[j, c] y[..., c] instead of y (include/shdr.h:
-    shdr_conv2d_fwd_prepared_projected_f32), or None when the planned kernel of the layer cannot form it."""
+    shdr_conv2d_fwd_prepared_projected_f32), or None when the planned kernel of the layer cannot form it.
+    lowres=True: the caller accepts the form that mixes the channels at LOW resolution (csrc/up2_lowres.hip: a 1x1 GEMM Cin -> 9 Cout on
+    x, then a stencil pass; the accuracy class of the split-operand kernels, not the bits of the default form) where the library takes the
+    layer (shdr_conv2d_up2_lowres_ok_f32); elsewhere, and with the default, this is the call below."""
+    if lowres and proj is None and not _is_h(x) and _AUTO_ALGO[PRECISION] == ALGO_AUTO and WINOGRAD and not EXACT_FP32 \
+            and not _needs_grad(x, w, bias, scale, shift):
+        y = _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2)
+        if y is not None:
+            return y
     algo = _AUTO_ALGO[PRECISION]
     if _is_h(x) or algo != ALGO_AUTO or not WINOGRAD or _needs_grad(x, w, bias, scale, shift):
         if proj is not None:
@@ -277,6 +285,55 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
         return conv2d(resize2x(x), w, bias, act1=act1, scale=scale, shift=shift, act2=act2)
     return _conv2d_raw(x, w, bias, 1, None, 1.0, act1, scale, shift, None, act2, algo, None, None, None, None, 0, None,
                        prologue=PROLOGUE_BILINEAR2X, proj=proj)
+
+
+def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
+    """conv2d_up2 through shdr_conv2d_fwd_up2_lowres_f32, or None where the library does not take the layer.  Plumbing only: the
+    descriptor of _conv2d_raw's bilinear-prologue call, the prepared filter kept on the variable per version, the workspace."""
+    lib = _lib.load()
+    x_in = x
+    x, w_var = _d(x), w
+    w = _d(w)
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[:2]) != (3, 3) or w.shape[2] != x.shape[3]:
+        return None
+    n, h, wd, c1 = x.shape
+    cout = w.shape[3]
+    d = _lib.ConvDesc()
+    d.N, d.H, d.W, d.C1, d.C2 = n, 2 * h, 2 * wd, c1, 0
+    d.Cout, d.KH, d.KW, d.stride = cout, 3, 3, 1
+    d.cout_valid, d.y_cstride = cout, cout
+    d.pad_t, d.pad_l, d.Ho, d.Wo = 1, 1, 2 * h, 2 * wd
+    d.x2_scale = 1.0
+    d.act1, d.act2 = act1, act2
+    d.algo = ALGO_AUTO
+    d.prologue = PROLOGUE_BILINEAR2X
+    if not int(lib.shdr_conv2d_up2_lowres_ok_f32(ctypes.byref(d))):
+        return None
+    _chk(x, "x")
+    _chk(w, "w")
+    for t, nm in ((bias, "bias"), (scale, "scale"), (shift, "shift")):
+        if t is not None and (_chk(_d(t), nm).numel() != cout):
+            raise ValueError("conv2d_up2: %s must have %d elements" % (nm, cout))
+    persistent = _is_persistent(w_var)
+    nprep = int(lib.shdr_conv2d_up2_lowres_filter_elems_f32(ctypes.byref(d)))       # (follows the padding of the GEMM's columns)
+    key = ("up2_lowres", c1, cout, nprep)
+    prepared = _filter_cache_get(w_var, "_shdr_packed", key) if persistent else None
+    if prepared is None:
+        prepared = torch.empty(nprep, device=w.device, dtype=torch.float32)
+        _lib.check(lib.shdr_conv2d_up2_lowres_prepare_filter_f32(ctypes.byref(d), _ptr(w), _ptr(prepared), _stream()),
+                   "shdr_conv2d_up2_lowres_prepare_filter_f32")
+        if persistent:
+            _filter_cache_put(w_var, "_shdr_packed", key, prepared)
+    xr = _range_of(x_in)
+    if xr is None:
+        RANGE_MISSES[(tuple(x.shape), None, tuple(w.shape))] += 1     # measured below the ABI
+    ws = torch.empty(int(lib.shdr_conv2d_up2_lowres_workspace_bytes_f32(ctypes.byref(d))), device=x.device, dtype=torch.uint8)
+    out = torch.empty((n, 2 * h, 2 * wd, cout), device=x.device, dtype=torch.float32)
+    yr = _new_slot(x.device)
+    rc = lib.shdr_conv2d_fwd_up2_lowres_f32(ctypes.byref(d), _ptr(x), _ptr(prepared), _ptr(_d(bias)), _ptr(_d(scale)), _ptr(_d(shift)),
+                                            _ptr(out), _ptr(ws), _ptr(xr), _ptr(yr), _stream())
+    _lib.check(rc, "shdr_conv2d_fwd_up2_lowres_f32")
+    return _set_range(out, yr)
 
 
 def _conv2d_raw(x, w, bias, stride, x2, x2_scale, act1, scale, shift, residual, act2, algo, out, cout_valid, pad, out_hw,

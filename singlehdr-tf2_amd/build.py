@@ -38,6 +38,7 @@ SOURCES = {
     "winograd_fused.hip": [],
     "frontend.hip": ["-ffp-contract=off"],
     "pool.hip": [],
+    "up2_lowres.hip": [],
     "crf.hip": [],
     "glue.hip": [],
     "imageio.hip": [],

@@ -73,7 +73,10 @@ class up(Layer):
             return self.norm1.frozen_apply(self.conv1(K.resize2x(x), act1=K.ACT_RELU), relu=True)
         scale, shift = self.norm1.folded()
         # inference: resize, conv, relu, folded BN, relu in ONE kernel -- the up-sampled tensor never reaches HBM
-        return self.conv1.call_up2(x, act1=K.ACT_RELU, scale=scale, shift=shift, act2=K.ACT_RELU)
+        if x.dtype != torch.float32 or not K.WINOGRAD:
+            return self.conv1.call_up2(x, act1=K.ACT_RELU, scale=scale, shift=shift, act2=K.ACT_RELU)
+        # fp32: the channel mix at low resolution where the library takes the layer (csrc/up2_lowres.hip), else the call above
+        return self.conv1.call_up2(x, act1=K.ACT_RELU, scale=scale, shift=shift, act2=K.ACT_RELU, lowres=True)
 
     def call_projected(self, x, proj):
         """tape-free inference: sum_c proj[j, c] up(x)[..., c] from the same kernel's epilogue -- the block's own output is not written --
