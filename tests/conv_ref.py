@@ -3,8 +3,9 @@
 stride-2 layer is padded asymmetrically), two sources concatenated along the channels with the second one scaled by `x2_scale`.
 
 It calls nothing of the product.  tests/test_conv_ref.py pins it to oracle.ops.conv2d and to float64 autograd;
-tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element, and
-tests/test_gpu_wgrad_f32_exact.py the fp32 weight-gradient kernels (section 4.4).
+tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element,
+tests/test_gpu_wgrad_f32_exact.py the fp32 weight-gradient kernels (section 4.4), tests/test_gpu_conv_x3_exact.py the split-operand
+kernels (section 4.5) and tests/test_gpu_up2_lowres_exact.py the low-resolution channel mix (section 4.6).
 """
 import numpy as np
 
@@ -311,3 +312,76 @@ def project(y, proj):
     y = np.asarray(y, dtype=np.float64)
     p = np.asarray(proj, dtype=np.float64)
     return y @ p.T, np.abs(y) @ np.abs(p).T
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the low-resolution channel mix of the up-sampling 3x3 layers (csrc/up2_lowres.hip), for tests/test_gpu_up2_lowres_exact.py
+# (DESIGN.md section 4.6): what the two launches compute, not the ideal layer
+# ---------------------------------------------------------------------------------------------------------------------------------
+def up2_lowres_columns(cout, pad=None):
+    """columns of z (z_columns): 9 Cout rounded up to 256 where that pads at most an eighth, else to 128; `pad` = 128 | 256 forces one, as
+    SHDR_UP2_LOWRES_PAD does"""
+    cols = 9 * cout
+    c128, c256 = -(-cols // 128) * 128, -(-cols // 256) * 256
+    if pad is not None:
+        return c256 if int(pad) == 256 else c128
+    return c256 if (c256 - cols) * 8 <= cols else c128
+
+
+def up2_lowres_filter(w, cp):
+    """st[0, 0, ci, t Cout + co] = w[ty, tx, ci, co], t = 3 ty + tx (up2_lowres_filter_kernel); columns >= 9 Cout are zero"""
+    w = np.asarray(w, dtype=np.float64)
+    kh, kw, cin, cout = w.shape
+    assert (kh, kw) == (3, 3) and cp >= 9 * cout
+    st = np.zeros((1, 1, cin, cp))
+    st[0, 0, :, :9 * cout] = w.reshape(9, cin, cout).transpose(1, 0, 2).reshape(cin, 9 * cout)
+    return st
+
+
+def _bilinear_taps(n, t):
+    """per hi-res output index r of 2n and tap t of three: (inside, ia, wa, ib, wb) -- the hi-res cell q = r + t - 1 the tap reads, whether
+    it lies inside [0, 2n), and its two low-res neighbours with the half-pixel weights of resize2x (indices clamped)"""
+    q = np.arange(2 * n) + t - 1
+    inside = (q >= 0) & (q < 2 * n)
+    qc = np.clip(q, 0, 2 * n - 1)
+    m, odd = qc >> 1, (qc & 1) == 1
+    ia = np.where(odd, m, np.maximum(m - 1, 0))
+    ib = np.where(odd, np.minimum(m + 1, n - 1), m)
+    return inside, ia, np.where(odd, 0.75, 0.25), ib, np.where(odd, 0.25, 0.75)
+
+
+def up2_lowres_stencil(z, cout):
+    """(y, A) of up2_lowres_stencil_kernel before its epilogue, z [N, h, w, >= 9 Cout] the tap planes:
+        y[r, s, c] = sum_t [tap inside 2h x 2w] sum_{m, j} B_{r+ty-1}(m) B_{s+tx-1}(j) z[m, j, t Cout + c]
+    B the half-pixel bilinear weights with clamped indices; A the same sum over |z| (every weight is >= 0).  The cells are gathered, not
+    multiplied by zero weights: a NaN of z reaches exactly the outputs whose taps read it."""
+    z = np.asarray(z, dtype=np.float64)
+    n, h, w = z.shape[:3]
+    y = np.zeros((n, 2 * h, 2 * w, cout))
+    a = np.zeros_like(y)
+    for ty in range(3):
+        rin, *rows = _bilinear_taps(h, ty)
+        for tx in range(3):
+            sin, *cols = _bilinear_taps(w, tx)
+            zt = z[..., (3 * ty + tx) * cout:(3 * ty + tx + 1) * cout]
+            inside = (rin[:, None] & sin[None, :])[None, :, :, None]
+            for ri, rw in (rows[0:2], rows[2:4]):
+                for si, sw in (cols[0:2], cols[2:4]):
+                    g = zt[:, ri][:, :, si] * (rw[:, None] * sw[None, :])[None, :, :, None]
+                    y += np.where(inside, g, 0.0)
+                    a += np.where(inside, np.abs(g), 0.0)
+    return y, a
+
+
+def up2_lowres(x, bound, w, pad=None):
+    """the layer as csrc/up2_lowres.hip computes it: conv_split of the LOW-RES x with the restaged 1x1 filter (launch A), then the stencil
+    (launch B).  Returns (z [N, h, w, Cp], y [N, 2h, 2w, Cout], gemm, stencil): gemm = max sum |terms| / lsb of the GEMM's accumulator,
+    stencil = max A / (lsb_z / 16) with lsb_z = lsb 2^-(S + T).  Every stencil weight is a multiple of 1 / 16 (the horizontal ones of
+    1 / 4), so the terms of one output share that lsb; below 2^24 every fp32 partial sum of the pass is exact, the horizontal sums H
+    included (|H| <= 4 A in units four times as coarse)."""
+    cout = np.asarray(w).shape[3]
+    st = up2_lowres_filter(w, up2_lowres_columns(cout, pad))
+    z, total, lsb = conv_split(x, None, st, None, 1, 1.0, bound)
+    lsb_z = lsb * 2.0 ** -(weight_exponent(st) + range_exponent(bound))
+    y, a = up2_lowres_stencil(z, cout)
+    return z, y, float(total.max()) / lsb, float(a.max()) / (lsb_z / 16)

@@ -251,6 +251,7 @@ def test_wgrad_split_is_exact_when_one_low_plane_is_empty(low_plane_of, k, strid
 # the split-operand forward model (tests/test_gpu_conv_x3_exact.py)
 # ---------------------------------------------------------------------------------------------------------------------------------
 import test_gpu_conv_x3_exact as X                                       # (no device is touched by importing it: the operand recipes live there)
+import test_gpu_up2_lowres_exact as U
 
 
 def test_weight_exponent_and_planes():
@@ -391,7 +392,7 @@ def test_pooled_and_projected_outputs():
     assert C.common_lsb(np.array([0.75, 2.0]), np.array([0.0])) == 0.25 and C.common_lsb(np.zeros(3)) == 1.0
 
 
-_ALL = X.X3_3X3 + X.X3_POOLED + X.X3_UP + X.X3_1X1 + X.X3_STEM + X.X3N + X.TANH
+_ALL = X.X3_3X3 + X.X3_POOLED + X.X3_UP + X.XW_3X3 + X.XW_POOLED + X.XW_UP + X.X3_1X1 + X.X3_STEM + X.X3N + X.TANH
 
 
 @pytest.mark.parametrize("o", _ALL)
@@ -405,7 +406,7 @@ def test_every_forward_case_meets_its_precondition_on_the_reference_alone(o):
         assert (ideal != split)[..., :r["cv"]].mean() > 0.5
 
 
-@pytest.mark.parametrize("o", X.DGRAD)
+@pytest.mark.parametrize("o", X.DGRAD + X.DGRAD_WIDE)
 def test_every_input_gradient_case_meets_its_precondition_on_the_reference_alone(o):
     X.dgrad_reference(o)
 
@@ -416,3 +417,70 @@ def test_every_1056_tile_case_meets_its_precondition_on_the_reference_alone(o):
     assert (o["h"] // 16) * (o["w"] // 16) == 1056 and o["mode"] == "int"
     r = X.big_reference(o) if o["c1"] == 16 and o["c2"] == 0 else X.reference(o)
     assert r["worst"] < 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the low-resolution channel mix (csrc/up2_lowres.hip): the model of tests/test_gpu_up2_lowres_exact.py
+# ---------------------------------------------------------------------------------------------------------------------------------
+def test_up2_lowres_columns_and_filter():
+    assert [C.up2_lowres_columns(c) for c in (64, 128, 192, 256, 512)] == [640, 1280, 1792, 2304, 4608]
+    assert C.up2_lowres_columns(128, 128) == 1152 and C.up2_lowres_columns(128, 256) == 1280 and C.up2_lowres_columns(64, 256) == 768
+    assert C.up2_lowres_columns(64, 128) == 640 and C.up2_lowres_columns(320) == 3072
+    rng = np.random.default_rng(3)
+    w = rng.normal(size=(3, 3, 5, 7))
+    st = C.up2_lowres_filter(w, 128)
+    assert st.shape == (1, 1, 5, 128) and not st[..., 63:].any()
+    for ty in range(3):
+        for tx in range(3):
+            np.testing.assert_array_equal(st[0, 0, :, (3 * ty + tx) * 7:(3 * ty + tx + 1) * 7], w[ty, tx])
+    # one exponent S for all nine taps: that of the 3x3 filter
+    for wt in (X.fine_w(rng, (3, 3, 64, 64))[0], X.int_w(rng, (3, 3, 32, 64)), rng.normal(size=(3, 3, 32, 64)) * 37.0, w * 1e-3):
+        assert C.weight_exponent(C.up2_lowres_filter(wt, C.up2_lowres_columns(wt.shape[3]))) == C.weight_exponent(wt)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 3, 2), (1, 1, 7, 2, 3), (2, 6, 1, 3, 2), (1, 2, 2, 2, 2), (2, 5, 9, 4, 3)])
+def test_up2_lowres_stencil_is_the_convolution_of_the_resized_image(shape):
+    """on float64 Gaussian z = x W[t] the stencil equals conv2d(resize_bilinear_2x(x)) of the oracle at 1e-12: the algebra, zero padding
+    and edge clamp included"""
+    n, h, w, cin, cout = shape
+    rng = np.random.default_rng(sum(shape))
+    x = rng.normal(size=(n, h, w, cin))
+    wt = rng.normal(size=(3, 3, cin, cout))
+    z = C.conv2d(x, None, C.up2_lowres_filter(wt, 9 * cout + 5), None, 1, 1.0)
+    y, a = C.up2_lowres_stencil(z, cout)
+    close(y, ops.conv2d(ops.resize_bilinear_2x(x), wt))
+    close(y, C.conv2d(C.resize2x(x), None, wt, None, 1, 1.0))
+    assert (a >= np.abs(y)).all() and np.array_equal(a, C.up2_lowres_stencil(np.abs(z), cout)[0])
+
+
+def test_up2_lowres_in_int_mode_is_the_convolution_of_the_resized_image_exactly():
+    for name, n, h, w, cin, cout in (("a", 1, 1, 1, 32, 16), ("b", 2, 3, 5, 64, 16), ("c", 1, 4, 1, 32, 8), ("d", 1, 1, 6, 32, 8)):
+        x, xb, _, _, wt = X.operands("pin_ul_int_" + name, n, h, w, cin, 0, cout, 3, "int")
+        z, y, gemm, stencil = C.up2_lowres(x, xb, wt)
+        assert gemm < 2.0 ** 24 and stencil < 2.0 ** 24
+        np.testing.assert_array_equal(y, C.conv2d(C.resize2x(x), None, wt, None, 1, 1.0))
+        np.testing.assert_array_equal(z[..., :9 * cout], C.conv2d(x, None, C.up2_lowres_filter(wt, 9 * cout), None, 1, 1.0))
+        assert z.shape[3] == C.up2_lowres_columns(cout) and not z[..., 9 * cout:].any()
+
+
+def test_up2_lowres_stencil_carries_a_nan_to_the_taps_that_read_it_only():
+    z = np.ones((1, 4, 5, 18))
+    z[0, 2, 2, :] = np.nan
+    mask = np.isnan(C.up2_lowres_stencil(z, 2)[0])
+    hand = np.zeros((1, 8, 10, 2), dtype=bool)
+    hand[0, 2:8, 2:8] = True
+    assert np.array_equal(mask, hand)
+
+
+@pytest.mark.parametrize("o", U.CASES + [U.RANGES_CASE, U.NAN_CASE])
+def test_every_up2_lowres_case_meets_its_preconditions_on_the_reference_alone(o):
+    """both ratios below 2^24 and y exact in fp32 (asserted inside U.reference); the fxw cases differ from the true layer on most outputs"""
+    r = U.reference(o)
+    assert r["gemm"] < 1.0 and r["stencil"] < 1.0
+    assert np.array_equal(r["v"].astype(np.float32).astype(np.float64), r["v"])
+    assert r["cp"] == C.up2_lowres_columns(o["cout"], o.get("pad")) and not r["z"][..., 9 * o["cout"]:].any()
+    ideal = C.conv2d(C.resize2x(r["x"]), None, r["w"], None, 1, 1.0)
+    if o["mode"] == "int":
+        np.testing.assert_array_equal(r["v"], ideal)
+    if o["mode"] == "fxw":
+        assert (ideal != r["v"]).mean() > 0.5

@@ -1,6 +1,6 @@
-"""The split-operand fp32 convolution kernels -- conv_x3_kernel, conv_x3_1x1_kernel (csrc/conv_x3.hip) and conv_x3n_kernel
+"""The split-operand fp32 convolution kernels -- conv_x3_kernel, conv_x3_wide_kernel, conv_x3_1x1_kernel (csrc/conv_x3.hip) and conv_x3n_kernel
 (csrc/conv_x3n.hip), forward and input gradient -- against the float64 model of tests/conv_ref.py (conv_split), EXACTLY and element
-by element.
+by element (DESIGN.md sections 4.5 and 4.6).
 
 The model restates what the kernels compute, not the ideal convolution: x 2^T = xh + xl 2^-11 (T from the range slot), w 2^S =
 wh + wl, and acc = sum xh wh + sum xl (wh 2^-11) + sum xh wl -- the xl wl 2^-11 term is dropped.  Three operand modes:
@@ -199,9 +199,21 @@ class Slot:
             what, float(raw[GUARD:GUARD + 1].view(np.float32)[0]), float(np.float32(ymax)), self.preset)
 
 
+def wide_3x3(o, up):
+    """the rule of x3_forward for the 128-cout blocks: stride 1, Cout % 128 == 0, Cout >= the cout threshold (128 with the prologue in the
+    kernel, else 512; SHDR_X3_WIDE_MIN_COUT), no projected output, 16 x 16 tiles x Cout / 128 >= the block threshold (256;
+    SHDR_X3_WIDE_MIN_BLOCKS), and no SHDR_X3_SLICED"""
+    env, cout = o["env"], o["cout"]
+    h, w = (2 * o["h"], 2 * o["w"]) if o.get("up") else (o["h"], o["w"])
+    blocks = o["n"] * (-(-h // 16)) * (-(-w // 16)) * (cout // 128)
+    return (o["k"] == 3 and o["stride"] == 1 and cout % 128 == 0 and cout >= int(env.get("SHDR_X3_WIDE_MIN_COUT", 128 if up else 512))
+            and not o.get("proj") and blocks >= int(env.get("SHDR_X3_WIDE_MIN_BLOCKS", 256)) and "SHDR_X3_SLICED" not in env)
+
+
 def instance(o):
     """the kernel instantiation the dispatch code runs for a case (see the module docstring).  It labels failure messages and the
-    case table of DESIGN.md section 4.5 and is asserted against nothing: the library exports the plan, not the instantiation."""
+    case tables of DESIGN.md sections 4.5 and 4.6; the library exports the plan, not the instantiation, so only the 128-cout blocks are
+    asserted, by kernel name (test_wide_kernel_names)."""
     k, c1, c2, cout = o["k"], o["c1"], o["c2"], o["cout"]
     env = o["env"]
     if o["plan"] == "x3n":
@@ -218,6 +230,8 @@ def instance(o):
         wide = cout % 128 == 0 and not o.get("pool") and not o.get("proj") and "SHDR_X3_1X1_SLICED" not in env
         return "conv_x3_1x1_kernel<%d>" % (4 if cout % 256 == 0 else 2) if wide else "conv_x3_kernel<false, 1, 1, false, %d>" % min(look, 1)
     up = bool(o.get("up")) and (cout <= 256 or "SHDR_X3_UP_ALWAYS" in env)
+    if wide_3x3(o, up):
+        return "%sconv_x3_wide_kernel<%s>" % ("resize2x_kernel + " if o.get("up") and not up else "", "true" if up else "false")
     return "%sconv_x3_kernel<%s, 3, 3, false, %d>" % ("resize2x_kernel + " if o.get("up") and not up else "", "true" if up else "false", look)
 
 
@@ -442,6 +456,56 @@ def test_x3_bilinear_prologue(K, lib, o, monkeypatch):
     run_forward(K, lib, o, monkeypatch)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# conv_x3_wide_kernel<UP>: the 128-cout blocks (8 waves, the next chunk's patch loaded and split under the MFMAs, pcnt from the pieces of an
+# edge tile that lie inside the image, the low-res patch parked and expanded once per 128 couts).  The two switches take the dispatch
+# thresholds (256 blocks, 512 couts: speed only) out of the way; `instance()` restates the rule and test_wide_kernel_names asserts it.
+# ---------------------------------------------------------------------------------------------------------------------------------
+WB = dict(MB, SHDR_X3_WIDE_MIN_BLOCKS="1", SHDR_X3_WIDE_MIN_COUT="128")
+XW_3X3 = [
+    # 1, 2, 3 and 5 chunks x Cout 128 / 256 / 384; N 1 / 3; the ten SIZES; the four operand modes; every epilogue
+    case("xw_c32_128_1x1x1_int", "x3", 1, 1, 1, 32, 0, 128, 3, env=WB),
+    case("xw_c64_128_1x15x16_fx_relu", "x3", 1, 15, 16, 64, 0, 128, 3, mode="fx", epi="relu", env=WB),
+    case("xw_c96_256_3x16x17_fw_lrelu", "x3", 3, 16, 17, 96, 0, 256, 3, mode="fw", epi="lrelu", env=WB),
+    case("xw_c160_128_1x17x15_fxw_affine", "x3", 1, 17, 15, 160, 0, 128, 3, mode="fxw", epi="affine", env=WB),
+    case("xw_c32_384_1x33x16_fx_res", "x3", 1, 33, 16, 32, 0, 384, 3, mode="fx", epi="res", env=WB),
+    case("xw_c64_256_1x16x33_fxw_act2", "x3", 1, 16, 33, 64, 0, 256, 3, mode="fxw", epi="act2", env=WB),
+    case("xw_c96_128_3x1x33_fw_nobias", "x3", 3, 1, 33, 96, 0, 128, 3, mode="fw", epi="nobias", env=WB),
+    case("xw_c160_256_1x33x1_int_res", "x3", 1, 33, 1, 160, 0, 256, 3, epi="res", env=WB),
+    case("xw_c64_384_1x15x15_fx", "x3", 1, 15, 15, 64, 0, 384, 3, mode="fx", env=WB),
+    case("xw_c96_128_1x17x33_fxw_relu", "x3", 1, 17, 33, 96, 0, 128, 3, mode="fxw", epi="relu", env=WB),
+    # two sources: the chunk loop crosses from x1 to x2 after 1 and after 2 chunks, the second source at 2^-8 and at 0.5
+    case("xw_two_32_32_scaled_128_1x17x33_int", "x3", 1, 17, 33, 32, 32, 128, 3, x2s=S8, env=WB),
+    case("xw_two_64_32_half_256_3x15x15_fw_relu", "x3", 3, 15, 15, 64, 32, 256, 3, mode="fw", epi="relu", x2s=0.5, env=WB),
+    case("xw_two_32_64_scaled_128_1x16x17_fw_affine", "x3", 1, 16, 17, 32, 64, 128, 3, mode="fw", epi="affine", x2s=S8, env=WB),
+    case("xw_two_64_64_half_128_1x33x16_fx_res", "x3", 1, 33, 16, 64, 64, 128, 3, mode="fx", epi="res", x2s=0.5, env=WB),
+]
+XW_POOLED = [
+    case("xw_maxpool_with_y_c32_128_1x2x2_int", "x3", 1, 2, 2, 32, 0, 128, 3, pool="max", env=WB),
+    case("xw_maxpool_with_y_c64_256_1x18x22_fx_relu", "x3", 1, 18, 22, 64, 0, 256, 3, mode="fx", epi="relu", pool="max", env=WB),
+    case("xw_maxpool_only_c64_128_3x16x34_fw_lrelu", "x3", 3, 16, 34, 64, 0, 128, 3, mode="fw", epi="lrelu", pool="only", env=WB),
+    case("xw_maxpool_only_c32_128_1x18x22_fxw", "x3", 1, 18, 22, 32, 0, 128, 3, mode="fxw", pool="only", env=WB),
+    case("xw_avgpool_c96_128_1x18x22_fx_relu", "x3", 1, 18, 22, 96, 0, 128, 3, mode="fx", epi="relu", pool="avg", env=WB),
+    case("xw_avgpool_two_32_32_half_128_1x2x34_fw", "x3", 1, 2, 34, 32, 32, 128, 3, mode="fw", x2s=0.5, pool="avg", env=WB),
+]
+# conv_x3_wide_kernel<true>: (h, w) the LOW-RES sizes 1 x 3, 8 x 8 and 9 x 11; modes int and fw (see X3_UP)
+XW_UP = [
+    case("xw_up_c32_128_1x1x3_int", "x3", 1, 1, 3, 32, 0, 128, 3, up=True, env=WB),
+    case("xw_up_c64_256_1x8x8_fw_relu", "x3", 1, 8, 8, 64, 0, 256, 3, mode="fw", epi="relu", keep=0.5, up=True, env=WB),
+    case("xw_up_c96_128_3x9x11_fw_affine", "x3", 3, 9, 11, 96, 0, 128, 3, mode="fw", epi="affine", keep=0.5, up=True, env=WB),
+    case("xw_up_c32_256_1x9x11_int_lrelu", "x3", 1, 9, 11, 32, 0, 256, 3, epi="lrelu", up=True, env=WB),
+    case("xw_up_c64_128_1x9x11_fw_act2", "x3", 1, 9, 11, 64, 0, 128, 3, mode="fw", epi="act2", keep=0.5, up=True, env=WB),
+    case("xw_up_c96_256_1x8x8_int_nobias", "x3", 1, 8, 8, 96, 0, 256, 3, epi="nobias", up=True, env=WB),
+    case("xw_up_cout512_in_kernel_c32_1x9x11_fw", "x3", 1, 9, 11, 32, 0, 512, 3, mode="fw", up=True, env=dict(WB, SHDR_X3_UP_ALWAYS="1")),
+]
+
+
+@pytest.mark.parametrize("o", XW_3X3 + XW_POOLED + XW_UP)
+def test_x3_wide_blocks(K, lib, o, monkeypatch):
+    assert ("conv_x3_wide_kernel<true>" if o.get("up") else "conv_x3_wide_kernel<false>") in instance(o) and "resize2x" not in instance(o)
+    run_forward(K, lib, o, monkeypatch)
+
+
 # 1 x 1 layers: conv_x3_1x1_kernel<4> (Cout % 256 == 0), <2> (Cout % 128 == 0), conv_x3_kernel<false, 1, 1> (Cout 64, or SHDR_X3_1X1_SLICED).
 # 2, 3, 5 and 16 chunks (the two-deep prefetch at odd and even counts); pixel counts 1, 127, 128, 129, 323; stride 2 at even and odd sizes.
 SL = dict(MB, SHDR_X3_1X1_SLICED="1")
@@ -641,9 +705,9 @@ def test_x3n_persistent_loop_two_sources_and_image_layer(K, lib, o, monkeypatch)
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the input gradient (shdr_conv2d_dgrad_ranged_f32): filter transform (flip, slice, the source's scale), then the same kernels on dz
 # ---------------------------------------------------------------------------------------------------------------------------------
-def dcase(name, kernel, n, h, w, c1, c2, cout, k, which, mode="int", x2s=1.0, ranges=None):
+def dcase(name, kernel, n, h, w, c1, c2, cout, k, which, mode="int", x2s=1.0, ranges=None, env=MB):
     return pytest.param(dict(name=name, kernel=kernel, n=n, h=h, w=w, c1=c1, c2=c2, cout=cout, k=k, which=which, mode=mode, x2s=x2s,
-                             ranges=ranges), id=name)
+                             ranges=ranges, env=env), id=name)
 
 
 DGRAD = [
@@ -669,6 +733,12 @@ DGRAD = [
 ]
 
 
+# the transposed layer dz -> dx of a Cx = 128 source runs x3_forward with 128 couts: under the two switches the 128-cout blocks take it
+# (test_wide_kernel_names asserts the kernel by name)
+DGRAD_WIDE = [dcase("dgrad_xw_cx128_from_64_1x17x15_fx", "x3", 1, 17, 15, 128, 0, 64, 3, 0, mode="fx", env=WB),
+              dcase("dgrad_xw_two_64_128_which1_scaled_from_96_3x15x16_fw", "x3", 3, 15, 16, 64, 128, 96, 3, 1, mode="fw", x2s=S8, ranges="none", env=WB)]
+
+
 def dgrad_reference(o):
     n, h, w, c1, c2, cout, k, which, x2s = (o[f] for f in ("n", "h", "w", "c1", "c2", "cout", "k", "which", "x2s"))
     rng = np.random.default_rng(seed_of(o["name"]))
@@ -689,9 +759,10 @@ def dgrad_reference(o):
     return dz, zb, wt, dx.astype(np.float32), cc
 
 
-@pytest.mark.parametrize("o", DGRAD)
+@pytest.mark.parametrize("o", DGRAD + DGRAD_WIDE)
 def test_input_gradient(K, lib, o, monkeypatch):
-    monkeypatch.setenv("SHDR_X3_MIN_BLOCKS", "1")
+    for name, value in o["env"].items():
+        monkeypatch.setenv(name, value)
     dz, zb, wt, dx_ref, cc = dgrad_reference(o)
     n, h, w = o["n"], o["h"], o["w"]
     cv = o["cout"]
@@ -727,10 +798,42 @@ def test_input_gradient(K, lib, o, monkeypatch):
 
 
 def named(name):
-    for p in X3_3X3 + X3_POOLED + X3_UP + X3_1X1 + X3_STEM + X3N + TANH + X3N_BIG + X3N_BIG_OTHER + DGRAD:
+    for p in X3_3X3 + X3_POOLED + X3_UP + XW_3X3 + XW_POOLED + XW_UP + X3_1X1 + X3_STEM + X3N + TANH + X3N_BIG + X3N_BIG_OTHER + DGRAD + DGRAD_WIDE:
         if p.id == name:
             return p
     raise KeyError(name)
+
+
+def kernels_of(fn):
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return {e.name for e in prof.events() if "conv_x3" in e.name}
+
+
+def test_wide_kernel_names(K, lib, monkeypatch):
+    """the library exports the plan, not the instantiation: the kernels this file's switches launch, by name.  Plain, with the prologue
+    and on the input gradient the 128-cout blocks answer; under SHDR_X3_SLICED=1 the 64-cout kernel does."""
+    plain, up, dg = named("xw_c64_128_1x15x16_fx_relu").values[0], named("xw_up_c64_256_1x8x8_fw_relu").values[0], named("dgrad_xw_cx128_from_64_1x17x15_fx")
+    for o, tag in ((plain, "conv_x3_wide_kernel<false>"), (up, "conv_x3_wide_kernel<true>")):
+        r = reference(o)
+        names = kernels_of(lambda: run_forward(K, lib, o, monkeypatch, r=r))
+        assert any(tag in k for k in names) and not any("conv_x3_kernel" in k for k in names), (o["name"], names)
+        sliced = dict(o, env=dict(o["env"], SHDR_X3_SLICED="1"))
+        assert "wide" not in instance(sliced)
+        names = kernels_of(lambda: run_forward(K, lib, sliced, monkeypatch, r=r))
+        own = "conv_x3_kernel<%s" % ("true" if o.get("up") else "false")
+        assert any(own in k for k in names) and not any("conv_x3_wide_kernel" in k for k in names), names
+        monkeypatch.delenv("SHDR_X3_SLICED")
+    names = kernels_of(lambda: test_input_gradient(K, lib, dg.values[0], monkeypatch))
+    assert any("conv_x3_wide_kernel<false>" in k for k in names) and not any("conv_x3_kernel" in k for k in names), names
+    # without the two switches the same layer stays on the 64-cout kernel (one block of 128 couts, far below 256)
+    monkeypatch.delenv("SHDR_X3_WIDE_MIN_BLOCKS")
+    monkeypatch.delenv("SHDR_X3_WIDE_MIN_COUT")
+    o = dict(plain, env=MB)
+    assert "wide" not in instance(o)
+    names = kernels_of(lambda: run_forward(K, lib, o, monkeypatch, r=reference(plain)))
+    assert names and not any("conv_x3_wide_kernel" in k for k in names), names
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

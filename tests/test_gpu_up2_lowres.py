@@ -2,7 +2,8 @@
 Cin -> 9 Cout on the low-res input (conv_x3_1x1_kernel) and the stencil pass that sums the nine tap planes with the bilinear weights.
 Checked against the float64 oracle (resize, then conv) at the bar of tests/test_gpu_ops.py, against today's path at the bar
 tests/test_gpu_switches.py sets between two fp32-grade kernels, and for its range slot, determinism, switch, launches and fall-back.
-SHDR_X3_MIN_BLOCKS=1 takes the fill-the-chip threshold (speed only) of the low-res GEMM out of the way."""
+SHDR_X3_MIN_BLOCKS=1 takes the fill-the-chip threshold (speed only) of the low-res GEMM out of the way.
+The per-element comparison with a float64 model of the two launches is tests/test_gpu_up2_lowres_exact.py."""
 import ctypes
 
 import numpy as np
