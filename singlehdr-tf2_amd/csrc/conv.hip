@@ -1164,12 +1164,13 @@ extern "C" int shdr_conv2d_fwd_yrange_f32(const shdr_conv2d_desc* d, const float
   if (algo == SHDR_ALGO_DIRECT) {
     SHDR_REQUIRE(cout_valid == a.Cout, SHDR_E_SHAPE, "conv2d: direct path does not take padded filters");
     SHDR_REQUIRE(a.w_bstride == 0, SHDR_E_SHAPE, "conv2d: direct path does not take per-image filters");
+    // (checked BEFORE the launch: a refused call writes nothing)
+    SHDR_REQUIRE(!y_range || (d->y_pix_stride <= 1 && y_cs == cout_valid), SHDR_E_SHAPE, "conv2d: y_range needs a dense output");
     int rc;
     if (a.Cout <= 3) rc = launch_direct<3>(a, st);
     else if (a.Cout % 16 == 0) rc = launch_direct<16>(a, st);
     else rc = launch_direct<8>(a, st);
     if (rc || !y_range) return rc;
-    SHDR_REQUIRE(d->y_pix_stride <= 1 && y_cs == cout_valid, SHDR_E_SHAPE, "conv2d: y_range needs a dense output");
     return shdr_absmax_f32(y, (int64_t)d->N * d->Ho * d->Wo * cout_valid, y_range, stream);     // the VALU kernel's epilogue does not track it
   }
   return shdr::fail(SHDR_E_SHAPE, "conv2d: unknown algo %d", d->algo);

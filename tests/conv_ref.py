@@ -5,7 +5,8 @@ stride-2 layer is padded asymmetrically), two sources concatenated along the cha
 It calls nothing of the product.  tests/test_conv_ref.py pins it to oracle.ops.conv2d and to float64 autograd;
 tests/test_gpu_fp16_conv_exact.py compares the HIP kernels with it element by element,
 tests/test_gpu_wgrad_f32_exact.py the fp32 weight-gradient kernels (section 4.4), tests/test_gpu_conv_x3_exact.py the split-operand
-kernels (section 4.5) and tests/test_gpu_up2_lowres_exact.py the low-resolution channel mix (section 4.6).
+kernels (section 4.5), tests/test_gpu_up2_lowres_exact.py the low-resolution channel mix (section 4.6) and tests/test_gpu_conv_f32_exact.py the
+exact-fp32 kernels: implicit GEMM, register-A, direct, Winograd, the input-gradient plumbing (section 4.7).
 """
 import numpy as np
 
@@ -385,3 +386,85 @@ def up2_lowres(x, bound, w, pad=None):
     lsb_z = lsb * 2.0 ** -(weight_exponent(st) + range_exponent(bound))
     y, a = up2_lowres_stencil(z, cout)
     return z, y, float(total.max()) / lsb, float(a.max()) / (lsb_z / 16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the exact-fp32 kernels (csrc/conv.hip, winograd.hip, winograd_fused.hip, the input-gradient plumbing of conv_plan.hip), for
+# tests/test_gpu_conv_f32_exact.py: Winograd F(2x2, 3x3) by its definition, bf16 rounding, the packed filter
+# ---------------------------------------------------------------------------------------------------------------------------------
+WINO_G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]], dtype=np.float64)
+WINO_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64)
+WINO_AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=np.float64)
+
+
+def to_bf16(v):
+    """round to the nearest bfloat16, ties to even, returned in float64: the upper 16 bits of the fp32 word after adding 0x7FFF + (bit
+    16).  The fp32 subnormals round the same way (bf16 shares fp32's exponent range); values beyond the largest bf16 become infinity."""
+    with np.errstate(over="ignore"):
+        a = np.ascontiguousarray(v, dtype=np.float64).astype(np.float32)
+    assert not np.isnan(a).any()
+    b = a.view(np.uint32).astype(np.uint64)
+    b = (b + np.uint64(0x7FFF) + ((b >> np.uint64(16)) & np.uint64(1))) & np.uint64(0xFFFF0000)
+    return b.astype(np.uint32).view(np.float32).astype(np.float64).reshape(np.shape(v))
+
+
+def winograd_filter(w):
+    """U[xi = 4 i + j][ci][co] = (G g G^T)[i][j] of a 3x3 HWIO filter (winograd_filter_kernel)"""
+    w = np.asarray(w, dtype=np.float64)
+    assert w.shape[:2] == (3, 3)
+    return np.einsum("ia,abco,jb->ijco", WINO_G, w, WINO_G).reshape(16, w.shape[2], w.shape[3])
+
+
+def winograd_rows(n, h, w):
+    """(tiles, rows of a V / M plane): N ceil(H / 2) ceil(W / 2), and that rounded up to the 128-row GEMM tile (shdr_winograd_tiles)"""
+    t = n * ((h + 1) // 2) * ((w + 1) // 2)
+    return t, -(-t // 128) * 128
+
+
+def winograd_input(x):
+    """V[xi = 4 i + j][t][c] = (B^T d B)[i][j], d the 4x4 patch at (2 th - 1, 2 tw - 1) of tile t = (n TH + th) TW + tw, zero outside
+    the image (winograd_input_kernel); the planes carry the tiles only, not the padding rows"""
+    x = np.asarray(x, dtype=np.float64)
+    n, h, w, c = x.shape
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    xp = np.zeros((n, 2 * th + 2, 2 * tw + 2, c))
+    xp[:, 1:h + 1, 1:w + 1] = x
+    d = np.stack([np.stack([xp[:, i:i + 2 * th:2, j:j + 2 * tw:2] for j in range(4)]) for i in range(4)])       # [4, 4, n, th, tw, c]
+    return np.einsum("ia,abntwc,jb->ijntwc", WINO_BT, d, WINO_BT).reshape(16, n * th * tw, c)
+
+
+def winograd_output(m, n, h, w):
+    """Y = A^T M A per tile, m [16][tiles][C] -> [N, H, W, C] (the cells of a half tile beyond an odd H or W are dropped)"""
+    m = np.asarray(m, dtype=np.float64)
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    c = m.shape[2]
+    y = np.einsum("ia,abntwc,jb->ntiwjc", WINO_AT, m.reshape(4, 4, n, th, tw, c), WINO_AT).reshape(n, 2 * th, 2 * tw, c)
+    return y[:, :h, :w]
+
+
+def winograd_conv(x, x2, w):
+    """the 3x3 / stride-1 / SAME convolution of concat[x, x2] in the Winograd domain, float64: (y, gemm, out) with
+        gemm = max over (xi, tile, cout) of sum_c |V| |U| / lsb,   out = max over (tile, cout) of sum_xi |M| / lsb,   lsb = lsb(V) lsb(U)
+    -- where both are below 2^24 the fp32 sums over the channels (in any order, chunk by chunk) and the 16-term output transform are
+    exact, every intermediate being a multiple of lsb: the kernels must then reproduce the direct convolution bit for bit."""
+    xin = _sources(x, x2, 1.0)
+    n, h, wd, _ = xin.shape
+    v, u = winograd_input(xin), winograd_filter(w)
+    m = np.einsum("xtc,xco->xto", v, u)
+    lsb = common_lsb(v) * common_lsb(u)
+    gemm = float(np.einsum("xtc,xco->xto", np.abs(v), np.abs(u)).max()) / lsb
+    out = float(np.abs(m).sum(axis=0).max()) / lsb
+    return winograd_output(m, n, h, wd), gemm, out
+
+
+def winograd_packed_index(cin, cout):
+    """idx[xi][ci][co] = offset of U[xi][ci][co] in the operand order of winograd_fused_kernel (winograd_filter_packed_kernel):
+        ((((pn 8 + w8) nch + c) 4 + j) 64 + lane) 4 + nt,   pn = co >> 6, w8 = xi >> 1, nch = Cin / 8, c = ci >> 3,
+        j = 2 (xi & 1) + (ci & 1), lane = 16 ((ci & 7) >> 1) + (co & 15), nt = (co & 63) >> 4
+    -- a bijection onto [0, 16 Cin Cout) for Cin % 8 == 0 and Cout % 64 == 0"""
+    assert cin % 8 == 0 and cout % 64 == 0
+    xi, ci, co = np.meshgrid(np.arange(16), np.arange(cin), np.arange(cout), indexing="ij")
+    nch = cin // 8
+    j = 2 * (xi & 1) + (ci & 1)
+    lane = 16 * ((ci & 7) >> 1) + (co & 15)
+    return ((((((co >> 6) * 8 + (xi >> 1)) * nch + (ci >> 3)) * 4 + j) * 64 + lane) * 4 + ((co & 63) >> 4)).astype(np.int64)

@@ -484,3 +484,168 @@ def test_every_up2_lowres_case_meets_its_preconditions_on_the_reference_alone(o)
         np.testing.assert_array_equal(r["v"], ideal)
     if o["mode"] == "fxw":
         assert (ideal != r["v"]).mean() > 0.5
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the exact-fp32 kernels (tests/test_gpu_conv_f32_exact.py): the Winograd helpers, bf16 rounding, the packed filter,
+# every case's precondition, and the sensitivity of every case to the mistakes a kernel can make
+# ---------------------------------------------------------------------------------------------------------------------------------
+import test_gpu_conv_f32_exact as F                                      # (no device is touched by importing it)
+
+
+@pytest.mark.parametrize("n,h,w,c1,c2,cout,mode", [(1, 1, 1, 8, 0, 4, "int"), (2, 5, 7, 3, 0, 2, "fx"), (1, 8, 9, 4, 4, 3, "fw"), (1, 2, 2, 2, 0, 2, "fx"),
+                                                   (2, 17, 33, 8, 8, 5, "int"), (1, 16, 18, 24, 0, 3, "fw")])
+def test_winograd_by_its_definition_is_the_convolution_exactly(n, h, w, c1, c2, cout, mode):
+    o = F.wc("wino_pin_%d_%d_%d_%s" % (h, w, c1, mode), n, h, w, c1, c2, cout, mode=mode).values[0]
+    x, x2, wt = F.operands(o)
+    y, gemm, out = C.winograd_conv(x, x2, wt)
+    assert gemm < F.LIMIT and out < F.LIMIT
+    assert np.array_equal(y, C.conv2d(x, x2, wt, None, 1, 1.0))
+    # the pieces: the plane layout of the kernels (tile t = (n TH + th) TW + tw) and the documented row count
+    xin = x if x2 is None else np.concatenate([x, x2], -1)
+    v, u = C.winograd_input(xin), C.winograd_filter(wt)
+    tiles, rows = C.winograd_rows(n, h, w)
+    assert v.shape == (16, tiles, c1 + c2) and u.shape == (16, c1 + c2, cout) and rows % 128 == 0 and 0 <= rows - tiles < 128
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    t = ((n - 1) * th + (th - 1)) * tw + (tw - 1)                          # the last tile: its patch starts at (2 th - 3, 2 tw - 3)
+    d = np.zeros((4, 4, c1 + c2))
+    for i in range(4):
+        for j in range(4):
+            hh, ww = 2 * (th - 1) - 1 + i, 2 * (tw - 1) - 1 + j
+            if 0 <= hh < h and 0 <= ww < w:
+                d[i, j] = xin[n - 1, hh, ww]
+    assert np.array_equal(v[:, t].reshape(4, 4, -1), np.einsum("ia,abc,jb->ijc", C.WINO_BT, d, C.WINO_BT))
+    assert np.array_equal(u[5], 0.25 * wt.sum(axis=(0, 1))) and np.array_equal(u[0], wt[0, 0]) and np.array_equal(u[15], wt[2, 2])
+
+
+def test_winograd_packed_index_follows_the_documented_formula():
+    for cin, cout in ((8, 64), (24, 128), (72, 64)):
+        idx = C.winograd_packed_index(cin, cout)
+        assert idx.shape == (16, cin, cout) and np.array_equal(np.sort(idx.reshape(-1)), np.arange(16 * cin * cout))
+    idx = C.winograd_packed_index(24, 128)
+    nch = 3
+    for xi, ci, co in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 2, 0), (0, 8, 0), (2, 0, 0), (0, 0, 16), (0, 0, 64), (15, 23, 127), (7, 13, 85)):
+        pn, w8, c, j, lane, nt = co >> 6, xi >> 1, ci >> 3, 2 * (xi & 1) + (ci & 1), 16 * ((ci & 7) >> 1) + (co & 15), (co & 63) >> 4
+        assert idx[xi, ci, co] == ((((pn * 8 + w8) * nch + c) * 4 + j) * 64 + lane) * 4 + nt
+    assert [int(idx[a]) for a in ((1, 0, 0), (0, 1, 0), (0, 2, 0), (0, 0, 1), (0, 0, 16))] == [512, 256, 64, 4, 1]
+
+
+def test_to_bf16_rounds_to_nearest_even_ties_and_subnormals():
+    f = np.float32
+    e = 2.0 ** -8                                                          # half an ulp of bf16 at 1.0 (8 significand bits)
+    assert C.to_bf16([1 + e, 1 + 3 * e, 1 + e + 2.0 ** -20, 1 + e - 2.0 ** -20, -(1 + e), -(1 + 3 * e)]).tolist() == [1.0, 1 + 4 * e, 1 + 2 * e, 1.0, -1.0, -(1 + 4 * e)]
+    assert C.to_bf16([0.0, -0.0, 3.0, 0.5, 255.0, 257.0, 258.0]).tolist() == [0.0, -0.0, 3.0, 0.5, 255.0, 256.0, 258.0]
+    assert np.signbit(C.to_bf16(-0.0))
+    # subnormals: bf16 shares fp32's exponent range; its smallest subnormal is 2^-133
+    tiny = 2.0 ** -133
+    assert C.to_bf16([tiny, tiny * 0.5, tiny * 0.5 + 2.0 ** -149, tiny * 1.5, tiny * 2.5, 2.0 ** -126 - 2.0 ** -149]).tolist() == \
+        [tiny, 0.0, tiny, 2 * tiny, 2 * tiny, 2.0 ** -126]
+    # the largest finite bf16, and the fp32 values just above it that round to infinity
+    top = float(f(2.0 ** 127 * (2 - 2.0 ** -7)))
+    assert C.to_bf16([top, top * (1 + 2.0 ** -10)]).tolist() == [top, top] and np.isinf(C.to_bf16(float(np.finfo(f).max)))
+    # every bf16 value is a fixed point, and the rounding agrees with torch's on random words
+    rng = np.random.default_rng(5)
+    words = rng.integers(0, 1 << 32, size=4096, dtype=np.uint64).astype(np.uint32)
+    a = words.view(f)
+    a = a[np.isfinite(a)]
+    want = torch.from_numpy(a.copy()).to(torch.bfloat16).to(torch.float32).numpy().astype(np.float64)
+    assert np.array_equal(C.to_bf16(a.astype(np.float64)), want) and np.array_equal(C.to_bf16(want), want)
+    # the recipes: rounding to fp16 or bf16 removes exactly the fine part
+    x, _, k, j = F.fine_x(rng, (3, 5, 7, 4))
+    assert j.any() and np.array_equal(C.to_bf16(x), np.ldexp(k, -7)) and np.array_equal(C.to_f16(x).astype(np.float64), np.ldexp(k, -7))
+    wf, q, r = F.fine_w(rng, (3, 3, 4, 8))
+    assert r.any() and np.array_equal(C.to_bf16(wf), q / 2) and np.array_equal(C.to_f16(wf).astype(np.float64), q / 2)
+
+
+F32_FAMILIES = dict(tiles=F.TILE_CASES, geometry=F.GEOMETRY, outputs=F.OUTPUT_FORMS, epilogues=F.EPILOGUE_CASES, rega=F.REGA + F.REGA_REFUSED + F.REGA_PERSISTENT,
+                    direct=F.DIRECT, prec=F.PREC)
+_F32_FORWARD = [p for cases in F32_FAMILIES.values() for p in cases]
+
+
+@pytest.mark.parametrize("o", _F32_FORWARD)
+def test_every_f32_forward_case_meets_its_precondition_on_the_reference_alone(o):
+    r = F.reference(o)
+    assert r["worst"] < 1.0 and r["y"].dtype == np.float32 and np.isfinite(r["y"]).all() and r["y"].any()
+    assert F.plan_expected(o) in ("mfma", "direct"), "a forward case of this file runs below the plan: no Winograd shapes here"
+    if o["mode"] == "int":
+        assert np.array_equal(F.model(o, *F.operands(o))[0], F.model(dict(o, algo="exact"), *F.operands(o))[0]), "int mode survives fp16 / bf16 operands"
+
+
+@pytest.mark.parametrize("o", F.WINO + F.PLANES)
+def test_every_winograd_case_meets_its_transform_domain_precondition(o):
+    r = F.wino_reference(o)                                                # (asserts both bounds and winograd_conv == conv2d)
+    assert np.isfinite(r["y"]).all() and r["y"].any()
+
+
+@pytest.mark.parametrize("o", F.DGRAD)
+def test_every_f32_input_gradient_case_meets_its_precondition_on_the_reference_alone(o):
+    assert F.dgrad_kind(o) == o["kind"]
+    dz, wt, dx, cc = F.dgrad_reference(o)
+    assert dx.any() and dx.shape == (o["n"], o["h"], o["w"], cc)
+    if o["kind"] == "1x1s2":
+        rest = dx.copy()
+        rest[:, ::2, ::2] = 0.0
+        assert not rest.any()
+
+
+def test_every_named_instantiation_is_reached():
+    reached = {F.instance(p.values[0]) for p in _F32_FORWARD}
+    want = {"conv_%s<128, %s, %s>" % (k, t, f) for k in ("mfma_dma_kernel", "mfma_kernel") for t in ("128, 2, 2", "64, 4, 1", "32, 4, 1", "16, 4, 1")
+            for f in ("true", "false")}
+    want |= {"conv_mfma_dma_kernel<128, %s, %s, %d>" % (t, f, p) for t in ("128, 2, 2", "64, 4, 1", "32, 4, 1", "16, 4, 1") for f in ("true", "false") for p in (1, 2)
+             if (t, f) not in (("128, 2, 2", "false"), ("64, 4, 1", "false"), ("16, 4, 1", "true"))}
+    want |= {"conv_rega_kernel<4, %d, %d, %d>" % (nt, ct, kk) for nt in (1, 2) for ct in (4, 16, 32) for kk in (0, 3, 5, 7) if (nt, ct, kk) != (2, 32, 7)}
+    want |= {"conv_rega_kernel<4, 4, 4, 3>", "conv_direct_kernel<3>", "conv_direct_kernel<8>", "conv_direct_kernel<16>"}
+    assert not want - reached, sorted(want - reached)
+    # chunk counts of the LDS-DMA kernel per tile: one, two, an odd and an even >= 4 number (the 128-cout tile starts at K > 128: five)
+    for tile, need in (("128, 2, 2", (5, 6, 7, 8)), ("64, 4, 1", (1, 2, 9, 4)), ("32, 4, 1", (1, 2, 9, 4)), ("16, 4, 1", (1, 2, 9, 4))):
+        for kernel in ("conv_mfma_dma_kernel<128, " + tile, "conv_mfma_kernel<128, " + tile):
+            chunks = set()
+            for p in F.TILE_CASES:
+                o = p.values[0]
+                if F.instance(o).startswith(kernel):
+                    ct, kk = o["c1"] + o["c2"], o["kh"] * o["kw"] * (o["c1"] + o["c2"])
+                    fast = ct % 32 == 0 and (o["c2"] == 0 or o["c1"] % 32 == 0)
+                    chunks.add(o["kh"] * o["kw"] * ct // 32 if fast else -(-kk // 32))
+            assert set(need) <= chunks, (kernel, sorted(chunks))
+
+
+def _differs(a, b):
+    return a.shape != b.shape or not np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("family", list(F32_FAMILIES) + ["winograd", "planes"])
+def test_forward_cases_tell_a_wrong_model_from_the_right_one(family):
+    """every deliberately wrong model -- one tap dropped, pad off by one, the last k-chunk dropped, the two sources swapped, the right-halo
+    column zeroed, operands rounded to fp16 -- changes at least one element of the expected output of EVERY case whose geometry lets it show
+    (all-ones operands decide that: a 1 x 1 image reads one tap of a 3 x 3 filter, a 1x1 / 2 layer no odd column), and shows in every family: the inputs are not
+    degenerate, thinning has not emptied the edge a case exists to test."""
+    cases = F32_FAMILIES.get(family) or (F.WINO if family == "winograd" else F.PLANES)
+    ref = F.reference if family in F32_FAMILIES else F.wino_reference
+    seen = set()
+    for p in cases:
+        o = p.values[0]
+        if o["n"] * o["h"] * o["w"] > 20000:
+            continue                                                       # (the persistent-loop cases: their small twins carry the check)
+        right, probe = ref(o)["y"], ref(o, probe=True)["y"]
+        for wrong in F.wrong_models(o):
+            if wrong in ("tap", "pad", "chunk", "halo") and not _differs(probe, ref(o, wrong=wrong, probe=True)["y"]):
+                continue                                                   # this geometry cannot show it
+            assert _differs(right, ref(o, wrong=wrong)["y"]), "%s: the model with '%s' gives the same output" % (p.id, wrong)
+            seen.add(wrong)
+    want = {"tap", "pad", "chunk", "halo", "f16"} | ({"swap"} if any(p.values[0]["c2"] for p in cases) else set())
+    assert seen == want, (family, sorted(want - seen))
+
+
+def test_input_gradient_cases_tell_a_wrong_model_from_the_right_one():
+    seen = {}
+    for p in F.DGRAD:
+        o = p.values[0]
+        right, probe = F.dgrad_reference(o)[2], F.dgrad_reference(o, probe=True)[2]
+        for wrong in F.dgrad_wrong_models(o):
+            if wrong in ("tap", "pad", "chunk", "phase") and not _differs(probe, F.dgrad_reference(o, wrong=wrong, probe=True)[2]):
+                continue
+            assert _differs(right, F.dgrad_reference(o, wrong=wrong)[2]), "%s: the model with '%s' gives the same gradient" % (p.id, wrong)
+            seen.setdefault(o["kind"], set()).add(wrong)
+    assert seen["poly"] >= {"tap", "pad", "chunk", "phase", "swap", "f16"} and seen["mfma"] >= {"tap", "pad", "chunk", "swap", "f16"}, seen
+    assert seen["wino"] >= {"tap", "pad", "chunk", "swap", "f16"} and seen["1x1s2"] >= {"tap", "pad", "chunk", "f16"}, seen
