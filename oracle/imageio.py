@@ -2,15 +2,16 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this package.  cv2 is not installed
 here, so `resize_cubic` restates OpenCV's INTER_CUBIC from its published definition (resize.cpp: interpolateCubic with
-A = -0.75, source coordinate (d + 0.5) * scale - 0.5, replicated border) and `rgbe_encode` restates Ward's RGBE pixel
+A = -0.75, replicated border; source coordinate (float)((d + 0.5) * scale - 0.5) with scale = 1 / (n_out / n_in) in
+double, as resize.cpp computes it) and `rgbe_encode` restates Ward's RGBE pixel
 conversion as cv2.imwrite('.hdr') applies it: parity unpinned (no cv2-written fixture exists in the reference).
 """
 import numpy as np
 
 
 def _cubic_weights(n_in, n_out):
-    scale = np.float32(np.float64(n_in) / n_out)
-    f = (np.arange(n_out, dtype=np.float32) + np.float32(0.5)) * scale - np.float32(0.5)
+    scale = np.float64(1.0) / (np.float64(n_out) / np.float64(n_in))
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)     # the ONE rounding to fp32
     i0 = np.floor(f).astype(np.int64)
     t = (f - i0.astype(np.float32)).astype(np.float32)
     A = np.float32(-0.75)

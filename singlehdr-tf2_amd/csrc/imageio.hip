@@ -18,8 +18,19 @@ __global__ __launch_bounds__(256) void u8_to_unit_kernel(const uint8_t* __restri
   }
 }
 
-// OpenCV INTER_CUBIC (resize.cpp interpolateCubic, A = -0.75): source coordinate (d + 0.5) * scale - 0.5, taps
-// floor-1 .. floor+2 clamped to the image (replicated border), no antialiasing in either direction.
+// OpenCV INTER_CUBIC (resize.cpp interpolateCubic, A = -0.75): taps floor-1 .. floor+2 clamped to the image (replicated
+// border), no antialiasing in either direction.  The source coordinate follows resize.cpp to the bit, as linear_taps of
+// linear_resize.h does: scale = 1 / (n_out / n_in) and (d + 0.5) * scale - 0.5 in double, ONE rounding to float, then
+// floorf and an exact fp32 difference.  (A coordinate computed in fp32 from an fp32 scale drifts along a wide row: at
+// 4000 -> 4032 columns a pixel is off by up to 4e-3 of its absolute tap sum.)
+__device__ __forceinline__ float cubic_coord(int d, double scale, int* s) {
+#pragma clang fp contract(off)                             // product and difference round separately, as on the host
+  const float f = (float)(((double)d + 0.5) * scale - 0.5);
+  const float fl = floorf(f);
+  *s = (int)fl;
+  return f - fl;
+}
+
 __device__ __forceinline__ void cubic_coeffs(float t, float* c) {
   const float A = -0.75f;
   c[0] = ((A * (t + 1.0f) - 5.0f * A) * (t + 1.0f) + 8.0f * A) * (t + 1.0f) - 4.0f * A;
@@ -29,7 +40,7 @@ __device__ __forceinline__ void cubic_coeffs(float t, float* c) {
 }
 
 __global__ __launch_bounds__(256) void resize_cubic_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H,
-                                                           int W, int C, int Ho, int Wo, float sy, float sx) {
+                                                           int W, int C, int Ho, int Wo, double sy, double sx) {
   const long total = (long)N * Ho * Wo * C;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const int c = (int)(e % C);
@@ -38,11 +49,11 @@ __global__ __launch_bounds__(256) void resize_cubic_kernel(const float* __restri
     t /= Wo;
     const int oh = (int)(t % Ho);
     const long n = t / Ho;
-    const float fy = ((float)oh + 0.5f) * sy - 0.5f, fx = ((float)ow + 0.5f) * sx - 0.5f;
-    const int iy = (int)floorf(fy), ix = (int)floorf(fx);
+    int iy, ix;
+    const float ty = cubic_coord(oh, sy, &iy), tx = cubic_coord(ow, sx, &ix);
     float cy[4], cx[4];
-    cubic_coeffs(fy - (float)iy, cy);
-    cubic_coeffs(fx - (float)ix, cx);
+    cubic_coeffs(ty, cy);
+    cubic_coeffs(tx, cx);
     const float* xn = x + n * (long)H * W * C + c;
     float acc = 0.0f;
 #pragma unroll
@@ -112,7 +123,7 @@ extern "C" int shdr_resize_cubic_f32(const float* x, float* y, int N, int H, int
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, SHDR_E_SHAPE, "resize_cubic: non-positive dimension");
   const long total = (long)N * Ho * Wo * C;
   hipLaunchKernelGGL(resize_cubic_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), x, y, N, H, W, C, Ho, Wo,
-                     (float)((double)H / Ho), (float)((double)W / Wo));
+                     1.0 / ((double)Ho / H), 1.0 / ((double)Wo / W));
   return shdr::check_launch("resize_cubic");
 }
 

@@ -7,6 +7,7 @@ import io
 import numpy as np
 import pytest
 
+import camera_ref as R
 from oracle import camera as O
 
 pkg = importlib.import_module("singlehdr-tf2_amd")
@@ -31,7 +32,7 @@ def images():
     yield "training crop", np.clip(np.cumsum(rng.normal(size=(256, 256, 3)), axis=1) * 6 + 128, 0, 255).astype(np.uint8)
 
 
-@pytest.mark.parametrize("q", [90, 91, 93, 95, 97, 99, 100, 75, 30])
+@pytest.mark.parametrize("q", [90, 91, 93, 95, 97, 99, 100, 75, 30, 1, 2, 10, 49, 50, 51])
 def test_jpeg_restatement_is_bit_exact_against_libjpeg(q):
     for name, img in images():
         if name == "training crop" and q not in (90, 95, 100):
@@ -86,3 +87,98 @@ def test_loss_mask_rule():
     assert O.loss_mask(img).reshape(-1).tolist() == [0.0, 0.0, 1.0]
     g = O.rgb_to_gray_u8(np.array([[[255, 255, 255], [249, 249, 249], [6, 6, 6], [255, 0, 0]]], dtype=np.uint8))
     assert g.tolist() == [[255, 249, 6, 76]]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tests/camera_ref.py and the inputs of tests/test_gpu_camera_elem.py: the GPU tests must be able to fail.  Every wrong model -- the
+# reference with ONE plausible error -- differs from the true reference at those inputs (any byte for the JPEG round trip and the mask,
+# more than K_EXPOSE u scale in at least one element for the exposure).
+# ---------------------------------------------------------------------------------------------------------------------------------
+JPEG_WRONG = {
+    "half-away-from-zero 8-bit rounding": dict(half_away=True),
+    "the q >= 50 scale used below 50": dict(high_scale_everywhere=True),
+    "luma table for chroma": dict(luma_for_chroma=True),
+    "box instead of fancy up-sampling": dict(upsample="box"),
+    "up-sampling clamped at MCU borders": dict(upsample="per_mcu"),
+}
+MASK_WRONG = {
+    ">= instead of > at 32768": dict(inclusive=True),
+    "grey thresholds 250 and 5": dict(bright=250, dark=5),
+}
+EXPOSE_WRONG = {
+    "one sigma per sample": dict(per_sample_sigma=True),
+    "z0 and z1 swapped": dict(swap_z=True),
+    "clip before relu": dict(clip_first=True),
+}
+
+
+def test_jpeg_model_is_the_oracle_behind_the_quantiser():
+    c = R.jpeg_contents(32, 32, 1)
+    for q in (1, 49, 50, 100):
+        u8 = R.quantise_u8(c["off"])
+        assert np.array_equal(R.jpeg_model(c["off"], q), O.jpeg_round_trip(u8, q))
+        assert np.array_equal(R.jpeg_model(c["off"], q), pil_round_trip(u8, q))
+
+
+def test_off_grid_inputs_hold_every_tie_and_both_overflows():
+    assert len(R.ties()) == 255 and {k % 2 for _, k in R.ties()} == {0, 1}
+    for x, k in R.ties():
+        assert x * np.float32(255) == np.float32(k + 0.5)
+    off = R.jpeg_contents(16, 16, 1)["off"]
+    p = off * np.float32(255)
+    assert {int(v) for v in np.floor(p[(p - np.floor(p)) == np.float32(0.5)])} >= {k for _, k in R.ties()}
+    assert off.min() < 0 and off.max() > 1
+    u8 = R.quantise_u8(off)
+    assert u8.min() == 0 and u8.max() == 255
+    assert R.quantise_u8(np.float32([-0.3, 1.7, 0.5 / 255, 1.5 / 255, 2.5 / 255])).tolist()[:2] == [0, 255]
+
+
+def test_jpeg_inputs_catch_every_wrong_model():
+    for name, kw in JPEG_WRONG.items():
+        hits = 0
+        for h, w in R.JPEG_SIZES[:4]:
+            for ldr, q in R.jpeg_batches(h, w):
+                hits += sum(not np.array_equal(R.jpeg_model(ldr[i], q[i], **kw), R.jpeg_model(ldr[i], q[i])) for i in range(3))
+        assert hits >= 3, (name, hits)
+    one_mcu = [(ldr, q) for ldr, q in R.jpeg_batches(16, 16)]
+    assert all(np.array_equal(R.jpeg_model(ldr[i], q[i], upsample="per_mcu"), R.jpeg_model(ldr[i], q[i]))
+               for ldr, q in one_mcu for i in range(3))              # one MCU: its borders ARE the image borders
+
+
+def test_quality_clamp_and_low_quality_tables():
+    for given, means in R.JPEG_CLAMPED:
+        for g, m in zip(given, means):
+            assert all(np.array_equal(a, b) for a, b in zip(O.quant_tables(g), O.quant_tables(m)))
+    assert O.quant_tables(1)[0].max() == 255 and O.quant_tables(1)[0].min() == 255      # 5000 / 1 * 10 / 100: every entry clamps
+    assert O.quant_tables(49)[0][0, 0] == (16 * 102 + 50) // 100 and O.quant_tables(51)[0][0, 0] == (16 * 98 + 50) // 100
+
+
+def test_mask_inputs_sit_at_the_thresholds_and_catch_every_wrong_model():
+    cases = R.mask_cases()
+    for name, (img, counts, mask) in cases.items():
+        j = O.jpeg_round_trip(img, 100)
+        assert R.census(j) == counts and R.loss_mask(j) == mask, name
+        assert float(O.loss_mask(j[None]).reshape(())) == mask, name
+    for name, kw in MASK_WRONG.items():
+        hits = [n for n, (img, _, mask) in cases.items() if R.loss_mask(O.jpeg_round_trip(img, 100), **kw) != mask]
+        assert len(hits) >= 2, (name, hits)
+    e = cases["second_trip"][0]                                          # without the pixels past 1024 * 256 the sample would be kept
+    assert R.loss_mask(O.jpeg_round_trip(e, 100)[:512]) == 1.0 and e.shape[0] * e.shape[1] > 1024 * 256
+
+
+@pytest.mark.parametrize("case", R.EXPOSE_CASES, ids=lambda c: "%dx%dx%d" % c)
+def test_expose_restatement_within_the_per_element_bound_and_wrong_models_outside(case):
+    """the fp32 numpy restatement alone: worst err / (u scale) = 3.6 on the 2 x 300 x 300 case"""
+    assert R.K_EXPOSE <= 32
+    hdr, t, seed = R.expose_input(case)
+    want, clipped, scale = R.expose64(hdr, t, seed)
+    got, got_c = O.camera_expose(hdr, t, seed)
+    assert np.all(np.abs(got - want) <= R.K_EXPOSE * R.U * scale), float((np.abs(got - want) / (R.U * scale + 1e-300)).max())
+    assert np.array_equal(clipped, np.minimum(want, 1)) and want.min() >= 0
+    if hdr.size < 100:
+        return
+    for name, kw in EXPOSE_WRONG.items():
+        if name == "one sigma per sample" and hdr.shape[0] * hdr.shape[1] * hdr.shape[2] < 50:
+            continue
+        bad, _, _ = R.expose64(hdr, t, seed, **kw)
+        assert np.any(np.abs(bad - want) > 32 * R.U * scale), name
