@@ -206,6 +206,21 @@ int shdr_conv2d_fwd_up2_lowres_f32(const shdr_conv2d_desc* d, const float* x, co
                                    const float* scale, const float* shift, float* y, void* workspace, const float* x_range,
                                    float* y_range, void* stream);
 
+/* The same layer in ONE launch for 64 output channels (csrc/up2_fused.hip; the Hallucination-Net's u1, whose tap planes would be 2.7 GB at
+ * batch 16): a block computes the nine tap planes on a low-res tile with its one-pixel halo and folds them in registers, so neither the
+ * planes nor -- with a projected output -- the 64-channel result reach memory.  Descriptor, prepared filter (the _lowres_ one: same
+ * packed taps, same scale) and arithmetic are those of shdr_conv2d_fwd_up2_lowres_f32: y is bit-identical to it, range slot included.
+ * _ok: 1 if the layer is taken -- as _lowres_ok without the fill threshold, and Cout == 64, 64 <= Cin <= 128; 0 under SHDR_NO_UP2_FUSED=1.
+ * _fwd: writes y [N,H,W,64], the projected output y_proj [N,H,W,3] = sum_c proj[j][c] y[c] (proj [3][64], as in
+ *      shdr_conv2d_fwd_prepared_projected_f32), or both (y_proj with proj; at least one output).  x_range: the input's range slot
+ *      (required); y_range (or NULL): receives max |y| when y is written. */
+int shdr_conv2d_up2_fused_ok_f32(const shdr_conv2d_desc* d);
+int64_t shdr_conv2d_up2_fused_filter_elems_f32(const shdr_conv2d_desc* d);
+int shdr_conv2d_up2_fused_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream);
+int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const float* x, const float* prepared, const float* bias,
+                                  const float* scale, const float* shift, const float* proj, float* y_proj, float* y,
+                                  const float* x_range, float* y_range, void* stream);
+
 /*
  * Convolution backward (GradientTape.gradient through Conv2D: joint_training.py:185,
  * train.py:175,195,242, finetune_real_dataset.py:177).

@@ -108,6 +108,10 @@ SIGNATURES = {
     "shdr_conv2d_up2_lowres_prepare_filter_f32": (c_int, [ctypes.POINTER(ConvDesc), c_ptr, c_ptr, c_ptr]),
     "shdr_conv2d_up2_lowres_workspace_bytes_f32": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "shdr_conv2d_fwd_up2_lowres_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 10),
+    "shdr_conv2d_up2_fused_ok_f32": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "shdr_conv2d_up2_fused_filter_elems_f32": (c_i64, [ctypes.POINTER(ConvDesc)]),
+    "shdr_conv2d_up2_fused_prepare_filter_f32": (c_int, [ctypes.POINTER(ConvDesc), c_ptr, c_ptr, c_ptr]),
+    "shdr_conv2d_fwd_up2_fused_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 11),
     "shdr_conv2d_fwd_x3_projected_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 14),
     "shdr_conv2d_fwd_x3_residual_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 12),
     "shdr_conv2d_dgrad_workspace_bytes_f32": (c_i64, [ctypes.POINTER(ConvDesc), c_int]),

@@ -272,7 +272,13 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
     shdr_conv2d_fwd_prepared_projected_f32), or None when the planned kernel of the layer cannot form it.
     lowres=True: the caller accepts the form that mixes the channels at LOW resolution (csrc/up2_lowres.hip: a 1x1 GEMM Cin -> 9 Cout on
     x, then a stencil pass; the accuracy class of the split-operand kernels, not the bits of the default form) where the library takes the
-    layer (shdr_conv2d_up2_lowres_ok_f32); elsewhere, and with the default, this is the call below."""
+    layer (shdr_conv2d_up2_lowres_ok_f32); elsewhere, and with the default, this is the call below.  With proj it is the one-launch
+    form of the same arithmetic (csrc/up2_fused.hip, shdr_conv2d_up2_fused_ok_f32), which writes the projected output alone."""
+    if lowres and proj is not None and not _is_h(x) and _AUTO_ALGO[PRECISION] == ALGO_AUTO and WINOGRAD and not EXACT_FP32 \
+            and not _needs_grad(x, w, bias, scale, shift):
+        yj = _conv2d_up2_fused(x, w, bias, act1, scale, shift, act2, proj)
+        if yj is not None:
+            return yj
     if lowres and proj is None and not _is_h(x) and _AUTO_ALGO[PRECISION] == ALGO_AUTO and WINOGRAD and not EXACT_FP32 \
             and not _needs_grad(x, w, bias, scale, shift):
         y = _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2)
@@ -287,11 +293,11 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
                        prologue=PROLOGUE_BILINEAR2X, proj=proj)
 
 
-def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
-    """conv2d_up2 through shdr_conv2d_fwd_up2_lowres_f32, or None where the library does not take the layer.  Plumbing only: the
-    descriptor of _conv2d_raw's bilinear-prologue call, the prepared filter kept on the variable per version, the workspace."""
+def _up2_layer(form, x, w, bias, act1, scale, shift, act2):
+    """(descriptor, x, prepared filter) of conv2d_up2 on one of the low-res forms -- "lowres": csrc/up2_lowres.hip, "fused":
+    csrc/up2_fused.hip -- or None where the library does not take the layer.  The descriptor is that of _conv2d_raw's bilinear-prologue
+    call; the prepared filter is kept on the variable per version under a key of the form's own."""
     lib = _lib.load()
-    x_in = x
     x, w_var = _d(x), w
     w = _d(w)
     if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[:2]) != (3, 3) or w.shape[2] != x.shape[3]:
@@ -307,7 +313,7 @@ def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
     d.act1, d.act2 = act1, act2
     d.algo = ALGO_AUTO
     d.prologue = PROLOGUE_BILINEAR2X
-    if not int(lib.shdr_conv2d_up2_lowres_ok_f32(ctypes.byref(d))):
+    if not int(getattr(lib, "shdr_conv2d_up2_%s_ok_f32" % form)(ctypes.byref(d))):
         return None
     _chk(x, "x")
     _chk(w, "w")
@@ -315,25 +321,69 @@ def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
         if t is not None and (_chk(_d(t), nm).numel() != cout):
             raise ValueError("conv2d_up2: %s must have %d elements" % (nm, cout))
     persistent = _is_persistent(w_var)
-    nprep = int(lib.shdr_conv2d_up2_lowres_filter_elems_f32(ctypes.byref(d)))       # (follows the padding of the GEMM's columns)
-    key = ("up2_lowres", c1, cout, nprep)
+    nprep = int(getattr(lib, "shdr_conv2d_up2_%s_filter_elems_f32" % form)(ctypes.byref(d)))      # (follows the padding of the GEMM's columns)
+    key = ("up2_" + form, c1, cout, nprep)
     prepared = _filter_cache_get(w_var, "_shdr_packed", key) if persistent else None
     if prepared is None:
         prepared = torch.empty(nprep, device=w.device, dtype=torch.float32)
-        _lib.check(lib.shdr_conv2d_up2_lowres_prepare_filter_f32(ctypes.byref(d), _ptr(w), _ptr(prepared), _stream()),
-                   "shdr_conv2d_up2_lowres_prepare_filter_f32")
+        name = "shdr_conv2d_up2_%s_prepare_filter_f32" % form
+        _lib.check(getattr(lib, name)(ctypes.byref(d), _ptr(w), _ptr(prepared), _stream()), name)
         if persistent:
             _filter_cache_put(w_var, "_shdr_packed", key, prepared)
+    return d, x, prepared
+
+
+def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
+    """conv2d_up2 through shdr_conv2d_fwd_up2_lowres_f32, or None where the library does not take the layer.  Plumbing only."""
+    layer = _up2_layer("lowres", x, w, bias, act1, scale, shift, act2)
+    if layer is None:
+        return None
+    lib = _lib.load()
+    x_in = x
+    d, x, prepared = layer
     xr = _range_of(x_in)
     if xr is None:
-        RANGE_MISSES[(tuple(x.shape), None, tuple(w.shape))] += 1     # measured below the ABI
+        RANGE_MISSES[(tuple(x.shape), None, tuple(_d(w).shape))] += 1     # measured below the ABI
     ws = torch.empty(int(lib.shdr_conv2d_up2_lowres_workspace_bytes_f32(ctypes.byref(d))), device=x.device, dtype=torch.uint8)
-    out = torch.empty((n, 2 * h, 2 * wd, cout), device=x.device, dtype=torch.float32)
+    out = torch.empty((d.N, d.H, d.W, d.Cout), device=x.device, dtype=torch.float32)
     yr = _new_slot(x.device)
     rc = lib.shdr_conv2d_fwd_up2_lowres_f32(ctypes.byref(d), _ptr(x), _ptr(prepared), _ptr(_d(bias)), _ptr(_d(scale)), _ptr(_d(shift)),
                                             _ptr(out), _ptr(ws), _ptr(xr), _ptr(yr), _stream())
     _lib.check(rc, "shdr_conv2d_fwd_up2_lowres_f32")
     return _set_range(out, yr)
+
+
+def _conv2d_up2_fused(x, w, bias, act1, scale, shift, act2, proj=None, want_y=None):
+    """conv2d_up2 through shdr_conv2d_fwd_up2_fused_f32, or None where the library does not take the layer: the projected output
+    [N, 2h, 2w, 3] for proj [3, 64], y (the bits of _conv2d_up2_lowres) without one, (y_proj, y) with want_y=True.  Plumbing only."""
+    layer = _up2_layer("fused", x, w, bias, act1, scale, shift, act2)
+    if layer is None:
+        return None
+    lib = _lib.load()
+    x_in = x
+    d, x, prepared = layer
+    if proj is not None:
+        proj = _chk(_d(proj), "proj")
+        if tuple(proj.shape) != (3, d.Cout):
+            raise ValueError("conv2d_up2: proj must be [3, %d]" % d.Cout)
+    if want_y is None:
+        want_y = proj is None
+    xr = _range_of(x_in)
+    if xr is None:                                                    # measured here: the entry takes the slot, not a workspace
+        RANGE_MISSES[(tuple(x.shape), None, tuple(_d(w).shape))] += 1
+        xr = _new_slot(x.device)
+        _lib.check(lib.shdr_absmax_f32(_ptr(x), x.numel(), _ptr(xr), _stream()), "shdr_absmax_f32")
+    out = torch.empty((d.N, d.H, d.W, d.Cout), device=x.device, dtype=torch.float32) if want_y else None
+    yj = torch.empty((d.N, d.H, d.W, 3), device=x.device, dtype=torch.float32) if proj is not None else None
+    yr = _new_slot(x.device) if want_y else None
+    rc = lib.shdr_conv2d_fwd_up2_fused_f32(ctypes.byref(d), _ptr(x), _ptr(prepared), _ptr(_d(bias)), _ptr(_d(scale)), _ptr(_d(shift)),
+                                           _ptr(proj), _ptr(yj), _ptr(out), _ptr(xr), _ptr(yr), _stream())
+    _lib.check(rc, "shdr_conv2d_fwd_up2_fused_f32")
+    if proj is not None:
+        PROJECTED_LAUNCHES[0] += 1
+    if want_y:
+        _set_range(out, yr)
+    return out if proj is None else ((yj, out) if want_y else yj)
 
 
 def _conv2d_raw(x, w, bias, stride, x2, x2_scale, act1, scale, shift, residual, act2, algo, out, cout_valid, pad, out_hw,

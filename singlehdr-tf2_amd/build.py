@@ -39,6 +39,7 @@ SOURCES = {
     "frontend.hip": ["-ffp-contract=off"],
     "pool.hip": [],
     "up2_lowres.hip": [],
+    "up2_fused.hip": [],
     "crf.hip": [],
     "glue.hip": [],
     "imageio.hip": [],

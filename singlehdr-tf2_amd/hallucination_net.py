@@ -80,9 +80,10 @@ class up(Layer):
 
     def call_projected(self, x, proj):
         """tape-free inference: sum_c proj[j, c] up(x)[..., c] from the same kernel's epilogue -- the block's own output is not written --
-        or None when the planned kernel cannot form it"""
+        or None when the planned kernel cannot form it.  lowres: the one-launch low-res form where the library takes the layer (u1: 64 couts,
+        csrc/up2_fused.hip), else today's bilinear-prologue kernel"""
         scale, shift = self.norm1.folded()
-        return self.conv1.call_up2(x, act1=K.ACT_RELU, scale=scale, shift=shift, act2=K.ACT_RELU, proj=proj)
+        return self.conv1.call_up2(x, act1=K.ACT_RELU, scale=scale, shift=shift, act2=K.ACT_RELU, proj=proj, lowres=True)
 
 
 class skipLayer(Layer):
