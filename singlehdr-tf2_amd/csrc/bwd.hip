@@ -57,8 +57,10 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void act_bwd_bias_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                            float* __restrict__ dz, float* __restrict__ db, float* __restrict__ ws,
                                                            long nquads, int Q, int act) {
-  __shared__ float4 part[256];
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  // The sums run in double: a bias in front of a training-mode BatchNorm has a gradient of exactly zero, its terms cancel, and the
+  // whole fp32 error of the sum would be what is left of it.  The kernel streams dy / y / dz; four double adds per quad are free.
+  __shared__ double part[256][4];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
   auto one = [&](long e, const float4 g, const float4 yv) {
     float4 d = g;
     if (act != SHDR_ACT_NONE) {
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void act_bwd_bias_kernel(const float* __restri
       }
       *reinterpret_cast<float4*>(dz + 4 * e) = d;
     }
-    s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+    s0 += (double)d.x; s1 += (double)d.y; s2 += (double)d.z; s3 += (double)d.w;
   };
   // four quads per trip: the grid is capped (one atomic per block and channel on the same C addresses), so the bytes in
   // flight have to come from the loop
@@ -96,19 +98,18 @@ __global__ __launch_bounds__(256) void act_bwd_bias_kernel(const float* __restri
     if (act != SHDR_ACT_NONE) y0 = *reinterpret_cast<const float4*>(y + 4 * e);
     one(e, g0, y0);
   }
-  part[threadIdx.x] = s;
+  part[threadIdx.x][0] = s0; part[threadIdx.x][1] = s1; part[threadIdx.x][2] = s2; part[threadIdx.x][3] = s3;
   __syncthreads();
   for (int off = 128; off >= Q; off >>= 1) {            // threads t and t + k*Q hold the same channel quad
     if ((int)threadIdx.x < off) {
-      const float4 o = part[threadIdx.x + off];
-      float4 m = part[threadIdx.x];
-      m.x += o.x; m.y += o.y; m.z += o.z; m.w += o.w;
-      part[threadIdx.x] = m;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) part[threadIdx.x][k] += part[threadIdx.x + off][k];
     }
     __syncthreads();
   }
   if ((int)threadIdx.x < Q) {
-    const float4 m = part[threadIdx.x];
+    const float4 m = make_float4((float)part[threadIdx.x][0], (float)part[threadIdx.x][1], (float)part[threadIdx.x][2],
+                                 (float)part[threadIdx.x][3]);     // the block's sums, rounded once
     if (ws) {
       *reinterpret_cast<float4*>(ws + (size_t)blockIdx.x * 4 * Q + 4 * threadIdx.x) = m;
     } else {
@@ -863,14 +864,18 @@ extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz,
   // <= 512 blocks: every block ends with one atomic per channel on the SAME C addresses (2048 blocks measured slower than
   // the unfused pair)
   int grid = shdr::stream_grid(nquads);
-  if (ws && nquads >= (1L << 22)) {                   // partial rows + fold: the grid of a plain streaming kernel (pays from ~64 MB on)
+  const int cap = nquads >= (1L << 24) ? 512 : (nquads >= (1L << 23) ? 384 : 256);     // measured per tensor size
+  if (ws) {
+    // partial rows + fold.  From ~64 MB on with the grid of a plain streaming kernel (that is where it pays in time); below that with
+    // the capped grid, for the SUM: the blocks' sums are added in double by the fold instead of by fp32 atomics in arrival order, so
+    // db carries one rounding per block sum and one of the total
     SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "act_bwd_bias: ws must be 16-byte aligned");
-    if (grid > shdr::kBiasMaxBlocks) grid = shdr::kBiasMaxBlocks;
+    const int rows = nquads >= (1L << 22) ? shdr::kBiasMaxBlocks : cap;        // <= kBiasMaxBlocks rows of C floats: the workspace
+    if (grid > rows) grid = rows;
     hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, S(stream), dy, y, dz, db, ws, nquads, Q, act);
     shdr::launch_col_fold(ws, db, grid, C, S(stream));
     return shdr::check_launch("act_bwd_bias");
   }
-  const int cap = nquads >= (1L << 24) ? 512 : (nquads >= (1L << 23) ? 384 : 256);     // measured per tensor size
   if (grid > cap) grid = cap;
   hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, S(stream), dy, y, dz, db, (float*)nullptr, nquads, Q, act);
   return shdr::check_launch("act_bwd_bias");

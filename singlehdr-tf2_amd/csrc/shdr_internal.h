@@ -97,11 +97,11 @@ inline long slice_for_rounds(long slots, long tiles, long units, long min_slice)
 // of ending in atomics on the same C addresses).  Block = 16 columns x 16 row lanes, four independent loads in flight per thread
 // (64 columns x 4 row lanes with one dependent load chain per thread took 43 us on 2048 rows: latency-bound), blockIdx.y = row slice.
 __global__ __launch_bounds__(256) static void col_fold_kernel(const float* __restrict__ ws, float* __restrict__ out, int g, int C) {
-  __shared__ float part[16][17];
+  __shared__ double part[16][17];                      // the fold adds in double: its result carries ONE rounding, at the atomic
   const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   const int r0 = blockIdx.y * 256, r1 = r0 + 256 < g ? r0 + 256 : g;
-  float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
   if (c < C) {
     int r = r0 + rl;
     for (; r + 48 < r1; r += 64) {
@@ -112,10 +112,10 @@ __global__ __launch_bounds__(256) static void col_fold_kernel(const float* __res
   part[rl][cl] = (t0 + t1) + (t2 + t3);
   __syncthreads();
   if (rl == 0 && c < C) {
-    float t = 0.f;
+    double t = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += part[k][cl];
-    atomicAdd(out + c, t);
+    atomicAdd(out + c, (float)t);
   }
 }
 inline void launch_col_fold(const float* ws, float* out, int g, int C, hipStream_t st) {
