@@ -619,6 +619,52 @@ int shdr_exr_load_resize_f32(const uint8_t* planes, int64_t size, const int64_t*
                              int64_t row_bytes, const int64_t* chan_off, const int32_t* chan_type, int H0, int W0, float* y,
                              int H, int W, int clip, void* stream);
 
+/* ---- zlib streams inflated (exr.py read_stored / upload_batch; csrc/inflate.h, csrc/inflate.hip) ------------------------- */
+/* Per-chunk status of the decoder, host and device alike (csrc/inflate.h holds the code both run). */
+#define SHDR_INFLATE_OK               0
+#define SHDR_INFLATE_TRUNCATED        1   /* the stream ends inside the header, a block or the Adler-32 */
+#define SHDR_INFLATE_HEADER           2   /* CM != 8, CINFO > 7 or the header check */
+#define SHDR_INFLATE_DICTIONARY       3   /* FDICT */
+#define SHDR_INFLATE_BLOCK_TYPE       4   /* BTYPE 3 */
+#define SHDR_INFLATE_STORED_LENGTH    5   /* LEN != ~NLEN */
+#define SHDR_INFLATE_COUNTS           6   /* HLIT > 286 or HDIST > 30 */
+#define SHDR_INFLATE_CODE_LENGTH_SET  7   /* the code-length code is over-subscribed or incomplete */
+#define SHDR_INFLATE_REPEAT           8   /* repeat-16 with no previous length */
+#define SHDR_INFLATE_RUN              9   /* a run overflows HLIT + HDIST */
+#define SHDR_INFLATE_NO_END_OF_BLOCK 10   /* symbol 256 has no code */
+#define SHDR_INFLATE_LITERAL_SET     11   /* literal/length code set over-subscribed or incomplete */
+#define SHDR_INFLATE_DISTANCE_SET    12   /* distance code set over-subscribed or incomplete */
+#define SHDR_INFLATE_LITERAL_CODE    13   /* a code no literal/length symbol owns, or symbol 286 / 287 */
+#define SHDR_INFLATE_DISTANCE_CODE   14   /* a code no distance symbol owns, or symbol 30 / 31 */
+#define SHDR_INFLATE_DISTANCE_FAR    15   /* a distance beyond the bytes produced so far */
+#define SHDR_INFLATE_OVERFLOW        16   /* the output is longer than the slot */
+#define SHDR_INFLATE_SHORT           17   /* the stream is complete, its output shorter than the slot */
+#define SHDR_INFLATE_CHECKSUM        18   /* Adler-32 */
+#define SHDR_INFLATE_RAW_SIZE        19   /* (batch) a stored-raw chunk whose size is not the slot's */
+#define SHDR_INFLATE_MODE            20   /* (batch) a mode byte other than 0 / 1 */
+/* The zlib stream src[0 .. n) (RFC 1950 / 1951: stored, fixed and dynamic blocks; zlib's acceptance rules, no preset dictionary;
+ * bytes after the Adler-32 are ignored) into dst[0 .. capacity), capacity <= 2^30 being the size the output must have (host).
+ * Returns the number of bytes written, never more than `capacity`, and stores the status in *status; nothing outside
+ * [src, src + n) is read, whatever the bytes are.  -1 (see shdr_last_error) for bad arguments only. */
+int64_t shdr_inflate_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity, int* status);
+/* The same decoder on the device for a BATCH of chunks in one launch, one 64-lane workgroup per chunk: chunk c is read from
+ * src[src_off[c] .. src_off[c + 1]) and written into the slot dst[dst_off[c] .. dst_off[c + 1]); any byte alignment of both.
+ *      src_off, dst_off   int64 [n_chunks + 1], non-decreasing, inside the buffers, chunks and slots of 0 .. 2^30 bytes: host arrays,
+ *                         which are validated before anything is launched, and the device copies of those very arrays (_dev),
+ *                         which the kernel reads and clamps into the buffers again
+ *      mode               device uint8 [n_chunks], or NULL for all 1: 1 a zlib stream, 0 stored raw (copied if its size is the slot's)
+ *      status, written    device int32 [n_chunks] and int64 [n_chunks]: SHDR_INFLATE_* and the bytes written into the slot
+ *                         (never more than the slot; bytes of the slot beyond them are left untouched)
+ *      stage_ms           NULL, or float [SHDR_INFLATE_STAGES] for the device-event time of the launch (measurement only: the call
+ *                         then waits for it)
+ * Stream-ordered, deterministic, no global atomics, no host wait, no allocation.  shdr_inflate_batch_sizes validates the two tables
+ * and returns the bytes that src and dst must hold at least. */
+#define SHDR_INFLATE_STAGES 1
+int shdr_inflate_batch_sizes(const int64_t* src_off, const int64_t* dst_off, int n_chunks, int64_t* src_bytes, int64_t* dst_bytes);
+int shdr_inflate_batch(const uint8_t* src, int64_t src_bytes, const int64_t* src_off, const int64_t* src_off_dev, uint8_t* dst,
+                       int64_t dst_bytes, const int64_t* dst_off, const int64_t* dst_off_dev, const uint8_t* mode, int n_chunks,
+                       int32_t* status, int64_t* written, void* stream, float* stage_ms);
+
 /* ---- OpenEXR output (exr.py encode_exr / write_exr; csrc/exr_write.hip, csrc/deflate.hip) ------------------------------ */
 /* Huffman-only zlib stream of src[0 .. n), 1 <= n <= 2^30 (host): 78 01, one final dynamic-Huffman block of literals with a
  * fixed-length header (csrc/deflate_huffman.h), the big-endian Adler-32.  zlib's inflate reads it.  Returns the stream's length,

@@ -2055,6 +2055,99 @@ def deflate_huffman(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offs
     return out, out_offsets, coded
 
 
+# ---------------------------------------------------------------------------
+# zlib streams inflated (exr.py read_stored / upload_batch), see csrc/inflate.h and csrc/inflate.hip
+# ---------------------------------------------------------------------------
+INFLATE_REASONS = (                                   # SHDR_INFLATE_*: the per-chunk status of the host routine and of the kernel
+    "ok", "truncated stream", "bad zlib header", "preset dictionary", "invalid block type", "invalid stored block lengths",
+    "too many length or distance symbols", "invalid code lengths set", "invalid bit length repeat", "code length run overflows",
+    "missing end-of-block", "invalid literal/lengths set", "invalid distances set", "invalid literal/length code",
+    "invalid distance code", "invalid distance too far back", "output longer than its slot", "output shorter than its slot",
+    "incorrect data check", "raw chunk size is not its slot's", "invalid mode byte")
+
+
+def inflate_reason(status):
+    status = int(status)
+    return INFLATE_REASONS[status] if 0 <= status < len(INFLATE_REASONS) else "status %d" % status
+
+
+def inflate_host(stream, capacity):
+    """a zlib stream -> (bytes, status): libshdr's host decoder (csrc/inflate.h, the code the kernel runs).  capacity: the size the
+    output must have; status 0 means exactly that many bytes came out and the Adler-32 holds, any other value is an index into
+    INFLATE_REASONS and `bytes` is what had been written by then (never more than capacity)"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    capacity = int(capacity)
+    out = np.empty(max(capacity, 1), dtype=np.uint8)
+    st = ctypes.c_int(-1)
+    n = lib.shdr_inflate_host(_hptr(src) if src.size else None, src.size, _hptr(out), capacity, ctypes.byref(st))
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n].tobytes(), st.value
+
+
+def _offsets_pair(what, name, offsets, offsets_dev):
+    """(host int64 array, device tensor or None) of an offset table given as a host array (+ the caller's device copy) or a tensor"""
+    if isinstance(offsets, torch.Tensor):
+        host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
+        dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
+    else:
+        host, dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
+        if dev is not None and _chk(dev, name + "_dev", torch.int64).numel() != host.size:
+            raise ValueError("%s: %s_dev is not a copy of %s" % (what, name, name))
+    if host.ndim != 1 or host.size < 2:
+        raise ValueError("%s: %s must be [n_chunks + 1]" % (what, name))
+    return host, dev
+
+
+def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets_dev=None, dst_offsets_dev=None, dst=None):
+    """a batch of zlib streams inflated on the device in one launch (csrc/inflate.hip): chunk c is src[src_offsets[c]:src_offsets[c + 1]]
+    and is written into the slot dst[dst_offsets[c]:dst_offsets[c + 1]], which its output must fill exactly.  src: uint8 device tensor;
+    the offsets: int64 [n + 1], non-decreasing (host arrays or tensors; *_dev: the device copies of host arrays, if the caller has
+    them); mode: uint8 [n] on the device, 1 a zlib stream, 0 stored raw (copied if its size is the slot's), default all 1; dst: a
+    uint8 device tensor of at least dst_offsets[-1] bytes to write into (default: a new one of that size, not cleared).  Returns
+    (dst, written int64 [n], status int32 [n]) on the device: status 0, or an index into INFLATE_REASONS; bytes of a slot beyond
+    `written` are left as they were.  Stream-ordered, no host wait.  stage_ms: a list that receives the launch's device time
+    (measurement: the call then waits)."""
+    lib = _lib.load()
+    src = _chk(src, "src", torch.uint8)
+    s_host, s_dev = _offsets_pair("inflate", "src_offsets", src_offsets, src_offsets_dev)
+    d_host, d_dev = _offsets_pair("inflate", "dst_offsets", dst_offsets, dst_offsets_dev)
+    n = s_host.size - 1
+    if src.dim() != 1 or d_host.size != n + 1:
+        raise ValueError("inflate: expected src [size] and two offset tables [n_chunks + 1]")
+    src_b, dst_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_inflate_batch_sizes(_hptr(s_host), _hptr(d_host), n, ctypes.byref(src_b), ctypes.byref(dst_b)),
+               "shdr_inflate_batch_sizes")
+    if src_b.value > src.numel():
+        raise ValueError("inflate: src_offsets end at %d, src holds %d bytes" % (src_b.value, src.numel()))
+    dev = src.device
+    if dst is None:
+        dst = torch.empty(dst_b.value, device=dev, dtype=torch.uint8)
+    else:
+        dst = _chk(dst, "dst", torch.uint8)
+        if dst.dim() != 1 or dst.numel() < dst_b.value:
+            raise ValueError("inflate: dst_offsets end at %d, dst holds %d bytes" % (dst_b.value, dst.numel()))
+    if mode is not None:
+        mode = _chk(mode, "mode", torch.uint8)
+        if mode.numel() != n:
+            raise ValueError("inflate: mode must be uint8 [n_chunks]")
+    if s_dev is None:
+        s_dev = torch.from_numpy(s_host).to(dev)
+    if d_dev is None:
+        d_dev = torch.from_numpy(d_host).to(dev)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    written = torch.empty(n, device=dev, dtype=torch.int64)
+    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
+    _lib.check(lib.shdr_inflate_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev),
+                                      _ptr(dst) if dst.numel() else None, dst.numel(), _hptr(d_host), _ptr(d_dev),
+                                      _ptr(mode) if mode is not None else None, n, _ptr(status), _ptr(written), _stream(), ms),
+               "shdr_inflate_batch")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return dst, written, status
+
+
 EXR_HALF, EXR_FLOAT = 1, 2
 
 

@@ -204,7 +204,7 @@ def _load_pkl(name):
 
 def _source_shape(item):
     """(h, w) of an item of HDRDataset"""
-    if isinstance(item, exr.Payload):
+    if isinstance(item, (exr.Payload, exr.Stored)):
         return item.header.height, item.header.width
     return item.shape[:2]
 
@@ -270,17 +270,21 @@ class HDRDataset(Dataset):
     """the file list; items are the RGBE bytes of a Radiance file or the exr.Payload of an OpenEXR one (the pixels are
     converted on the device, see PatchHDRDataset)"""
 
-    def __init__(self, hdr_prefix, hdr_posfix_list, is_training):
+    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, exr_inflate="host"):
+        """exr_inflate "device": ZIP / ZIPS OpenEXR files come back as exr.Stored (checked, not inflated; exr.upload_batch's input)"""
         self._hdr_prefix = hdr_prefix
         self._hdr_posfix_list = list(hdr_posfix_list)
         self.is_training = is_training
+        self.exr_inflate = exr.check_inflate_option("HDRDataset", exr_inflate)
 
     def path(self, idx):
         return os.path.join(self._hdr_prefix, self._hdr_posfix_list[idx])
 
     def __getitem__(self, idx):
         path = self.path(idx)
-        return exr.read_payload(path) if exr.is_exr(path) else hdr_io.read_rgbe(path)
+        if not exr.is_exr(path):
+            return hdr_io.read_rgbe(path)
+        return exr.read_stored(path) if self.exr_inflate == "device" else exr.read_payload(path)
 
     def __len__(self):
         return len(self._hdr_posfix_list)
@@ -290,9 +294,11 @@ class PatchHDRDataset(Dataset):
     """2 patches per file (:212-252): the first and last 512 rows (portrait) or columns (otherwise) of the resized image,
     normalised to mean 0.5; training adds a random resize, 256 crop, rot90 and flips.  Every file is resident on the device."""
 
-    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, load_to_mem=True, device=None, seed=0):
-        """load_to_mem is the reference's argument; the images are always resident (on the device)"""
-        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training)
+    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, load_to_mem=True, device=None, seed=0, exr_inflate="host"):
+        """load_to_mem is the reference's argument; the images are always resident (on the device).  exr_inflate: who inflates the
+        ZIP / ZIPS chunks of OpenEXR files -- "host" (zlib, in the loading threads) or "device" (all files' chunks in one
+        exr.upload_batch; the time moves from load_seconds["host_decode"] to load_seconds["device"]); the arena is the same"""
+        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training, exr_inflate)
         self._is_training = is_training
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.rng = np.random.default_rng(seed)          # draws of __getitem__ (the reader has its own)
@@ -319,10 +325,14 @@ class PatchHDRDataset(Dataset):
         sizes = [h * w * 3 for h, w in shapes]
         offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         self.arena = torch.empty(int(sum(sizes)), device=self.device, dtype=torch.float32)
+        batched = {}
+        if self._hdr_dataset.exr_inflate == "device":                # every OpenEXR file of the list in one batch
+            which = [i for i, r in enumerate(items) if isinstance(r, (exr.Payload, exr.Stored))]
+            batched = dict(zip(which, exr.upload_batch([items[i] for i in which], self.device)))
         for i, (r, (h, w)) in enumerate(zip(items, shapes)):
             out = self.arena[offsets[i]:offsets[i] + sizes[i]].view(h, w, 3)
-            if isinstance(r, exr.Payload):
-                planes, chunk_offsets = exr.upload(r, self.device)
+            if isinstance(r, (exr.Payload, exr.Stored)):
+                planes, chunk_offsets = batched[i] if i in batched else exr.upload(r, self.device)
                 exr.load_resize(r, planes, chunk_offsets, out, "BGR", clip=True)
             else:
                 K.hdr_load_resize(torch.from_numpy(r).to(self.device), out)
@@ -408,21 +418,23 @@ def _merge(patches, tables):
     return MergeDataset([patches, CatDataset([crf, invcrf]), t])
 
 
-def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None):
+def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
     tables = crf_tables("train", crf_path)                     # first: a missing DoRF file fails before any file is loaded
-    return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_train"), True, device=device), tables)
+    return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_train"), True, device=device,
+                                  exr_inflate=exr_inflate), tables)
 
 
-def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None):
+def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
     tables = crf_tables("vali", crf_path)
     posfix_list = _posfix_list(hdr_prefix, posfix_list, "i_dataset_test")
     np.random.RandomState(730).shuffle(posfix_list)
-    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device), tables)
+    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device, exr_inflate=exr_inflate), tables)
 
 
-def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None):
+def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
     tables = crf_tables("test", crf_path)
-    return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_test"), False, device=device), tables)
+    return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_test"), False, device=device,
+                                  exr_inflate=exr_inflate), tables)
 
 
 # --- RandDatasetReader (dataset.py:318-363) -------------------------------------------------------------------------

@@ -22,6 +22,12 @@ Split of the work: the host reads and checks the bytes and inflates (zlib, which
 interleave (shdr_exr_unpredict_u8) and converts / resizes straight from the planar scanlines (shdr_exr_load_resize_f32,
 csrc/exr.hip).  Every refusal is a ValueError naming the file and the reason.
 
+With inflate="device" (read_exr; exr_inflate= of dataset.PatchHDRDataset and hdr_real.HdrRealFolder; opt-in) the host keeps only the
+container checks (read_stored) and the device inflates too: the stored bytes of all chunks of all files go up in one copy, one
+launch of K.inflate (csrc/inflate.hip, a zlib decoder with one wave per chunk; csrc/inflate.h is the decoder, shared with the host
+routine K.inflate_host that the tests judge against zlib) decodes them into place, one launch undoes the predictor, and one small
+copy of the chunks' status codes back is the only wait (upload_batch).  The pixels are the same bits.
+
 Writing (encode_exr / write_exr) mirrors that split.  The device converts float32 to HALF or FLOAT, lays the samples out as planar
 scanlines (B, G, R) and applies the interleave and the delta predictor, all chunks of a batch of images in one launch
 (K.exr_pack, csrc/exr_write.hip).  With encoder="host" the predicted bytes come back and zlib.compress deflates every chunk in a
@@ -61,9 +67,14 @@ Channel = collections.namedtuple("Channel", "name type offset")      # offset: b
 Header = collections.namedtuple("Header", "data_window width height channels compression line_order lines row_bytes n_chunks "
                                           "table_offset")
 Payload = collections.namedtuple("Payload", "header data offsets coded")
+Stored = collections.namedtuple("Stored", "header path data src_offsets offsets mode")
 """data: uint8 [offsets[-1]], the chunks in increasing-y order; offsets: int64 [n_chunks + 1], chunk c at
 data[offsets[c]:offsets[c + 1]] (min(lines, rows left) * row_bytes bytes); coded: uint8 [n_chunks], 1 where the predictor and
 the interleave are still to be undone (0 for raw chunks and NO_COMPRESSION)"""
+"""Stored (read_stored): a ZIP / ZIPS file whose chunks are still as the file holds them.  data: uint8, the chunks' stored bytes back to
+back in increasing-y order, chunk headers stripped; src_offsets: int64 [n_chunks + 1], chunk c is data[src_offsets[c]:src_offsets[c + 1]];
+offsets: the decoded offsets, identical to Payload.offsets; mode: uint8 [n_chunks], 1 a zlib stream, 0 stored raw (K.inflate's mode
+bytes); path: the file, for error messages"""
 
 
 def is_exr(path):
@@ -208,7 +219,10 @@ def read_payload(path):
     """the file's chunks decoded on the host (inflated / run-length decoded, predictor and interleave NOT undone): a Payload"""
     with open(path, "rb") as f:
         data = f.read()
-    hdr = _parse_header(data, path)
+    return _payload(data, _parse_header(data, path), path)
+
+
+def _payload(data, hdr, path):
     n, lines, row_bytes = hdr.n_chunks, hdr.lines, hdr.row_bytes
     table = np.frombuffer(data, dtype="<u8", count=n, offset=hdr.table_offset).astype(np.uint64)
     table_end = hdr.table_offset + 8 * n
@@ -258,6 +272,109 @@ def read_payload(path):
     return Payload(hdr, out, offsets, coded)
 
 
+def check_inflate_option(what, inflate):
+    if inflate not in ("host", "device"):
+        raise ValueError("%s: inflate must be 'host' or 'device', got %r" % (what, inflate))
+    return inflate
+
+
+def read_stored(path):
+    """the host half of the device route: every container check of read_payload, with its messages, and nothing inflated.  ZIP and
+    ZIPS files come back as a Stored (the chunks' bytes as the file holds them); RLE and NO_COMPRESSION files as read_payload's
+    Payload.  upload_batch takes both."""
+    with open(path, "rb") as f:
+        data = f.read()
+    hdr = _parse_header(data, path)
+    if hdr.compression not in (ZIP_COMPRESSION, ZIPS_COMPRESSION):
+        return _payload(data, hdr, path)
+    n, lines, row_bytes = hdr.n_chunks, hdr.lines, hdr.row_bytes
+    table = np.frombuffer(data, dtype="<u8", count=n, offset=hdr.table_offset).astype(np.uint64)
+    table_end = hdr.table_offset + 8 * n
+    rows = np.minimum(lines, hdr.height - np.arange(n, dtype=np.int64) * lines)
+    offsets = np.concatenate([[0], np.cumsum(rows * row_bytes)]).astype(np.int64)
+    src = np.frombuffer(data, dtype=np.uint8)
+    mode = np.ones(n, dtype=np.uint8)
+    parts, src_offsets = [], np.zeros(n + 1, dtype=np.int64)
+    ymin = hdr.data_window[1]
+    for c in range(n):
+        o = int(table[c])
+        if o < table_end or o > len(data) - 8:
+            raise _fail(path, "chunk %d: offset %d lies outside the file's chunk data" % (c, o))
+        y, size = struct.unpack_from("<ii", data, o)
+        if y != ymin + c * lines:
+            raise _fail(path, "chunk %d: y is %d, its table slot implies %d" % (c, y, ymin + c * lines))
+        if size < 0 or size > len(data) - o - 8:
+            raise _fail(path, "chunk %d: size %d runs past the end of the file" % (c, size))
+        want = int(offsets[c + 1] - offsets[c])
+        if size == want:                                                 # stored raw (compression would not shrink it)
+            mode[c] = 0
+        elif size > want:
+            raise _fail(path, "chunk %d: %d bytes stored, its %d scanlines hold %d" % (c, size, int(rows[c]), want))
+        parts.append(src[o + 8:o + 8 + size])
+        src_offsets[c + 1] = src_offsets[c] + size
+    return Stored(hdr, path, np.concatenate(parts), src_offsets, offsets, mode)
+
+
+def upload_batch(items, device):
+    """any mix of read_stored's Stored items and Payloads -> [(planes, offsets)] as upload() gives them, one pair per item, with all
+    the work of all the files batched: one staging buffer and one copy carry the stored bytes to the device, one K.inflate launch
+    decodes every chunk of every file into its place (chunks that are decoded already, or stored raw, are copied by that launch), one
+    K.exr_unpredict launch undoes the predictor, and one small copy of the chunks' status and byte counts back is the only host
+    wait.  ValueError("<path>: chunk <c>: inflate error: <reason>") for the first chunk, in file order, that the kernel refuses."""
+    items = list(items)
+    if not items:
+        return []
+    n_chunks = [it.header.n_chunks for it in items]
+    first = np.concatenate([[0], np.cumsum(n_chunks)]).astype(np.int64)
+    n = int(first[-1])
+    # one int64 table: source offsets, slot offsets, then every file's own chunk offsets (what load_resize reads)
+    tables = np.empty(2 * (n + 1) + n + len(items), dtype=np.int64)
+    src_off, dst_off, own = tables[:n + 1], tables[n + 1:2 * (n + 1)], tables[2 * (n + 1):]
+    flags = np.empty(2 * n, dtype=np.uint8)
+    mode, coded = flags[:n], flags[n:]
+    parts, s_at, d_at, own_at = [], 0, 0, []
+    for i, it in enumerate(items):
+        a, b = int(first[i]), int(first[i + 1])
+        if isinstance(it, Stored):
+            parts.append(it.data)
+            src_off[a:b + 1] = s_at + it.src_offsets
+            mode[a:b] = it.mode
+            coded[a:b] = it.mode
+            s_at += int(it.src_offsets[-1])
+        else:                                                            # decoded on the host: copied as it is
+            parts.append(it.data)
+            src_off[a:b + 1] = s_at + it.offsets
+            mode[a:b] = 0
+            coded[a:b] = it.coded
+            s_at += int(it.offsets[-1])
+        dst_off[a:b + 1] = d_at + it.offsets
+        d_at += int(it.offsets[-1])
+        own_at.append(a + i)
+        own[a + i:b + i + 1] = it.offsets
+    staging = torch.empty(max(s_at, 1), dtype=torch.uint8).pin_memory()         # alive until the wait below
+    if s_at:
+        np.concatenate(parts, out=staging.numpy()[:s_at])
+    src = staging.to(device, non_blocking=True)[:s_at]
+    tables_dev = torch.from_numpy(tables).to(device)
+    flags_dev = torch.from_numpy(flags).to(device)
+    src_off_dev, dst_off_dev, own_dev = tables_dev[:n + 1], tables_dev[n + 1:2 * (n + 1)], tables_dev[2 * (n + 1):]
+    dst, written, status = K.inflate(src, src_off, dst_off, mode=flags_dev[:n], src_offsets_dev=src_off_dev, dst_offsets_dev=dst_off_dev)
+    planes = K.exr_unpredict(dst, dst_off_dev, flags_dev[n:]) if coded.any() else dst
+    result = torch.stack([status.to(torch.int64), written]).cpu().numpy()       # the host waits here, once
+    bad = np.flatnonzero((result[0] != 0) | (result[1] != np.diff(dst_off)))
+    if bad.size:
+        c = int(bad[0])
+        i = int(np.searchsorted(first, c, side="right")) - 1
+        st = int(result[0, c])
+        raise _fail(getattr(items[i], "path", "item %d" % i), "chunk %d: inflate error: %s" % (
+            c - int(first[i]), K.inflate_reason(st) if st else "%d bytes written, its slot holds %d" % (result[1, c], dst_off[c + 1] - dst_off[c])))
+    out = []
+    for i, it in enumerate(items):
+        lo = int(dst_off[first[i]])
+        out.append((planes[lo:lo + int(it.offsets[-1])], own_dev[own_at[i]:own_at[i] + n_chunks[i] + 1]))
+    return out
+
+
 def channel_table(header, order="RGB"):
     """(byte offsets, types) of the channels named by `order` ("RGB", or "BGR" for the training arena)"""
     by_name = {ch.name: ch for ch in header.channels}
@@ -281,12 +398,18 @@ def load_resize(payload, planes, offsets, out, order="RGB", clip=False):
     return K.exr_load_resize(planes, offsets, hdr.lines, hdr.row_bytes, chan_off, chan_type, hdr.height, hdr.width, out, clip)
 
 
-def read_exr(path, device=None):
+def read_exr(path, device=None, inflate="host"):
     """OpenEXR file -> float32 RGB [H, W, 3] on the device (the data window; the file's values, HALF converted exactly, no
-    clipping): the EXR counterpart of hdr_io.read_hdr"""
-    payload = read_payload(path)
+    clipping): the EXR counterpart of hdr_io.read_hdr.  inflate: who inflates ZIP / ZIPS chunks -- "host" (zlib) or "device"
+    (K.inflate, csrc/inflate.hip: the stored bytes are uploaded); the pixels are the same"""
+    check_inflate_option("read_exr", inflate)
     device = device or torch.device("cuda", torch.cuda.current_device())
-    planes, offsets = upload(payload, device)
+    if inflate == "device":
+        payload = read_stored(path)
+        (planes, offsets), = upload_batch([payload], device)
+    else:
+        payload = read_payload(path)
+        planes, offsets = upload(payload, device)
     out = torch.empty((payload.header.height, payload.header.width, 3), device=device, dtype=torch.float32)
     return load_resize(payload, planes, offsets, out, "RGB", clip=False)
 

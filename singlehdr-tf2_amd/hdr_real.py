@@ -95,12 +95,15 @@ class HdrRealFolder:
     Flips are u0 < 0.5 and rots int(u1 * 4 + 0.5) of float32 uniforms, as tfrecord.HdrRealDataset draws them: rot 4 occurs and is
     rot 0.  augment=False gives flip 0 and rot 0.
     jpeg_decoder="device" decodes all LDR files in ONE jpeg.decode batch whose output arena IS ldr_arena (the same bytes as "pil",
-    hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch)."""
+    hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch).
+    exr_inflate="device" leaves the ZIP / ZIPS chunks of OpenEXR files to the device (exr.read_stored, then ONE exr.upload_batch for
+    all of them; the same arena as with "host", where zlib inflates them one file after the other)."""
 
     def __init__(self, dirpath, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1, batch_size=BATCH_SIZE,
-                 augment=True, jpeg_decoder="pil"):
+                 augment=True, jpeg_decoder="pil", exr_inflate="host"):
         if jpeg_decoder not in ("pil", "device"):
             raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil' or 'device', got %r" % (jpeg_decoder,))
+        exr.check_inflate_option("HdrRealFolder", exr_inflate)
         hdr_paths = sorted(p for ext in ("*.hdr", "*.exr") for p in glob.glob(os.path.join(dirpath, "HDR_gt", ext)))
         ldr_paths = sorted(glob.glob(os.path.join(dirpath, "LDR_in", "*.jpg")))
         if len(hdr_paths) != len(ldr_paths):
@@ -115,7 +118,8 @@ class HdrRealFolder:
             ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device)
         else:
             ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
-        hdr = [exr.read_payload(p) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
+        read = exr.read_stored if exr_inflate == "device" else exr.read_payload
+        hdr = [read(p) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
         self.files = list(zip(hdr_paths, ldr_paths))
         self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0, ldr_arena)
 
@@ -170,7 +174,7 @@ class HdrRealFolder:
     # --- loading ---------------------------------------------------------------------------------------------------
     @staticmethod
     def _hdr_shape(item):
-        if isinstance(item, exr.Payload):
+        if isinstance(item, (exr.Payload, exr.Stored)):
             return item.header.height, item.header.width
         return tuple(item.shape[:2])
 
@@ -183,7 +187,7 @@ class HdrRealFolder:
         shapes = []
         for i, (l, h) in enumerate(zip(ldr, hdr)):
             hs = self._hdr_shape(h)
-            if tuple(l.shape[:2]) != hs or (not isinstance(h, exr.Payload) and h.ndim != 3):
+            if tuple(l.shape[:2]) != hs or (not isinstance(h, (exr.Payload, exr.Stored)) and h.ndim != 3):
                 raise ValueError("HdrRealFolder: %s is %d x %d but %s is %d x %d" % (
                     self.files[i][0], hs[0], hs[1], self.files[i][1], l.shape[0], l.shape[1]))
             shapes.append(hs)
@@ -198,10 +202,14 @@ class HdrRealFolder:
         else:
             self.ldr_arena = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in ldr])).to(self.device)
         self.hdr_arena = torch.empty(total * 3, device=self.device, dtype=torch.float32)
+        batched = {}
+        if any(isinstance(item, exr.Stored) for item in hdr):      # exr_inflate="device": every OpenEXR file in one batch
+            which = [i for i, item in enumerate(hdr) if isinstance(item, (exr.Payload, exr.Stored))]
+            batched = dict(zip(which, exr.upload_batch([hdr[i] for i in which], self.device)))
         for i, (item, (h, w)) in enumerate(zip(hdr, shapes)):
             out = self.hdr_arena[3 * offsets[i]:3 * (offsets[i] + h * w)].view(h, w, 3)
-            if isinstance(item, exr.Payload):                      # HALF / FLOAT converted on the device, the file's values
-                planes, chunk_offsets = exr.upload(item, self.device)
+            if isinstance(item, (exr.Payload, exr.Stored)):        # HALF / FLOAT converted on the device, the file's values
+                planes, chunk_offsets = batched[i] if i in batched else exr.upload(item, self.device)
                 exr.load_resize(item, planes, chunk_offsets, out, "RGB", clip=False)
             elif item.dtype == np.uint8 and item.shape[2] == 4:    # RGBE bytes: decoded on the device (a same-size "resize" is an
                 tmp = torch.empty_like(out)                        # exact copy), BGR -> the records' RGB
