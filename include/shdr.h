@@ -698,6 +698,25 @@ int shdr_deflate_huffman_batch_sizes(const int64_t* offsets, int n_chunks, int p
 int shdr_deflate_huffman_batch(const uint8_t* data, const uint8_t* raw, const int64_t* offsets, const int64_t* offsets_dev,
                                int n_chunks, int pad, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, uint8_t* coded,
                                void* workspace, void* stream, float* stage_ms);
+/* zlib stream WITH LZ77 matches of src[0 .. n), 1 <= n <= 2^30 (host): 78 01, one final dynamic-Huffman block of literals,
+ * lengths and distances with a fixed-length header, the big-endian Adler-32 (csrc/deflate_lz.h states the parse: a chainless
+ * hash table read in groups of 64 positions, the run candidate p - 1, greedy).  zlib's inflate reads it.  Returns and the
+ * caller's coded-only-if-strictly-smaller rule as shdr_deflate_huffman_host; the call allocates 4 n bytes of scratch. */
+int64_t shdr_deflate_lz_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity);
+/* The parse of that stream (host): tokens[n], one per position -- 0 where an earlier match covers the position,
+ * SHDR_DEFLATE_LZ_LITERAL | byte for a literal, length << 16 | distance for a match (3..258, 1..32768). */
+#define SHDR_DEFLATE_LZ_LITERAL 0x80000000u
+int shdr_deflate_lz_parse_host(const uint8_t* src, int64_t n, uint32_t* tokens);
+/* The same encoder on the device for a BATCH of chunks: the arguments, the stored form, the status codes and the refusals of
+ * shdr_deflate_huffman_batch, with the streams of shdr_deflate_lz_host.  The workspace also holds one 4-byte token per input
+ * byte (workspace_bytes of this _sizes call).  Three stream-ordered launches (parse + counts + code lengths + Adler-32, one
+ * 64-lane wave per chunk; the scan; the write pass in tiles of SHDR_DEFLATE_LZ_TILE positions), no global atomics, no host
+ * wait, no allocation; stage_ms receives SHDR_DEFLATE_STAGES times. */
+#define SHDR_DEFLATE_LZ_TILE 1024
+int shdr_deflate_lz_batch_sizes(const int64_t* offsets, int n_chunks, int pad, int64_t* out_bytes, int64_t* workspace_bytes);
+int shdr_deflate_lz_batch(const uint8_t* data, const uint8_t* raw, const int64_t* offsets, const int64_t* offsets_dev,
+                          int n_chunks, int pad, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, uint8_t* coded,
+                          void* workspace, void* stream, float* stage_ms);
 
 /* float32 images [H][W][3] -> OpenEXR scanline bytes, for a BATCH of images of different sizes in one launch.  A chunk is `lines`
  * scanlines (1: NONE / ZIPS, 16: ZIP; the last chunk of an image may hold fewer); a scanline is W samples of B, then G, then R

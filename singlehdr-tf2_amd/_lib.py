@@ -58,6 +58,10 @@ SIGNATURES = {
     "shdr_deflate_huffman_lengths_host": (c_int, [c_ptr, c_i64, c_ptr]),
     "shdr_deflate_huffman_batch_sizes": (c_int, [c_ptr, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "shdr_deflate_huffman_batch": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "shdr_deflate_lz_host": (c_i64, [c_ptr, c_i64, c_ptr, c_i64]),
+    "shdr_deflate_lz_parse_host": (c_int, [c_ptr, c_i64, c_ptr]),
+    "shdr_deflate_lz_batch_sizes": (c_int, [c_ptr, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "shdr_deflate_lz_batch": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "shdr_inflate_host": (c_i64, [c_ptr, c_i64, c_ptr, c_i64, ctypes.POINTER(c_int)]),
     "shdr_inflate_batch_sizes": (c_int, [c_ptr, c_ptr, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "shdr_inflate_batch": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -2055,6 +2055,79 @@ def deflate_huffman(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offs
     return out, out_offsets, coded
 
 
+DEFLATE_LZ_TILE = 1024       # SHDR_DEFLATE_LZ_TILE: positions per tile of the device writer of deflate_lz
+DEFLATE_LZ_LITERAL = 0x80000000   # SHDR_DEFLATE_LZ_LITERAL
+
+
+def deflate_lz_host(chunk):
+    """zlib stream with LZ77 matches of a chunk of bytes (libshdr host routine, csrc/deflate_lz.h; zlib.decompress reads it).  The
+    stream is returned whatever its size: a chunk counts as coded only if len(stream) < len(chunk)"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(chunk), dtype=np.uint8)
+    out = np.empty(2 * src.size + 512, dtype=np.uint8)                    # 1354 + 16 bits per position at the very most
+    n = lib.shdr_deflate_lz_host(_hptr(src), src.size, _hptr(out), out.size)
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n].tobytes()
+
+
+def deflate_lz_parse_host(chunk):
+    """the parse behind deflate_lz_host's stream: a list of (position, length, distance), one per token in stream order; a literal
+    has length 1 and distance 0, a match 3..258 and 1..32768"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(chunk), dtype=np.uint8)
+    tokens = np.empty(max(src.size, 1), dtype=np.uint32)
+    rc = lib.shdr_deflate_lz_parse_host(_hptr(src), src.size, _hptr(tokens))
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    at = np.flatnonzero(tokens)
+    t = tokens[at].astype(np.int64)
+    lit = (t & DEFLATE_LZ_LITERAL) != 0
+    length = np.where(lit, 1, t >> 16)
+    dist = np.where(lit, 0, t & 0xFFFF)
+    return list(zip(at.tolist(), length.tolist(), dist.tolist()))
+
+
+def deflate_lz(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offsets_dev=None):
+    """zlib streams with LZ77 matches of a batch of chunks, coded on the device (csrc/deflate_lz.hip): byte for byte what the host
+    routine shdr_deflate_lz_host writes.  Arguments and the returned (bytes, out_offsets, coded) as deflate_huffman; the workspace
+    holds 4 bytes per input byte for the parse's tokens.  stage_ms: the device times of the parse, scan and write launches."""
+    lib = _lib.load()
+    data = _chk(data, "data", torch.uint8)
+    if isinstance(offsets, torch.Tensor):
+        off_host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
+        off_dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
+    else:
+        off_host, off_dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
+        if off_dev is not None and _chk(off_dev, "offsets_dev", torch.int64).numel() != off_host.size:
+            raise ValueError("deflate_lz: offsets_dev is not a copy of offsets")
+    if data.dim() != 1 or off_host.ndim != 1 or off_host.size < 2 or int(off_host[-1]) > data.numel():
+        raise ValueError("deflate_lz: expected data [size] and offsets [n_chunks + 1] that end within it")
+    if raw is not None:
+        raw = _chk(raw, "raw", torch.uint8)
+        if raw.dim() != 1 or raw.numel() < int(off_host[-1]):
+            raise ValueError("deflate_lz: raw must hold the chunks' bytes too")
+    n = off_host.size - 1
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_deflate_lz_batch_sizes(_hptr(off_host), n, int(pad), ctypes.byref(out_b), ctypes.byref(ws_b)),
+               "shdr_deflate_lz_batch_sizes")
+    dev = data.device
+    if off_dev is None:
+        off_dev = torch.from_numpy(off_host).to(dev)
+    front = int(front)
+    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
+    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    coded = torch.empty(n, device=dev, dtype=torch.uint8)
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    ms = (ctypes.c_float * 3)() if stage_ms is not None else None
+    _lib.check(lib.shdr_deflate_lz_batch(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n,
+                                         int(pad), out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws),
+                                         _stream(), ms), "shdr_deflate_lz_batch")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return out, out_offsets, coded
+
+
 # ---------------------------------------------------------------------------
 # zlib streams inflated (exr.py read_stored / upload_batch), see csrc/inflate.h and csrc/inflate.hip
 # ---------------------------------------------------------------------------

@@ -50,6 +50,7 @@ SOURCES = {
     "exr.hip": ["-ffp-contract=off"],
     "exr_write.hip": ["-ffp-contract=off"],
     "deflate.hip": [],
+    "deflate_lz.hip": [],
     "inflate.hip": [],
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
@@ -76,6 +77,7 @@ def build(force=False, verbose=True):
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
+               os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
                os.path.join(CSRC, "inflate.h"),
                os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []

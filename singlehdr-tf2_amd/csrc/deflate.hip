@@ -5,7 +5,8 @@
 //   1  deflate_stats_kernel  one block per chunk: byte histogram in LDS (one per wave), Adler-32 as two block reductions, then ONE lane
 //                            runs build_lengths on the 257 counts; stores the lengths, the block's size in bits, the checksum and the
 //                            stored size of the chunk: its stream if that is strictly smaller than the chunk, else the chunk itself
-//   2  deflate_scan_kernel   exclusive int64 scan of the stored sizes (+ `pad` bytes in front of each) -> out_offsets   (1 block)
+//   2  deflate_scan_kernel   exclusive int64 scan of the stored sizes (+ `pad` bytes in front of each) -> out_offsets   (1 block;
+//                            deflate_batch.h, shared with deflate_lz.hip)
 //   3  deflate_write_kernel  one block per chunk: the header, then tiles of kTile symbols: a block prefix sum of the code lengths
 //                            gives every symbol its bit, the codes are OR-ed into LDS words and the whole bytes of the tile are
 //                            stored; the partial byte and the bit position carry to the next tile; then the tail and the Adler-32.
@@ -14,10 +15,12 @@
 // most 2^22 bytes (a 2^30-byte chunk over 256 threads) into 64 bits, so nothing overflows at any size.
 #include "shdr_internal.h"
 #include "deflate_huffman.h"
+#include "deflate_batch.h"
 
 namespace {
 
 using namespace shdr_deflate;
+using namespace shdr_deflate_batch;
 
 constexpr int kThreads = 256;
 constexpr int kPerThread = 4;
@@ -25,9 +28,6 @@ constexpr int kTile = kThreads * kPerThread;                   // symbols per ti
 constexpr int kTileWords = (7 + kTile * kMaxBits) / 32 + 3;      // carried bits + the tile's bits, and the word a shifted code spills into
 constexpr int kLenStride = 272;                                  // bytes per chunk of the stored code lengths
 static_assert(kTile == SHDR_DEFLATE_TILE, "shdr.h names the tile size");
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct Workspace {                                               // carved out of the caller's workspace, every part 16-byte aligned
   uint8_t* lens;                                                 // [C][kLenStride]
@@ -46,16 +46,6 @@ inline Workspace carve(void* ws, int64_t c) {
   w.adler = reinterpret_cast<uint32_t*>(p + o); o += align16(4 * c);
   w.bytes = o;
   return w;
-}
-
-// chunk c of the batch, clamped into the data: [lo, lo + n)
-__device__ __forceinline__ void chunk_range(const int64_t* __restrict__ offsets, int64_t c, int64_t total, int64_t& lo, int64_t& n) {
-  int64_t a = offsets[c], b = offsets[c + 1];
-  a = a < 0 ? 0 : a > total ? total : a;
-  b = b < a ? a : b > total ? total : b;
-  if (b - a > kMaxChunk) b = a + kMaxChunk;
-  lo = a;
-  n = b - a;
 }
 
 __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* part) {
@@ -105,34 +95,6 @@ __global__ __launch_bounds__(kThreads) void deflate_stats_kernel(const uint8_t* 
   }
   __syncthreads();
   for (int s = tid; s < kLenStride; s += kThreads) lens[c * kLenStride + s] = s < kSyms ? len[s] : 0;
-}
-
-// out_offsets[c] = sum of the sizes before c, out_offsets[C] = the total.  One block.
-__global__ __launch_bounds__(1024) void deflate_scan_kernel(const int64_t* __restrict__ sizes, int64_t count, int64_t* __restrict__ out_offsets) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < count; base += 1024) {
-    const int64_t r = base + threadIdx.x;
-    const int64_t v = r < count ? sizes[r] : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int64_t before = carry_s;
-    for (int w = 0; w < wave; ++w) before += part[w];
-    if (r < count) out_offsets[r] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out_offsets[count] = carry_s;
 }
 
 __global__ __launch_bounds__(kThreads) void deflate_write_kernel(const uint8_t* __restrict__ data, const uint8_t* __restrict__ raw,
@@ -223,20 +185,6 @@ __global__ __launch_bounds__(kThreads) void deflate_write_kernel(const uint8_t* 
       dst[o] = (uint8_t)(a >> 24); dst[o + 1] = (uint8_t)(a >> 16); dst[o + 2] = (uint8_t)(a >> 8); dst[o + 3] = (uint8_t)a;
     }
   }
-}
-
-int check_offsets(const char* what, const int64_t* offsets, int n_chunks, int pad, int64_t* total, int64_t* bound) {
-  SHDR_REQUIRE(offsets, SHDR_E_NULL, "%s: null offsets", what);
-  SHDR_REQUIRE(n_chunks > 0, SHDR_E_SHAPE, "%s: the number of chunks must be positive, got %d", what, n_chunks);
-  SHDR_REQUIRE(pad >= 0 && pad <= 4096, SHDR_E_SHAPE, "%s: pad must be in [0, 4096], got %d", what, pad);
-  SHDR_REQUIRE(offsets[0] == 0, SHDR_E_SHAPE, "%s: offsets[0] must be 0", what);
-  for (int c = 0; c < n_chunks; ++c) {
-    const int64_t n = offsets[c + 1] - offsets[c];
-    SHDR_REQUIRE(n >= 1 && n <= kMaxChunk, SHDR_E_SHAPE, "%s: chunk %d has %lld bytes (1 .. 2^30 are supported)", what, c, (long long)n);
-  }
-  *total = offsets[n_chunks];
-  *bound = offsets[n_chunks] + (int64_t)pad * n_chunks;          // a stored chunk is never larger than the chunk
-  return SHDR_OK;
 }
 
 }  // namespace

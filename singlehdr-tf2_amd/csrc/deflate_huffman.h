@@ -23,20 +23,25 @@ constexpr int kHeaderBytes = 141;             // bytes that hold bits 0..1121; t
 constexpr int64_t kMaxChunk = (int64_t)1 << 30;
 constexpr uint32_t kAdlerMod = 65521;
 
-struct HuffWork {                             // scratch of build_lengths: LDS on the device, the stack on the host
-  uint32_t w[2 * kSyms];                      // weights: sorted leaves 0..n-1, then the internal nodes in the order they are made
-  uint16_t sym[kSyms];
-  uint16_t parent[2 * kSyms];
-  uint16_t depth[2 * kSyms];
+template <int N>
+struct HuffWorkT {                            // scratch of build_lengths over N symbols: LDS on the device, the stack on the host
+  uint32_t w[2 * N];                          // weights: sorted leaves 0..n-1, then the internal nodes in the order they are made
+  uint16_t sym[N];
+  uint16_t parent[2 * N];
+  uint16_t depth[2 * N];
 };
+using HuffWork = HuffWorkT<kSyms>;
 
 // Code lengths of the symbols with freq != 0 (0 for the others): Huffman's algorithm on the used symbols, ties broken by
 // (weight, symbol) and leaves before internal nodes; while the deepest leaf lies below 15 the weights are halved (rounded up, so
 // none reaches 0) and the tree is rebuilt.  A Huffman tree is full, so the lengths are complete (Kraft sum 1) whenever two or more
-// symbols occur; equal weights end at depth <= 9, so the loop ends.  One symbol alone gets length 1.
-SHDR_HD inline void build_lengths(const uint32_t* freq, uint8_t* len, HuffWork& k) {
+// symbols occur; equal weights end at depth <= 9, so the loop ends.  One symbol alone gets length 1.  The alphabet's size is a
+// template argument (deflate_lz.h codes 286 literal/length and 30 distance symbols by the same rule); the sort's result does not
+// depend on its gaps, since (weight, symbol) is a total order.
+template <int N>
+SHDR_HD inline void build_lengths_n(const uint32_t* freq, uint8_t* len, HuffWorkT<N>& k) {
   int n = 0;
-  for (int s = 0; s < kSyms; ++s) {
+  for (int s = 0; s < N; ++s) {
     len[s] = 0;
     if (freq[s]) {
       k.sym[n] = (uint16_t)s;
@@ -90,13 +95,15 @@ SHDR_HD inline void build_lengths(const uint32_t* freq, uint8_t* len, HuffWork& 
   }
   for (int i = 0; i < n; ++i) len[k.sym[i]] = (uint8_t)k.depth[i];
 }
+SHDR_HD inline void build_lengths(const uint32_t* freq, uint8_t* len, HuffWork& k) { build_lengths_n<kSyms>(freq, len, k); }
 
 // Canonical codes of RFC 1951 section 3.2.2, bit-reversed: a stream takes Huffman codes from their most significant bit, and the
 // writers put bit 0 of a value first.
-SHDR_HD inline void build_codes(const uint8_t* len, uint16_t* code) {
+template <int N>
+SHDR_HD inline void build_codes_n(const uint8_t* len, uint16_t* code) {
   uint16_t count[kMaxBits + 1], next[kMaxBits + 1];
   for (int b = 0; b <= kMaxBits; ++b) count[b] = 0;
-  for (int s = 0; s < kSyms; ++s) ++count[len[s]];
+  for (int s = 0; s < N; ++s) ++count[len[s]];
   count[0] = 0;
   uint32_t c = 0;
   next[0] = 0;
@@ -104,7 +111,7 @@ SHDR_HD inline void build_codes(const uint8_t* len, uint16_t* code) {
     c = (c + count[b - 1]) << 1;
     next[b] = (uint16_t)c;
   }
-  for (int s = 0; s < kSyms; ++s) {
+  for (int s = 0; s < N; ++s) {
     const int l = len[s];
     uint32_t v = 0;
     if (l) {
@@ -114,6 +121,7 @@ SHDR_HD inline void build_codes(const uint8_t* len, uint16_t* code) {
     code[s] = (uint16_t)v;
   }
 }
+SHDR_HD inline void build_codes(const uint8_t* len, uint16_t* code) { build_codes_n<kSyms>(len, code); }
 
 // values go into the stream from their bit 0, bytes fill from their bit 0
 struct BitPut {

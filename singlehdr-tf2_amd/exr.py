@@ -32,7 +32,8 @@ Writing (encode_exr / write_exr) mirrors that split.  The device converts float3
 scanlines (B, G, R) and applies the interleave and the delta predictor, all chunks of a batch of images in one launch
 (K.exr_pack, csrc/exr_write.hip).  With encoder="host" the predicted bytes come back and zlib.compress deflates every chunk in a
 bounded thread pool (full deflate, the better ratio); with encoder="device" a Huffman-only zlib encoder codes them on the device
-(K.deflate_huffman, csrc/deflate.hip), a last kernel writes the chunk headers and the offset tables, and everything that follows
+(K.deflate_huffman, csrc/deflate.hip), with encoder="device_lz" one that also finds LZ77 matches (K.deflate_lz, csrc/deflate_lz.hip:
+smaller files than "device", larger than "host"); a last kernel writes the chunk headers and the offset tables, and everything that follows
 the file headers comes back in one copy.  Either way a chunk that does not get strictly smaller is stored raw.  Files are
 single-part scanline, channels B, G, R of one type, data window (0, 0) - (W - 1, H - 1), INCREASING_Y, NONE / ZIPS / ZIP.
 """
@@ -445,8 +446,8 @@ def _write_options(what, pixel_type, compression, encoder):
     if compression not in WRITE_COMPRESSIONS:
         raise ValueError("%s: %s compression is not supported ('none', 'zips' and 'zip' are)" % (
             what, compression.upper() if isinstance(compression, str) else repr(compression)))
-    if encoder not in ("host", "device"):
-        raise ValueError("%s: encoder must be 'host' or 'device', got %r" % (what, encoder))
+    if encoder not in ("host", "device", "device_lz"):
+        raise ValueError("%s: encoder must be 'host', 'device' or 'device_lz', got %r" % (what, encoder))
     return PIXEL_TYPES[pixel_type], WRITE_COMPRESSIONS[compression]
 
 
@@ -479,16 +480,19 @@ def encode_exr(images, pixel_type="half", compression="zip", encoder="host", sat
     saturate: finite values beyond +-65504 become +-65504 instead of inf) or "float"; compression "none", "zips" or "zip";
     reverse_channels: channel 0 is blue (HdrReconstructor.reconstruct_device's order).  encoder: who deflates ZIP / ZIPS chunks --
     "host": zlib.compress per chunk in a thread pool; "device": the Huffman-only encoder of csrc/deflate.hip (larger files, no host
-    deflate, one copy of the finished bytes).  The whole batch is packed, predicted and (device) coded in one call each."""
+    deflate, one copy of the finished bytes); "device_lz": the same route with the LZ77 encoder of csrc/deflate_lz.hip (matches
+    from a chainless hash table and runs: files between the two).  The whole batch is packed, predicted and (device) coded in one
+    call each."""
     ptype, comp = _write_options("encode_exr", pixel_type, compression, encoder)
     lines = LINES_PER_CHUNK[comp]
     packed = K.exr_pack(_on_device(images, "encode_exr"), ptype, lines, reverse_channels, saturate, predict=comp != NO_COMPRESSION)
     headers = [file_header(int(h), int(w), ptype, comp) for h, w in packed.shapes]
     first, chunk_off = packed.table[0], packed.chunk_off
     n_chunks = chunk_off.size - 1
-    if comp != NO_COMPRESSION and encoder == "device":
-        out, out_offsets, _ = K.deflate_huffman(packed.predicted, chunk_off, raw=packed.planar, pad=8, front=8 * n_chunks,
-                                                offsets_dev=packed.chunk_off_dev)
+    if comp != NO_COMPRESSION and encoder != "host":
+        deflate = K.deflate_lz if encoder == "device_lz" else K.deflate_huffman
+        out, out_offsets, _ = deflate(packed.predicted, chunk_off, raw=packed.planar, pad=8, front=8 * n_chunks,
+                                      offsets_dev=packed.chunk_off_dev)
         K.exr_finish_chunks(out, out_offsets, packed, [len(h) for h in headers])
         off = out_offsets.cpu().numpy()
         blob = memoryview(out[:8 * n_chunks + int(off[-1])].cpu().numpy())          # sliced without copies, joined once per file

@@ -67,9 +67,12 @@ def rle_encode_device(rgbe):
     return [blob[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
 
 
-def _check_encoder(encoder, what):
-    if encoder not in ("host", "device"):
-        raise ValueError("%s: encoder must be 'host' or 'device', got %r" % (what, encoder))
+def _check_encoder(encoder, what, output_format="hdr"):
+    """"device_lz" (the device deflate encoder with LZ77 matches, exr.encode_exr) exists for OpenEXR output only"""
+    if encoder not in ("host", "device", "device_lz"):
+        raise ValueError("%s: encoder must be 'host', 'device' or 'device_lz', got %r" % (what, encoder))
+    if encoder == "device_lz" and output_format == "hdr":
+        raise ValueError("%s: encoder 'device_lz' is for OpenEXR output (output_format='exr'); Radiance files take 'host' or 'device'" % what)
 
 
 def _check_format(output_format, what):
@@ -225,8 +228,8 @@ class HdrReconstructor:
         the coded bytes (write_hdr: the same file).
         output_format: "hdr" writes a Radiance file; "exr" writes the float estimate as OpenEXR without the RGBE conversion
         (exr.encode_exr with `exr_options`, a dict of its keyword arguments such as pixel_type or compression; `encoder` then says
-        who deflates)"""
-        _check_encoder(encoder, "reconstruct_file")
+        who deflates, and "device_lz", the device encoder with LZ77 matches, is a third choice that only this format has)"""
+        _check_encoder(encoder, "reconstruct_file", output_format)
         _check_format(output_format, "reconstruct_file")
         y = self._read_device(ldr_path, decoder, "reconstruct_file")
         if output_format == "exr":
@@ -243,7 +246,7 @@ class HdrReconstructor:
         encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
         4 B per pixel.  output_format="exr": the float estimates of the whole list go through ONE exr.encode_exr call, whatever the
         encoder"""
-        _check_encoder(encoder, "reconstruct_files")
+        _check_encoder(encoder, "reconstruct_files", output_format)
         _check_format(output_format, "reconstruct_files")
         ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
         if len(ldr_paths) != len(hdr_paths):
@@ -273,19 +276,19 @@ class HdrReconstructor:
         """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder, encoder: as reconstruct_file;
         with encoder="device" the files go through reconstruct_files in groups of `group`.  output_format="exr" names the outputs
         *.exr"""
-        _check_encoder(encoder, "reconstruct_dir")
+        _check_encoder(encoder, "reconstruct_dir", output_format)
         _check_format(output_format, "reconstruct_dir")
         fmt = dict(output_format=output_format, exr_options=exr_options)
         os.makedirs(output_dir, exist_ok=True)
         written = []
         paths = sorted(glob.glob(os.path.join(dataset_dir, pattern)))
-        step = max(int(group), 1) if encoder == "device" else 1
+        step = max(int(group), 1) if encoder != "host" else 1
         for i in range(0, len(paths), step):
             start = time.perf_counter()
             part = paths[i:i + step]
             outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + "." + output_format) for path in part]        # :148-149
-            if encoder == "device":
-                self.reconstruct_files(part, outs, decoder=decoder, encoder="device", **fmt)
+            if encoder != "host":
+                self.reconstruct_files(part, outs, decoder=decoder, encoder=encoder, **fmt)
             else:
                 self.reconstruct_file(part[0], outs[0], decoder=decoder, **fmt)
             written.extend(outs)

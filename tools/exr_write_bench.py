@@ -1,14 +1,16 @@
 """OpenEXR output: float HDR images on the device -> finished HALF / ZIP files on the host, with the chunks deflated by the host
-(zlib in a thread pool) and by the device (the Huffman-only encoder of csrc/deflate.hip), measured, not gated.
+(zlib in a thread pool) and by the device (the Huffman-only encoder of csrc/deflate.hip and the LZ77 encoder of csrc/deflate_lz.hip),
+measured, not gated.
 
     python tools/exr_write_bench.py [--out result.json]
 
 Inputs, made on the device: 16 x 512 x 512, 1 x 512 x 512 and 1 x 4096 x 3072 float images, a ramp with 2 % noise and a smooth variant
-of each.  One process, alternating windows (host route, device route, host, ...), the median of 5 windows each, wall time from a
-synchronised start to the files' bytes on the host:
-  host route    K.exr_pack -> copy of the predicted bytes -> zlib.compress per chunk (16 threads) -> assembly
-  device route  K.exr_pack -> K.deflate_huffman (three launches) -> K.exr_finish_chunks -> copy of the offsets and of the finished bytes
-and the parts of both, each from a synchronised start, plus the device-event times of the encoder's three launches.  Both routes'
+of each.  One process, alternating windows (host route, device route, device_lz route, host, ...), the median of 5 windows each, wall
+time from a synchronised start to the files' bytes on the host:
+  host route       K.exr_pack -> copy of the predicted bytes -> zlib.compress per chunk (16 threads) -> assembly
+  device route     K.exr_pack -> K.deflate_huffman (three launches) -> K.exr_finish_chunks -> copy of the offsets and of the finished bytes
+  device_lz route  the same with K.deflate_lz (three launches: parse, scan, write)
+and the parts of all, each from a synchronised start, plus the device-event times of both encoders' three launches.  All routes'
 files are read back with exr.read_exr and compared with the HALF-rounded input before anything is timed."""
 import argparse
 import concurrent.futures
@@ -30,6 +32,7 @@ K, exr = shdr._ops, shdr.exr
 
 WINDOWS = 5
 STAGES = ("stats", "scan", "write")
+LZ_STAGES = ("parse", "scan", "write")
 
 
 def content(n, h, w, noise, seed):
@@ -66,15 +69,20 @@ def measure(x):
     n, h, w, _ = x.shape
     host_files = exr.encode_exr(x, "half", "zip", "host")               # warm-up, and the bench measures encoders that are right
     dev_files = exr.encode_exr(x, "half", "zip", "device")
+    lz_files = exr.encode_exr(x, "half", "zip", "device_lz")
     check(x, host_files)
     check(x, dev_files)
+    check(x, lz_files)
     raw = 6 * n * h * w
-    host, dev = [], []
-    parts = {k: [] for k in ("pack", "predicted_copy", "host_deflate", "device_deflate", "finish", "finished_copy")}
+    host, dev, lz = [], [], []
+    parts = {k: [] for k in ("pack", "predicted_copy", "host_deflate", "device_deflate", "device_lz_deflate", "finish", "finished_copy",
+                             "lz_finished_copy")}
     stages = {k: [] for k in STAGES}
+    lz_stages = {k: [] for k in LZ_STAGES}
     for _ in range(WINDOWS):
         host.append(wall(lambda: exr.encode_exr(x, "half", "zip", "host")))
         dev.append(wall(lambda: exr.encode_exr(x, "half", "zip", "device")))
+        lz.append(wall(lambda: exr.encode_exr(x, "half", "zip", "device_lz")))
         box = {}
         parts["pack"].append(wall(lambda: box.__setitem__("p", K.exr_pack(x, K.EXR_HALF, 16))))
         p = box["p"]
@@ -94,11 +102,21 @@ def measure(x):
         K.deflate_huffman(p.predicted, p.chunk_off, stage_ms=ms, **kw)
         for k, v in zip(STAGES, ms):
             stages[k].append(v)
+        parts["device_lz_deflate"].append(wall(lambda: box.__setitem__("lz", K.deflate_lz(p.predicted, p.chunk_off, **kw))))
+        lz_out, lz_off, _ = box["lz"]
+        K.exr_finish_chunks(lz_out, lz_off, p, [300] * n)
+        parts["lz_finished_copy"].append(wall(lambda: lz_out[:8 * n_chunks + int(lz_off.cpu()[-1])].cpu()))
+        ms = []
+        K.deflate_lz(p.predicted, p.chunk_off, stage_ms=ms, **kw)
+        for k, v in zip(LZ_STAGES, ms):
+            lz_stages[k].append(v)
     med = statistics.median
     return {"images": n, "height": h, "width": w, "raw_bytes": raw, "chunks": n_chunks,
             "host_coded_over_raw": sum(len(f) for f in host_files) / raw, "device_coded_over_raw": sum(len(f) for f in dev_files) / raw,
-            "host_route_ms": med(host), "device_route_ms": med(dev), "parts_ms": {k: med(v) for k, v in parts.items()},
-            "stage_event_ms": {k: med(v) for k, v in stages.items()}}
+            "device_lz_coded_over_raw": sum(len(f) for f in lz_files) / raw,
+            "host_route_ms": med(host), "device_route_ms": med(dev), "device_lz_route_ms": med(lz),
+            "parts_ms": {k: med(v) for k, v in parts.items()}, "stage_event_ms": {k: med(v) for k, v in stages.items()},
+            "lz_stage_event_ms": {k: med(v) for k, v in lz_stages.items()}}
 
 
 def main():
