@@ -210,11 +210,17 @@ int shdr_conv2d_fwd_up2_lowres_f32(const shdr_conv2d_desc* d, const float* x, co
  * batch 16): a block computes the nine tap planes on a low-res tile with its one-pixel halo and folds them in registers, so neither the
  * planes nor -- with a projected output -- the 64-channel result reach memory.  Descriptor, prepared filter (the _lowres_ one: same
  * packed taps, same scale) and arithmetic are those of shdr_conv2d_fwd_up2_lowres_f32: y is bit-identical to it, range slot included.
- * _ok: 1 if the layer is taken -- as _lowres_ok without the fill threshold, and Cout == 64, 64 <= Cin <= 128; 0 under SHDR_NO_UP2_FUSED=1.
- * _fwd: writes y [N,H,W,64], the projected output y_proj [N,H,W,3] = sum_c proj[j][c] y[c] (proj [3][64], as in
+ * The narrow forms (the `up` blocks of the Dequantization-Net: 32 and 16 output channels) are the same kernel with Cout / 16 waves per
+ * low-res patch, so a block of four waves finishes two or four patches; their prepared filter is the same pack of the [Cin, 9 Cout]
+ * matrix padded to whole 64-column slices.  They write y only.
+ * _ok: 1 if the layer is taken -- as _lowres_ok without the fill threshold, and Cout == 64 with 64 <= Cin <= 128, Cout == 32 with
+ *      32 <= Cin <= 128, or Cout == 16 with Cin 32 or 64 (Cout < 64: not under SHDR_NO_UP2_NARROW=1); 0 under SHDR_NO_UP2_FUSED=1.
+ * _narrow_enabled: 0 under SHDR_NO_UP2_NARROW=1, the A/B arm of the narrow forms and of the Dequantization-Net's use of the low-res forms.
+ * _fwd: writes y [N,H,W,Cout], at 64 couts the projected output y_proj [N,H,W,3] = sum_c proj[j][c] y[c] (proj [3][64], as in
  *      shdr_conv2d_fwd_prepared_projected_f32), or both (y_proj with proj; at least one output).  x_range: the input's range slot
  *      (required); y_range (or NULL): receives max |y| when y is written. */
 int shdr_conv2d_up2_fused_ok_f32(const shdr_conv2d_desc* d);
+int shdr_conv2d_up2_narrow_enabled(void);
 int64_t shdr_conv2d_up2_fused_filter_elems_f32(const shdr_conv2d_desc* d);
 int shdr_conv2d_up2_fused_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream);
 int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const float* x, const float* prepared, const float* bias,

@@ -116,6 +116,7 @@ SIGNATURES = {
     "shdr_conv2d_up2_lowres_workspace_bytes_f32": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "shdr_conv2d_fwd_up2_lowres_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 10),
     "shdr_conv2d_up2_fused_ok_f32": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "shdr_conv2d_up2_narrow_enabled": (c_int, []),
     "shdr_conv2d_up2_fused_filter_elems_f32": (c_i64, [ctypes.POINTER(ConvDesc)]),
     "shdr_conv2d_up2_fused_prepare_filter_f32": (c_int, [ctypes.POINTER(ConvDesc), c_ptr, c_ptr, c_ptr]),
     "shdr_conv2d_fwd_up2_fused_f32": (c_int, [ctypes.POINTER(ConvDesc)] + [c_ptr] * 11),

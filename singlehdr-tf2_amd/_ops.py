@@ -263,7 +263,7 @@ def conv2d(x, w, bias=None, stride=1, x2=None, x2_scale=1.0, act1=ACT_NONE, scal
                        w_batch_stride, None)
 
 
-def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_NONE, proj=None, lowres=False):
+def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_NONE, proj=None, lowres=False, one_launch=False):
     """Conv2D(SAME, stride 1)(tf.image.resize(x, 2x, BILINEAR)) with the conv2d epilogue -- the `up` blocks of
     hallucination_net.py:86-88 and dequantization_net.py:25-27.  Without a gradient tape the library fuses the resize into the
     convolution where the plan allows it (desc.prologue, csrc/conv_plan.hip); under a tape, and in the reduced-precision operand
@@ -273,7 +273,10 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
     lowres=True: the caller accepts the form that mixes the channels at LOW resolution (csrc/up2_lowres.hip: a 1x1 GEMM Cin -> 9 Cout on
     x, then a stencil pass; the accuracy class of the split-operand kernels, not the bits of the default form) where the library takes the
     layer (shdr_conv2d_up2_lowres_ok_f32); elsewhere, and with the default, this is the call below.  With proj it is the one-launch
-    form of the same arithmetic (csrc/up2_fused.hip, shdr_conv2d_up2_fused_ok_f32), which writes the projected output alone."""
+    form of the same arithmetic (csrc/up2_fused.hip, shdr_conv2d_up2_fused_ok_f32), which writes the projected output alone.
+    one_launch=True (with lowres=True, without proj): the one-launch form comes first where its predicate takes the layer (16, 32 or 64
+    couts, at most 128 input channels: the `up` blocks of the Dequantization-Net), then the two-launch form; not under
+    SHDR_NO_UP2_NARROW=1."""
     if lowres and proj is not None and not _is_h(x) and _AUTO_ALGO[PRECISION] == ALGO_AUTO and WINOGRAD and not EXACT_FP32 \
             and not _needs_grad(x, w, bias, scale, shift):
         yj = _conv2d_up2_fused(x, w, bias, act1, scale, shift, act2, proj)
@@ -281,6 +284,10 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
             return yj
     if lowres and proj is None and not _is_h(x) and _AUTO_ALGO[PRECISION] == ALGO_AUTO and WINOGRAD and not EXACT_FP32 \
             and not _needs_grad(x, w, bias, scale, shift):
+        if one_launch and up2_narrow_enabled():
+            y = _conv2d_up2_fused(x, w, bias, act1, scale, shift, act2)
+            if y is not None:
+                return y
         y = _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2)
         if y is not None:
             return y
@@ -291,6 +298,12 @@ def conv2d_up2(x, w, bias=None, act1=ACT_NONE, scale=None, shift=None, act2=ACT_
         return conv2d(resize2x(x), w, bias, act1=act1, scale=scale, shift=shift, act2=act2)
     return _conv2d_raw(x, w, bias, 1, None, 1.0, act1, scale, shift, None, act2, algo, None, None, None, None, 0, None,
                        prologue=PROLOGUE_BILINEAR2X, proj=proj)
+
+
+def up2_narrow_enabled():
+    """False under SHDR_NO_UP2_NARROW=1: the A/B arm in which the `up` blocks of the Dequantization-Net stay on the bilinear-prologue
+    kernels (the library reads the switch: shdr_conv2d_up2_narrow_enabled)"""
+    return bool(_lib.load().shdr_conv2d_up2_narrow_enabled())
 
 
 def _up2_layer(form, x, w, bias, act1, scale, shift, act2):
@@ -356,6 +369,8 @@ def _conv2d_up2_lowres(x, w, bias, act1, scale, shift, act2):
 def _conv2d_up2_fused(x, w, bias, act1, scale, shift, act2, proj=None, want_y=None):
     """conv2d_up2 through shdr_conv2d_fwd_up2_fused_f32, or None where the library does not take the layer: the projected output
     [N, 2h, 2w, 3] for proj [3, 64], y (the bits of _conv2d_up2_lowres) without one, (y_proj, y) with want_y=True.  Plumbing only."""
+    if proj is not None and _d(w).shape[-1] != 64:                    # the projected output is the 64-cout form's
+        return None
     layer = _up2_layer("fused", x, w, bias, act1, scale, shift, act2)
     if layer is None:
         return None

@@ -1,4 +1,4 @@
-// Conv2D 3x3 (SAME, stride 1) of tf.image.resize(x, 2x, BILINEAR) for 64 output channels in ONE launch: the low-res channel mix of
+// Conv2D 3x3 (SAME, stride 1) of tf.image.resize(x, 2x, BILINEAR) for 64, 32 or 16 output channels in ONE launch: the low-res channel mix of
 // up2_lowres.hip (z_t = x W[t] for the nine taps) and its stencil pass fused, so that the tap planes z -- 2.7 GB for the Hallucination-Net's
 // u1 at batch 16, written and read back by the two-launch form -- never leave the CU, and with a projected output neither does the
 // 64-channel result.
@@ -19,6 +19,9 @@
 // per accumulator the chunks in order and per chunk wh xh, (wh 2^-11) xl, wl xh, then 2^-S 2^-T), the folds are the explicit multiply / FMA
 // sequences of up2_lowres_stencil_kernel with its border rules, the epilogue is its `finish`: y is bit-identical to
 // shdr_conv2d_fwd_up2_lowres_f32.  A/B switch SHDR_NO_UP2_FUSED=1.
+// The text above is the 64-cout form (CW = 4).  With 32 or 16 couts (the `up` blocks of the Dequantization-Net; A/B switch
+// SHDR_NO_UP2_NARROW=1) a patch takes CW = 2 or 1 waves, each doing exactly the work above for its 16 couts, and the four waves of a block
+// finish 2 or 4 patches, each with its own pair of images in LDS.
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
@@ -38,8 +41,11 @@ constexpr int UF_IMG_HALVES = 64 * 32, UF_UNIT_HALVES = 2 * UF_IMG_HALVES;      
 constexpr int UF_R = 8;                                         // patch rows: interior 6 x 14 of a 8 x 16 patch
 constexpr int UF_COLS = 14;                                     // interior columns of the 16 lanes
 constexpr int UF_MAX_CIN = 128;
-constexpr int UF_STRIDE = UF_MAX_CIN + 8;                       // halves per patch pixel: 16 bytes of padding spread the pixels over the banks
 constexpr int UF_THREADS = 256;
+// halves per patch pixel of an instantiation that holds up to CMAX input channels: 16 bytes of padding spread the pixels over the banks;
+// none at 32 channels, where four patches with it would be 80 KB + the static range words, past two blocks per CU (reads 2-way, 1/4 of
+// the MFMA time of a patch row)
+constexpr int uf_stride(int CMAX) { return CMAX == 32 ? 32 : CMAX + 8; }
 
 struct UpFusedArgs {
   const float* x;          // [N, h, w, C1] low-res
@@ -54,6 +60,7 @@ struct UpFusedArgs {
   const unsigned* xr;      // the input's range slot
   unsigned* yr;            // the output's, or null
   int N, h, w, C1, nty, ntx, act1, act2;
+  int npatch;              // N nty ntx
 };
 
 // conv_x3.hip's x3_range_scale for one source: 2^T brings the bound into [2^10, 2^11); 1 for an empty, zero or non-finite bound
@@ -124,15 +131,27 @@ __device__ __forceinline__ int uf_xcd_remap(int bid, int nwg) {      // conv_x3.
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-template <int R>
+// CW = Cout / 16 waves finish one patch (wave cw of them the couts 16 cw .. 16 cw + 15), so the four waves of a block finish PPB = 4 / CW
+// patches, each with its own pair of images in LDS; a patch past the end of the grid leaves its waves idle (they still reach every barrier).
+// CMAX: the most input channels the images hold.  Per wave the work is that of CW = 4 whatever CW is.
+template <int R, int CW, int CMAX>
 __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedArgs a) {
+  constexpr int UF_STRIDE = uf_stride(CMAX);
+  constexpr int COUT = 16 * CW, PPB = 4 / CW, GT = 64 * CW;      // couts; patches per block; threads per patch
   constexpr int NPIX = 16 * R, IMG = NPIX * UF_STRIDE;           // halves of one fp16 image of the patch
   constexpr int RO = R - 2;                                      // interior rows
-  extern __shared__ __attribute__((aligned(16))) _Float16 fsm[];  // [h, l][NPIX][UF_STRIDE]; behind the GEMM: the waves' projected partial sums
+  extern __shared__ __attribute__((aligned(16))) _Float16 fsm_all[];      // [patch][h, l][NPIX][UF_STRIDE]; behind the GEMM: the waves' projected partial sums
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int cw = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int L = uf_xcd_remap(blockIdx.x, gridDim.x);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ps = PPB == 1 ? 0 : wave / CW;                       // the wave's patch of the block
+  const int cw = PPB == 1 ? wave : wave % CW;
+  const int tid = PPB == 1 ? threadIdx.x : threadIdx.x & (GT - 1);        // among the threads of the patch
+  _Float16* const fsm = fsm_all + ps * (2 * IMG);
+  const float* const projp = CW == 4 ? a.proj : nullptr;         // the projection is the 64-cout form's
+  int L = uf_xcd_remap(blockIdx.x, gridDim.x) * PPB + ps;
+  const bool patch_ok = PPB == 1 || L < a.npatch;                // wave-uniform
+  if (!patch_ok) L = 0;
   const int tx_ = L % a.ntx; L /= a.ntx;
   const int ty_ = L % a.nty;
   const int n = L / a.nty;
@@ -146,12 +165,12 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
     const float* xb = a.x + (size_t)n * a.h * a.w * a.C1;
     uf_range_scale(a.xr, xs, ixs);
 #pragma unroll 1
-    for (int id0 = tid; id0 < total; id0 += 4 * UF_THREADS) {
+    for (int id0 = patch_ok ? tid : total; id0 < total; id0 += 4 * GT) {
       f32x4 v[4];
       int dst[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const int id = id0 + k * UF_THREADS;
+        const int id = id0 + k * GT;
         dst[k] = -1;
         if (id < total) {
           const int pp = id / f4n, f = id - pp * f4n;
@@ -181,7 +200,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   const float wl0 = j0 >= 1 ? 0.75f : 0.0f, wl1 = j0 >= 1 ? 0.25f : 0.0f;
   const float wr0 = j0 + 1 < a.w ? 0.25f : 0.0f, wr1 = j0 + 1 < a.w ? 0.75f : 0.0f;
   const float inv_s = a.hdr[1] * ixs;
-  const _Float16* wlane = a.wp + (16 * cw + p) * 32 + 8 * fg;    // A operand: cout row 16 cw + (lane & 15), channels 8 fg .. 8 fg + 7 of the chunk
+  const _Float16* wlane = a.wp + p * 32 + 8 * fg;                // A operand: row (lane & 15) of the wave's 16 couts, channels 8 fg .. 8 fg + 7 of the chunk
   const _Float16* xlane = fsm + p * UF_STRIDE + 8 * fg;          // B operand: patch pixel (q, p), the same channels; + 16 q UF_STRIDE, + 32 c
 
   f32x4 out[RO][2][2];                                           // [interior row][hi-res row 2 m0 + a][hi-res column 2 j0 + s]
@@ -194,13 +213,19 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
 #pragma unroll
       for (int q = 0; q < R; ++q) z[t][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // the GEMM of the three taps (TY, 0 .. 2): per chunk the wave's fragments of the three taps, each patch row read once for nine MFMAs
-    const _Float16* wt = wlane + (size_t)(3 * TY) * nch * UF_UNIT_HALVES;
+    // tap t of cout group cw starts at column t COUT + 16 cw of the packed [Cin, 9 COUT (+ pad)] filter: slice column / 64, row column % 64
+    size_t wo[3];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int col = (3 * TY + t) * COUT + 16 * cw;
+      wo[t] = (size_t)(col >> 6) * nch * UF_UNIT_HALVES + (col & 63) * 32;
+    }
 #pragma unroll 1
     for (int c = 0; c < nch; ++c) {
       f16x8 wh[3], wl[3], ws[3];
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        const _Float16* g = wt + ((size_t)t * nch + c) * UF_UNIT_HALVES;
+        const _Float16* g = wlane + wo[t] + (size_t)c * UF_UNIT_HALVES;
         wh[t] = *reinterpret_cast<const f16x8*>(g);
         wl[t] = *reinterpret_cast<const f16x8*>(g + UF_IMG_HALVES);
       }
@@ -284,9 +309,11 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
       if (q >= 2) asm volatile("" : "+v"(out[q - 2][0][0]), "+v"(out[q - 2][0][1]), "+v"(out[q - 2][1][0]), "+v"(out[q - 2][1][1]));
     }
   };
-  pass(std::integral_constant<int, 0>{});
-  pass(std::integral_constant<int, 1>{});
-  pass(std::integral_constant<int, 2>{});
+  if (patch_ok) {
+    pass(std::integral_constant<int, 0>{});
+    pass(std::integral_constant<int, 1>{});
+    pass(std::integral_constant<int, 2>{});
+  }
 
   // ---- epilogue: up2_lowres_stencil_kernel's `finish` per output, y and / or this wave's share of the projected pixel ---------------------
   const int c = 16 * cw + 4 * fg;
@@ -296,14 +323,14 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   const f32x4 shift_r = a.scale ? ld(a.shift + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 pq[3];
 #pragma unroll
-  for (int j = 0; j < 3; ++j) pq[j] = a.proj ? ld(a.proj + j * 64 + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (a.proj) __syncthreads();                                   // every wave is done with the patch images: their LDS takes the partial sums
+  for (int j = 0; j < 3; ++j) pq[j] = projp ? ld(projp + j * 64 + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (projp) __syncthreads();                                    // every wave is done with the patch images: their LDS takes the partial sums
   float* part = reinterpret_cast<float*>(fsm);                   // [4 waves][RO * 64 slots][3], slot = (qo * 2 + a) * 32 + 2 p + s
   float ym = 0.0f;
 #pragma unroll
   for (int qo = 0; qo < RO; ++qo) {
     const int m0 = m_start + qo;
-    const bool row_ok = m0 < a.h;                                // wave-uniform
+    const bool row_ok = patch_ok && m0 < a.h;                    // wave-uniform
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -314,10 +341,10 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
         if (a.scale) v = fma4v(v, scale_r, shift_r);
         shdr::act_apply4<0>(v, a.act2);
         if (a.y && row_ok && lane_ok) {
-          *reinterpret_cast<f32x4*>(a.y + (((size_t)n * 2 * a.h + 2 * m0 + r) * 2 * a.w + 2 * j0 + s) * 64 + c) = v;
+          *reinterpret_cast<f32x4*>(a.y + (((size_t)n * 2 * a.h + 2 * m0 + r) * 2 * a.w + 2 * j0 + s) * COUT + c) = v;
           ym = fmaxf(fmaxf(fmaxf(fmaxf(ym, fabsf(v[0])), fabsf(v[1])), fabsf(v[2])), fabsf(v[3]));
         }
-        if (a.proj) {
+        if (projp) {
 #pragma unroll
           for (int j = 0; j < 3; ++j) {
             float t = v[0] * pq[j][0] + v[1] * pq[j][1] + v[2] * pq[j][2] + v[3] * pq[j][3];
@@ -328,7 +355,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
         }
       }
   }
-  if (a.proj) {
+  if (projp) {
     __syncthreads();
     for (int slot = tid; slot < RO * 64; slot += UF_THREADS) {
       const int s = slot & 1, pp = (slot >> 1) & 15, r = (slot >> 5) & 1, qo = slot >> 6;
@@ -344,39 +371,103 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   if (a.y && a.yr) shdr::range_out_block256(a.yr, ym);           // one atomicMax per block, every thread calls
 }
 
-constexpr int uf_lds_bytes(int R) { return 2 * 16 * R * UF_STRIDE * 2; }
+constexpr int uf_lds_bytes(int R, int CW, int CMAX) { return (4 / CW) * 2 * 16 * R * uf_stride(CMAX) * 2; }
 
-bool uf_shape_ok(const shdr_conv2d_desc* d) {
+bool uf_geometry_ok(const shdr_conv2d_desc* d) {
   return d && d->N > 0 && d->H > 0 && d->W > 0 && d->H % 2 == 0 && d->W % 2 == 0 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad_t == 1 &&
-         d->pad_l == 1 && d->Ho == d->H && d->Wo == d->W && d->C2 == 0 && d->C1 % 32 == 0 && d->C1 >= 64 && d->C1 <= UF_MAX_CIN && d->Cout == 64;
+         d->pad_l == 1 && d->Ho == d->H && d->Wo == d->W && d->C2 == 0 && d->C1 % 32 == 0 && d->C1 <= UF_MAX_CIN;
+}
+// the 64-cout form (the Hallucination-Net's u1, the Dequantization-Net's u3)
+bool uf_shape_ok(const shdr_conv2d_desc* d) { return uf_geometry_ok(d) && d->C1 >= 64 && d->Cout == 64; }
+// the narrow forms: 32 couts (two patches per block), 16 couts (four patches per block, whose images fit up to 64 input channels)
+bool uf_narrow_shape_ok(const shdr_conv2d_desc* d) {
+  return uf_geometry_ok(d) && d->C1 >= 32 && (d->Cout == 32 || (d->Cout == 16 && d->C1 <= 64));
+}
+// columns of the narrow forms' packed filter: 9 Cout rounded up to the pack's 64-cout slices (16 -> 192, 32 -> 320)
+inline int uf_narrow_columns(int Cout) { return (9 * Cout + 63) / 64 * 64; }
+bool uf_narrow_gemm_desc(const shdr_conv2d_desc* d, shdr_conv2d_desc* g) {
+  if (!uf_narrow_shape_ok(d)) return false;
+  *g = shdr_conv2d_desc{};
+  g->N = d->N; g->H = d->H / 2; g->W = d->W / 2; g->C1 = d->C1; g->C2 = 0;
+  g->Cout = uf_narrow_columns(d->Cout);
+  g->KH = 1; g->KW = 1; g->stride = 1; g->pad_t = 0; g->pad_l = 0; g->Ho = g->H; g->Wo = g->W;
+  g->x2_scale = 1.0f; g->act1 = SHDR_ACT_NONE; g->act2 = SHDR_ACT_NONE; g->algo = SHDR_ALGO_AUTO; g->cout_valid = g->Cout; g->y_cstride = g->Cout;
+  return true;
+}
+// up2_lowres.hip's staging: st[ci][t * Cout + co] = w[t][ci][co] (t = 3 ty + tx), zero in the padded columns
+__global__ __launch_bounds__(256) void up2_fused_filter_kernel(const float* __restrict__ w, float* __restrict__ st, int Cin, int Cout, int Cp) {
+  const long total = (long)Cin * Cp;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int col = (int)(e % Cp), ci = (int)(e / Cp);
+    const int t = col / Cout, co = col - t * Cout;
+    st[e] = t < 9 ? w[((size_t)t * Cin + ci) * Cout + co] : 0.0f;
+  }
+}
+
+template <int CW, int CMAX>
+int uf_launch(const UpFusedArgs& a, hipStream_t st) {
+  constexpr int lds = uf_lds_bytes(UF_R, CW, CMAX), PPB = 4 / CW;
+  static_assert(lds <= 160 * 1024 - 64, "the patch images of a block must fit the CU's LDS");
+  static bool attr_done[shdr::kMaxDevices] = {};
+  const int dev_slot = shdr::device_slot();
+  if (!attr_done[dev_slot]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up2_fused_kernel<UF_R, CW, CMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    attr_done[dev_slot] = true;
+  }
+  const long nblk = ((long)a.npatch + PPB - 1) / PPB;
+  hipLaunchKernelGGL((up2_fused_kernel<UF_R, CW, CMAX>), dim3((unsigned)nblk), dim3(UF_THREADS), lds, st, a);
+  return shdr::check_launch("up2_fused_kernel");
 }
 
 }  // namespace
 
+// 1 unless SHDR_NO_UP2_NARROW=1 (the A/B arm of the narrow forms and of the Dequantization-Net's use of the low-res forms: under it every
+// launch of an inference step is the one from before they existed)
+extern "C" int shdr_conv2d_up2_narrow_enabled(void) { return SHDR_ENV("SHDR_NO_UP2_NARROW") == nullptr ? 1 : 0; }
+
 // 1 if shdr_conv2d_fwd_up2_fused_f32 takes the layer `d` (the descriptor of shdr_conv2d_up2_lowres_ok_f32): fp32 3x3 / stride 1 / SAME on the
-// bilinear prologue, one source, even H and W, 64 couts, Cin = 64, 96 or 128 (the patch of every input channel is resident in LDS), no TANH,
-// the split-operand kernels not switched off.  SHDR_NO_UP2_FUSED=1: never (the A/B arm).
+// bilinear prologue, one source, even H and W, no TANH, the split-operand kernels not switched off, and
+//   64 couts, Cin = 64, 96 or 128 (the patch of every input channel is resident in LDS), or
+//   32 couts, Cin = 32 .. 128, or 16 couts, Cin = 32 or 64 (the narrow forms; not under SHDR_NO_UP2_NARROW=1).
+// SHDR_NO_UP2_FUSED=1: never (the A/B arm).
 extern "C" int shdr_conv2d_up2_fused_ok_f32(const shdr_conv2d_desc* d) {
-  if (!uf_shape_ok(d) || SHDR_ENV("SHDR_NO_UP2_FUSED") != nullptr || SHDR_ENV("SHDR_NO_UP2_LOWRES") != nullptr || SHDR_ENV("SHDR_NO_WINOGRAD") != nullptr ||
-      SHDR_ENV("SHDR_NO_X3") != nullptr)
+  const bool narrow = uf_narrow_shape_ok(d) && shdr_conv2d_up2_narrow_enabled();
+  if (!(uf_shape_ok(d) || narrow) || SHDR_ENV("SHDR_NO_UP2_FUSED") != nullptr || SHDR_ENV("SHDR_NO_UP2_LOWRES") != nullptr ||
+      SHDR_ENV("SHDR_NO_WINOGRAD") != nullptr || SHDR_ENV("SHDR_NO_X3") != nullptr)
     return 0;
   if (d->algo != SHDR_ALGO_AUTO || d->prologue != SHDR_PROLOGUE_BILINEAR2X) return 0;
   if ((d->cout_valid != 0 && d->cout_valid != d->Cout) || d->w_batch_stride != 0 || d->y_pix_stride > 1 || (d->y_cstride != 0 && d->y_cstride != d->Cout)) return 0;
   if (d->act1 == SHDR_ACT_TANH || d->act2 == SHDR_ACT_TANH) return 0;
   const long nblk = (long)d->N * ((d->H / 2 + UF_R - 3) / (UF_R - 2)) * ((d->W / 2 + UF_COLS - 1) / UF_COLS);
-  return nblk <= 0x7fffffffL ? 1 : 0;
+  return nblk <= 0x7fffffffL - (narrow ? 4 : 0) ? 1 : 0;     // (a narrow block numbers its patches past the last one)
 }
 
-// the prepared filter is the two-launch form's (its packed [Cin, 9 Cout (+ pad)] filter: slice t = tap t)
+// 64 couts: the prepared filter is the two-launch form's (its packed [Cin, 9 Cout (+ pad)] filter: slice t = tap t); the narrow forms: the
+// same pack of the [Cin, 9 Cout] matrix padded to whole 64-column slices, then its fp32 staging copy
 extern "C" int64_t shdr_conv2d_up2_fused_filter_elems_f32(const shdr_conv2d_desc* d) {
-  return uf_shape_ok(d) ? shdr_conv2d_up2_lowres_filter_elems_f32(d) : -1;
+  if (uf_shape_ok(d)) return shdr_conv2d_up2_lowres_filter_elems_f32(d);
+  shdr_conv2d_desc g;
+  if (!uf_narrow_gemm_desc(d, &g)) return -1;
+  const int64_t packed = shdr_conv2d_x3_filter_elems_f32(&g);
+  return packed < 0 ? -1 : packed + (int64_t)g.C1 * g.Cout;
 }
 extern "C" int shdr_conv2d_up2_fused_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream) {
-  SHDR_REQUIRE(uf_shape_ok(d), SHDR_E_SHAPE, "up2_fused_prepare_filter: need a 3x3 layer with one source, Cin 64 / 96 / 128, Cout 64, even H and W");
-  return shdr_conv2d_up2_lowres_prepare_filter_f32(d, w, prepared, stream);
+  if (uf_shape_ok(d)) return shdr_conv2d_up2_lowres_prepare_filter_f32(d, w, prepared, stream);
+  SHDR_REQUIRE(d && w && prepared, SHDR_E_NULL, "up2_fused_prepare_filter: null pointer");
+  shdr_conv2d_desc g;
+  SHDR_REQUIRE(uf_narrow_gemm_desc(d, &g), SHDR_E_SHAPE,
+               "up2_fused_prepare_filter: need a 3x3 layer with one source, even H and W, and Cin 64 / 96 / 128 -> 64, Cin 32 .. 128 -> 32 or Cin 32 / 64 -> 16");
+  const int64_t packed = shdr_conv2d_x3_filter_elems_f32(&g);
+  SHDR_REQUIRE(packed > 0, SHDR_E_SHAPE, "up2_fused_prepare_filter: the 1x1 form of this layer has no packed filter");
+  float* staged = prepared + packed;
+  const long total = (long)g.C1 * g.Cout;
+  hipLaunchKernelGGL(up2_fused_filter_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), w, staged, g.C1, d->Cout, g.Cout);
+  if (int rc = shdr::check_launch("up2_fused_filter")) return rc;
+  return shdr_conv2d_x3_prepare_filter_f32(&g, staged, prepared, stream);
 }
 
-// x the LOW-RES tensor [N, H/2, W/2, Cin]; y [N, H, W, 64] = act2(affine(act1(conv3x3(resize2x(x)) + bias))) and / or
+// x the LOW-RES tensor [N, H/2, W/2, Cin]; y [N, H, W, Cout] = act2(affine(act1(conv3x3(resize2x(x)) + bias))) and / or, at 64 couts,
 // y_proj [N, H, W, 3][j] = sum_c proj[j][c] y[c]; one launch on `stream`.  x_range: the input's range slot; y_range (or NULL): receives
 // max |y| when y is written (atomicMax, the caller zeroes it).
 extern "C" int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const float* x, const float* prepared, const float* bias, const float* scale,
@@ -386,6 +477,7 @@ extern "C" int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const fl
   SHDR_REQUIRE(y || y_proj, SHDR_E_NULL, "conv2d_up2_fused: neither y nor y_proj");
   SHDR_REQUIRE((proj == nullptr) == (y_proj == nullptr), SHDR_E_NULL, "conv2d_up2_fused: proj and y_proj come together");
   SHDR_REQUIRE(shdr_conv2d_up2_fused_ok_f32(d), SHDR_E_SHAPE, "conv2d_up2_fused: layer not taken (shdr_conv2d_up2_fused_ok_f32)");
+  SHDR_REQUIRE(!proj || d->Cout == 64, SHDR_E_SHAPE, "conv2d_up2_fused: the projected output is the 64-cout form's");
   SHDR_REQUIRE((scale == nullptr) == (shift == nullptr), SHDR_E_NULL, "conv2d_up2_fused: scale and shift come together");
   SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(prepared) && (!y || shdr::aligned16(y)) && (!bias || shdr::aligned16(bias)) &&
                    (!scale || (shdr::aligned16(scale) && shdr::aligned16(shift))) && (!proj || shdr::aligned16(proj)),
@@ -397,15 +489,9 @@ extern "C" int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const fl
   a.N = d->N; a.h = d->H / 2; a.w = d->W / 2; a.C1 = d->C1; a.act1 = d->act1; a.act2 = d->act2;
   a.nty = (a.h + UF_R - 3) / (UF_R - 2);
   a.ntx = (a.w + UF_COLS - 1) / UF_COLS;
-  constexpr int lds = uf_lds_bytes(UF_R);
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up2_fused_kernel<UF_R>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
-  const long nblk = (long)a.N * a.nty * a.ntx;
-  hipLaunchKernelGGL((up2_fused_kernel<UF_R>), dim3((unsigned)nblk), dim3(UF_THREADS), lds, S(stream), a);
-  return shdr::check_launch("up2_fused_kernel");
+  a.npatch = (int)((long)a.N * a.nty * a.ntx);
+  hipStream_t st = S(stream);
+  if (d->Cout == 64) return uf_launch<4, 128>(a, st);
+  if (d->Cout == 32) return d->C1 <= 64 ? uf_launch<2, 64>(a, st) : uf_launch<2, 128>(a, st);
+  return d->C1 <= 32 ? uf_launch<1, 32>(a, st) : uf_launch<1, 64>(a, st);
 }

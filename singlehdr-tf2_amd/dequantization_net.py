@@ -10,10 +10,10 @@ import torch
 
 try:
     from . import _ops as K
-    from ._layers import Layer, Conv2D
+    from ._layers import Layer, Conv2D, taping
 except ImportError:
     import _ops as K
-    from _layers import Layer, Conv2D
+    from _layers import Layer, Conv2D, taping
 
 
 class down(Layer):
@@ -46,7 +46,13 @@ class up(Layer):
         self.conv2 = Conv2D(outChannels + skipChannels, outChannels, kernel_size, device=device)
 
     def call(self, x, skpCn):
-        x = self.conv1.call_up2(x, act1=K.ACT_LRELU)       # resize fused into the conv without a tape (K.conv2d_up2)
+        # tape-free fp32: the channel mix at low resolution where the library takes the layer (csrc/up2_fused.hip in one launch for u3,
+        # u2 and u1, csrc/up2_lowres.hip for u4), else -- and under SHDR_NO_UP2_NARROW=1 -- the call below
+        if x.dtype == torch.float32 and K.WINOGRAD and not K.EXACT_FP32 and K.up2_narrow_enabled() \
+                and not taping(x, self.conv1.kernel, self.conv1.bias):
+            x = self.conv1.call_up2(x, act1=K.ACT_LRELU, lowres=True, one_launch=True)
+        else:
+            x = self.conv1.call_up2(x, act1=K.ACT_LRELU)   # resize fused into the conv without a tape (K.conv2d_up2)
         return self.conv2(x, x2=skpCn, act1=K.ACT_LRELU)
 
 
