@@ -989,6 +989,58 @@ int shdr_jpeg_decode_u8(const shdr_jpeg_batch* batch, int16_t* coef, uint8_t* ou
  * changed during the decode that last used `workspace`, copied to the host array rounds [n_sub]; waits on `stream` */
 int shdr_jpeg_sync_rounds(const void* workspace, int64_t n_sub, int64_t n_blocks, int64_t plane_bytes, int32_t* rounds, void* stream);
 
+/* ---- the `data` arena of shdr_jpeg_batch built on the device (csrc/jpeg_scan.hip; the rules are csrc/jpeg_scan.h, shared with the
+ *      host twin): a BATCH of scan regions, each the bytes of a file from the first byte after its SOS header to the end of the file.
+ *      In a region b[0 .. n) a marker is FF followed by a byte that is not 00, not FF and not D0 .. D7; `end` is the first marker.
+ *      Before `end`, FF D0 .. D7 is a restart marker (neither byte is kept, a new segment starts after it), a 00 after FF is dropped,
+ *      FF FF sets the fill flag, every other byte is kept; nothing at or after `end` counts.
+ *
+ *      src        device bytes, 16-byte aligned: the regions, each at image.offset (a multiple of 16); fewer than 2^33 bytes
+ *      images     one shdr_jpeg_scan_image per region, as a host array, which is validated, and as the device copy of that very
+ *                 array, which the kernels read
+ *      report     device, one shdr_jpeg_scan_report per region
+ *      bounds     device int64 [n_bounds]: slot image.first_bound + k receives the number of kept bytes before restart marker k,
+ *                 for k < seg_cap - 1; slots that no marker fills hold -1, markers beyond the slots are counted in n_rst only
+ *      workspace  shdr_jpeg_scan_workspace_bytes(n_images, n_tiles) bytes, 16-byte aligned, owned by the caller; n_tiles: the sum
+ *                 of ceil(length / SHDR_JPEG_SCAN_TILE).  shdr_jpeg_compact reads what shdr_jpeg_scan left in it for the same batch.
+ *      seg_dword  device int32: entry s * seg_stride is the SHDR_JPEG_SEG_DWORD of segment s (the `segs` table itself with
+ *                 seg_stride = SHDR_JPEG_SEG_FIELDS will do); segment image.first_seg + s holds the kept bytes between boundaries
+ *                 s - 1 and s of the image (everything after the last slot is in the last segment)
+ *      arena      device bytes: filled with FF, then kept byte j of a segment goes to arena[seg_dword * 4 + (j - its boundary)];
+ *                 a byte whose place is outside [0, arena_bytes) is not written
+ *      Whatever the bytes of `src`, no read leaves a region and no write leaves report, the image's slots or the arena.  Both
+ *      calls are asynchronous on `stream`, run no host work between their launches (7 and 1, plus a fill each) and allocate
+ *      nothing; stage_ms, if not NULL, receives the device-event time of the call in ms (the call then waits for its last kernel).
+ *      shdr_jpeg_scan_host is the same on host memory, byte by byte: report and bounds, and with seg_dword != NULL the arena. ---- */
+#define SHDR_JPEG_SCAN_TILE 4096
+typedef struct shdr_jpeg_scan_image {
+  int64_t offset;               /* first byte of the region in `src`, a multiple of 16 */
+  int64_t length;
+  int64_t first_tile;           /* the tiles of the images before it */
+  int32_t seg_cap;              /* the segments its header implies: ceil(MCUs / restart interval), or 1 */
+  int32_t first_bound;          /* its first slot in `bounds`: the sum of seg_cap - 1 over the images before it */
+  int32_t first_seg;            /* its first segment: the sum of seg_cap over the images before it */
+  int32_t reserved;
+} shdr_jpeg_scan_image;
+typedef struct shdr_jpeg_scan_report {
+  int64_t end;                  /* position of the end marker's FF in the region, -1: the region has none */
+  int64_t kept;                 /* kept bytes */
+  int32_t n_rst;                /* restart markers before `end` */
+  int32_t fill;                 /* 1: FF FF before `end` */
+  int32_t end_marker;           /* the byte after that FF (D9: EOI), -1 without an end */
+  int32_t reserved;
+} shdr_jpeg_scan_report;
+int64_t shdr_jpeg_scan_workspace_bytes(int n_images, int64_t n_tiles);                       /* -1 on bad sizes */
+int shdr_jpeg_scan(const uint8_t* src, int64_t src_bytes, const shdr_jpeg_scan_image* images, const shdr_jpeg_scan_image* images_dev,
+                   int n_images, shdr_jpeg_scan_report* report, int64_t* bounds, int64_t n_bounds, void* workspace, void* stream,
+                   float* stage_ms);
+int shdr_jpeg_compact(const uint8_t* src, int64_t src_bytes, const shdr_jpeg_scan_image* images, const shdr_jpeg_scan_image* images_dev,
+                      int n_images, const int64_t* bounds, int64_t n_bounds, const int32_t* seg_dword, int seg_stride, int64_t n_segs,
+                      uint8_t* arena, int64_t arena_bytes, const void* workspace, void* stream, float* stage_ms);
+int shdr_jpeg_scan_host(const uint8_t* src, int64_t src_bytes, const shdr_jpeg_scan_image* images, int n_images,
+                        shdr_jpeg_scan_report* report, int64_t* bounds, int64_t n_bounds, const int32_t* seg_dword, int seg_stride,
+                        int64_t n_segs, uint8_t* arena, int64_t arena_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,10 @@ SIGNATURES = {
     "shdr_jpeg_entropy_decode": (c_int, [c_ptr] * 5),
     "shdr_jpeg_decode_u8": (c_int, [c_ptr] * 6),
     "shdr_jpeg_sync_rounds": (c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
+    "shdr_jpeg_scan_workspace_bytes": (c_i64, [c_int, c_i64]),
+    "shdr_jpeg_scan": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    "shdr_jpeg_compact": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_int, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    "shdr_jpeg_scan_host": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_int, c_i64, c_ptr, c_i64]),
 }
 
 _lib = None

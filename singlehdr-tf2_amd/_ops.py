@@ -2236,6 +2236,99 @@ def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets
     return dst, written, status
 
 
+# ---------------------------------------------------------------------------
+# JPEG scan regions unstuffed and laid out (jpeg.plan_device), see csrc/jpeg_scan.h and csrc/jpeg_scan.hip
+# ---------------------------------------------------------------------------
+JPEG_SCAN_IMAGE_BYTES, JPEG_SCAN_REPORT_BYTES = 40, 32          # shdr_jpeg_scan_image, shdr_jpeg_scan_report
+JPEG_SCAN_TILE = 4096                                           # SHDR_JPEG_SCAN_TILE: raw bytes per workgroup
+
+
+def _jpeg_scan_images(images, what):
+    """(the descriptors as a contiguous host array, boundary slots, segments) of a structured array shaped like shdr_jpeg_scan_image
+    (jpeg.SCAN_IMAGE_DTYPE)"""
+    images = np.ascontiguousarray(images)
+    if images.ndim != 1 or images.size == 0 or images.dtype.itemsize != JPEG_SCAN_IMAGE_BYTES or "seg_cap" not in (images.dtype.names or ()):
+        raise ValueError("%s: images must be a non-empty array of jpeg.SCAN_IMAGE_DTYPE" % what)
+    cap = images["seg_cap"].astype(np.int64)
+    return images, int((cap - 1).sum()), int(cap.sum())
+
+
+def jpeg_scan_host(src, images, seg_dword=None, seg_stride=1, arena_bytes=0):
+    """libshdr's host twin of jpeg_scan / jpeg_compact (csrc/jpeg_scan.h, the rules the kernels run).  src: the bytes of the batch's
+    scan regions; images: jpeg.SCAN_IMAGE_DTYPE [n].  Returns (report uint8 [n * 32]: view it as jpeg.SCAN_REPORT_DTYPE, bounds int64
+    [sum(seg_cap - 1)], arena): arena is None without seg_dword (int32: entry s * seg_stride is the arena dword of segment s), else
+    uint8 [arena_bytes]"""
+    lib = _lib.load()
+    src = np.ascontiguousarray(np.frombuffer(src, dtype=np.uint8) if isinstance(src, (bytes, bytearray, memoryview)) else src, dtype=np.uint8)
+    images, n_bounds, n_segs = _jpeg_scan_images(images, "jpeg_scan_host")
+    report = np.zeros(images.size * JPEG_SCAN_REPORT_BYTES, dtype=np.uint8)
+    bounds = np.zeros(max(n_bounds, 1), dtype=np.int64)
+    arena = None
+    if seg_dword is not None:
+        seg_dword = np.ascontiguousarray(seg_dword, dtype=np.int32).reshape(-1)
+        arena = np.zeros(max(int(arena_bytes), 1), dtype=np.uint8)
+    _lib.check(lib.shdr_jpeg_scan_host(_hptr(src) if src.size else None, src.size, _hptr(images), images.size, _hptr(report), _hptr(bounds),
+                                       n_bounds, _hptr(seg_dword) if seg_dword is not None else None, int(seg_stride),
+                                       seg_dword.size // int(seg_stride) if seg_dword is not None else 0,
+                                       _hptr(arena) if arena is not None else None, int(arena_bytes)), "shdr_jpeg_scan_host")
+    return report, bounds[:n_bounds], None if arena is None else arena[:int(arena_bytes)]
+
+
+def jpeg_scan(src, images, images_dev=None, stage_ms=None):
+    """the scan call on the device (csrc/jpeg_scan.hip): src uint8 device tensor, the regions at images["offset"] (multiples of 16);
+    images: jpeg.SCAN_IMAGE_DTYPE [n] on the host (validated by libshdr), images_dev its device copy as uint8 (made here if None).
+    Returns (result, workspace, images_dev): result is ONE uint8 device tensor, n reports of 32 bytes (jpeg.SCAN_REPORT_DTYPE) followed by
+    the int64 boundaries [sum(seg_cap - 1)], so that one copy brings both back; workspace and images_dev are what jpeg_compact wants.
+    Stream-ordered, no host wait.  stage_ms: a list that receives the device time of the call (measurement: the call then waits)."""
+    lib = _lib.load()
+    src = _chk(src, "src", torch.uint8)
+    images, n_bounds, _ = _jpeg_scan_images(images, "jpeg_scan")
+    dev, n = src.device, images.size
+    if images_dev is None:
+        images_dev = torch.from_numpy(images.view(np.uint8)).to(dev)
+    if _chk(images_dev, "images_dev", torch.uint8).numel() != n * JPEG_SCAN_IMAGE_BYTES:
+        raise ValueError("jpeg_scan: images_dev is not a copy of images")
+    n_tiles = int((-(-images["length"].astype(np.int64) // JPEG_SCAN_TILE)).sum())
+    ws_bytes = lib.shdr_jpeg_scan_workspace_bytes(n, n_tiles)
+    if ws_bytes < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    result = torch.empty(n * JPEG_SCAN_REPORT_BYTES + 8 * n_bounds, device=dev, dtype=torch.uint8)
+    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
+    _lib.check(lib.shdr_jpeg_scan(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n, _ptr(result),
+                                  ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
+                                  _ptr(ws), _stream(), ms), "shdr_jpeg_scan")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return result, ws, images_dev
+
+
+def jpeg_compact(src, images, images_dev, result, workspace, seg_dword, seg_stride, arena_bytes, stage_ms=None):
+    """the compaction call: src, images, images_dev as for jpeg_scan, result and workspace what it returned for them; seg_dword: int32
+    device tensor whose entry s * seg_stride is the arena dword of segment s (the uploaded `segs` table with seg_stride 6 will do).
+    Returns the arena, uint8 [arena_bytes] on the device: FF, then every kept byte at its place.  Stream-ordered, no host wait."""
+    lib = _lib.load()
+    src = _chk(src, "src", torch.uint8)
+    images, n_bounds, n_segs = _jpeg_scan_images(images, "jpeg_compact")
+    n, seg_stride, arena_bytes = images.size, int(seg_stride), int(arena_bytes)
+    seg_dword = _chk(seg_dword, "seg_dword", torch.int32)
+    if _chk(result, "result", torch.uint8).numel() != n * JPEG_SCAN_REPORT_BYTES + 8 * n_bounds or \
+            _chk(images_dev, "images_dev", torch.uint8).numel() != n * JPEG_SCAN_IMAGE_BYTES:
+        raise ValueError("jpeg_compact: result and images_dev must be those of jpeg_scan for these images")
+    if seg_stride < 1 or seg_dword.numel() < n_segs * seg_stride or arena_bytes < 0:
+        raise ValueError("jpeg_compact: seg_dword must hold %d segments of stride %d" % (n_segs, seg_stride))
+    _chk(workspace, "workspace", torch.uint8)
+    arena = torch.empty(arena_bytes, device=src.device, dtype=torch.uint8)
+    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
+    _lib.check(lib.shdr_jpeg_compact(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n,
+                                     ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
+                                     _ptr(seg_dword), seg_stride, seg_dword.numel() // seg_stride, _ptr(arena) if arena_bytes else None,
+                                     arena_bytes, _ptr(workspace), _stream(), ms), "shdr_jpeg_compact")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return arena
+
+
 EXR_HALF, EXR_FLOAT = 1, 2
 
 

@@ -54,6 +54,7 @@ SOURCES = {
     "inflate.hip": [],
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
+    "jpeg_scan.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]
@@ -78,7 +79,7 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
                os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
-               os.path.join(CSRC, "inflate.h"),
+               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "jpeg_scan.h"),
                os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []

@@ -209,21 +209,22 @@ class HdrReconstructor:
         return y[0]
 
     def _read_device(self, ldr_path, decoder, what):
-        if decoder not in ("pil", "device"):
-            raise ValueError("%s: decoder must be 'pil' or 'device', got %r" % (what, decoder))
-        if decoder == "device":
+        if decoder not in ("pil", "device", "device_scan"):
+            raise ValueError("%s: decoder must be 'pil', 'device' or 'device_scan', got %r" % (what, decoder))
+        if decoder != "pil":
             try:
                 from . import jpeg
             except ImportError:
                 import jpeg
-            return self.reconstruct_device(jpeg.read_ldr_device(ldr_path))
+            return self.reconstruct_device(jpeg.read_ldr_device(ldr_path, unstuff="device" if decoder == "device_scan" else "host"))
         return self.reconstruct_device(read_ldr(ldr_path))
 
     def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host", output_format="hdr",
                          exr_options=None):
         """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
         decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
-        (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope).
+        (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope); "device_scan" is "device" with the scan prepared on
+        the device too (unstuff="device": the end of the scan, the byte stuffing and the restart segments; the same bytes again).
         encoder: "host" copies the RGBE pixels back and codes the scanlines on the host; "device" codes them on the device and copies
         the coded bytes (write_hdr: the same file).
         output_format: "hdr" writes a Radiance file; "exr" writes the float estimate as OpenEXR without the RGBE conversion
@@ -251,8 +252,8 @@ class HdrReconstructor:
         ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
         if len(ldr_paths) != len(hdr_paths):
             raise ValueError("reconstruct_files: %d inputs but %d outputs" % (len(ldr_paths), len(hdr_paths)))
-        if decoder not in ("pil", "device"):
-            raise ValueError("reconstruct_files: decoder must be 'pil' or 'device', got %r" % (decoder,))
+        if decoder not in ("pil", "device", "device_scan"):
+            raise ValueError("reconstruct_files: decoder must be 'pil', 'device' or 'device_scan', got %r" % (decoder,))
         if output_format == "exr":
             if not ldr_paths:
                 return

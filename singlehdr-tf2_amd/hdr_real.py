@@ -95,14 +95,15 @@ class HdrRealFolder:
     Flips are u0 < 0.5 and rots int(u1 * 4 + 0.5) of float32 uniforms, as tfrecord.HdrRealDataset draws them: rot 4 occurs and is
     rot 0.  augment=False gives flip 0 and rot 0.
     jpeg_decoder="device" decodes all LDR files in ONE jpeg.decode batch whose output arena IS ldr_arena (the same bytes as "pil",
-    hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch).
+    hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch); "device_scan" is the
+    same with the scans prepared on the device too (jpeg.Decoded(unstuff="device")).
     exr_inflate="device" leaves the ZIP / ZIPS chunks of OpenEXR files to the device (exr.read_stored, then ONE exr.upload_batch for
     all of them; the same arena as with "host", where zlib inflates them one file after the other)."""
 
     def __init__(self, dirpath, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1, batch_size=BATCH_SIZE,
                  augment=True, jpeg_decoder="pil", exr_inflate="host"):
-        if jpeg_decoder not in ("pil", "device"):
-            raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil' or 'device', got %r" % (jpeg_decoder,))
+        if jpeg_decoder not in ("pil", "device", "device_scan"):
+            raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil', 'device' or 'device_scan', got %r" % (jpeg_decoder,))
         exr.check_inflate_option("HdrRealFolder", exr_inflate)
         hdr_paths = sorted(p for ext in ("*.hdr", "*.exr") for p in glob.glob(os.path.join(dirpath, "HDR_gt", ext)))
         ldr_paths = sorted(glob.glob(os.path.join(dirpath, "LDR_in", "*.jpg")))
@@ -114,8 +115,8 @@ class HdrRealFolder:
         t0 = time.perf_counter()
         device = device or torch.device("cuda", torch.cuda.current_device())
         ldr_arena = None
-        if jpeg_decoder == "device":
-            ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device)
+        if jpeg_decoder != "pil":
+            ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device, "device" if jpeg_decoder == "device_scan" else "host")
         else:
             ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
         read = exr.read_stored if exr_inflate == "device" else exr.read_payload
@@ -124,22 +125,31 @@ class HdrRealFolder:
         self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0, ldr_arena)
 
     @staticmethod
-    def _decode_ldr_on_device(paths, device):
+    def _decode_ldr_on_device(paths, device, unstuff="host"):
         """(uint8 [H, W, 3] device views per file, the flat arena they lie in).  Every baseline JPEG of the folder is decoded in ONE
         jpeg batch; when all files are such and stored upright, the batch's output arena is returned as it is.  Files outside the
         decoder's scope (progressive, CMYK, ...) are read by PIL and uploaded, files with an EXIF Orientation are turned, and the
-        arena is then assembled from the pieces: still one batch, whatever the number of files."""
+        arena is then assembled from the pieces: still one batch, whatever the number of files.  unstuff="device": the host looks at
+        the headers only; a file that turns out of scope in its scan (fill bytes, a second scan) is named by the batch call, left to
+        PIL, and the batch is called again without it."""
         in_scope = []
         for i, p in enumerate(paths):
             try:
                 with open(p, "rb") as f:
-                    jpeg.device_tables(jpeg.parse(f.read()))
+                    jpeg.device_tables((jpeg.parse_header if unstuff == "device" else jpeg.parse)(f.read()))
                 in_scope.append(i)
             except jpeg.Unsupported:
                 pass
         images = [None] * len(paths)
+        d = None
+        while in_scope and d is None:
+            try:
+                d = jpeg.Decoded([paths[i] for i in in_scope], device, unstuff=unstuff)
+            except jpeg.Unsupported as exc:
+                if unstuff != "device" or getattr(exc, "index", None) is None:
+                    raise
+                del in_scope[exc.index]
         if in_scope:
-            d = jpeg.Decoded([paths[i] for i in in_scope], device)
             d.check()
             if len(in_scope) == len(paths) and all(h.orientation == 1 for h in d.plan.headers):
                 return [d.image(i) for i in range(len(paths))], d.out

@@ -8,6 +8,8 @@ the EXIF Orientation), removes the FF 00 byte stuffing and cuts the scan at its 
 per Huffman table what the kernel reads (a 9-bit look-ahead table, maxcode / valoff for longer codes, as libjpeg's jdhuff.c).
 It touches no bit and no coefficient.  The device (csrc/jpeg.hip) decodes the Huffman stream with the self-synchronising
 scheme of Weissenberger & Schmidt, undoes the DC prediction, dequantises, runs the islow IDCT, upsamples and converts to RGB.
+With unstuff="device" (opt-in) the host walks the markers only up to SOS (parse_header) and the device also finds the end of the
+scan, removes the stuffing and fills the segment arena (plan_device, csrc/jpeg_scan.hip): the same arena, the same exceptions.
 
 In scope: SOF0 / SOF1 (8-bit, Huffman), one component (grey) or three (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1
 (4:4:4, 4:2:2, 4:2:0), one interleaved scan, any restart interval, any legal DHT.  Everything else raises Unsupported with the
@@ -114,8 +116,13 @@ SOF_NAMES = {0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequenti
              0xCF: "arithmetic-coded differential"}
 
 
-def parse(data):
-    """bytes of a JPEG file -> Header; Unsupported / CorruptJpeg with the reason"""
+ScanHeader = collections.namedtuple("ScanHeader", "width height components layout qtables htables restart_interval scan_start orientation")
+"""what parse_header returns: the fields of Header that do not depend on the bytes of the scan"""
+
+
+def parse_header(data):
+    """bytes of a JPEG file -> ScanHeader: the marker walk up to and including the SOS header.  No byte of the scan is touched;
+    Unsupported / CorruptJpeg with the reason"""
     data = bytes(data)
     n = len(data)
     if n < 2 or data[0] != 0xFF:
@@ -239,8 +246,15 @@ def parse(data):
         if key not in LAYOUTS or any((c.h, c.v) != (1, 1) for c in comps[1:]):
             raise Unsupported("sampling factors %s (4:4:4, 4:2:2 and 4:2:0 only)" % "/".join("%dx%d" % (c.h, c.v) for c in comps))
         layout = LAYOUTS[key]
+    return ScanHeader(width, height, tuple(comps), layout, qtables, htables, restart, pos, orientation if orientation is not None else 1)
+
+
+def parse(data):
+    """bytes of a JPEG file -> Header; Unsupported / CorruptJpeg with the reason"""
+    data = bytes(data)
+    hd = parse_header(data)
     # the entropy-coded data ends at the first marker that is neither stuffing (FF 00), a fill byte (FF FF) nor RSTn
-    scan_start = pos
+    scan_start = hd.scan_start
     buf = np.frombuffer(data, dtype=np.uint8, offset=scan_start)
     nxt = buf[1:]
     is_ff = buf[:-1] == 0xFF
@@ -256,8 +270,8 @@ def parse(data):
     if np.any(is_ff[:end] & (nxt[:end] == 0xFF)):
         raise Unsupported("fill bytes inside the entropy-coded data")
     rst_offsets = np.flatnonzero(rst[:end]).astype(np.int64) + scan_start
-    return Header(width, height, tuple(comps), layout, qtables, htables, restart, scan_start, scan_start + end, rst_offsets,
-                  orientation if orientation is not None else 1)
+    return Header(hd.width, hd.height, hd.components, hd.layout, hd.qtables, hd.htables, hd.restart_interval, scan_start, scan_start + end,
+                  rst_offsets, hd.orientation)
 
 
 def geometry(header):
@@ -354,92 +368,282 @@ class Batch(ctypes.Structure):
 Plan = collections.namedtuple("Plan", "headers data tables images segs sub_seg n_blocks plane_bytes out_bytes subseq_bits")
 
 
-def plan(items, subseq_bits=SUBSEQ_BITS):
-    """parse every item and lay the batch out: the host half of decode().  items: paths or bytes."""
-    headers, chunks, tabs, seg_rows, sub_rows = [], [], [], [], []
-    images = np.zeros(len(items), dtype=IMAGE_DTYPE)
-    dword = blk = plane = out = n_sub = 0
-    for i, item in enumerate(items):
-        try:
-            raw = _read(item)
-            hd = parse(raw)
-            blob, qslot, hslot = device_tables(hd)
-        except (Unsupported, CorruptJpeg) as exc:
-            raise type(exc)("%s: %s" % (_name(item), exc)) from None
-        mx, my, bpm, comps = geometry(hd)
-        stream, offs = unstuff(raw, hd)
+class _Layout:
+    """the O(segments) part of a plan, shared by plan() and plan_device(): from the lengths of an image's unstuffed restart segments
+    its rows of `segs`, its subsequence slots and its record of `images`, and the running offsets of the batch"""
+
+    def __init__(self, n_items, subseq_bits):
+        self.subseq_bits = int(subseq_bits)
+        self.images = np.zeros(n_items, dtype=IMAGE_DTYPE)
+        self.headers, self.tabs, self.seg_rows, self.sub_rows = [], [], [], []
+        self.dword = self.blk = self.plane = self.out = self.n_sub = self.n_segs = 0
+
+    @staticmethod
+    def segments(hd):
+        """the restart segments the header implies"""
+        mx, my, _, _ = geometry(hd)
         ri = hd.restart_interval
-        want = -(-mx * my // ri) if ri else 1
-        if offs.size - 1 != want:
+        return -(-mx * my // ri) if ri else 1
+
+    def check(self, item, hd, n_segments, n_bytes):
+        """the two checks that follow the unstuffing, with the host route's words"""
+        mx, my, _, _ = geometry(hd)
+        ri = hd.restart_interval
+        want = self.segments(hd)
+        if n_segments != want:
             raise CorruptJpeg("%s: %d restart segments, its %d MCUs at restart interval %d make %d" % (
-                _name(item), offs.size - 1, mx * my, ri, want))
-        if stream.size >= 1 << 27:
+                _name(item), n_segments, mx * my, ri, want))
+        if n_bytes >= 1 << 27:
             raise Unsupported("%s: more than 128 MiB of entropy-coded data" % _name(item))
-        lengths = np.diff(offs)
+
+    def add(self, hd, tables, lengths):
+        """image len(self.headers) of the batch; tables: device_tables(hd); lengths: int64 per restart segment.  Returns the arena dword
+        of every segment (int64) and the dwords the image takes"""
+        i = len(self.headers)
+        blob, qslot, hslot = tables
+        mx, my, bpm, comps = geometry(hd)
+        ri = hd.restart_interval
         # every segment starts on a dword of the arena; pad bytes read as 1-bits like libjpeg's, though no decoder sees them
         dwords = (lengths + 3) // 4
-        seg_dword = dword + np.concatenate([[0], np.cumsum(dwords)[:-1]])
-        arena = np.full(int(dwords.sum()) * 4, 0xFF, dtype=np.uint8)
-        seg_of = np.repeat(np.arange(lengths.size), lengths)
-        arena[(seg_dword[seg_of] - dword) * 4 + np.arange(stream.size) - offs[:-1][seg_of]] = stream
-        chunks.append(arena)
-        dword += int(dwords.sum())
-        subs = np.maximum(1, -(-lengths * 8 // subseq_bits))
-        first_sub = n_sub + np.concatenate([[0], np.cumsum(subs)[:-1]])
-        seg0 = sum(len(r) for r in seg_rows)
+        seg_dword = self.dword + np.concatenate([[0], np.cumsum(dwords)[:-1]])
+        total = int(dwords.sum())
+        self.dword += total
+        subs = np.maximum(1, -(-lengths * 8 // self.subseq_bits))
+        first_sub = self.n_sub + np.concatenate([[0], np.cumsum(subs)[:-1]])
         per = (ri if ri else mx * my) * bpm
         first_block = np.arange(lengths.size, dtype=np.int64) * per
         rows = np.zeros((lengths.size, 6), dtype=np.int32)
         rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = seg_dword, lengths * 8, first_sub, first_block
         rows[:, 4], rows[:, 5] = np.minimum(per, mx * my * bpm - first_block), i
-        seg_rows.append(rows)
+        self.seg_rows.append(rows)
         total_subs = int(subs.sum())
         n_wg = -(-total_subs // WG)
         slot = np.full(n_wg * WG, -1, dtype=np.int32)
-        slot[:total_subs] = seg0 + np.repeat(np.arange(lengths.size), subs)
-        sub_rows.append(slot)
-        im = images[i]
-        im["blk_off"], im["plane_off"], im["out_off"], im["table_off"] = blk, plane, out, TABLE_BYTES * i
+        slot[:total_subs] = self.n_segs + np.repeat(np.arange(lengths.size), subs)
+        self.sub_rows.append(slot)
+        self.n_segs += lengths.size
+        im = self.images[i]
+        im["blk_off"], im["plane_off"], im["out_off"], im["table_off"] = self.blk, self.plane, self.out, TABLE_BYTES * i
         im["width"], im["height"], im["ncomp"], im["mcus_x"], im["mcus_y"] = hd.width, hd.height, len(comps), mx, my
-        im["blocks_per_mcu"], im["restart_interval"], im["first_wg"], im["n_wg"] = bpm, ri, n_sub // WG, n_wg
+        im["blocks_per_mcu"], im["restart_interval"], im["first_wg"], im["n_wg"] = bpm, ri, self.n_sub // WG, n_wg
         cb = 0
         for c, (h, v, bw, bh, cw, ch) in enumerate(comps):
             k = hd.components[c]
             im["comp"][c] = (h, v, qslot[k.tq], hslot[(0, k.td)], hslot[(1, k.ta)], bw, bh, cb, cb * 64, cw, ch)
             cb += bw * bh
-        blk += cb
-        plane += cb * 64
-        out += hd.width * hd.height * 3
-        n_sub += n_wg * WG
-        headers.append(hd)
-        tabs.append(blob)
-    return Plan(headers, np.concatenate(chunks), np.concatenate(tabs), images, np.ascontiguousarray(np.concatenate(seg_rows)),
-                np.concatenate(sub_rows), blk, plane, out, int(subseq_bits))
+        self.blk += cb
+        self.plane += cb * 64
+        self.out += hd.width * hd.height * 3
+        self.n_sub += n_wg * WG
+        self.headers.append(hd)
+        self.tabs.append(blob)
+        return seg_dword, total
+
+    def plan(self, data):
+        return Plan(self.headers, data, np.concatenate(self.tabs), self.images, np.ascontiguousarray(np.concatenate(self.seg_rows)),
+                    np.concatenate(self.sub_rows), self.blk, self.plane, self.out, self.subseq_bits)
+
+
+def plan(items, subseq_bits=SUBSEQ_BITS):
+    """parse every item and lay the batch out: the host half of decode().  items: paths or bytes."""
+    lay = _Layout(len(items), subseq_bits)
+    chunks = []
+    for i, item in enumerate(items):
+        try:
+            raw = _read(item)
+            hd = parse(raw)
+            tables = device_tables(hd)
+        except (Unsupported, CorruptJpeg) as exc:
+            raise type(exc)("%s: %s" % (_name(item), exc)) from None
+        stream, offs = unstuff(raw, hd)
+        lay.check(item, hd, offs.size - 1, stream.size)
+        lengths = np.diff(offs)
+        dword = lay.dword
+        seg_dword, total = lay.add(hd, tables, lengths)
+        arena = np.full(total * 4, 0xFF, dtype=np.uint8)
+        seg_of = np.repeat(np.arange(lengths.size), lengths)
+        arena[(seg_dword[seg_of] - dword) * 4 + np.arange(stream.size) - offs[:-1][seg_of]] = stream
+        chunks.append(arena)
+    return lay.plan(np.concatenate(chunks))
+
+
+SCAN_TILE = 4096               # SHDR_JPEG_SCAN_TILE: raw bytes per workgroup of csrc/jpeg_scan.hip
+SCAN_PREFIX_TILES = 256        # tiles per workgroup of its cross-tile prefix sum (kScanChunk): a region of more than 1 MiB spans two
+SCAN_IMAGE_DTYPE = np.dtype([("offset", np.int64), ("length", np.int64), ("first_tile", np.int64), ("seg_cap", np.int32),
+                             ("first_bound", np.int32), ("first_seg", np.int32), ("reserved", np.int32)])
+"""mirror of shdr_jpeg_scan_image (include/shdr.h)"""
+assert SCAN_IMAGE_DTYPE.itemsize == 40
+SCAN_REPORT_DTYPE = np.dtype([("end", np.int64), ("kept", np.int64), ("n_rst", np.int32), ("fill", np.int32), ("end_marker", np.int32),
+                              ("reserved", np.int32)])
+"""mirror of shdr_jpeg_scan_report"""
+assert SCAN_REPORT_DTYPE.itemsize == 32
+
+
+def scan_images(lengths, seg_caps):
+    """SCAN_IMAGE_DTYPE [n] of regions of these lengths laid one after the other, each on a multiple of 16, and the bytes they take"""
+    lengths, seg_caps = np.asarray(lengths, dtype=np.int64), np.asarray(seg_caps, dtype=np.int64)
+    im = np.zeros(lengths.size, dtype=SCAN_IMAGE_DTYPE)
+    padded = (lengths + 15) // 16 * 16
+    im["offset"] = np.cumsum(padded) - padded
+    im["length"] = lengths
+    tiles = -(-lengths // SCAN_TILE)
+    im["first_tile"] = np.cumsum(tiles) - tiles
+    im["seg_cap"] = seg_caps
+    im["first_bound"] = np.cumsum(seg_caps - 1) - (seg_caps - 1)
+    im["first_seg"] = np.cumsum(seg_caps) - seg_caps
+    return im, int(padded.sum())
+
+
+def _scan_checks(report):
+    """the end of parse(), on the scan call's report of one region: its exceptions and words"""
+    if report["end"] < 0:
+        raise CorruptJpeg("no EOI marker: the file is cut inside its entropy-coded data")
+    m = int(report["end_marker"])
+    if m != 0xD9:
+        if m in (0xDA, 0xC4, 0xDB, 0xDD):
+            raise Unsupported("several scans")
+        raise Unsupported("marker FF%02X after the scan" % m)
+    if report["fill"]:
+        raise Unsupported("fill bytes inside the entropy-coded data")
+
+
+def _indexed(exc, index):
+    exc.index = index                                             # which item of the batch: hdr_real sorts files out of scope with it
+    return exc
+
+
+def plan_device(items, device=None, subseq_bits=SUBSEQ_BITS, timing=None, events=None):
+    """plan() with the per-byte work on the device (csrc/jpeg_scan.hip): the host reads the files and walks the markers up to SOS
+    (parse_header), the scan regions go up in one copy from a pinned buffer, the scan call finds every region's end, counts its kept
+    bytes and restart markers and returns the kept bytes before every marker; the host reads that small report back, makes parse()'s
+    and plan()'s checks on it (the same exceptions, naming the same item, with an attribute `index`), lays the segments out as
+    plan() does, and the compaction call writes the arena.  The Plan's `data` is that arena, a uint8 device tensor; everything else
+    is plan()'s.  Headers have rst_offsets None (nobody located the markers on the host).  timing: a dict that receives the wall
+    time in ms of read_parse, stage (into the pinned buffer), scan_launch (upload + launches), scan_wait (the report's readback),
+    layout, compact_launch (the table uploads and the launch); events: a dict that receives the device-event time in ms of the scan
+    call and of the compaction call (measurement: each call then waits for its last kernel)."""
+    import time
+    import torch
+    try:
+        from . import _ops as K
+    except ImportError:
+        import _ops as K
+    t0 = time.perf_counter()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    raws, heads, tables = [], [], []
+    deferred = None                                               # the first item the header walk refuses: items after it do not matter
+    for i, item in enumerate(items):
+        try:
+            raw = _read(item)
+            hd = parse_header(raw)
+        except (Unsupported, CorruptJpeg) as exc:
+            deferred = (i, type(exc)("%s: %s" % (_name(item), exc)), False)
+            break
+        raws.append(raw)
+        heads.append(hd)
+        try:
+            tables.append(device_tables(hd))
+        except (Unsupported, CorruptJpeg) as exc:                 # (the host route looks at the scan before it looks at the tables)
+            deferred = (i, type(exc)("%s: %s" % (_name(item), exc)), True)
+            break
+    if not raws:
+        raise _indexed(deferred[1], deferred[0]) from None
+    t1 = time.perf_counter()
+    caps = [_Layout.segments(hd) for hd in heads]
+    desc, total = scan_images([len(r) - hd.scan_start for r, hd in zip(raws, heads)], caps)
+    if total >= 1 << 33:
+        raise Unsupported("more than 8 GiB of files in one batch")
+    staging = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    for r, hd, d in zip(raws, heads, desc):
+        host[d["offset"]:d["offset"] + d["length"]] = np.frombuffer(r, dtype=np.uint8, count=int(d["length"]), offset=hd.scan_start)
+    t2 = time.perf_counter()
+    with torch.cuda.device(dev):
+        src = staging.to(dev, non_blocking=True)
+        scan_ms, compact_ms = ([], []) if events is not None else (None, None)
+        result, ws, desc_dev = K.jpeg_scan(src, desc, stage_ms=scan_ms)
+        t3 = time.perf_counter()
+        back = result.cpu().numpy()                               # the one readback: a few words per image, one per restart marker
+    t4 = time.perf_counter()
+    n = len(raws)
+    report = back[:n * SCAN_REPORT_DTYPE.itemsize].view(SCAN_REPORT_DTYPE)
+    bounds = back[n * SCAN_REPORT_DTYPE.itemsize:].view(np.int64)
+    lay = _Layout(n, subseq_bits)
+    for i, (item, hd, rep, d) in enumerate(zip(items, heads, report, desc)):
+        try:
+            _scan_checks(rep)
+        except (Unsupported, CorruptJpeg) as exc:
+            raise _indexed(type(exc)("%s: %s" % (_name(item), exc)), i) from None
+        if deferred is not None and deferred[0] == i:
+            raise _indexed(deferred[1], i) from None
+        try:
+            lay.check(item, hd, int(rep["n_rst"]) + 1, int(rep["kept"]))
+        except (Unsupported, CorruptJpeg) as exc:
+            raise _indexed(exc, i) from None
+        b = bounds[d["first_bound"]:d["first_bound"] + d["seg_cap"] - 1]
+        lengths = np.diff(np.concatenate([[0], b, [rep["kept"]]])).astype(np.int64)
+        lay.add(Header(hd.width, hd.height, hd.components, hd.layout, hd.qtables, hd.htables, hd.restart_interval, hd.scan_start,
+                       hd.scan_start + int(rep["end"]), None, hd.orientation), tables[i], lengths)
+    if deferred is not None:
+        raise _indexed(deferred[1], deferred[0]) from None
+    p = lay.plan(None)
+    t5 = time.perf_counter()
+    with torch.cuda.device(dev):
+        segs_dev = torch.from_numpy(p.segs.reshape(-1)).to(dev)
+        arena = K.jpeg_compact(src, desc, desc_dev, result, ws, segs_dev, p.segs.shape[1], lay.dword * 4, stage_ms=compact_ms)
+    t6 = time.perf_counter()
+    if timing is not None:
+        timing.update(read_parse=(t1 - t0) * 1e3, stage=(t2 - t1) * 1e3, scan_launch=(t3 - t2) * 1e3, scan_wait=(t4 - t3) * 1e3,
+                      layout=(t5 - t4) * 1e3, compact_launch=(t6 - t5) * 1e3)
+    if events is not None:
+        events.update(scan=scan_ms[0], compact=compact_ms[0], raw_bytes=total, arena_bytes=lay.dword * 4)
+    return p._replace(data=arena)
 
 
 STAGE_NAMES = ("clear", "sync_passes", "scan_write", "dc", "idct", "finish")       # SHDR_JPEG_STAGES of shdr_jpeg_batch.stage_ms
 
 
+def check_unstuff_option(what, unstuff):
+    if unstuff not in ("host", "device"):
+        raise ValueError("%s: unstuff must be 'host' or 'device', got %r" % (what, unstuff))
+    return unstuff
+
+
 class Decoded:
     """what one batch call left on the device (decode() / decode_coefficients() wrap it).  host_ms: wall time of the host half
     (read + parse + unstuff + lay out, then the uploads); stages=True also fills stage_ms, the device-event time of every stage
-    of the library call (STAGE_NAMES), at the price of waiting for the call's last kernel."""
+    of the library call (STAGE_NAMES), at the price of waiting for the call's last kernel.
+    unstuff: who finds the end of the scan, removes the stuffing and fills the segment arena -- "host" (plan: NumPy) or "device"
+    (plan_device: csrc/jpeg_scan.hip; the same arena, the same exceptions).  host_ms then names the parts of that route: read_parse,
+    stage, scan_launch, scan_wait (the host waits for the scan's report), layout, compact_launch, and upload (the other tables);
+    stages=True also fills scan_ms: the device-event times "scan" and "compact" of the two calls, and the bytes they moved."""
 
-    def __init__(self, items, device=None, pixels=True, subseq_bits=SUBSEQ_BITS, out=None, stages=False):
+    def __init__(self, items, device=None, pixels=True, subseq_bits=SUBSEQ_BITS, out=None, stages=False, unstuff="host"):
         import time
         import torch
         lib = _lib.load()
+        check_unstuff_option("jpeg.decode", unstuff)
         self.items = list(items)
         if not self.items:
             raise ValueError("jpeg.decode: no items")
-        t0 = time.perf_counter()
-        self.plan = p = plan(self.items, subseq_bits)
-        t1 = time.perf_counter()
-        self.device = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        device_of = lambda: torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         up = lambda a: torch.from_numpy(a).to(dev)
-        self._keep = (up(p.data), up(p.tables), up(p.images.view(np.uint8)), up(p.segs.reshape(-1)), up(p.sub_seg))
+        t0 = time.perf_counter()
+        if unstuff == "device":
+            self.device = dev = device_of()
+            self.host_ms = {}
+            self.scan_ms = {} if stages else None
+            self.plan = p = plan_device(self.items, dev, subseq_bits, timing=self.host_ms, events=self.scan_ms)
+            t1 = time.perf_counter()
+            self._keep = (p.data, up(p.tables), up(p.images.view(np.uint8)), up(p.segs.reshape(-1)), up(p.sub_seg))
+            self.host_ms["upload"] = (time.perf_counter() - t1) * 1e3
+        else:
+            self.plan = p = plan(self.items, subseq_bits)
+            t1 = time.perf_counter()
+            self.device = dev = device_of()
+            self._keep = (up(p.data), up(p.tables), up(p.images.view(np.uint8)), up(p.segs.reshape(-1)), up(p.sub_seg))
+            self.host_ms = {"plan": (t1 - t0) * 1e3, "upload": (time.perf_counter() - t1) * 1e3}
         data, tables, images, segs, sub_seg = self._keep
-        self.host_ms = {"plan": (t1 - t0) * 1e3, "upload": (time.perf_counter() - t1) * 1e3}
         n_sub = p.sub_seg.size
         ws_bytes = lib.shdr_jpeg_workspace_bytes(n_sub, p.n_blocks, p.plane_bytes)
         if ws_bytes < 0:
@@ -454,7 +658,7 @@ class Decoded:
         stage_ms = (ctypes.c_float * len(STAGE_NAMES))()
         b = Batch(data.data_ptr(), tables.data_ptr(), p.images.ctypes.data, images.data_ptr(), p.segs.ctypes.data, segs.data_ptr(),
                   p.sub_seg.ctypes.data, sub_seg.data_ptr(), ctypes.addressof(self._passes),
-                  ctypes.addressof(stage_ms) if stages else None, p.data.size, p.tables.size, n_sub,
+                  ctypes.addressof(stage_ms) if stages else None, data.numel(), p.tables.size, n_sub,
                   p.n_blocks, p.plane_bytes, p.out_bytes, len(self.items), p.segs.shape[0], p.subseq_bits, 0)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
@@ -521,11 +725,11 @@ def apply_orientation(img, orientation):
     return img.contiguous()
 
 
-def decode(items, device=None, subseq_bits=SUBSEQ_BITS, orient=True):
+def decode(items, device=None, subseq_bits=SUBSEQ_BITS, orient=True, unstuff="host"):
     """paths or bytes -> one uint8 RGB [H, W, 3] device tensor per item, from ONE batch call; byte for byte PIL's
     Image.open(f).convert("RGB") (orient=True: with the EXIF Orientation applied, as hdr_io.read_ldr).  Unsupported / CorruptJpeg
-    name the offending item."""
-    d = Decoded(items, device, True, subseq_bits)
+    name the offending item.  unstuff="device" prepares the scan on the device too (Decoded): the same pixels."""
+    d = Decoded(items, device, True, subseq_bits, unstuff=unstuff)
     d.check()
     res = []
     for i, hd in enumerate(d.plan.headers):
@@ -534,20 +738,21 @@ def decode(items, device=None, subseq_bits=SUBSEQ_BITS, orient=True):
     return res
 
 
-def decode_coefficients(item, device=None, subseq_bits=SUBSEQ_BITS):
+def decode_coefficients(item, device=None, subseq_bits=SUBSEQ_BITS, unstuff="host"):
     """one file -> per component the quantised coefficients int16 [bh, bw, 64] on the device (natural order, DC prediction undone,
     the padded block grid): for tests and debugging"""
-    d = Decoded([item], device, False, subseq_bits)
+    d = Decoded([item], device, False, subseq_bits, unstuff=unstuff)
     d.check()
     return d.coefficients(0)
 
 
-def read_ldr_device(path, device=None):
+def read_ldr_device(path, device=None, unstuff="host"):
     """hdr_io.read_ldr(path) as a uint8 device tensor: decoded on the device when the file is in scope, by PIL and uploaded when it is
-    not (Unsupported: progressive, CMYK, ..., or no JPEG at all).  CorruptJpeg propagates."""
+    not (Unsupported: progressive, CMYK, ..., or no JPEG at all).  CorruptJpeg propagates.  unstuff: as decode()."""
     import torch
+    check_unstuff_option("jpeg.read_ldr_device", unstuff)
     try:
-        return decode([path], device)[0]
+        return decode([path], device, unstuff=unstuff)[0]
     except Unsupported:
         pass
     try:
