@@ -888,7 +888,8 @@ int shdr_lin_frontend_bwd_f16(const float* img, const void* dF, float* dimg, int
  *        ssim_mu = SSIM (Wang et al. 2004) of T(p) against T(g) per channel: 11x11 Gaussian window of sigma 1.5 with weights summing
  *                  to 1, the (H-10)(W-10) valid windows only, weighted population variances, C1 = 1e-4, C2 = 9e-4, mean over
  *                  windows and channels.
- *      peak == 0 (an all-black gt) is not special-cased: the results are the IEEE ones (NaN / inf).
+ *      peak == 0 (an all-black gt) is not special-cased: the results are the IEEE ones -- mse_l = inf (NaN for a black pred),
+ *      mse_mu = ssim_mu = NaN (T(0 / 0) is NaN: the min passes it on), l1_logc finite.
  *      Every reduction has two stages: a grid that depends on the shape alone writes float64 partial sums into `workspace`
  *      (shdr_metrics_workspace_bytes(N, H, W) bytes, owned by the caller, 8-byte aligned), one block per image adds them in a fixed
  *      order.  No floating-point atomics: the same inputs give the same bits.  NULL pointer -> SHDR_E_NULL; H < 11, W < 11 or

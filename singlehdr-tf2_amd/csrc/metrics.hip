@@ -122,8 +122,15 @@ __global__ __launch_bounds__(64) void pair_moments_final_kernel(const double* __
 }
 
 // ---- the fused pass -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float tone(float x, float peak, float mu, float inv_log) {
+// fminf drops a NaN operand: tone_sat maps 0 / 0 (a black pixel under a peak of 0) to T = 1, which the preview keeps (a defined
+// code).  The metrics use tone, which lets the NaN through: an all-black ground truth must not report SSIM = 1.  For every other
+// quotient the two give the same bits.
+__device__ __forceinline__ float tone_sat(float x, float peak, float mu, float inv_log) {
   return log1pf(mu * fminf(x / peak, 1.0f)) * inv_log;
+}
+__device__ __forceinline__ float tone(float x, float peak, float mu, float inv_log) {
+  const float q = x / peak;
+  return log1pf(mu * (q > 1.0f ? 1.0f : q)) * inv_log;
 }
 
 // part[(n * tiles + tile) * 4 + {0,1,2,3}] = sum (p-g)^2, sum (T(p)-T(g))^2, sum |logc(p)-logc(g)| over the tile's own pixels,
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(256) void tonemap_u8_kernel(const float* __restrict
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float v = fmaxf(s * x[3 * p + (reverse ? 2 - c : c)], 0.0f);
-      y[3 * p + c] = (uint8_t)rintf(255.0f * powf(tone(v, pk, mu, inv_log), 1.0f / 2.2f));
+      y[3 * p + c] = (uint8_t)rintf(255.0f * powf(tone_sat(v, pk, mu, inv_log), 1.0f / 2.2f));
     }
   }
 }

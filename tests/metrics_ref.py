@@ -77,10 +77,63 @@ def hdr_metrics(pred, gt, normalise=True, mu=5000.0):
     return {k: np.array([r[k] for r in rows], dtype=np.float64) for k in rows[0]}
 
 
-def tonemap_u8(x, peak=None, reverse_channels=False, mu=5000.0):
-    """[H, W, 3] -> uint8: round(255 * T(max(x, 0))^(1/2.2)); peak None -> the image's maximum"""
-    x = np.maximum(np.asarray(x, dtype=np.float64), 0.0)
+def tonemap_value(x, peak=None, reverse_channels=False, mu=5000.0, scale=None):
+    """[H, W, 3] -> float64: 255 * T(max(scale * x, 0))^(1/2.2) before the rounding to a code, and T itself; scale None -> 1,
+    peak None -> the scaled image's maximum"""
+    x = np.asarray(x, dtype=np.float64)
+    if scale is not None:
+        x = float(scale) * x
+    x = np.maximum(x, 0.0)
     if reverse_channels:
         x = x[..., ::-1]
     peak = float(x.max()) if peak is None else float(peak)
-    return np.rint(255.0 * tone(x, peak, mu) ** (1.0 / 2.2)).astype(np.uint8)
+    t = tone(x, peak, mu)
+    return 255.0 * t ** (1.0 / 2.2), t
+
+
+def tonemap_u8(x, peak=None, reverse_channels=False, mu=5000.0, scale=None):
+    """[H, W, 3] -> uint8: round(255 * T(max(scale * x, 0))^(1/2.2)); scale None -> 1, peak None -> the scaled image's maximum"""
+    return np.rint(tonemap_value(x, peak, reverse_channels, mu, scale)[0]).astype(np.uint8)
+
+
+# ---- exact inputs (tests/test_gpu_metrics_exact.py) ---------------------------------------------------------------------------------
+TAPS = 11
+HALO = TAPS - 1
+
+
+def ownership_classes(h, w, th, tw):
+    """[h, w] int: the class 5 * cy + cx of a pixel in the tiling of csrc/metrics.hip (a tile of th x tw windows stages
+    (th + 10) x (tw + 10) pixels).  Per axis: 4 the band of 10 pixels beyond the last window, 1 the first staged line of a tile,
+    2 the last line a tile owns, 3 the last line a tile stages (owned by the next tile), 0 the interior."""
+    def axis(n, t):
+        i = np.arange(n)
+        c = np.zeros(n, dtype=np.int64)
+        c[(i % t == (t + HALO - 1) % t) & (i >= t + HALO - 1)] = 3
+        c[i % t == t - 1] = 2
+        c[i % t == 0] = 1
+        c[i >= n - HALO] = 4
+        return c
+    return 5 * axis(h, th)[:, None] + axis(w, tw)[None, :]
+
+
+def exact_pair(shape, th, tw, seed):
+    """(pred, gt, delta) float32 [N, H, W, 3] on which mse_l has no rounding: gt holds multiples of 2^-10 in [2^-4, 1] with an exact
+    1.0 per image (peak = 1 without normalisation; image 0 has it at its LAST element), pred = gt + delta with delta in
+    +-{2^-4, 2^-6} chosen per image by the ownership class of the pixel.  Every p - g and its square is exact in float32 and every
+    sum of them in float64, in any order."""
+    n, h, w = shape
+    rng = np.random.default_rng(seed)
+    gt = rng.integers(64, 1025, size=(n, h, w, 3)).astype(np.float64) / 1024.0
+    cls = ownership_classes(h, w, th, tw)
+    delta = np.empty((n, h, w, 3))
+    for i in range(n):
+        table = rng.choice([2.0 ** -4, -2.0 ** -4, 2.0 ** -6, -2.0 ** -6], size=25)
+        delta[i] = table[cls][:, :, None]
+        gt[i].reshape(-1)[-1 if i == 0 else int(rng.integers(0, h * w * 3))] = 1.0
+    pred = gt + delta
+    out = []
+    for a in (pred, gt, delta):
+        assert np.array_equal(a.astype(np.float32).astype(np.float64), a)
+        out.append(a.astype(np.float32))
+    assert pred.min() >= 0.0 and gt.min() >= 2.0 ** -4 and (gt.max(axis=(1, 2, 3)) == 1.0).all()
+    return tuple(out)

@@ -205,6 +205,63 @@ def test_restatement_resize_rule():
     assert D.resized_shape(300, 200) == (768, 512)
 
 
+def test_restatement_edge_axes():
+    """the clamp rules on 1- and 2-pixel axes: a one-pixel axis has both taps on its only line; the horizontal rule gives the edge
+    tap the whole weight, the vertical rule keeps the weight and clamps the rows"""
+    for clamp in (False, True):
+        s0, s1, f = R._axis(5, 1, clamp)
+        assert s0.tolist() == [0] * 5 == s1.tolist()
+        assert (f == 0).all() if clamp else (f != 0).any()
+    s0, s1, f = R._axis(7, 2, True)
+    assert s0.tolist() == [0, 0, 0, 0, 0, 1, 1] and s1.tolist() == [1] * 7
+    assert (f[[0, 1, 5, 6]] == 0).all() and f[3] == 0.5 and 0 < f[2] < f[3] < f[4] < 1
+    s0, s1, g = R._axis(7, 2, False)
+    assert s0.tolist() == [0, 0, 0, 0, 0, 1, 1] and s1.tolist() == [0, 0, 1, 1, 1, 1, 1]
+    assert (g[[0, 1, 5, 6]] != 0).all() and np.array_equal(g[2:5], f[2:5])
+    x = np.float32([[[1.0, 2.0, 3.0]]])
+    y, _ = R.resize_linear(x, (4, 5))
+    assert np.abs(y - x).max() <= 2.0 ** -22                    # v (1 - f) + v f: the value up to the two roundings
+    y, _ = R.resize_linear(np.float32([[[0.0], [1.0]], [[2.0], [3.0]]]), (7, 7))
+    assert y[0, 0, 0] == 0.0 and abs(y[-1, -1, 0] - 3.0) <= 2.0 ** -21 and (np.diff(y[..., 0], axis=1) >= 0).all()
+
+
+def test_restatement_decoders():
+    rng = np.random.default_rng(12)
+    img = rng.integers(0, 256, size=(9, 11, 4), dtype=np.uint8)
+    img[0, :5, 3] = [0, 1, 9, 128, 255]
+    img[1, :2, :3] = [[0, 0, 0], [255, 255, 255]]
+    img[1, :2, 3] = 1
+    bgr = R.rgbe_bgr(img)
+    assert bgr.dtype == np.float32 and np.array_equal(bgr, IO.rgbe_decode(img)[:, :, ::-1])
+    assert (bgr[0, 0] == 0).all() and bgr[1, 1, 0] == np.float32(255 * 2.0 ** -135) and 0 < bgr[1, 1, 0] < np.finfo(np.float32).tiny
+    assert np.isfinite(bgr).all() and bgr[0, 4].max() <= 255 * 2.0 ** 119
+    h = np.arange(65536, dtype=np.uint16)
+    f = R.half_bits_to_float(h)
+    ref = h.view(np.float16).astype(np.float32)
+    finite = ~np.isnan(ref)
+    assert np.array_equal(f[finite].view(np.uint32), ref[finite].view(np.uint32))          # +-0, subnormals, +-inf included
+    assert np.isnan(f[~finite]).all() and f.view(np.uint32)[0x7C01] == 0x7F802000 and f.view(np.uint32)[0xFE00] == 0xFFC00000
+    c = R.clip0(np.float32([-1.0, -0.0, 0.5, np.inf, -np.inf, np.nan]))
+    assert c.view(np.uint32)[:5].tolist() == [0, 0x80000000, 0x3F000000, 0x7F800000, 0] and np.isnan(c[5])
+
+
+def test_cropped_patch_equals_full_patch():
+    """dataset_ref.patch_crop (the reference of tests/test_gpu_dataset_exact.py, which evaluates only the crop's rows and columns)
+    against patch() at P = 256 on the parameter table of the sampler's GPU test: the same bits"""
+    from test_gpu_dataset import _forced_params
+    rng = np.random.default_rng(40)
+    imgs = [np.exp(rng.normal(0.0, 2.5, hw + (3,))).astype(np.float32) for hw in ((512, 530), (540, 512))]
+    params = _forced_params(2)
+    assert len(params) == 2 * 8 + 64 and {tuple(r) for r in params[:, 4:7].tolist()} == {(k, a, b) for k in range(4) for a in (0, 1)
+                                                                                        for b in (0, 1)}
+    for idx, S, y0, x0, k, f0, f1 in params.tolist():
+        img, mean = imgs[(idx // 2) % 2], np.float32(0.37 + idx)
+        full, tap = R.patch(img, idx, S, y0, x0, k, f0, f1, mean)
+        crop, ctap = R.patch_crop(img, idx, S, y0, x0, k, f0, f1, mean, 256)
+        assert np.array_equal(full.view(np.uint32), crop.view(np.uint32)), (idx, S, y0, x0, k, f0, f1)
+        assert np.array_equal(tap, ctap)
+
+
 def test_import_without_data_files(tmp_path):
     code = ("import sys; sys.path.insert(0, %r)\n"
             "from dataset import get_train_dataset, RandDatasetReader\n"

@@ -106,16 +106,20 @@ def test_read_exr_special_values(tmp_path):
         assert got.view(np.uint32)[0, 11, 0] == 0x7f802000      # signalling NaN payload kept (numpy's conversion)
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 4095, 4096, 4097, 8191, 40000, 400001])
+@pytest.mark.parametrize("n", [1, 2, 3, 4095, 4096, 4097, 8191, 8192, 8193, 40000, 400001])
 def test_unpredict_kernel_matches_restatement(n):
+    """n = 8192, 8193: h = 4096 and 4097 pairs, a whole number of 256 x 8-pair steps and one pair more (both halves carry into a
+    second step).  An EMPTY coded chunk lies between two others: its workgroup writes nothing and its neighbours keep their bytes."""
     rng = np.random.default_rng(n)
-    chunks = [rng.integers(0, 256, n, dtype=np.uint8).tobytes(), bytes(range(256)) * 3, rng.integers(0, 256, 7, dtype=np.uint8).tobytes()]
-    coded = np.array([1, 0, 1], dtype=np.uint8)
+    chunks = [rng.integers(0, 256, n, dtype=np.uint8).tobytes(), b"", bytes(range(256)) * 3, b"",
+              rng.integers(0, 256, 7, dtype=np.uint8).tobytes()]
+    coded = np.array([1, 1, 0, 0, 1], dtype=np.uint8)
     data = np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()
     offsets = np.concatenate([[0], np.cumsum([len(c) for c in chunks])]).astype(np.int64)
     dev = torch.device("cuda")
     got = _host(K.exr_unpredict(torch.from_numpy(data).to(dev), torch.from_numpy(offsets).to(dev), torch.from_numpy(coded).to(dev)))
-    want = X.unpredict(chunks[0]) + chunks[1] + X.unpredict(chunks[2])
+    want = X.unpredict(chunks[0]) + X.unpredict(chunks[1]) + chunks[2] + chunks[3] + X.unpredict(chunks[4])
+    assert offsets[1] == offsets[2] and offsets[3] == offsets[4] and len(want) == n + 768 + 7
     assert got.tobytes() == want
 
 

@@ -101,6 +101,59 @@ def test_tonemap_reference_end_points():
     assert np.array_equal(R.tonemap_u8(x, reverse_channels=True), y[..., ::-1])
 
 
+def test_tonemap_reference_scale_and_value():
+    """the `scale` argument multiplies before the clamp; tonemap_u8 is the rounding of tonemap_value"""
+    rng = np.random.default_rng(9)
+    x = rng.uniform(-0.5, 5.0, (11, 12, 3))
+    assert np.array_equal(R.tonemap_u8(x, peak=3.0, scale=0.75), R.tonemap_u8(0.75 * x, peak=3.0))
+    assert np.array_equal(R.tonemap_u8(x, scale=2.0), R.tonemap_u8(x))                 # peak None follows the scaled image
+    assert np.array_equal(R.tonemap_u8(x, peak=3.0, scale=-1.0), R.tonemap_u8(-x, peak=3.0))
+    val, t = R.tonemap_value(x, 3.0, True, 5000.0, 0.75)
+    assert np.array_equal(np.rint(val).astype(np.uint8), R.tonemap_u8(x, 3.0, True, 5000.0, 0.75))
+    assert np.array_equal(val, 255.0 * t ** (1.0 / 2.2)) and t.min() == 0.0 and t.max() == 1.0
+    # the law of the GPU test: the share of values within k * 2^-24 (relative) of a rounding tie stays far below its 0.5 % condition
+    x = rng.integers(0, 1025, size=(2, 300, 300, 3)) / 1024.0 * rng.uniform(1.0, 4.0, (2, 300, 300, 3))
+    val, _ = R.tonemap_value(x.astype(np.float32), 3.0)
+    tie = np.abs(val - (np.floor(val) + 0.5))
+    for k, share in ((16, 0.001), (64, 0.004)):
+        assert (tie <= val * k * 2.0 ** -24).mean() <= share
+
+
+def test_exact_pair_and_ownership_classes():
+    th, tw = 16, 32
+    cls = R.ownership_classes(49, 83, th, tw)
+    assert cls.shape == (49, 83) and set(np.unique(cls // 5)) == {0, 1, 2, 3, 4} == set(np.unique(cls % 5))
+    rows = (cls // 5)[:, 0].tolist()
+    assert rows[0] == 1 and rows[15] == 2 and rows[16] == 1 and rows[25] == 3 and rows[31] == 2 and rows[38] == 0
+    assert rows[39:] == [4] * 10 and rows[9] == 0 and rows[41 - 16] == 3
+    cols = (cls % 5)[0].tolist()
+    assert cols[0] == 1 and cols[31] == 2 and cols[32] == 1 and cols[41] == 3 and cols[72] == 0 and cols[73:] == [4] * 10
+    assert set(np.unique(R.ownership_classes(11, 11, th, tw))) == {6, 9, 21, 24}
+    pred, gt, delta = R.exact_pair((3, 27, 43), th, tw, seed=5)
+    assert pred.dtype == gt.dtype == np.float32 and gt[0].reshape(-1)[-1] == 1.0
+    assert set(np.abs(delta).ravel().tolist()) == {2.0 ** -4, 2.0 ** -6}
+    assert np.array_equal(pred.astype(np.float64) - gt.astype(np.float64), delta.astype(np.float64))
+    m = R.hdr_metrics(pred, gt, normalise=False)
+    assert np.array_equal(m["peak"], np.ones(3)) and np.array_equal(m["scale_gt"], np.ones(3))
+    # the reference's own mean is exact: multiples of 2^-12 below 2^53 add without rounding in any order
+    assert np.array_equal(m["mse_l"], (delta.astype(np.float64) ** 2).sum(axis=(1, 2, 3)) / (27 * 43 * 3.0))
+    # normalised: the mean is the exact sum over the count, the scale its float32 rounding
+    n = R.hdr_metrics(pred, gt, normalise=True)
+    mean = gt.astype(np.float64).sum(axis=(1, 2, 3)) / (27 * 43 * 3.0)
+    assert np.array_equal(n["scale_gt"], (0.5 / (1e-6 + mean)).astype(np.float32).astype(np.float64))
+    assert np.array_equal(n["peak"], n["scale_gt"] * 1.0)
+
+
+def test_reference_of_a_black_ground_truth():
+    """peak 0: mse_l is inf, everything that goes through T(0 / 0) is NaN, the loss stays finite -- what csrc/metrics.hip must
+    report for such an image (tests/test_gpu_metrics_exact.py)"""
+    pred, _ = _pair(6)
+    with np.errstate(all="ignore"):
+        m = R.hdr_metrics_one(pred, np.zeros_like(pred), normalise=False)
+    assert m["peak"] == 0.0 and m["mse_l"] == np.inf and np.isnan(m["mse_mu"]) and np.isnan(m["ssim_mu"])
+    assert np.isfinite(m["l1_logc"]) and m["l1_logc"] > 0.0
+
+
 def test_no_cpu_fallback(shdr):
     x = torch.rand(1, 16, 16, 3)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
