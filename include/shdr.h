@@ -579,7 +579,8 @@ int64_t shdr_rgbe_rle_decode(const uint8_t* data, int64_t size, int width, int h
  * Four stream-ordered launches (first rows, coded sizes per row and component, an exclusive scan over all rows, the write pass), no
  * atomics -- the same input gives the same bytes -- no host wait and no allocation.  Arguments are checked before anything is
  * launched.  The _timed form also fills stage_ms [SHDR_RLE_STAGES] with the device-event times of the four launches and then waits
- * for the last one (measurement only). */
+ * for the last one (measurement only).  For every stage_ms of this library: an event call that fails never fails the call that is
+ * measured; each time that could not be read is reported as -1. */
 #define SHDR_RLE_STAGES 4
 int shdr_rgbe_rle_encode_batch_sizes(const int32_t* shapes, int n_images, int64_t* out_bytes, int64_t* workspace_bytes);
 int shdr_rgbe_rle_encode_batch(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shapes_dev, int n_images, uint8_t* out,

@@ -1997,21 +1997,59 @@ def exr_load_resize(planes, offsets, lines, row_bytes, chan_off, chan_type, h0, 
 
 
 # ---------------------------------------------------------------------------
+# what the batched byte coders below (deflate, inflate, the JPEG scan) share: offset tables and stage times
+# ---------------------------------------------------------------------------
+def _offsets_pair(what, name, offsets, offsets_dev):
+    """(host int64 array, device tensor or None) of an offset table given as a host array (+ the caller's device copy) or a tensor"""
+    if isinstance(offsets, torch.Tensor):
+        host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
+        dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
+    else:
+        host, dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
+        if dev is not None and _chk(dev, name + "_dev", torch.int64).numel() != host.size:
+            raise ValueError("%s: %s_dev is not a copy of %s" % (what, name, name))
+    if host.ndim != 1 or host.size < 2:
+        raise ValueError("%s: %s must be [n_chunks + 1]" % (what, name))
+    return host, dev
+
+
+class _stage_times:
+    """with _stage_times(stage_ms, n) as ms: the float [n] that a library call fills with the device times of its n stages, or None
+    where the caller gave no list (stage_ms is None); after the call the times replace the contents of the list"""
+
+    def __init__(self, stage_ms, n):
+        self._list, self._ms = stage_ms, (ctypes.c_float * n)() if stage_ms is not None else None
+
+    def __enter__(self):
+        return self._ms
+
+    def __exit__(self, exc_type, *exc):
+        if exc_type is None and self._ms is not None:
+            self._list[:] = list(self._ms)
+        return False
+
+
+# ---------------------------------------------------------------------------
 # OpenEXR output (exr.py encode_exr), see csrc/exr_write.hip and csrc/deflate.hip
 # ---------------------------------------------------------------------------
 DEFLATE_TILE = 1024          # SHDR_DEFLATE_TILE: symbols per tile of the device writer
 
 
-def deflate_huffman_host(chunk):
-    """Huffman-only zlib stream of a chunk of bytes (libshdr host routine; zlib.decompress reads it).  The stream is returned
-    whatever its size: a chunk counts as coded only if len(stream) < len(chunk)"""
+def _deflate_host(fn_name, chunk):
+    """deflate_huffman_host and deflate_lz_host: the stream that the library's host routine `fn_name` writes for a chunk"""
     lib = _lib.load()
     src = np.frombuffer(bytes(chunk), dtype=np.uint8)
-    out = np.empty(2 * src.size + 512, dtype=np.uint8)                    # 1122 + 15 bits per symbol at the very most
-    n = lib.shdr_deflate_huffman_host(_hptr(src), src.size, _hptr(out), out.size)
+    out = np.empty(2 * src.size + 512, dtype=np.uint8)                    # a header of 1122 or 1354 bits + 16 per byte at the very most
+    n = getattr(lib, fn_name)(_hptr(src), src.size, _hptr(out), out.size)
     if n < 0:
         raise ValueError(lib.shdr_last_error().decode())
     return out[:n].tobytes()
+
+
+def deflate_huffman_host(chunk):
+    """Huffman-only zlib stream of a chunk of bytes (libshdr host routine; zlib.decompress reads it).  The stream is returned
+    whatever its size: a chunk counts as coded only if len(stream) < len(chunk)"""
+    return _deflate_host("shdr_deflate_huffman_host", chunk)
 
 
 def deflate_huffman_lengths_host(chunk):
@@ -2025,6 +2063,35 @@ def deflate_huffman_lengths_host(chunk):
     return out
 
 
+def _deflate_batch(what, sizes_fn_name, batch_fn_name, data, offsets, raw, pad, front, stage_ms, offsets_dev):
+    """deflate_huffman and deflate_lz: the same arguments, buffers and call; the two library symbols differ"""
+    lib = _lib.load()
+    data = _chk(data, "data", torch.uint8)
+    off_host, off_dev = _offsets_pair(what, "offsets", offsets, offsets_dev)
+    if data.dim() != 1 or int(off_host[-1]) > data.numel():
+        raise ValueError("%s: expected data [size] and offsets [n_chunks + 1] that end within it" % what)
+    if raw is not None:
+        raw = _chk(raw, "raw", torch.uint8)
+        if raw.dim() != 1 or raw.numel() < int(off_host[-1]):
+            raise ValueError("%s: raw must hold the chunks' bytes too" % what)
+    n = off_host.size - 1
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(getattr(lib, sizes_fn_name)(_hptr(off_host), n, int(pad), ctypes.byref(out_b), ctypes.byref(ws_b)), sizes_fn_name)
+    dev = data.device
+    if off_dev is None:
+        off_dev = torch.from_numpy(off_host).to(dev)
+    front = int(front)
+    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
+    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    coded = torch.empty(n, device=dev, dtype=torch.uint8)
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    with _stage_times(stage_ms, 3) as ms:
+        _lib.check(getattr(lib, batch_fn_name)(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n, int(pad),
+                                               out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws), _stream(), ms),
+                   batch_fn_name)
+    return out, out_offsets, coded
+
+
 def deflate_huffman(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offsets_dev=None):
     """Huffman-only zlib streams of a batch of chunks, coded on the device (csrc/deflate.hip): byte for byte what the host routine
     shdr_deflate_huffman_host writes.  data: uint8 device tensor; offsets: int64 [n + 1] (host array or tensor), chunk c is
@@ -2034,40 +2101,8 @@ def deflate_huffman(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offs
     of every stored chunk; front: bytes left free in front of all of them.  Stream-ordered, no host wait.  stage_ms: a list that
     receives the three launches' device times (measurement: the call then waits); offsets_dev: the device copy of a host `offsets`,
     if the caller has one."""
-    lib = _lib.load()
-    data = _chk(data, "data", torch.uint8)
-    if isinstance(offsets, torch.Tensor):
-        off_host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
-        off_dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
-    else:
-        off_host, off_dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
-        if off_dev is not None and _chk(off_dev, "offsets_dev", torch.int64).numel() != off_host.size:
-            raise ValueError("deflate_huffman: offsets_dev is not a copy of offsets")
-    if data.dim() != 1 or off_host.ndim != 1 or off_host.size < 2 or int(off_host[-1]) > data.numel():
-        raise ValueError("deflate_huffman: expected data [size] and offsets [n_chunks + 1] that end within it")
-    if raw is not None:
-        raw = _chk(raw, "raw", torch.uint8)
-        if raw.dim() != 1 or raw.numel() < int(off_host[-1]):
-            raise ValueError("deflate_huffman: raw must hold the chunks' bytes too")
-    n = off_host.size - 1
-    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(lib.shdr_deflate_huffman_batch_sizes(_hptr(off_host), n, int(pad), ctypes.byref(out_b), ctypes.byref(ws_b)),
-               "shdr_deflate_huffman_batch_sizes")
-    dev = data.device
-    if off_dev is None:
-        off_dev = torch.from_numpy(off_host).to(dev)
-    front = int(front)
-    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
-    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
-    coded = torch.empty(n, device=dev, dtype=torch.uint8)
-    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
-    ms = (ctypes.c_float * 3)() if stage_ms is not None else None
-    _lib.check(lib.shdr_deflate_huffman_batch(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n,
-                                              int(pad), out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws),
-                                              _stream(), ms), "shdr_deflate_huffman_batch")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
-    return out, out_offsets, coded
+    return _deflate_batch("deflate_huffman", "shdr_deflate_huffman_batch_sizes", "shdr_deflate_huffman_batch", data, offsets, raw, pad, front,
+                          stage_ms, offsets_dev)
 
 
 DEFLATE_LZ_TILE = 1024       # SHDR_DEFLATE_LZ_TILE: positions per tile of the device writer of deflate_lz
@@ -2077,13 +2112,7 @@ DEFLATE_LZ_LITERAL = 0x80000000   # SHDR_DEFLATE_LZ_LITERAL
 def deflate_lz_host(chunk):
     """zlib stream with LZ77 matches of a chunk of bytes (libshdr host routine, csrc/deflate_lz.h; zlib.decompress reads it).  The
     stream is returned whatever its size: a chunk counts as coded only if len(stream) < len(chunk)"""
-    lib = _lib.load()
-    src = np.frombuffer(bytes(chunk), dtype=np.uint8)
-    out = np.empty(2 * src.size + 512, dtype=np.uint8)                    # 1354 + 16 bits per position at the very most
-    n = lib.shdr_deflate_lz_host(_hptr(src), src.size, _hptr(out), out.size)
-    if n < 0:
-        raise ValueError(lib.shdr_last_error().decode())
-    return out[:n].tobytes()
+    return _deflate_host("shdr_deflate_lz_host", chunk)
 
 
 def deflate_lz_parse_host(chunk):
@@ -2107,40 +2136,8 @@ def deflate_lz(data, offsets, raw=None, pad=0, front=0, stage_ms=None, offsets_d
     """zlib streams with LZ77 matches of a batch of chunks, coded on the device (csrc/deflate_lz.hip): byte for byte what the host
     routine shdr_deflate_lz_host writes.  Arguments and the returned (bytes, out_offsets, coded) as deflate_huffman; the workspace
     holds 4 bytes per input byte for the parse's tokens.  stage_ms: the device times of the parse, scan and write launches."""
-    lib = _lib.load()
-    data = _chk(data, "data", torch.uint8)
-    if isinstance(offsets, torch.Tensor):
-        off_host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
-        off_dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
-    else:
-        off_host, off_dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
-        if off_dev is not None and _chk(off_dev, "offsets_dev", torch.int64).numel() != off_host.size:
-            raise ValueError("deflate_lz: offsets_dev is not a copy of offsets")
-    if data.dim() != 1 or off_host.ndim != 1 or off_host.size < 2 or int(off_host[-1]) > data.numel():
-        raise ValueError("deflate_lz: expected data [size] and offsets [n_chunks + 1] that end within it")
-    if raw is not None:
-        raw = _chk(raw, "raw", torch.uint8)
-        if raw.dim() != 1 or raw.numel() < int(off_host[-1]):
-            raise ValueError("deflate_lz: raw must hold the chunks' bytes too")
-    n = off_host.size - 1
-    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(lib.shdr_deflate_lz_batch_sizes(_hptr(off_host), n, int(pad), ctypes.byref(out_b), ctypes.byref(ws_b)),
-               "shdr_deflate_lz_batch_sizes")
-    dev = data.device
-    if off_dev is None:
-        off_dev = torch.from_numpy(off_host).to(dev)
-    front = int(front)
-    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
-    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
-    coded = torch.empty(n, device=dev, dtype=torch.uint8)
-    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
-    ms = (ctypes.c_float * 3)() if stage_ms is not None else None
-    _lib.check(lib.shdr_deflate_lz_batch(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n,
-                                         int(pad), out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws),
-                                         _stream(), ms), "shdr_deflate_lz_batch")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
-    return out, out_offsets, coded
+    return _deflate_batch("deflate_lz", "shdr_deflate_lz_batch_sizes", "shdr_deflate_lz_batch", data, offsets, raw, pad, front, stage_ms,
+                          offsets_dev)
 
 
 # ---------------------------------------------------------------------------
@@ -2172,20 +2169,6 @@ def inflate_host(stream, capacity):
     if n < 0:
         raise ValueError(lib.shdr_last_error().decode())
     return out[:n].tobytes(), st.value
-
-
-def _offsets_pair(what, name, offsets, offsets_dev):
-    """(host int64 array, device tensor or None) of an offset table given as a host array (+ the caller's device copy) or a tensor"""
-    if isinstance(offsets, torch.Tensor):
-        host = np.ascontiguousarray(offsets.detach().cpu().numpy(), dtype=np.int64)
-        dev = offsets if offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() else None
-    else:
-        host, dev = np.ascontiguousarray(offsets, dtype=np.int64), offsets_dev
-        if dev is not None and _chk(dev, name + "_dev", torch.int64).numel() != host.size:
-            raise ValueError("%s: %s_dev is not a copy of %s" % (what, name, name))
-    if host.ndim != 1 or host.size < 2:
-        raise ValueError("%s: %s must be [n_chunks + 1]" % (what, name))
-    return host, dev
 
 
 def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets_dev=None, dst_offsets_dev=None, dst=None):
@@ -2226,13 +2209,11 @@ def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets
         d_dev = torch.from_numpy(d_host).to(dev)
     status = torch.empty(n, device=dev, dtype=torch.int32)
     written = torch.empty(n, device=dev, dtype=torch.int64)
-    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
-    _lib.check(lib.shdr_inflate_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev),
-                                      _ptr(dst) if dst.numel() else None, dst.numel(), _hptr(d_host), _ptr(d_dev),
-                                      _ptr(mode) if mode is not None else None, n, _ptr(status), _ptr(written), _stream(), ms),
-               "shdr_inflate_batch")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
+    with _stage_times(stage_ms, 1) as ms:
+        _lib.check(lib.shdr_inflate_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev),
+                                          _ptr(dst) if dst.numel() else None, dst.numel(), _hptr(d_host), _ptr(d_dev),
+                                          _ptr(mode) if mode is not None else None, n, _ptr(status), _ptr(written), _stream(), ms),
+                   "shdr_inflate_batch")
     return dst, written, status
 
 
@@ -2294,12 +2275,10 @@ def jpeg_scan(src, images, images_dev=None, stage_ms=None):
         raise ValueError(lib.shdr_last_error().decode())
     ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
     result = torch.empty(n * JPEG_SCAN_REPORT_BYTES + 8 * n_bounds, device=dev, dtype=torch.uint8)
-    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
-    _lib.check(lib.shdr_jpeg_scan(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n, _ptr(result),
-                                  ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
-                                  _ptr(ws), _stream(), ms), "shdr_jpeg_scan")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
+    with _stage_times(stage_ms, 1) as ms:
+        _lib.check(lib.shdr_jpeg_scan(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n, _ptr(result),
+                                      ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
+                                      _ptr(ws), _stream(), ms), "shdr_jpeg_scan")
     return result, ws, images_dev
 
 
@@ -2319,13 +2298,11 @@ def jpeg_compact(src, images, images_dev, result, workspace, seg_dword, seg_stri
         raise ValueError("jpeg_compact: seg_dword must hold %d segments of stride %d" % (n_segs, seg_stride))
     _chk(workspace, "workspace", torch.uint8)
     arena = torch.empty(arena_bytes, device=src.device, dtype=torch.uint8)
-    ms = (ctypes.c_float * 1)() if stage_ms is not None else None
-    _lib.check(lib.shdr_jpeg_compact(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n,
-                                     ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
-                                     _ptr(seg_dword), seg_stride, seg_dword.numel() // seg_stride, _ptr(arena) if arena_bytes else None,
-                                     arena_bytes, _ptr(workspace), _stream(), ms), "shdr_jpeg_compact")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
+    with _stage_times(stage_ms, 1) as ms:
+        _lib.check(lib.shdr_jpeg_compact(_ptr(src) if src.numel() else None, src.numel(), _hptr(images), _ptr(images_dev), n,
+                                         ctypes.c_void_p(result.data_ptr() + n * JPEG_SCAN_REPORT_BYTES) if n_bounds else None, n_bounds,
+                                         _ptr(seg_dword), seg_stride, seg_dword.numel() // seg_stride, _ptr(arena) if arena_bytes else None,
+                                         arena_bytes, _ptr(workspace), _stream(), ms), "shdr_jpeg_compact")
     return arena
 
 

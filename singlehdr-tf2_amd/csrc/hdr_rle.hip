@@ -292,29 +292,18 @@ int encode_batch(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shap
   const RleWorkspace w = carve(workspace, n_images, rows);
   hipStream_t st = S(stream);
   const uint32_t* px = reinterpret_cast<const uint32_t*>(rgbe);
-  hipEvent_t ev[SHDR_RLE_STAGES + 1] = {};
-  if (stage_ms)
-    for (auto& e : ev) SHDR_REQUIRE(hipEventCreate(&e) == hipSuccess, SHDR_E_LAUNCH, "%s: hipEventCreate failed", what);
-  auto mark = [&](int i) { if (stage_ms) (void)hipEventRecord(ev[i], st); };
-  mark(0);
+  shdr::StageTimer<SHDR_RLE_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(rle_setup_kernel, dim3(1), dim3(64), 0, st, shapes_dev, n_images, w.rowstart, w.pixoff);
-  mark(1);
+  timer.mark();
   hipLaunchKernelGGL(rle_rows_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, px, shapes_dev, n_images, w.rowstart, w.pixoff,
                      w.sizes, w.rowoff, out, out_capacity);
-  mark(2);
+  timer.mark();
   hipLaunchKernelGGL(rle_scan_kernel, dim3(1), dim3(1024), 0, st, w.sizes, rows, w.rowoff, w.rowstart, n_images, offsets);
-  mark(3);
+  timer.mark();
   hipLaunchKernelGGL(rle_rows_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, px, shapes_dev, n_images, w.rowstart, w.pixoff,
                      w.sizes, w.rowoff, out, out_capacity);
-  mark(4);
-  const int rc = shdr::check_launch(what);
-  if (stage_ms) {
-    const bool ok = hipEventSynchronize(ev[SHDR_RLE_STAGES]) == hipSuccess;
-    for (int i = 0; i < SHDR_RLE_STAGES; ++i)
-      if (!ok || hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) stage_ms[i] = -1.0f;
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
-  return rc;
+  timer.mark();
+  return shdr::check_launch(what);
 }
 }  // namespace
 

@@ -252,19 +252,9 @@ extern "C" int shdr_inflate_batch(const uint8_t* src, int64_t src_bytes, const i
                    (reinterpret_cast<uintptr_t>(written) & 7u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0,
                SHDR_E_ALIGN, "%s: the offset tables and `written` must be 8-byte aligned, `status` 4-byte aligned", what);
   hipStream_t st = S(stream);
-  hipEvent_t ev[SHDR_INFLATE_STAGES + 1] = {};
-  if (stage_ms)
-    for (auto& e : ev) SHDR_REQUIRE(hipEventCreate(&e) == hipSuccess, SHDR_E_LAUNCH, "%s: hipEventCreate failed", what);
-  if (stage_ms) (void)hipEventRecord(ev[0], st);
+  shdr::StageTimer<SHDR_INFLATE_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n_chunks), dim3(kLanes), 0, st, src, src_bytes, src_off_dev, dst, dst_bytes, dst_off_dev,
                      mode, status, written);
-  if (stage_ms) (void)hipEventRecord(ev[1], st);
-  const int rc = shdr::check_launch(what);
-  if (stage_ms) {
-    const bool ok = hipEventSynchronize(ev[SHDR_INFLATE_STAGES]) == hipSuccess;
-    for (int i = 0; i < SHDR_INFLATE_STAGES; ++i)
-      if (!ok || hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]) != hipSuccess) stage_ms[i] = -1.0f;
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
-  return rc;
+  timer.mark();
+  return shdr::check_launch(what);
 }

@@ -558,26 +558,7 @@ Workspace layout(int64_t n_sub, int64_t n_blocks, int64_t plane_bytes) {
   return w;
 }
 
-// optional per-stage device times (shdr_jpeg_batch.stage_ms): an event after every stage, read back at the end of the call
-struct Stages {
-  hipEvent_t ev[SHDR_JPEG_STAGES + 1];
-  int n = 0;
-  float* out;
-  hipStream_t st;
-  Stages(float* out_, hipStream_t st_) : out(out_), st(st_) { mark(); }
-  void mark() {
-    if (out && n <= SHDR_JPEG_STAGES && hipEventCreate(&ev[n]) == hipSuccess) { (void)hipEventRecord(ev[n], st); ++n; }
-  }
-  ~Stages() {
-    if (!out) return;
-    if (n > 0) (void)hipEventSynchronize(ev[n - 1]);
-    for (int i = 0; i < SHDR_JPEG_STAGES; ++i) {
-      out[i] = 0.0f;
-      if (i + 1 < n) (void)hipEventElapsedTime(&out[i], ev[i], ev[i + 1]);
-    }
-    for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]);
-  }
-};
+using Stages = shdr::StageTimer<SHDR_JPEG_STAGES>;                // shdr_jpeg_batch.stage_ms: a mark() behind every stage
 
 void scan(const int32_t* in, int32_t* out, int32_t* partial, int64_t n, hipStream_t st) {
   const int64_t chunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;

@@ -329,25 +329,6 @@ __global__ __launch_bounds__(WG) void compact_kernel(const uint8_t* __restrict__
   }
 }
 
-struct Timer {                                                   // device-event time of a whole call, when the caller asks for it
-  float* out;
-  hipStream_t st;
-  hipEvent_t ev[2] = {};
-  bool ok = false;
-  Timer(float* out_, hipStream_t st_) : out(out_), st(st_) {
-    if (!out) return;
-    ok = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (ok) (void)hipEventRecord(ev[0], st);
-  }
-  ~Timer() {
-    if (!out) return;
-    *out = -1.0f;
-    if (ok && hipEventRecord(ev[1], st) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess) (void)hipEventElapsedTime(out, ev[0], ev[1]);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
-
 int check(const char* what, const shdr_jpeg_scan_image* images, int n_images, int64_t src_bytes, int64_t n_bounds, int64_t n_segs,
           int64_t* n_tiles) {
   SHDR_REQUIRE(images, SHDR_E_NULL, "%s: null descriptors", what);
@@ -384,7 +365,7 @@ extern "C" int shdr_jpeg_scan(const uint8_t* src, int64_t src_bytes, const shdr_
   const int64_t chunks = (n_tiles + 1 + kScanChunk - 1) / kScanChunk;
   const unsigned img_grid = (unsigned)((n_images + WG - 1) / WG);
   {
-    Timer timer(stage_ms, st);
+    shdr::StageTimer<1> timer(stage_ms, st);                     // the whole call is the one stage
     if (n_bounds) SHDR_REQUIRE(hipMemsetAsync(bounds, 0xFF, 8 * (size_t)n_bounds, st) == hipSuccess, SHDR_E_LAUNCH, "%s: hipMemsetAsync failed", what);
     hipLaunchKernelGGL(init_kernel, dim3(img_grid), dim3(WG), 0, st, w.end, w.fill, n_images);
     if (n_tiles) {
@@ -399,6 +380,7 @@ extern "C" int shdr_jpeg_scan(const uint8_t* src, int64_t src_bytes, const shdr_
                          w.part_rst, bounds);
     hipLaunchKernelGGL(report_kernel, dim3(img_grid), dim3(WG), 0, st, src, im, n_images, w.end, w.fill, w.pre_kept, w.pre_rst, w.part_kept,
                        w.part_rst, reinterpret_cast<Report*>(report));
+    timer.mark();
   }
   return shdr::check_launch(what);
 }
@@ -421,12 +403,13 @@ extern "C" int shdr_jpeg_compact(const uint8_t* src, int64_t src_bytes, const sh
   hipStream_t st = S(stream);
   const Workspace w = carve(const_cast<void*>(workspace), n_images, n_tiles);
   {
-    Timer timer(stage_ms, st);
+    shdr::StageTimer<1> timer(stage_ms, st);                     // the whole call is the one stage
     if (arena_bytes)
       SHDR_REQUIRE(hipMemsetAsync(arena, 0xFF, (size_t)arena_bytes, st) == hipSuccess, SHDR_E_LAUNCH, "%s: hipMemsetAsync failed", what);
     if (n_tiles)
       hipLaunchKernelGGL(compact_kernel, dim3((unsigned)n_tiles), dim3(WG), 0, st, src, reinterpret_cast<const Image*>(images_dev), n_images, w.end,
                          w.pre_kept, w.pre_rst, w.part_kept, w.part_rst, bounds, seg_dword, seg_stride, arena, arena_bytes);
+    timer.mark();
   }
   return shdr::check_launch(what);
 }

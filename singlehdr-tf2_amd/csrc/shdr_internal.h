@@ -64,6 +64,41 @@ inline const char* env_cached(EnvSlot& slot, const char* name) {
     if (!(cond)) return ::shdr::fail((code), __VA_ARGS__); \
   } while (0)
 
+// The optional device-event times of a call's N stages (the stage_ms arguments of shdr.h): an event in front of the first stage, mark()
+// behind every stage; the destructor waits for the last event recorded and fills out[0 .. N).  Measurement never fails the call it
+// measures: a time that an event call kept from being read is -1, a stage that the call never reached (no mark()) is 0.  Nothing is
+// created, recorded or waited for when out is NULL, nothing is allocated, and every event created is destroyed.
+template <int N>
+class StageTimer {
+ public:
+  StageTimer(float* out, hipStream_t st) : out_(out), st_(st) {
+    if (!out_) return;
+    while (made_ <= N && hipEventCreate(&ev_[made_]) == hipSuccess) ++made_;
+    mark();
+  }
+  StageTimer(const StageTimer&) = delete;
+  StageTimer& operator=(const StageTimer&) = delete;
+  void mark() {
+    if (marks_ == recorded_ && recorded_ < made_ && hipEventRecord(ev_[recorded_], st_) == hipSuccess) ++recorded_;
+    ++marks_;
+  }
+  ~StageTimer() {
+    if (!out_) return;
+    const bool ok = recorded_ > 0 && hipEventSynchronize(ev_[recorded_ - 1]) == hipSuccess;
+    for (int i = 0; i < N; ++i) {
+      if (i + 1 >= marks_) out_[i] = 0.0f;
+      else if (!ok || i + 1 >= recorded_ || hipEventElapsedTime(&out_[i], ev_[i], ev_[i + 1]) != hipSuccess) out_[i] = -1.0f;
+    }
+    for (int i = 0; i < made_; ++i) (void)hipEventDestroy(ev_[i]);
+  }
+
+ private:
+  float* out_;
+  hipStream_t st_;
+  hipEvent_t ev_[N + 1];
+  int made_ = 0, marks_ = 0, recorded_ = 0;      // events created; mark() calls; events recorded (the first `recorded_` marks)
+};
+
 // Grid size for HBM-bound grid-stride kernels: ~8 blocks of 256 threads per CU.
 inline int stream_grid(int64_t work_items, int block = 256) {
   int64_t g = (work_items + block - 1) / block;

@@ -132,3 +132,16 @@ def test_refusals(shdr):
     assert lib.shdr_deflate_huffman_host(ctypes.c_void_p(src.ctypes.data), src.size, ctypes.c_void_p(out.ctypes.data), need - 1) == -1
     assert b"too small" in lib.shdr_last_error() and np.all(out == 0xAB)          # nothing written
     assert lib.shdr_deflate_huffman_host(ctypes.c_void_p(src.ctypes.data), src.size, ctypes.c_void_p(out.ctypes.data), need) == need
+
+
+@pytest.mark.parametrize("offsets, pad, out_bytes, huffman_ws, lz_ws", [([0, 5, 12, 1012], 8, 1036, 896, 5088), ([0, 1], 0, 1, 320, 384)])
+def test_batch_sizes_of_both_encoders(shdr, offsets, pad, out_bytes, huffman_ws, lz_ws):
+    """the output bound (the chunks + pad in front of each) and the workspace layouts, C chunks of `total` bytes:
+    272 C + 2 align16(8 C) + align16(4 C) Huffman-only, 320 C + the same + align16(4 total) with the parse's tokens"""
+    import ctypes
+    lib = shdr._lib.load()
+    off = np.asarray(offsets, dtype=np.int64)
+    for fn, ws in ((lib.shdr_deflate_huffman_batch_sizes, huffman_ws), (lib.shdr_deflate_lz_batch_sizes, lz_ws)):
+        out_b, ws_b = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        assert fn(ctypes.c_void_p(off.ctypes.data), off.size - 1, pad, ctypes.byref(out_b), ctypes.byref(ws_b)) == 0
+        assert (out_b.value, ws_b.value) == (out_bytes, ws)

@@ -76,6 +76,30 @@ def test_pad_front_and_raw(shdr):
     assert zlib.decompress(out[off[2] + 8:off[3]].tobytes()) == chunks[2]
 
 
+def test_one_byte_tile_and_tile_minus_one_with_every_option(shdr):
+    """the smallest chunk (stored from `raw`), a chunk of exactly one tile (end-of-block alone in a second tile) and one of a tile
+    less one (one tile with it), with pad, front, a buffer of its own for `raw`, host offsets beside their device copy, and stage times"""
+    K = shdr._ops
+    T = K.DEFLATE_TILE
+    rng = np.random.default_rng(24)
+    chunks = [b"\x5a", (128 + rng.integers(-2, 3, T)).astype(np.uint8).tobytes(), b"\x07" * (T - 1)]
+    data, offsets = batch(chunks)
+    kw = dict(raw=data.clone(), pad=8, front=24, offsets_dev=torch.from_numpy(offsets).cuda())
+    ms = []
+    coded = check(K, chunks, stage_ms=ms, **kw)
+    assert coded.tolist() == [0, 1, 1]
+    assert len(ms) == 3 and all(v >= 0 for v in ms)
+    kw["raw"] = 255 - data                                                    # what is not coded comes from `raw`, not from `data`
+    ms = []
+    a, b = K.deflate_huffman(data, offsets, stage_ms=ms, **kw), K.deflate_huffman(data, offsets, **kw)
+    assert len(ms) == 3 and all(v >= 0 for v in ms)
+    assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]) and a[2].cpu().tolist() == [0, 1, 1]
+    off = a[1].cpu().numpy()
+    for c in range(3):                                                        # (the room of pad and front is never written)
+        assert torch.equal(a[0][24 + off[c] + 8:24 + off[c + 1]], b[0][24 + off[c] + 8:24 + off[c + 1]]), c
+    assert a[0][24 + 8:24 + off[1]].cpu().tolist() == [255 - 0x5a]
+
+
 def test_same_input_same_bytes_and_stage_times(shdr):
     K = shdr._ops
     data, offsets = batch([CHUNKS["noisy_ramp"], CHUNKS["fibonacci"]])
