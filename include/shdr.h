@@ -672,6 +672,60 @@ int shdr_inflate_batch(const uint8_t* src, int64_t src_bytes, const int64_t* src
                        int64_t dst_bytes, const int64_t* dst_off, const int64_t* dst_off_dev, const uint8_t* mode, int n_chunks,
                        int32_t* status, int64_t* written, void* stream, float* stage_ms);
 
+/* ---- OpenEXR PIZ chunks decoded (exr.py piz="host" / "device"; csrc/piz.h, csrc/piz.hip) -------------------------------- */
+/* Per-chunk status of the decoder, host and device alike (csrc/piz.h holds the rules both run).  The reader is UNPINNED: the format is
+ * restated from memory of OpenEXR 2.x, and no OpenEXR-written file has been read. */
+#define SHDR_PIZ_OK               0
+#define SHDR_PIZ_TRUNCATED        1   /* the chunk ends inside minNonZero / maxNonZero or the length field */
+#define SHDR_PIZ_BITMAP           2   /* maxNonZero >= 8192, or the bitmap runs past the chunk */
+#define SHDR_PIZ_LENGTH           3   /* the Huffman block's length is negative or runs past the chunk */
+#define SHDR_PIZ_NO_DATA          4   /* length == 0 or nBits == 0 */
+#define SHDR_PIZ_HUFF_HEADER      5   /* a block of fewer than 20 bytes, im or iM >= 65537, im > iM */
+#define SHDR_PIZ_TABLE_TRUNCATED  6   /* the code-length table runs past the block */
+#define SHDR_PIZ_TABLE_RUN        7   /* a zero run past iM + 1 */
+#define SHDR_PIZ_OVER_SUBSCRIBED  8   /* the code lengths' Kraft sum exceeds 1 */
+#define SHDR_PIZ_NBITS            9   /* nBits beyond the bytes that follow the table */
+#define SHDR_PIZ_BAD_CODE        10   /* bits that no code owns */
+#define SHDR_PIZ_DATA_TRUNCATED  11   /* a code word or a run count runs past nBits */
+#define SHDR_PIZ_RUN_NO_PREV     12   /* a run with no previous value */
+#define SHDR_PIZ_TOO_MANY        13   /* more values than the chunk holds */
+#define SHDR_PIZ_TOO_FEW         14   /* nBits consumed and fewer values than the chunk holds */
+#define SHDR_PIZ_RAW_SIZE        15   /* (batch) a stored-raw chunk, or a slot, whose size is not the shape's */
+#define SHDR_PIZ_MODE            16   /* (batch) a mode byte other than 0 / 1 */
+/* The PIZ chunk src[0 .. n) of `rows` (1 .. 32) scanlines of `width` pixels and n_chan (1 .. 64) channels in name order, chan_words[c]
+ * being 1 for a HALF channel and 2 for FLOAT / UINT, into dst[0 .. capacity): the planar scanlines (row by row, channel by channel
+ * within a row, little-endian) that shdr_exr_load_resize_f32 reads; capacity must be 2 * width * rows * sum(chan_words) <= 2^28 (host).
+ * Returns the bytes written -- capacity, or 0 for a refused chunk, whose dst is left untouched -- and stores the status in *status;
+ * nothing outside [src, src + n) is read, whatever the bytes are.  -1 (see shdr_last_error) for bad arguments only. */
+int64_t shdr_piz_decode_host(const uint8_t* src, int64_t n, int width, int rows, const int32_t* chan_words, int n_chan, uint8_t* dst,
+                             int64_t capacity, int* status);
+/* The same decoder on the device for a BATCH of chunks of any files and shapes, two launches (Huffman decode, one workgroup per chunk:
+ * header pass, self-synchronising subsequences of sub_bits bits, scan, write; then the inverse wavelet, one workgroup per strip of a
+ * word plane).  Chunk c is read from src[src_off[c] .. src_off[c + 1]) and written into the slot dst[dst_off[c] .. dst_off[c + 1]).
+ *      src_off, dst_off   int64 [n_chunks + 1] as for shdr_inflate_batch (host arrays, validated, and their device copies); chunks of
+ *                         at most 2^28 bytes; a slot starts at an even byte and has exactly the size of the chunk's shape
+ *      geom               int32 [n_chunks][4]: width, rows, first entry and number of entries in chan_words (host and device copy)
+ *      chan_words         int32 [n_words]: 1 or 2 per channel (host and device copy)
+ *      mode               device uint8 [n_chunks], or NULL for all 1: 1 a PIZ chunk, 0 stored raw (copied if its size is the slot's)
+ *      sub_bits           bits per subsequence, 128 .. 2^20; 0: the default (256)
+ *      workspace          device, 16-byte aligned, at least the bytes shdr_piz_batch_sizes returns for the same tables and sub_bits
+ *      status, written    device int32 [n_chunks] and int64 [n_chunks]: SHDR_PIZ_* and the bytes written into the slot (all or 0: the
+ *                         slot of a refused chunk is left untouched)
+ *      rounds             NULL, or device int32 [n_chunks][SHDR_PIZ_ROUND_STATS] (measurement): the synchronisation rounds each chunk
+ *                         took, then the subsequences that round 0, 1, ... decoded (round 0: all of them; zero past the last round)
+ *      stage_ms           NULL, or float [SHDR_PIZ_STAGES] for the device-event times of the two launches (measurement only: the call
+ *                         then waits for them)
+ * Stream-ordered, deterministic, no atomics, no host wait, no allocation. */
+#define SHDR_PIZ_STAGES 2
+#define SHDR_PIZ_ROUND_STATS 9
+int shdr_piz_batch_sizes(const int64_t* src_off, const int64_t* dst_off, const int32_t* geom, const int32_t* chan_words, int n_words,
+                         int n_chunks, int sub_bits, int64_t* src_bytes, int64_t* dst_bytes, int64_t* workspace_bytes);
+int shdr_piz_batch(const uint8_t* src, int64_t src_bytes, const int64_t* src_off, const int64_t* src_off_dev, uint8_t* dst,
+                   int64_t dst_bytes, const int64_t* dst_off, const int64_t* dst_off_dev, const uint8_t* mode, const int32_t* geom,
+                   const int32_t* geom_dev, const int32_t* chan_words, const int32_t* chan_words_dev, int n_words, int n_chunks,
+                   int sub_bits, void* workspace, int64_t workspace_bytes, int32_t* status, int64_t* written, int32_t* rounds,
+                   void* stream, float* stage_ms);
+
 /* ---- OpenEXR output (exr.py encode_exr / write_exr; csrc/exr_write.hip, csrc/deflate.hip) ------------------------------ */
 /* Huffman-only zlib stream of src[0 .. n), 1 <= n <= 2^30 (host): 78 01, one final dynamic-Huffman block of literals with a
  * fixed-length header (csrc/deflate_huffman.h), the big-endian Adler-32.  zlib's inflate reads it.  Returns the stream's length,

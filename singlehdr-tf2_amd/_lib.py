@@ -64,6 +64,10 @@ SIGNATURES = {
     "shdr_deflate_lz_batch": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "shdr_inflate_host": (c_i64, [c_ptr, c_i64, c_ptr, c_i64, ctypes.POINTER(c_int)]),
     "shdr_inflate_batch_sizes": (c_int, [c_ptr, c_ptr, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "shdr_piz_decode_host": (c_i64, [c_ptr, c_i64, c_int, c_int, c_ptr, c_int, c_ptr, c_i64, ctypes.POINTER(c_int)]),
+    "shdr_piz_batch_sizes": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int] + [ctypes.POINTER(c_i64)] * 3),
+    "shdr_piz_batch": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int,
+                               c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "shdr_inflate_batch": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
     "shdr_exr_pack_sizes": (c_int, [c_ptr, c_int, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr]),
     "shdr_exr_pack_f32": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -2218,6 +2218,103 @@ def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets
 
 
 # ---------------------------------------------------------------------------
+# OpenEXR PIZ chunks decoded (exr.py piz="host" / "device"), see csrc/piz.h and csrc/piz.hip
+# ---------------------------------------------------------------------------
+PIZ_REASONS = (                                       # SHDR_PIZ_*: the per-chunk status of the host routine and of the kernels
+    "ok", "truncated chunk", "invalid bitmap range", "invalid Huffman block length", "no data", "invalid Huffman header",
+    "truncated code-length table", "code-length run overflows", "over-subscribed code lengths", "nBits beyond the data", "invalid code",
+    "truncated data", "run with no previous value", "more values than the chunk holds", "fewer values than the chunk holds",
+    "raw chunk size is not its slot's", "invalid mode byte")
+PIZ_ROUND_STATS = 9                                   # SHDR_PIZ_ROUND_STATS
+PIZ_MIN_SUB_BITS, PIZ_SUB_BITS = 128, 256             # the smallest legal and the default subsequence of the device decoder
+
+
+def piz_reason(status):
+    status = int(status)
+    return PIZ_REASONS[status] if 0 <= status < len(PIZ_REASONS) else "status %d" % status
+
+
+def piz_decode_host(chunk, width, rows, chan_words, out=None):
+    """one PIZ chunk -> (bytes, status): libshdr's host decoder (csrc/piz.h, the rules the kernels run).  chan_words: 1 per HALF
+    channel, 2 per FLOAT / UINT channel, in name order.  status 0: `bytes` are the 2 * width * rows * sum(chan_words) bytes of the
+    chunk's planar scanlines; any other value is an index into PIZ_REASONS and `bytes` is empty.  out: a uint8 array of exactly that
+    size to decode into (then returned instead of bytes, left untouched by a refused chunk)."""
+    lib = _lib.load()
+    src = np.frombuffer(chunk, dtype=np.uint8) if not isinstance(chunk, np.ndarray) else chunk
+    words = np.ascontiguousarray(chan_words, dtype=np.int32)
+    capacity = 2 * int(width) * int(rows) * int(words.sum())
+    buf = np.empty(max(capacity, 1), dtype=np.uint8) if out is None else out
+    st = ctypes.c_int(-1)
+    n = lib.shdr_piz_decode_host(src.ctypes.data if src.size else None, src.size, int(width), int(rows), _hptr(words), words.size,
+                                 buf.ctypes.data, capacity if out is None else buf.size, ctypes.byref(st))
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return (buf[:n].tobytes() if out is None else buf), st.value
+
+
+def piz_decode(src, src_offsets, dst_offsets, geom, chan_words, mode=None, sub_bits=None, stage_ms=None, src_offsets_dev=None,
+               dst_offsets_dev=None, dst=None, shape_dev=None, rounds=False):
+    """a batch of PIZ chunks decoded on the device (csrc/piz.hip: Huffman decode by self-synchronising subsequences, then the inverse
+    wavelet and the LUT): chunk c is src[src_offsets[c]:src_offsets[c + 1]] and fills the slot dst[dst_offsets[c]:dst_offsets[c + 1]]
+    with its planar scanlines.  geom: int32 [n, 4] host array (width, rows, first entry and number of entries in chan_words);
+    chan_words: int32 host array, 1 per HALF channel and 2 per FLOAT / UINT channel; shape_dev: (geom, chan_words) on the device, if
+    the caller has them; mode: uint8 [n] on the device, 1 PIZ, 0 stored raw, default all 1; sub_bits: bits per subsequence
+    (PIZ_MIN_SUB_BITS .. 2^20, default PIZ_SUB_BITS); dst: a uint8 device tensor to write into (default: a new one, not cleared).
+    Returns (dst, written int64 [n], status int32 [n]) on the device -- status 0, or an index into PIZ_REASONS, whose slot is left
+    untouched -- and, with rounds=True, also an int32 [n, PIZ_ROUND_STATS] tensor: the synchronisation rounds each chunk took, then the
+    subsequences that round 0, 1, ... decoded (round 0: all of them).  Stream-ordered, no host wait.
+    stage_ms: a list that receives the two launches' device times (measurement: the call then waits)."""
+    lib = _lib.load()
+    src = _chk(src, "src", torch.uint8)
+    s_host, s_dev = _offsets_pair("piz_decode", "src_offsets", src_offsets, src_offsets_dev)
+    d_host, d_dev = _offsets_pair("piz_decode", "dst_offsets", dst_offsets, dst_offsets_dev)
+    n = s_host.size - 1
+    geom = np.ascontiguousarray(geom, dtype=np.int32)
+    words = np.ascontiguousarray(chan_words, dtype=np.int32)
+    if src.dim() != 1 or d_host.size != n + 1 or geom.shape != (n, 4) or words.ndim != 1:
+        raise ValueError("piz_decode: expected src [size], two offset tables [n_chunks + 1], geom [n_chunks, 4] and chan_words [n]")
+    sub = 0 if sub_bits is None else int(sub_bits)
+    src_b, dst_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_piz_batch_sizes(_hptr(s_host), _hptr(d_host), _hptr(geom), _hptr(words), words.size, n, sub, ctypes.byref(src_b),
+                                        ctypes.byref(dst_b), ctypes.byref(ws_b)), "shdr_piz_batch_sizes")
+    if src_b.value > src.numel():
+        raise ValueError("piz_decode: src_offsets end at %d, src holds %d bytes" % (src_b.value, src.numel()))
+    dev = src.device
+    if dst is None:
+        dst = torch.empty(dst_b.value, device=dev, dtype=torch.uint8)
+    else:
+        dst = _chk(dst, "dst", torch.uint8)
+        if dst.dim() != 1 or dst.numel() < dst_b.value:
+            raise ValueError("piz_decode: dst_offsets end at %d, dst holds %d bytes" % (dst_b.value, dst.numel()))
+    if mode is not None:
+        mode = _chk(mode, "mode", torch.uint8)
+        if mode.numel() != n:
+            raise ValueError("piz_decode: mode must be uint8 [n_chunks]")
+    if s_dev is None:
+        s_dev = torch.from_numpy(s_host).to(dev)
+    if d_dev is None:
+        d_dev = torch.from_numpy(d_host).to(dev)
+    if shape_dev is None:
+        both = torch.from_numpy(np.concatenate([geom.reshape(-1), words])).to(dev)
+        geom_dev, words_dev = both[:4 * n], both[4 * n:]
+    else:
+        geom_dev, words_dev = _chk(shape_dev[0], "geom_dev", torch.int32), _chk(shape_dev[1], "chan_words_dev", torch.int32)
+        if geom_dev.numel() != 4 * n or words_dev.numel() != words.size:
+            raise ValueError("piz_decode: shape_dev is not a copy of geom and chan_words")
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    written = torch.empty(n, device=dev, dtype=torch.int64)
+    rounds_dev = torch.empty((n, PIZ_ROUND_STATS), device=dev, dtype=torch.int32) if rounds else None
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    with _stage_times(stage_ms, 2) as ms:
+        _lib.check(lib.shdr_piz_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev),
+                                      _ptr(dst) if dst.numel() else None, dst.numel(), _hptr(d_host), _ptr(d_dev),
+                                      _ptr(mode) if mode is not None else None, _hptr(geom), _ptr(geom_dev), _hptr(words), _ptr(words_dev),
+                                      words.size, n, sub, _ptr(ws), ws.numel(), _ptr(status), _ptr(written),
+                                      _ptr(rounds_dev) if rounds else None, _stream(), ms), "shdr_piz_batch")
+    return (dst, written, status, rounds_dev) if rounds else (dst, written, status)
+
+
+# ---------------------------------------------------------------------------
 # JPEG scan regions unstuffed and laid out (jpeg.plan_device), see csrc/jpeg_scan.h and csrc/jpeg_scan.hip
 # ---------------------------------------------------------------------------
 JPEG_SCAN_IMAGE_BYTES, JPEG_SCAN_REPORT_BYTES = 40, 32          # shdr_jpeg_scan_image, shdr_jpeg_scan_report

@@ -52,6 +52,7 @@ SOURCES = {
     "deflate.hip": [],
     "deflate_lz.hip": [],
     "inflate.hip": [],
+    "piz.hip": [],
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
     "jpeg_scan.hip": [],
@@ -79,7 +80,7 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
                os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
-               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "jpeg_scan.h"),
+               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "piz.h"), os.path.join(CSRC, "jpeg_scan.h"),
                os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []

@@ -31,7 +31,9 @@ Deliberate differences from the reference:
     arrays, and starts no worker processes.  It is draw() followed by PatchHDRDataset.render() and the CRF / t gathers.
   * Radiance files (FORMAT=32-bit_rle_rgbe, -Y h +X w) and OpenEXR files are read, chosen by their magic bytes.  Of OpenEXR,
     single-part scanline files with NO_COMPRESSION, RLE, ZIPS or ZIP compression and HALF / FLOAT R, G, B channels (exr.py);
-    PIZ, PXR24, B44(A), DWAA / DWAB, tiled, deep, multi-part and luminance / chroma files raise ValueError.  Alpha and other
+    PIZ files too where exr_piz="host" or "device" asks for them (the default "refuse" raises ValueError; that reader is unpinned:
+    no OpenEXR-written PIZ file has been read); PXR24, B44(A), DWAA / DWAB, tiled, deep, multi-part and luminance / chroma files
+    raise ValueError.  Alpha and other
     extra channels are ignored: cv2.imread(path, IMREAD_UNCHANGED) would return 4 channels, which the reference's network
     cannot take.  The file list without a .pkl is the sorted *.hdr and *.exr files.
 """
@@ -270,12 +272,14 @@ class HDRDataset(Dataset):
     """the file list; items are the RGBE bytes of a Radiance file or the exr.Payload of an OpenEXR one (the pixels are
     converted on the device, see PatchHDRDataset)"""
 
-    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, exr_inflate="host"):
-        """exr_inflate "device": ZIP / ZIPS OpenEXR files come back as exr.Stored (checked, not inflated; exr.upload_batch's input)"""
+    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, exr_inflate="host", exr_piz="refuse"):
+        """exr_inflate "device": ZIP / ZIPS OpenEXR files come back as exr.Stored (checked, not inflated; exr.upload_batch's input).
+        exr_piz: PIZ files are refused ("refuse"), decoded on the host ("host") or come back as exr.Stored too ("device")"""
         self._hdr_prefix = hdr_prefix
         self._hdr_posfix_list = list(hdr_posfix_list)
         self.is_training = is_training
         self.exr_inflate = exr.check_inflate_option("HDRDataset", exr_inflate)
+        self.exr_piz = exr.check_piz_option("HDRDataset", exr_piz)
 
     def path(self, idx):
         return os.path.join(self._hdr_prefix, self._hdr_posfix_list[idx])
@@ -284,7 +288,7 @@ class HDRDataset(Dataset):
         path = self.path(idx)
         if not exr.is_exr(path):
             return hdr_io.read_rgbe(path)
-        return exr.read_stored(path) if self.exr_inflate == "device" else exr.read_payload(path)
+        return exr.read_item(path, self.exr_inflate, self.exr_piz)
 
     def __len__(self):
         return len(self._hdr_posfix_list)
@@ -294,11 +298,14 @@ class PatchHDRDataset(Dataset):
     """2 patches per file (:212-252): the first and last 512 rows (portrait) or columns (otherwise) of the resized image,
     normalised to mean 0.5; training adds a random resize, 256 crop, rot90 and flips.  Every file is resident on the device."""
 
-    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, load_to_mem=True, device=None, seed=0, exr_inflate="host"):
+    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, load_to_mem=True, device=None, seed=0, exr_inflate="host",
+                 exr_piz="refuse"):
         """load_to_mem is the reference's argument; the images are always resident (on the device).  exr_inflate: who inflates the
         ZIP / ZIPS chunks of OpenEXR files -- "host" (zlib, in the loading threads) or "device" (all files' chunks in one
-        exr.upload_batch; the time moves from load_seconds["host_decode"] to load_seconds["device"]); the arena is the same"""
-        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training, exr_inflate)
+        exr.upload_batch; the time moves from load_seconds["host_decode"] to load_seconds["device"]); the arena is the same.
+        exr_piz: PIZ-compressed OpenEXR files are refused ("refuse", the default), decoded in the loading threads by libshdr's host
+        routine ("host") or on the device, in that same batch ("device", K.piz_decode); the arena is the same either way"""
+        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training, exr_inflate, exr_piz)
         self._is_training = is_training
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.rng = np.random.default_rng(seed)          # draws of __getitem__ (the reader has its own)
@@ -326,7 +333,7 @@ class PatchHDRDataset(Dataset):
         offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         self.arena = torch.empty(int(sum(sizes)), device=self.device, dtype=torch.float32)
         batched = {}
-        if self._hdr_dataset.exr_inflate == "device":                # every OpenEXR file of the list in one batch
+        if self._hdr_dataset.exr_inflate == "device" or any(isinstance(r, exr.Stored) for r in items):     # every OpenEXR file in one batch
             which = [i for i, r in enumerate(items) if isinstance(r, (exr.Payload, exr.Stored))]
             batched = dict(zip(which, exr.upload_batch([items[i] for i in which], self.device)))
         for i, (r, (h, w)) in enumerate(zip(items, shapes)):
@@ -418,23 +425,23 @@ def _merge(patches, tables):
     return MergeDataset([patches, CatDataset([crf, invcrf]), t])
 
 
-def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
+def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
     tables = crf_tables("train", crf_path)                     # first: a missing DoRF file fails before any file is loaded
     return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_train"), True, device=device,
-                                  exr_inflate=exr_inflate), tables)
+                                  exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
 
 
-def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
+def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
     tables = crf_tables("vali", crf_path)
     posfix_list = _posfix_list(hdr_prefix, posfix_list, "i_dataset_test")
     np.random.RandomState(730).shuffle(posfix_list)
-    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device, exr_inflate=exr_inflate), tables)
+    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device, exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
 
 
-def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host"):
+def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
     tables = crf_tables("test", crf_path)
     return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_test"), False, device=device,
-                                  exr_inflate=exr_inflate), tables)
+                                  exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
 
 
 # --- RandDatasetReader (dataset.py:318-363) -------------------------------------------------------------------------

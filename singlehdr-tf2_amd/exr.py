@@ -6,7 +6,8 @@ cv2.imread(path, cv2.IMREAD_UNCHANGED) (dataset.py:181-186).
 Scope, restated from OpenEXR 2.x's published file layout (no OpenEXR library is used):
   * magic 76 2f 31 01, version 2, single-part scanline images (the long-names flag 0x400 is allowed; tiled 0x200, deep 0x800
     and multi-part 0x1000 files are refused);
-  * compression NO_COMPRESSION (0), RLE (1), ZIPS (2) and ZIP (3); PIZ, PXR24, B44, B44A, DWAA and DWAB are refused by name;
+  * compression NO_COMPRESSION (0), RLE (1), ZIPS (2) and ZIP (3); PIZ (4) only where the caller asks for it (piz=, below);
+    PXR24, B44, B44A, DWAA and DWAB are refused by name;
   * channels R, G and B, each HALF or FLOAT; other channels (A, Z, ...) of any type are skipped but occupy their bytes; every
     channel has x / y sampling 1;
   * any dataWindow (the image is the data window, as in OpenCV's decoder), line order INCREASING_Y or DECREASING_Y.
@@ -27,6 +28,16 @@ container checks (read_stored) and the device inflates too: the stored bytes of 
 launch of K.inflate (csrc/inflate.hip, a zlib decoder with one wave per chunk; csrc/inflate.h is the decoder, shared with the host
 routine K.inflate_host that the tests judge against zlib) decodes them into place, one launch undoes the predictor, and one small
 copy of the chunks' status codes back is the only wait (upload_batch).  The pixels are the same bits.
+
+PIZ (piz= of read_header / read_payload / read_stored / read_item / read_exr, exr_piz= of the dataset readers; "refuse" is the
+default and keeps the refusal by name): 32 scanlines per chunk, all channels inside the PIZ data; a chunk is a bitmap of the 16-bit
+values present, one Huffman-coded stream (code words of up to 58 bits, a run code) of the wavelet coefficients of every channel's
+word planes, and decodes -- Huffman, inverse wavelet, reverse LUT -- to the planar scanlines themselves, with no predictor to undo
+(csrc/piz.h: the rules, shared by both sides).  piz="host": libshdr's shdr_piz_decode_host decodes every chunk in the loading
+threads (ctypes: no GIL).  piz="device": the file comes back as a Stored and upload_batch hands its chunks to K.piz_decode
+(csrc/piz.hip) beside the K.inflate launch of the ZIP files, into one buffer.  The PIZ reader is UNPINNED: the format is restated
+from memory of OpenEXR 2.x, and no OpenEXR-written file has been read (the tests' files come from tests/piz_ref.py, an
+independent restatement of the same rules).
 
 Writing (encode_exr / write_exr) mirrors that split.  The device converts float32 to HALF or FLOAT, lays the samples out as planar
 scanlines (B, G, R) and applies the interleave and the delta predictor, all chunks of a batch of images in one launch
@@ -56,9 +67,11 @@ except ImportError:
 MAGIC = b"\x76\x2f\x31\x01"
 UINT, HALF, FLOAT = 0, 1, 2
 SAMPLE_BYTES = {UINT: 4, HALF: 2, FLOAT: 4}
-NO_COMPRESSION, RLE_COMPRESSION, ZIPS_COMPRESSION, ZIP_COMPRESSION = 0, 1, 2, 3
+NO_COMPRESSION, RLE_COMPRESSION, ZIPS_COMPRESSION, ZIP_COMPRESSION, PIZ_COMPRESSION = 0, 1, 2, 3, 4
 COMPRESSION_NAMES = ("NO_COMPRESSION", "RLE", "ZIPS", "ZIP", "PIZ", "PXR24", "B44", "B44A", "DWAA", "DWAB")
 LINES_PER_CHUNK = {NO_COMPRESSION: 1, RLE_COMPRESSION: 1, ZIPS_COMPRESSION: 1, ZIP_COMPRESSION: 16}
+LINES_PER_CHUNK_PIZ = {**LINES_PER_CHUNK, PIZ_COMPRESSION: 32}           # what a reader asked for PIZ (piz=) accepts
+PIZ_WORDS = {UINT: 2, HALF: 1, FLOAT: 2}                                    # 16-bit words of a sample in a PIZ chunk
 INCREASING_Y, DECREASING_Y = 0, 1
 FLAG_TILED, FLAG_LONG_NAMES, FLAG_DEEP, FLAG_MULTIPART = 0x200, 0x400, 0x800, 0x1000
 MAX_SIDE = 1 << 20                 # a larger data window is refused as absurd
@@ -72,10 +85,10 @@ Stored = collections.namedtuple("Stored", "header path data src_offsets offsets 
 """data: uint8 [offsets[-1]], the chunks in increasing-y order; offsets: int64 [n_chunks + 1], chunk c at
 data[offsets[c]:offsets[c + 1]] (min(lines, rows left) * row_bytes bytes); coded: uint8 [n_chunks], 1 where the predictor and
 the interleave are still to be undone (0 for raw chunks and NO_COMPRESSION)"""
-"""Stored (read_stored): a ZIP / ZIPS file whose chunks are still as the file holds them.  data: uint8, the chunks' stored bytes back to
+"""Stored (read_stored): a ZIP / ZIPS (or, with piz="device", PIZ) file whose chunks are still as the file holds them.  data: uint8, the chunks' stored bytes back to
 back in increasing-y order, chunk headers stripped; src_offsets: int64 [n_chunks + 1], chunk c is data[src_offsets[c]:src_offsets[c + 1]];
-offsets: the decoded offsets, identical to Payload.offsets; mode: uint8 [n_chunks], 1 a zlib stream, 0 stored raw (K.inflate's mode
-bytes); path: the file, for error messages"""
+offsets: the decoded offsets, identical to Payload.offsets; mode: uint8 [n_chunks], 1 a zlib stream (of a PIZ file: a PIZ chunk), 0
+stored raw (K.inflate's and K.piz_decode's mode bytes; header.compression says which); path: the file, for error messages"""
 
 
 def is_exr(path):
@@ -121,7 +134,7 @@ def _parse_chlist(value, path, max_name):
     return chans
 
 
-def _parse_header(data, path):
+def _parse_header(data, path, piz=False):
     if len(data) < 8:
         raise _fail(path, "truncated header")
     if data[:4] != MAGIC:
@@ -162,7 +175,8 @@ def _parse_header(data, path):
     if b"type" in attrs and attrs[b"type"][1].rstrip(b"\0") != b"scanlineimage":
         raise _fail(path, "part type %r is not supported (scanline images only)" % attrs[b"type"][1].decode("latin-1"))
     comp = attr(b"compression", b"compression", 1)[0]
-    if comp not in LINES_PER_CHUNK:
+    lines_per_chunk = LINES_PER_CHUNK_PIZ if piz else LINES_PER_CHUNK
+    if comp not in lines_per_chunk:
         name = COMPRESSION_NAMES[comp] if comp < len(COMPRESSION_NAMES) else "unknown (%d)" % comp
         raise _fail(path, "%s compression is not supported (NO_COMPRESSION, RLE, ZIPS and ZIP are)" % name)
     order = attr(b"lineOrder", b"lineOrder", 1)[0]
@@ -185,19 +199,20 @@ def _parse_header(data, path):
             raise _fail(path, "channel %s is UINT (colour channels must be HALF or FLOAT)" % n.decode())
         channels.append(Channel(n.decode("latin-1"), t, off))
         off += SAMPLE_BYTES[t] * width
-    lines = LINES_PER_CHUNK[comp]
+    lines = lines_per_chunk[comp]
     n_chunks = -(-height // lines)
     if pos + 8 * n_chunks > len(data):
         raise _fail(path, "truncated offset table")
     return Header((xmin, ymin, xmax, ymax), width, height, tuple(channels), comp, order, lines, off, n_chunks, pos)
 
 
-def read_header(path):
+def read_header(path, piz=False):
     """the data window, the channel list (name, type, byte offset in a scanline; layout order), compression, line order, lines
-    per chunk, scanline bytes and chunk count of an OpenEXR file; ValueError (naming the file) on anything out of scope"""
+    per chunk, scanline bytes and chunk count of an OpenEXR file; ValueError (naming the file) on anything out of scope.  piz: a
+    PIZ file is in scope (32 lines per chunk)"""
     with open(path, "rb") as f:
         data = f.read()
-    return _parse_header(data, path)
+    return _parse_header(data, path, piz)
 
 
 def _rle_decode(src, size, dst, capacity):
@@ -216,11 +231,25 @@ def rle_decode(data, capacity):
     return out[:n].tobytes()
 
 
-def read_payload(path):
-    """the file's chunks decoded on the host (inflated / run-length decoded, predictor and interleave NOT undone): a Payload"""
+def check_piz_option(what, piz, allowed=("refuse", "host", "device")):
+    if piz not in allowed:
+        raise ValueError("%s: piz must be %s, got %r" % (what, " or ".join(repr(a) for a in allowed), piz))
+    return piz
+
+
+def read_payload(path, piz="refuse"):
+    """the file's chunks decoded on the host (inflated / run-length decoded, predictor and interleave NOT undone): a Payload.
+    piz="host": a PIZ file is in scope; its chunks are decoded by libshdr's host routine (K.piz_decode_host, ctypes: no GIL) into
+    the planar scanlines, with nothing left to undo (coded 0)"""
+    check_piz_option("read_payload", piz, ("refuse", "host"))
     with open(path, "rb") as f:
         data = f.read()
-    return _payload(data, _parse_header(data, path), path)
+    return _payload(data, _parse_header(data, path, piz != "refuse"), path)
+
+
+def piz_words(hdr):
+    """the 16-bit words per sample of the header's channels, in layout order (K.piz_decode's chan_words)"""
+    return [PIZ_WORDS[ch.type] for ch in hdr.channels]
 
 
 def _payload(data, hdr, path):
@@ -250,6 +279,11 @@ def _payload(data, hdr, path):
             continue
         if size > want or hdr.compression == NO_COMPRESSION:
             raise _fail(path, "chunk %d: %d bytes stored, its %d scanlines hold %d" % (c, size, int(rows[c]), want))
+        if hdr.compression == PIZ_COMPRESSION:
+            _, st = K.piz_decode_host(raw, hdr.width, int(rows[c]), piz_words(hdr), out=out[lo:hi])
+            if st:
+                raise _fail(path, "chunk %d: PIZ error: %s" % (c, K.piz_reason(st)))
+            continue                                                     # planar scanlines already: no predictor to undo
         if hdr.compression == RLE_COMPRESSION:
             try:
                 got = _rle_decode(raw.ctypes.data, size, out[lo:hi].ctypes.data, want)
@@ -279,14 +313,26 @@ def check_inflate_option(what, inflate):
     return inflate
 
 
-def read_stored(path):
+def read_stored(path, piz="refuse"):
     """the host half of the device route: every container check of read_payload, with its messages, and nothing inflated.  ZIP and
     ZIPS files come back as a Stored (the chunks' bytes as the file holds them); RLE and NO_COMPRESSION files as read_payload's
-    Payload.  upload_batch takes both."""
+    Payload.  upload_batch takes both.  piz: a PIZ file is refused, decoded on the host into a Payload ("host"), or comes back as a
+    Stored ("device") whose mode bytes mean 1 a PIZ chunk, 0 stored raw: K.piz_decode's."""
+    return read_item(path, "device", piz)
+
+
+def read_item(path, inflate="host", piz="refuse"):
+    """read_payload or read_stored, file by file: a ZIP / ZIPS file is left stored with inflate="device", a PIZ file with
+    piz="device"; everything else is decoded on the host (a PIZ file only if piz="host")"""
+    check_inflate_option("read_item", inflate)
+    check_piz_option("read_item", piz)
     with open(path, "rb") as f:
         data = f.read()
-    hdr = _parse_header(data, path)
-    if hdr.compression not in (ZIP_COMPRESSION, ZIPS_COMPRESSION):
+    hdr = _parse_header(data, path, piz != "refuse")
+    if hdr.compression == PIZ_COMPRESSION:
+        if piz != "device":
+            return _payload(data, hdr, path)
+    elif hdr.compression not in (ZIP_COMPRESSION, ZIPS_COMPRESSION) or inflate != "device":
         return _payload(data, hdr, path)
     n, lines, row_bytes = hdr.n_chunks, hdr.lines, hdr.row_bytes
     table = np.frombuffer(data, dtype="<u8", count=n, offset=hdr.table_offset).astype(np.uint64)
@@ -319,29 +365,43 @@ def read_stored(path):
 def upload_batch(items, device):
     """any mix of read_stored's Stored items and Payloads -> [(planes, offsets)] as upload() gives them, one pair per item, with all
     the work of all the files batched: one staging buffer and one copy carry the stored bytes to the device, one K.inflate launch
-    decodes every chunk of every file into its place (chunks that are decoded already, or stored raw, are copied by that launch), one
-    K.exr_unpredict launch undoes the predictor, and one small copy of the chunks' status and byte counts back is the only host
-    wait.  ValueError("<path>: chunk <c>: inflate error: <reason>") for the first chunk, in file order, that the kernel refuses."""
+    decodes every ZIP / ZIPS chunk of every file into its place (chunks that are decoded already, or stored raw, are copied by that
+    launch), one K.piz_decode call does the same for every chunk of the PIZ files, into the same buffer (the PIZ files' chunks lie
+    behind the others in both buffers, so each call sees one contiguous part of the two offset tables), one K.exr_unpredict launch
+    undoes the predictor, and one small copy of the chunks' status and byte counts back is the only host wait.
+    ValueError("<path>: chunk <c>: inflate error: <reason>") (or "PIZ error") for the first chunk, in file order, that a kernel refuses."""
     items = list(items)
     if not items:
         return []
-    n_chunks = [it.header.n_chunks for it in items]
-    first = np.concatenate([[0], np.cumsum(n_chunks)]).astype(np.int64)
+    is_piz = [isinstance(it, Stored) and it.header.compression == PIZ_COMPRESSION for it in items]
+    order = [i for i in range(len(items)) if not is_piz[i]] + [i for i in range(len(items)) if is_piz[i]]
+    n_chunks = [items[i].header.n_chunks for i in order]
+    first = np.concatenate([[0], np.cumsum(n_chunks)]).astype(np.int64)          # of the items in `order`
     n = int(first[-1])
+    n_z = int(first[len(items) - sum(is_piz)])                                   # chunks in front of the PIZ files'
     # one int64 table: source offsets, slot offsets, then every file's own chunk offsets (what load_resize reads)
     tables = np.empty(2 * (n + 1) + n + len(items), dtype=np.int64)
     src_off, dst_off, own = tables[:n + 1], tables[n + 1:2 * (n + 1)], tables[2 * (n + 1):]
     flags = np.empty(2 * n, dtype=np.uint8)
     mode, coded = flags[:n], flags[n:]
+    geom, words = np.zeros((n - n_z, 4), dtype=np.int32), []
     parts, s_at, d_at, own_at = [], 0, 0, []
-    for i, it in enumerate(items):
-        a, b = int(first[i]), int(first[i + 1])
+    for k, i in enumerate(order):
+        it = items[i]
+        a, b = int(first[k]), int(first[k + 1])
         if isinstance(it, Stored):
             parts.append(it.data)
             src_off[a:b + 1] = s_at + it.src_offsets
             mode[a:b] = it.mode
-            coded[a:b] = it.mode
+            coded[a:b] = 0 if is_piz[i] else it.mode                      # a PIZ chunk decodes to the scanlines themselves
             s_at += int(it.src_offsets[-1])
+            if is_piz[i]:
+                hdr = it.header
+                geom[a - n_z:b - n_z, 0] = hdr.width
+                geom[a - n_z:b - n_z, 1] = np.minimum(hdr.lines, hdr.height - np.arange(b - a) * hdr.lines)
+                geom[a - n_z:b - n_z, 2] = len(words)
+                geom[a - n_z:b - n_z, 3] = len(hdr.channels)
+                words += piz_words(hdr)
         else:                                                            # decoded on the host: copied as it is
             parts.append(it.data)
             src_off[a:b + 1] = s_at + it.offsets
@@ -350,8 +410,8 @@ def upload_batch(items, device):
             s_at += int(it.offsets[-1])
         dst_off[a:b + 1] = d_at + it.offsets
         d_at += int(it.offsets[-1])
-        own_at.append(a + i)
-        own[a + i:b + i + 1] = it.offsets
+        own_at.append(a + k)
+        own[a + k:b + k + 1] = it.offsets
     staging = torch.empty(max(s_at, 1), dtype=torch.uint8).pin_memory()         # alive until the wait below
     if s_at:
         np.concatenate(parts, out=staging.numpy()[:s_at])
@@ -359,20 +419,34 @@ def upload_batch(items, device):
     tables_dev = torch.from_numpy(tables).to(device)
     flags_dev = torch.from_numpy(flags).to(device)
     src_off_dev, dst_off_dev, own_dev = tables_dev[:n + 1], tables_dev[n + 1:2 * (n + 1)], tables_dev[2 * (n + 1):]
-    dst, written, status = K.inflate(src, src_off, dst_off, mode=flags_dev[:n], src_offsets_dev=src_off_dev, dst_offsets_dev=dst_off_dev)
+    dst = torch.empty(d_at, device=device, dtype=torch.uint8)
+    status, written = [], []
+    if n_z:
+        _, w, st = K.inflate(src, src_off[:n_z + 1], dst_off[:n_z + 1], mode=flags_dev[:n_z], src_offsets_dev=src_off_dev[:n_z + 1],
+                             dst_offsets_dev=dst_off_dev[:n_z + 1], dst=dst)
+        status.append(st)
+        written.append(w)
+    if n > n_z:
+        _, w, st = K.piz_decode(src, src_off[n_z:], dst_off[n_z:], geom, words, mode=flags_dev[n_z:n], src_offsets_dev=src_off_dev[n_z:],
+                                dst_offsets_dev=dst_off_dev[n_z:], dst=dst)
+        status.append(st)
+        written.append(w)
     planes = K.exr_unpredict(dst, dst_off_dev, flags_dev[n:]) if coded.any() else dst
-    result = torch.stack([status.to(torch.int64), written]).cpu().numpy()       # the host waits here, once
+    result = torch.stack([torch.cat(status).to(torch.int64), torch.cat(written)]).cpu().numpy()       # the host waits here, once
     bad = np.flatnonzero((result[0] != 0) | (result[1] != np.diff(dst_off)))
     if bad.size:
-        c = int(bad[0])
-        i = int(np.searchsorted(first, c, side="right")) - 1
+        k = np.searchsorted(first, bad, side="right") - 1                        # the items (in `order`) of the bad chunks
+        j = int(np.argmin(np.asarray(order)[k]))                                 # the first of them in file order (bad is sorted)
+        c, k = int(bad[j]), int(k[j])
         st = int(result[0, c])
-        raise _fail(getattr(items[i], "path", "item %d" % i), "chunk %d: inflate error: %s" % (
-            c - int(first[i]), K.inflate_reason(st) if st else "%d bytes written, its slot holds %d" % (result[1, c], dst_off[c + 1] - dst_off[c])))
-    out = []
-    for i, it in enumerate(items):
-        lo = int(dst_off[first[i]])
-        out.append((planes[lo:lo + int(it.offsets[-1])], own_dev[own_at[i]:own_at[i] + n_chunks[i] + 1]))
+        reason = (K.piz_reason if c >= n_z else K.inflate_reason)(st)
+        raise _fail(getattr(items[order[k]], "path", "item %d" % order[k]), "chunk %d: %s error: %s" % (
+            c - int(first[k]), "PIZ" if c >= n_z else "inflate",
+            reason if st else "%d bytes written, its slot holds %d" % (result[1, c], dst_off[c + 1] - dst_off[c])))
+    out = [None] * len(items)
+    for k, i in enumerate(order):
+        lo = int(dst_off[first[k]])
+        out[i] = (planes[lo:lo + int(items[i].offsets[-1])], own_dev[own_at[k]:own_at[k] + n_chunks[k] + 1])
     return out
 
 
@@ -399,17 +473,18 @@ def load_resize(payload, planes, offsets, out, order="RGB", clip=False):
     return K.exr_load_resize(planes, offsets, hdr.lines, hdr.row_bytes, chan_off, chan_type, hdr.height, hdr.width, out, clip)
 
 
-def read_exr(path, device=None, inflate="host"):
+def read_exr(path, device=None, inflate="host", piz="refuse"):
     """OpenEXR file -> float32 RGB [H, W, 3] on the device (the data window; the file's values, HALF converted exactly, no
     clipping): the EXR counterpart of hdr_io.read_hdr.  inflate: who inflates ZIP / ZIPS chunks -- "host" (zlib) or "device"
-    (K.inflate, csrc/inflate.hip: the stored bytes are uploaded); the pixels are the same"""
+    (K.inflate, csrc/inflate.hip: the stored bytes are uploaded); piz: a PIZ file is refused ("refuse"), decoded by libshdr's host
+    routine ("host") or by K.piz_decode ("device", csrc/piz.hip); the pixels are the same"""
     check_inflate_option("read_exr", inflate)
+    check_piz_option("read_exr", piz)
     device = device or torch.device("cuda", torch.cuda.current_device())
-    if inflate == "device":
-        payload = read_stored(path)
+    payload = read_item(path, inflate, piz)
+    if inflate == "device" or isinstance(payload, Stored):
         (planes, offsets), = upload_batch([payload], device)
     else:
-        payload = read_payload(path)
         planes, offsets = upload(payload, device)
     out = torch.empty((payload.header.height, payload.header.width, 3), device=device, dtype=torch.float32)
     return load_resize(payload, planes, offsets, out, "RGB", clip=False)

@@ -98,13 +98,16 @@ class HdrRealFolder:
     hdr_io.read_ldr; files outside the device decoder's scope are read by PIL, the others still in one batch); "device_scan" is the
     same with the scans prepared on the device too (jpeg.Decoded(unstuff="device")).
     exr_inflate="device" leaves the ZIP / ZIPS chunks of OpenEXR files to the device (exr.read_stored, then ONE exr.upload_batch for
-    all of them; the same arena as with "host", where zlib inflates them one file after the other)."""
+    all of them; the same arena as with "host", where zlib inflates them one file after the other).
+    exr_piz: PIZ-compressed OpenEXR files are refused ("refuse", the default), decoded by libshdr's host routine ("host") or on the
+    device in that one batch ("device", K.piz_decode); the arena is the same either way."""
 
     def __init__(self, dirpath, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1, batch_size=BATCH_SIZE,
-                 augment=True, jpeg_decoder="pil", exr_inflate="host"):
+                 augment=True, jpeg_decoder="pil", exr_inflate="host", exr_piz="refuse"):
         if jpeg_decoder not in ("pil", "device", "device_scan"):
             raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil', 'device' or 'device_scan', got %r" % (jpeg_decoder,))
         exr.check_inflate_option("HdrRealFolder", exr_inflate)
+        exr.check_piz_option("HdrRealFolder", exr_piz)
         hdr_paths = sorted(p for ext in ("*.hdr", "*.exr") for p in glob.glob(os.path.join(dirpath, "HDR_gt", ext)))
         ldr_paths = sorted(glob.glob(os.path.join(dirpath, "LDR_in", "*.jpg")))
         if len(hdr_paths) != len(ldr_paths):
@@ -119,8 +122,7 @@ class HdrRealFolder:
             ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device, "device" if jpeg_decoder == "device_scan" else "host")
         else:
             ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
-        read = exr.read_stored if exr_inflate == "device" else exr.read_payload
-        hdr = [read(p) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
+        hdr = [exr.read_item(p, exr_inflate, exr_piz) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
         self.files = list(zip(hdr_paths, ldr_paths))
         self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0, ldr_arena)
 
