@@ -1097,6 +1097,73 @@ int shdr_jpeg_scan_host(const uint8_t* src, int64_t src_bytes, const shdr_jpeg_s
                         shdr_jpeg_scan_report* report, int64_t* bounds, int64_t n_bounds, const int32_t* seg_dword, int seg_stride,
                         int64_t n_segs, uint8_t* arena, int64_t arena_bytes);
 
+/* ---- baseline-JPEG writer (csrc/jpeg_enc.hip; the rules are csrc/jpeg_enc.h, shared with the host twin in csrc/api.cpp) ----
+ * Files as libjpeg writes them for 8-bit RGB pixels: JFIF YCbCr, 4:4:4 / 4:2:2 / 4:2:0, the Annex-K quantisation tables scaled by
+ * the IJG quality rule (clamped to 1 .. 255), the islow integer DCT, the four Annex-K Huffman tables, an optional restart interval --
+ * byte for byte what PIL's Image.save(f, "JPEG", quality=, subsampling=, restart_marker_blocks=) writes.  No grey or CMYK images,
+ * no optimised tables, no progressive or arithmetic coding, no EXIF / ICC / comment segments, no 4:4:0.
+ *
+ * An image is described by a shdr_jpeg_enc_image.  Its coefficient arena is int16 [blocks][64]: MCU after MCU in scan order, in an MCU
+ * the h*v Y blocks row-major, then Cb, then Cr, every block in zig-zag order with the DC as a value (not a difference), the dummy
+ * blocks of partial MCUs included.
+ *
+ * Host twin, two stages that can be called on their own (host memory; the negative SHDR_E_* code on failure, see shdr_last_error):
+ *      shdr_jpeg_encode_blocks          the blocks of an image; *out_bytes (may be NULL): an upper bound of its file
+ *      shdr_jpeg_encode_header_host     the bytes from SOI to the end of the SOS header into out [SHDR_JPEG_ENC_HEADER_MAX]; their count
+ *      shdr_jpeg_encode_transform_host  rgb uint8 [H][W][3] -> the arena (coef_blocks: its room, in blocks); the blocks written
+ *      shdr_jpeg_encode_entropy_host    the arena (coef_blocks: exactly the image's) -> the entropy-coded scan: the stuffed restart
+ *                                       segments with the RSTn markers between them, neither header nor EOI; the bytes written.  A
+ *                                       coefficient outside the baseline range (an AC of category > 10, a DC difference of category
+ *                                       > 11) fails with a message that names the block.  Nothing is written at or past out + capacity:
+ *                                       a scan that does not fit fails
+ *      shdr_jpeg_encode_host            both stages and the header: the complete file
+ *
+ * Device, a BATCH of images of different sizes, layouts, qualities and restart intervals in one call:
+ *      pixels      device: the images' [H][W][3] pixels back to back, uint8 (SHDR_JPEG_ENC_U8) or float32 in [0, 1]
+ *                  (SHDR_JPEG_ENC_F32, quantised as shdr_jpeg_round_trip_f32 does: rintf(x * 255), clamped)
+ *      images      one descriptor per image, as a host array, which is validated, and as the device copy of that very array
+ *                  (images_dev), which the kernels read
+ *      headers     [n_images][SHDR_JPEG_ENC_HEADER_MAX]: what shdr_jpeg_encode_header_host composes for every image, as a host array,
+ *                  which is validated, and as its device copy (headers_dev)
+ *      out         device bytes, 4-byte aligned: the files back to back; out_capacity must be at least the out_bytes of
+ *                  shdr_jpeg_encode_batch_sizes
+ *      offsets     device int64 [n_images + 1]: file i is out[offsets[i] .. offsets[i + 1])
+ *      status      device int32 [n_images]: 0, or SHDR_JPEG_ENC_OUT_OF_RANGE for an image with a coefficient outside the baseline range;
+ *                  the bytes of such an image are unspecified and its offset range is empty
+ *      workspace   workspace_bytes of shdr_jpeg_encode_batch_sizes, 16-byte aligned, owned by the caller
+ *      stage_ms    NULL, or [SHDR_JPEG_ENC_STAGES] device-event times: transform, bits per block, scan + segments, bit stream,
+ *                  FF count + scan, sizes + scan, final copy (measurement only: the call then waits)
+ * shdr_jpeg_encode_entropy_batch takes the images' coefficient arenas back to back (16-byte aligned, coef_blocks: the sum of their
+ * blocks) instead of pixels and writes what shdr_jpeg_encode_entropy_host writes: scans without header and EOI (quality is not used).
+ * Stream-ordered launches, no global atomics -- the same input gives the same bytes -- no host wait and no allocation.  Arguments are
+ * checked before anything is launched. */
+#define SHDR_JPEG_ENC_HEADER_MAX 640
+#define SHDR_JPEG_ENC_STAGES 7
+#define SHDR_JPEG_ENC_OUT_OF_RANGE 1
+#define SHDR_JPEG_ENC_U8 0
+#define SHDR_JPEG_ENC_F32 1
+typedef struct shdr_jpeg_enc_image {
+  int32_t height, width;
+  int32_t layout;                             /* 0: 4:4:4, 1: 4:2:2, 2: 4:2:0 */
+  int32_t quality;                            /* 1 .. 100 */
+  int32_t restart;                            /* MCUs per restart segment, 0 .. 65535; 0: none */
+  int32_t reserved;
+} shdr_jpeg_enc_image;
+int64_t shdr_jpeg_encode_blocks(const shdr_jpeg_enc_image* image, int64_t* out_bytes);
+int shdr_jpeg_encode_header_host(const shdr_jpeg_enc_image* image, uint8_t* out);
+int64_t shdr_jpeg_encode_transform_host(const uint8_t* rgb, const shdr_jpeg_enc_image* image, int16_t* coef, int64_t coef_blocks);
+int64_t shdr_jpeg_encode_entropy_host(const int16_t* coef, int64_t coef_blocks, const shdr_jpeg_enc_image* image, uint8_t* out,
+                                      int64_t capacity);
+int64_t shdr_jpeg_encode_host(const uint8_t* rgb, const shdr_jpeg_enc_image* image, uint8_t* out, int64_t capacity);
+int shdr_jpeg_encode_batch_sizes(const shdr_jpeg_enc_image* images, int n_images, int64_t* out_bytes, int64_t* n_blocks,
+                                 int64_t* workspace_bytes);
+int shdr_jpeg_encode_batch(const void* pixels, int pixel_type, const shdr_jpeg_enc_image* images, const shdr_jpeg_enc_image* images_dev,
+                           const uint8_t* headers, const uint8_t* headers_dev, int n_images, uint8_t* out, int64_t out_capacity,
+                           int64_t* offsets, int32_t* status, void* workspace, void* stream, float* stage_ms);
+int shdr_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_blocks, const shdr_jpeg_enc_image* images,
+                                   const shdr_jpeg_enc_image* images_dev, int n_images, uint8_t* out, int64_t out_capacity,
+                                   int64_t* offsets, int32_t* status, void* workspace, void* stream, float* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

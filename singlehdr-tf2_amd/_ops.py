@@ -2403,6 +2403,218 @@ def jpeg_compact(src, images, images_dev, result, workspace, seg_dword, seg_stri
     return arena
 
 
+# ---------------------------------------------------------------------------
+# baseline-JPEG writer (jpeg.encode), see csrc/jpeg_enc.hip and csrc/jpeg_enc.h
+# ---------------------------------------------------------------------------
+JPEG_ENC_IMAGE_DTYPE = np.dtype([(name, np.int32) for name in ("height", "width", "layout", "quality", "restart", "reserved")])   # shdr_jpeg_enc_image
+JPEG_ENC_HEADER_MAX = 640                                       # SHDR_JPEG_ENC_HEADER_MAX
+JPEG_ENC_STAGES = 7                                             # SHDR_JPEG_ENC_STAGES
+JPEG_ENC_STAGE_NAMES = ("transform", "bits", "scan_segments", "bit_stream", "ff_count_scan", "sizes_scan", "final")
+JPEG_ENC_OUT_OF_RANGE = 1                                       # SHDR_JPEG_ENC_OUT_OF_RANGE
+JPEG_ENC_LAYOUTS = {"444": 0, "422": 1, "420": 2}
+JPEG_ENC_GUARD = 0xA5                                           # what the guard bytes of jpeg_encode(..., guard=) hold
+
+
+def jpeg_enc_images(shapes, quality=75, subsampling="420", restart_interval=0):
+    """the descriptors (JPEG_ENC_IMAGE_DTYPE [n]) of images of `shapes` [(H, W)]; quality, subsampling ("444" | "422" | "420") and
+    restart_interval (MCUs, 0 .. 65535): one value for all images or one per image.  ValueError for anything outside the writer's scope."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    n = len(shapes)
+    if n == 0:
+        raise ValueError("jpeg_encode: no images")
+
+    def per_image(value, name):
+        values = list(value) if isinstance(value, (list, tuple, np.ndarray)) else [value] * n
+        if len(values) != n:
+            raise ValueError("jpeg_encode: %d values of %s for %d images" % (len(values), name, n))
+        return values
+    images = np.zeros(n, dtype=JPEG_ENC_IMAGE_DTYPE)
+    for i, (shape, q, sub, rst) in enumerate(zip(shapes, per_image(quality, "quality"), per_image(subsampling, "subsampling"),
+                                                 per_image(restart_interval, "restart_interval"))):
+        if len(shape) != 2 or not (1 <= shape[0] <= 65535 and 1 <= shape[1] <= 65535):
+            raise ValueError("jpeg_encode: image %d is %s: H and W must be 1 .. 65535" % (i, shape))
+        if str(sub) not in JPEG_ENC_LAYOUTS:
+            raise ValueError("jpeg_encode: subsampling must be '444', '422' or '420', got %r" % (sub,))
+        if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
+            raise ValueError("jpeg_encode: quality must be an integer 1 .. 100, got %r" % (q,))
+        if isinstance(rst, bool) or int(rst) != rst or not 0 <= int(rst) <= 65535:
+            raise ValueError("jpeg_encode: restart_interval must be an integer 0 .. 65535 (MCUs), got %r" % (rst,))
+        images[i] = (shape[0], shape[1], JPEG_ENC_LAYOUTS[str(sub)], int(q), int(rst), 0)
+    return images
+
+
+def _jpeg_enc_image(image, what):
+    image = np.ascontiguousarray(image)
+    if image.dtype != JPEG_ENC_IMAGE_DTYPE or image.size != 1:
+        raise ValueError("%s: expected one descriptor of JPEG_ENC_IMAGE_DTYPE (jpeg_enc_images)" % what)
+    return image.reshape(1)
+
+
+def _jpeg_enc_fail(lib, n):
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return n
+
+
+def jpeg_encode_blocks(image):
+    """(blocks of the image's coefficient arena, an upper bound of its file in bytes)"""
+    lib = _lib.load()
+    image = _jpeg_enc_image(image, "jpeg_encode_blocks")
+    bound = ctypes.c_int64(0)
+    return _jpeg_enc_fail(lib, lib.shdr_jpeg_encode_blocks(_hptr(image), ctypes.byref(bound))), bound.value
+
+
+def jpeg_encode_header_host(image):
+    """the bytes from SOI to the end of the SOS header"""
+    lib = _lib.load()
+    image = _jpeg_enc_image(image, "jpeg_encode_header_host")
+    out = np.zeros(JPEG_ENC_HEADER_MAX, dtype=np.uint8)
+    return out[:_jpeg_enc_fail(lib, lib.shdr_jpeg_encode_header_host(_hptr(image), _hptr(out)))].tobytes()
+
+
+def jpeg_encode_transform_host(rgb, image):
+    """first stage of the host twin: uint8 [H, W, 3] -> int16 [blocks, 64] (zig-zag order, MCU scan order, dummy blocks included)"""
+    lib = _lib.load()
+    image = _jpeg_enc_image(image, "jpeg_encode_transform_host")
+    rgb = np.ascontiguousarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.shape != (int(image["height"][0]), int(image["width"][0]), 3):
+        raise ValueError("jpeg_encode_transform_host: expected uint8 [H, W, 3] of the descriptor's size, got %s %s" % (rgb.dtype, rgb.shape))
+    blocks, _ = jpeg_encode_blocks(image)
+    coef = np.zeros((blocks, 64), dtype=np.int16)
+    _jpeg_enc_fail(lib, lib.shdr_jpeg_encode_transform_host(_hptr(rgb), _hptr(image), _hptr(coef), blocks))
+    return coef
+
+
+def jpeg_encode_entropy_host(coef, image, capacity=None, guard=0):
+    """second stage of the host twin: int16 [blocks, 64] -> the scan's bytes (stuffed segments and RSTn markers; no header, no EOI).
+    capacity: room of the output (default: the bound); guard: with it, returns (bytes, the guard bytes behind the room)"""
+    lib = _lib.load()
+    image = _jpeg_enc_image(image, "jpeg_encode_entropy_host")
+    coef = np.ascontiguousarray(coef)
+    if coef.dtype != np.int16 or coef.ndim != 2 or coef.shape[1] != 64:
+        raise ValueError("jpeg_encode_entropy_host: expected int16 [blocks, 64]")
+    cap = jpeg_encode_blocks(image)[1] if capacity is None else int(capacity)
+    out = np.full(max(cap, 0) + int(guard), JPEG_ENC_GUARD, dtype=np.uint8)
+    try:
+        n = _jpeg_enc_fail(lib, lib.shdr_jpeg_encode_entropy_host(_hptr(coef), coef.shape[0], _hptr(image), _hptr(out), cap))
+    except ValueError as e:
+        if guard:
+            e.guard = out[max(cap, 0):].copy()
+        raise
+    return (out[:n].tobytes(), out[cap:].copy()) if guard else out[:n].tobytes()
+
+
+def jpeg_encode_host(rgb, image, capacity=None, guard=0):
+    """the host twin: the complete file of uint8 [H, W, 3]; capacity, guard: as jpeg_encode_entropy_host"""
+    lib = _lib.load()
+    image = _jpeg_enc_image(image, "jpeg_encode_host")
+    rgb = np.ascontiguousarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.shape != (int(image["height"][0]), int(image["width"][0]), 3):
+        raise ValueError("jpeg_encode_host: expected uint8 [H, W, 3] of the descriptor's size, got %s %s" % (rgb.dtype, rgb.shape))
+    cap = jpeg_encode_blocks(image)[1] if capacity is None else int(capacity)
+    out = np.full(max(cap, 0) + int(guard), JPEG_ENC_GUARD, dtype=np.uint8)
+    try:
+        n = _jpeg_enc_fail(lib, lib.shdr_jpeg_encode_host(_hptr(rgb), _hptr(image), _hptr(out), cap))
+    except ValueError as e:
+        if guard:
+            e.guard = out[max(cap, 0):].copy()
+        raise
+    return (out[:n].tobytes(), out[cap:].copy()) if guard else out[:n].tobytes()
+
+
+def _jpeg_enc_pixels(pixels, what):
+    """(flat pixels, [(H, W)]) of one [H, W, 3] or [N, H, W, 3] device tensor (used as it is) or a list of [H, W, 3] tensors (packed back to
+    back on the device); uint8, or float32 in [0, 1]"""
+    def chk(t):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.uint8, torch.float32) and t.dim() in (3, 4) and t.shape[-1] == 3):
+            raise TypeError("%s: expected uint8 or float32 RGB device tensors [H, W, 3] or [N, H, W, 3]" % what)
+        if t.numel() == 0:
+            raise ValueError("%s: an image has no pixels: %s" % (what, tuple(t.shape)))
+        return t.contiguous()
+    if isinstance(pixels, (list, tuple)):
+        if not pixels:
+            raise ValueError("%s: no images" % what)
+        imgs = [chk(t) for t in pixels]
+        if any(t.dim() != 3 for t in imgs) or any(t.dtype != imgs[0].dtype for t in imgs):
+            raise TypeError("%s: a list holds single images [H, W, 3] of one dtype" % what)
+        flat = imgs[0].reshape(-1) if len(imgs) == 1 else torch.cat([t.reshape(-1) for t in imgs])
+        return flat, [tuple(t.shape[:2]) for t in imgs]
+    t = chk(pixels)
+    return t.reshape(-1), [tuple(t.shape[-3:-1])] * (1 if t.dim() == 3 else t.shape[0])
+
+
+def _jpeg_enc_run(what, images, dev, stage_ms, guard, info, call, buffers=None):
+    """the buffers and the call shared by jpeg_encode and jpeg_encode_entropy: call(lib, images_dev, out, cap, offsets, status, ws, ms).
+    buffers: a dict in which output and workspace are kept from call to call and grown when needed (both are sized for the worst
+    case, hundreds of MB for a 12-Mpixel image) -- for a caller that has finished with the previous call's output"""
+    lib = _lib.load()
+    n = images.size
+    out_b, blocks, ws_b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib.shdr_jpeg_encode_batch_sizes(_hptr(images), n, ctypes.byref(out_b), ctypes.byref(blocks), ctypes.byref(ws_b))
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    guard = (int(guard) + 15) // 16 * 16
+    fill = (lambda size: torch.full((size,), JPEG_ENC_GUARD, device=dev, dtype=torch.uint8)) if guard else \
+        (lambda size: torch.empty(size, device=dev, dtype=torch.uint8))
+    if buffers is not None and not guard:
+        kept = buffers.get("raw")
+        if kept is None or kept[0].device != dev or kept[0].numel() < out_b.value or kept[1].numel() < ws_b.value:
+            buffers["raw"] = kept = (fill(out_b.value), fill(ws_b.value))
+        out_raw, ws_raw = kept
+    else:
+        out_raw, ws_raw = fill(out_b.value + 2 * guard), fill(ws_b.value + 2 * guard)
+    out, ws = out_raw[guard:guard + out_b.value], ws_raw[guard:guard + ws_b.value]
+    offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    images_dev = torch.from_numpy(images.view(np.uint8).copy()).to(dev)
+    with _stage_times(stage_ms, JPEG_ENC_STAGES) as ms:
+        _lib.check(call(lib, images_dev, out, out_b.value, offsets, status, ws, ms, blocks.value), what)
+    if info is not None:
+        info.update(out_raw=out_raw, workspace_raw=ws_raw, guard=guard, blocks=blocks.value, out_bytes=out_b.value, workspace_bytes=ws_b.value)
+    return out, offsets, status
+
+
+def jpeg_encode(pixels, images, stage_ms=None, guard=0, info=None, buffers=None):
+    """Baseline-JPEG files of a batch of RGB images, written on the device (csrc/jpeg_enc.hip): byte for byte what the host twin
+    jpeg_encode_host -- and PIL, for the same quality, subsampling and restart_marker_blocks -- writes.  pixels: uint8, or float32 in
+    [0, 1] (quantised as jpeg_round_trip does), one device tensor [H, W, 3] or [N, H, W, 3] (no copy) or a list of [H, W, 3] tensors of
+    different sizes; images: their descriptors (jpeg_enc_images).  Returns (bytes uint8, offsets int64 [n + 1], status int32 [n]) on the
+    device: file i is bytes[offsets[i]:offsets[i + 1]]; status[i] != 0 (JPEG_ENC_OUT_OF_RANGE) leaves file i empty.  Stream-ordered, no
+    host wait.  stage_ms: a list that receives the device times of the JPEG_ENC_STAGE_NAMES (measurement: the call then waits); guard:
+    bytes of JPEG_ENC_GUARD around the output and the workspace, returned through `info` (a dict) for inspection; buffers: a dict
+    that keeps output and workspace for the next call (the returned bytes are then valid until that call)."""
+    flat, shapes = _jpeg_enc_pixels(pixels, "jpeg_encode")
+    images = np.ascontiguousarray(images)
+    if images.dtype != JPEG_ENC_IMAGE_DTYPE or images.ndim != 1 or [(int(a), int(b)) for a, b in zip(images["height"], images["width"])] != \
+            [(int(a), int(b)) for a, b in shapes]:
+        raise ValueError("jpeg_encode: images must be the descriptors (jpeg_enc_images) of exactly these pixels")
+    lib = _lib.load()
+    headers = np.zeros((images.size, JPEG_ENC_HEADER_MAX), dtype=np.uint8)
+    for i in range(images.size):
+        _jpeg_enc_fail(lib, lib.shdr_jpeg_encode_header_host(_hptr(images[i:i + 1]), _hptr(headers[i])))
+    headers_dev = torch.from_numpy(headers).to(flat.device)
+    ptype = 0 if flat.dtype == torch.uint8 else 1
+
+    def call(lib, images_dev, out, cap, offsets, status, ws, ms, blocks):
+        return lib.shdr_jpeg_encode_batch(_ptr(flat), ptype, _hptr(images), _ptr(images_dev), _hptr(headers), _ptr(headers_dev), images.size,
+                                          _ptr(out), cap, _ptr(offsets), _ptr(status), _ptr(ws), _stream(), ms)
+    return _jpeg_enc_run("shdr_jpeg_encode_batch", images, flat.device, stage_ms, guard, info, call, buffers)
+
+
+def jpeg_encode_entropy(coef, images, stage_ms=None, guard=0, info=None):
+    """the entropy stages alone: coef int16 device tensor [blocks, 64], the images' arenas back to back (jpeg_encode_transform_host's
+    layout); returns what jpeg_encode returns, file i being the scan jpeg_encode_entropy_host writes (no header, no EOI)"""
+    coef = _chk(coef, "coef", torch.int16)
+    images = np.ascontiguousarray(images)
+    if images.dtype != JPEG_ENC_IMAGE_DTYPE or images.ndim != 1 or coef.dim() != 2 or coef.shape[1] != 64:
+        raise ValueError("jpeg_encode_entropy: expected coef int16 [blocks, 64] and descriptors (jpeg_enc_images)")
+
+    def call(lib, images_dev, out, cap, offsets, status, ws, ms, blocks):
+        return lib.shdr_jpeg_encode_entropy_batch(_ptr(coef), coef.shape[0], _hptr(images), _ptr(images_dev), images.size, _ptr(out), cap,
+                                                  _ptr(offsets), _ptr(status), _ptr(ws), _stream(), ms)
+    return _jpeg_enc_run("shdr_jpeg_encode_entropy_batch", images, coef.device, stage_ms, guard, info, call)
+
+
 EXR_HALF, EXR_FLOAT = 1, 2
 
 

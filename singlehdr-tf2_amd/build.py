@@ -56,6 +56,7 @@ SOURCES = {
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
     "jpeg_scan.hip": [],
+    "jpeg_enc.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]
@@ -80,7 +81,7 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
                os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
-               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "piz.h"), os.path.join(CSRC, "jpeg_scan.h"),
+               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "piz.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_enc.h"),
                os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []

@@ -23,6 +23,27 @@ def jpeg_qualities(batch_size):
     return [int(round(float(i) / float(batch_size - 1) * 10.0 + 90.0)) for i in range(batch_size)]
 
 
+def write_ldr_jpegs(ldr, paths, qualities=None, subsampling="420", restart_interval=0):
+    """the simulated LDR batch as JPEG files: ldr float32 [b, h, w, 3] in [0, 1] on the device (CameraPipeline's first output) ->
+    one baseline-JPEG file per sample at `paths`, coded on the device straight from the float tensor (jpeg.encode: the 8-bit
+    quantisation of K.jpeg_round_trip, libjpeg's bytes) -- only the finished files reach the host.  qualities: one per sample,
+    default the qualities the simulator draws (jpeg_qualities).  Decoding such a file with libjpeg gives K.jpeg_round_trip's image
+    of the sample exactly; hdr_real.HdrRealFolder reads a folder of them from LDR_in/."""
+    try:
+        from . import jpeg
+    except ImportError:
+        import jpeg
+    paths = list(paths)
+    if ldr.dim() != 4 or ldr.shape[0] != len(paths):
+        raise ValueError("write_ldr_jpegs: expected ldr [b, h, w, 3] and b paths, got %s and %d" % (tuple(ldr.shape), len(paths)))
+    q = jpeg_qualities(ldr.shape[0]) if qualities is None else [int(v) for v in qualities]
+    files = jpeg.encode(ldr.detach().float().contiguous(), quality=q, subsampling=subsampling, restart_interval=restart_interval)
+    for path, data in zip(paths, files):
+        with open(path, "wb") as f:
+            f.write(data)
+    return files
+
+
 class CameraPipeline:
     def __init__(self, seed=1):
         self.seed, self.calls = int(seed), 0

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "shdr_internal.h"
+#include "jpeg_enc.h"
 
 namespace shdr {
 static thread_local char g_last_error[512] = "";
@@ -205,4 +206,81 @@ extern "C" int64_t shdr_exr_rle_decode(const uint8_t* data, int64_t size, uint8_
     }
   }
   return w;
+}
+
+// ---------------------------------------------------------------- baseline-JPEG writer: the host twin of csrc/jpeg_enc.hip
+// The rules are csrc/jpeg_enc.h, shared with the kernels; these entries add the argument checks and the messages.  Host only.
+namespace {
+int enc_image(const char* what, const shdr_jpeg_enc_image* im, jpegenc::Image* out) {
+  SHDR_REQUIRE(im, SHDR_E_NULL, "%s: null image descriptor", what);
+  static_assert(sizeof(shdr_jpeg_enc_image) == sizeof(jpegenc::Image), "shdr_jpeg_enc_image and jpegenc::Image differ");
+  memcpy(out, im, sizeof(*out));
+  SHDR_REQUIRE(jpegenc::image_ok(*out), SHDR_E_SHAPE,
+               "%s: need H and W in 1 .. 65535, layout 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), quality 1 .. 100 and a restart interval 0 .. "
+               "65535, got %d x %d, layout %d, quality %d, restart %d", what, out->height, out->width, out->layout, out->quality, out->restart);
+  return SHDR_OK;
+}
+int64_t enc_result(const char* what, int64_t n, int64_t bad_block, int64_t capacity) {
+  if (n == jpegenc::kRangeError)
+    return shdr::fail(SHDR_E_SHAPE, "%s: block %lld holds a coefficient outside the baseline range (an AC of category > 10 or a DC "
+                      "difference of category > 11)", what, (long long)bad_block);
+  if (n == jpegenc::kCapacityError) return shdr::fail(SHDR_E_SHAPE, "%s: the output does not fit into %lld bytes", what, (long long)capacity);
+  return n;
+}
+}  // namespace
+
+extern "C" int64_t shdr_jpeg_encode_blocks(const shdr_jpeg_enc_image* image, int64_t* out_bytes) {
+  jpegenc::Image im;
+  if (int rc = enc_image("jpeg_encode_blocks", image, &im)) return rc;
+  const jpegenc::Geometry g = jpegenc::geometry(im);
+  if (out_bytes) *out_bytes = jpegenc::out_bound(g);
+  return g.blocks;
+}
+
+extern "C" int shdr_jpeg_encode_header_host(const shdr_jpeg_enc_image* image, uint8_t* out) {
+  jpegenc::Image im;
+  if (int rc = enc_image("jpeg_encode_header_host", image, &im)) return rc;
+  SHDR_REQUIRE(out, SHDR_E_NULL, "jpeg_encode_header_host: null output");
+  return jpegenc::compose_header(im, out);
+}
+
+extern "C" int64_t shdr_jpeg_encode_transform_host(const uint8_t* rgb, const shdr_jpeg_enc_image* image, int16_t* coef, int64_t coef_blocks) {
+  const char* what = "jpeg_encode_transform_host";
+  jpegenc::Image im;
+  if (int rc = enc_image(what, image, &im)) return rc;
+  SHDR_REQUIRE(rgb && coef, SHDR_E_NULL, "%s: null pointer", what);
+  const jpegenc::Geometry g = jpegenc::geometry(im);
+  SHDR_REQUIRE(coef_blocks >= g.blocks, SHDR_E_SHAPE, "%s: the arena holds %lld blocks, the image has %lld", what, (long long)coef_blocks,
+               (long long)g.blocks);
+  jpegenc::transform_host(rgb, im, coef);
+  return g.blocks;
+}
+
+extern "C" int64_t shdr_jpeg_encode_entropy_host(const int16_t* coef, int64_t coef_blocks, const shdr_jpeg_enc_image* image, uint8_t* out,
+                                                 int64_t capacity) {
+  const char* what = "jpeg_encode_entropy_host";
+  jpegenc::Image im;
+  if (int rc = enc_image(what, image, &im)) return rc;
+  SHDR_REQUIRE(coef && out, SHDR_E_NULL, "%s: null pointer", what);
+  SHDR_REQUIRE(capacity >= 0, SHDR_E_SHAPE, "%s: negative capacity", what);
+  const jpegenc::Geometry g = jpegenc::geometry(im);
+  SHDR_REQUIRE(coef_blocks == g.blocks, SHDR_E_SHAPE, "%s: the arena holds %lld blocks, the image has %lld", what, (long long)coef_blocks,
+               (long long)g.blocks);
+  int64_t bad = -1;
+  return enc_result(what, jpegenc::entropy_host(coef, im, out, capacity, &bad), bad, capacity);
+}
+
+extern "C" int64_t shdr_jpeg_encode_host(const uint8_t* rgb, const shdr_jpeg_enc_image* image, uint8_t* out, int64_t capacity) {
+  const char* what = "jpeg_encode_host";
+  jpegenc::Image im;
+  if (int rc = enc_image(what, image, &im)) return rc;
+  SHDR_REQUIRE(rgb && out, SHDR_E_NULL, "%s: null pointer", what);
+  SHDR_REQUIRE(capacity >= 0, SHDR_E_SHAPE, "%s: negative capacity", what);
+  const jpegenc::Geometry g = jpegenc::geometry(im);
+  int16_t* coef = static_cast<int16_t*>(malloc((size_t)g.blocks * 128));
+  SHDR_REQUIRE(coef, SHDR_E_SHAPE, "%s: no memory for %lld blocks", what, (long long)g.blocks);
+  int64_t bad = -1;
+  const int64_t n = jpegenc::encode_host(rgb, im, coef, out, capacity, &bad);
+  free(coef);
+  return enc_result(what, n, bad, capacity);
 }

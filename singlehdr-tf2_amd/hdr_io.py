@@ -157,14 +157,37 @@ def rgbe_decode(rgbe):
     return rgbe[..., :3].astype(np.float32) * scale[..., None]
 
 
-def write_preview(path, hdr_tensor, peak=None, reverse_channels=False):
+def _check_preview_encoder(encoder, path, what):
+    if encoder not in ("pil", "device"):
+        raise ValueError("%s: the preview encoder must be 'pil' or 'device', got %r" % (what, encoder))
+    if encoder == "device" and os.path.splitext(str(path))[1].lower() not in (".jpg", ".jpeg"):
+        raise ValueError("%s: the device encoder writes JPEG files only (.jpg / .jpeg), got %r" % (what, path))
+
+
+def write_preview(path, hdr_tensor, peak=None, reverse_channels=False, encoder="pil", jpeg_options=None):
     """8-bit preview of an HDR image: float32 [H, W, 3] on the device -> K.tonemap_u8 (mu-law tone curve up to `peak`, default the
-    image's maximum, then a 2.2 gamma) -> an image file through PIL (the format follows the extension; PNG is lossless)"""
-    from PIL import Image
+    image's maximum, then a 2.2 gamma) -> an image file through PIL (the format follows the extension; PNG is lossless).
+    encoder="device" (only for .jpg / .jpeg paths) codes the file on the device instead (jpeg.encode) and copies the finished bytes:
+    the bytes PIL writes for the same 8-bit image and the same `jpeg_options` (quality, subsampling, restart_interval; PIL's defaults
+    where they are not given: quality 75, 4:2:0)."""
     if hdr_tensor.dim() != 3:
         raise ValueError("write_preview: expected one image [H, W, 3], got %s" % (tuple(hdr_tensor.shape),))
+    _check_preview_encoder(encoder, path, "write_preview")
+    options = dict(jpeg_options or {})
     u8 = K.tonemap_u8(hdr_tensor.contiguous(), peak, reverse_channels)
-    Image.fromarray(u8.cpu().numpy(), "RGB").save(path)
+    if encoder == "device":
+        try:
+            from . import jpeg
+        except ImportError:
+            import jpeg
+        jpeg.write_jpeg(path, u8, **options)
+        return
+    from PIL import Image
+    if "restart_interval" in options:
+        options["restart_marker_blocks"] = options.pop("restart_interval")
+    if "subsampling" in options:
+        options["subsampling"] = {"444": 0, "422": 1, "420": 2}.get(options["subsampling"], options["subsampling"])
+    Image.fromarray(u8.cpu().numpy(), "RGB").save(path, **options)
 
 
 class HdrReconstructor:
@@ -220,8 +243,9 @@ class HdrReconstructor:
         return self.reconstruct_device(read_ldr(ldr_path))
 
     def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host", output_format="hdr",
-                         exr_options=None):
-        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support.
+                         exr_options=None, preview_encoder="pil", preview_options=None):
+        """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support;
+        preview_encoder, preview_options: write_preview's encoder and jpeg_options ("device": a .jpg preview coded on the device).
         decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
         (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope); "device_scan" is "device" with the scan prepared on
         the device too (unstuff="device": the end of the scan, the byte stuffing and the restart segments; the same bytes again).
@@ -232,6 +256,8 @@ class HdrReconstructor:
         who deflates, and "device_lz", the device encoder with LZ77 matches, is a third choice that only this format has)"""
         _check_encoder(encoder, "reconstruct_file", output_format)
         _check_format(output_format, "reconstruct_file")
+        if preview_path is not None:
+            _check_preview_encoder(preview_encoder, preview_path, "reconstruct_file")
         y = self._read_device(ldr_path, decoder, "reconstruct_file")
         if output_format == "exr":
             exr.write_exr(hdr_path, y, **_exr_options(encoder, exr_options))
@@ -239,7 +265,7 @@ class HdrReconstructor:
             rgbe = K.rgbe_encode(y, reverse_channels=True)
             write_hdr(hdr_path, rgbe if encoder == "device" else rgbe.cpu().numpy(), encoder=encoder)
         if preview_path is not None:
-            write_preview(preview_path, y, reverse_channels=True)
+            write_preview(preview_path, y, reverse_channels=True, encoder=preview_encoder, jpeg_options=preview_options)
 
     def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host", output_format="hdr", exr_options=None):
         """reconstruct_file for a list of files: geometry and inference per image as there, then ALL results of the call coded in one

@@ -16,6 +16,11 @@ In scope: SOF0 / SOF1 (8-bit, Huffman), one component (grey) or three (YCbCr) wi
 reason (progressive, arithmetic, 12-bit, lossless, four components, Adobe transform=0 RGB, other samplings, several scans, not
 a JPEG at all); a damaged file raises CorruptJpeg, from the host checks before anything is launched or from the device's error
 word after it.
+
+The other direction (at the end of this file): encode() / write_jpeg() write baseline files on the device, byte for byte what PIL
+writes for the same quality, subsampling and restart interval (csrc/jpeg_enc.hip; the rules are csrc/jpeg_enc.h).
+
+    files = jpeg.encode([u8_a, u8_b], quality=90, subsampling="420")     # uint8 RGB device tensors of any sizes -> list of bytes
 """
 import collections
 import ctypes
@@ -761,3 +766,82 @@ def read_ldr_device(path, device=None, unstuff="host"):
         import hdr_io
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     return torch.from_numpy(hdr_io.read_ldr(path)).to(dev)
+
+
+# ---------------------------------------------------------------- the writer (csrc/jpeg_enc.hip, csrc/jpeg_enc.h)
+ENCODE_OPTIONS = ("quality", "subsampling", "restart_interval", "encoder")
+_ENCODE_BUFFERS = {}           # (thread, device, stream) -> encode()'s output and workspace, kept from call to call: encode() has copied
+                               # the files to the host before it returns, and both are sized for the worst case
+
+
+def _ops():
+    try:
+        from . import _ops as K
+    except ImportError:
+        import _ops as K
+    return K
+
+
+def _check_encode_options(what, options):
+    """the writer's scope: 8-bit RGB, the standard Huffman tables, sequential; what PIL would take beyond that is refused by name"""
+    refused = {"optimize": "optimised Huffman tables", "progressive": "progressive coding", "progression": "progressive coding",
+               "arithmetic": "arithmetic coding", "exif": "EXIF segments", "icc_profile": "ICC segments", "comment": "comment segments",
+               "qtables": "custom quantisation tables", "dpi": "a density other than 1:1"}
+    for key in options:
+        if key in refused:
+            raise ValueError("%s: %s are outside the writer's scope (option %r)" % (what, refused[key], key))
+        if key not in ENCODE_OPTIONS:
+            raise ValueError("%s: unknown option %r (known: %s)" % (what, key, ", ".join(ENCODE_OPTIONS)))
+
+
+def encode(images, quality=75, subsampling="420", restart_interval=0, encoder="device", stage_ms=None):
+    """8-bit RGB images -> baseline-JPEG files (a list of bytes), byte for byte what PIL writes with
+    Image.save(f, "JPEG", quality=quality, subsampling=subsampling[, restart_marker_blocks=restart_interval]).
+    images: a list of uint8 [H, W, 3] device tensors of any sizes, or one [N, H, W, 3] tensor (float32 in [0, 1] is taken too and
+    quantised as the camera simulator does); with encoder="host" host arrays, coded by libshdr's host twin.  quality: 1 .. 100, one
+    value or one per image; subsampling: "444" | "422" | "420"; restart_interval: MCUs per restart segment, 0 .. 65535.
+    encoder="device": ONE batch call (csrc/jpeg_enc.hip) and one copy of the finished files to the host.  Grey and CMYK images,
+    optimised Huffman tables, progressive and arithmetic coding, EXIF / ICC / comment segments and 4:4:0 raise ValueError."""
+    K = _ops()
+    if encoder not in ("device", "host"):
+        raise ValueError("jpeg.encode: encoder must be 'device' or 'host', got %r" % (encoder,))
+    if encoder == "host":
+        arrays = [np.asarray(a) for a in (images if isinstance(images, (list, tuple)) else (images if np.ndim(images) == 4 else [images]))]
+        for a in arrays:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("jpeg.encode: expected uint8 RGB images [H, W, 3] (grey and CMYK are outside the writer's scope), got %s %s"
+                                 % (a.dtype, a.shape))
+        desc = K.jpeg_enc_images([a.shape[:2] for a in arrays], quality, subsampling, restart_interval)
+        return [K.jpeg_encode_host(a, desc[i:i + 1]) for i, a in enumerate(arrays)]
+    import torch
+    tensors = images if isinstance(images, (list, tuple)) else [images]
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or t.shape[-1:] != (3,) or t.dim() not in (3, 4):
+            raise ValueError("jpeg.encode: expected RGB device tensors [H, W, 3] or [N, H, W, 3] (grey and CMYK are outside the writer's "
+                             "scope), got %s" % (tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__,))
+    if isinstance(images, (list, tuple)):
+        shapes = [tuple(t.shape[:2]) for t in images]
+    else:
+        shapes = [tuple(images.shape[-3:-1])] * (1 if images.dim() == 3 else images.shape[0])
+    desc = K.jpeg_enc_images(shapes, quality, subsampling, restart_interval)
+    import threading
+    first = images[0] if isinstance(images, (list, tuple)) else images
+    key = (threading.get_ident(), first.device, torch.cuda.current_stream(first.device).cuda_stream)
+    out, offsets, status = K.jpeg_encode(images, desc, stage_ms=stage_ms, buffers=_ENCODE_BUFFERS.setdefault(key, {}))
+    # the offsets and status words first (8 (n + 1) + 4 n bytes), then ONE copy of exactly the bytes written
+    off = offsets.cpu().numpy()
+    bad = np.flatnonzero(status.cpu().numpy())
+    if bad.size:
+        raise ValueError("jpeg.encode: image %d holds a coefficient outside the baseline range" % int(bad[0]))
+    data = out[:int(off[-1])].cpu().numpy()
+    return [data[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(shapes))]
+
+
+def write_jpeg(path, image, **options):
+    """one image [H, W, 3] -> a baseline-JPEG file at `path`; options: encode()'s (quality, subsampling, restart_interval, encoder)"""
+    _check_encode_options("jpeg.write_jpeg", options)
+    if getattr(image, "ndim", 0) != 3:
+        raise ValueError("jpeg.write_jpeg: expected one image [H, W, 3], got %s" % (tuple(getattr(image, "shape", ())),))
+    data = encode([image], **options)[0]
+    with open(path, "wb") as f:
+        f.write(data)
