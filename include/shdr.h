@@ -588,6 +588,48 @@ int shdr_rgbe_rle_encode_batch(const uint8_t* rgbe, const int32_t* shapes, const
 int shdr_rgbe_rle_encode_batch_timed(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shapes_dev, int n_images, uint8_t* out,
                                      int64_t out_capacity, int64_t* offsets, void* workspace, void* stream, float* stage_ms);
 
+/* ---- Radiance scanlines read on the device (hdr_io.rle_decode_device; csrc/hdr_rle_dec.h, csrc/hdr_rle_dec.hip) -------------- */
+/* Per-file status of the reader, host twin and device alike (csrc/hdr_rle_dec.h holds the rules both run).  With the failing
+ * scanline y, Python composes the text shdr_rgbe_rle_decode leaves in shdr_last_error (_ops.RGBE_DEC_REASONS). */
+#define SHDR_RGBE_DEC_OK               0
+#define SHDR_RGBE_DEC_TRUNCATED        1   /* "truncated data in scanline y": the data ends in front of a count byte or inside a packet */
+#define SHDR_RGBE_DEC_CORRUPT_RUN      2   /* "corrupt run in scanline y": a run past the line's end */
+#define SHDR_RGBE_DEC_CORRUPT_LITERAL  3   /* "corrupt literal in scanline y": a literal past the line's end */
+#define SHDR_RGBE_DEC_TRUNCATED_FLAT   4   /* "truncated data in flat scanline y": fewer than 4 W bytes left for a flat line */
+#define SHDR_RGBE_DEC_FALLBACK         5   /* (batch) more than 2 H + 64 line markers in the file: left to the host routine */
+/* The host twin of shdr_rgbe_rle_decode, written from csrc/hdr_rle_dec.h: accepts exactly what that routine accepts, the same pixels
+ * and the same return value (the bytes consumed; bytes behind line height - 1 are ignored).  On a refused file it returns -1 and
+ * stores the status, the failing scanline and the offset at which the reader stood: the count byte of the failing packet (size, when
+ * the data ended in front of a count byte) or the start of the flat line cut short.  Accepted: *status 0, *line -1, *stop the return
+ * value.  -1 with *status untouched (see shdr_last_error) for bad arguments only.  Never reads past `size` or writes past the image. */
+int64_t shdr_rgbe_rle_decode_status(const uint8_t* data, int64_t size, int width, int height, uint8_t* rgbe, int* status, int* line,
+                                    int64_t* stop);
+/* The same reader on the device for a BATCH of files of different shapes in one call.
+ *      src                 device bytes, any alignment: the scanline data of all files back to back (the bytes after the resolution line)
+ *      src_off             int64 [n_files + 1], non-decreasing, inside src, at most 2^31 - 1 bytes per file: a host array, which is
+ *                          validated, and the device copy of that very array (_dev), which the kernels read and clamp again
+ *      shapes              int32 [n_files][2] = (H, W), host array and device copy, as for shdr_rgbe_rle_encode_batch
+ *      out                 device bytes, 4-byte aligned: the [H][W][4] pixels of all files back to back; out_bytes must be at least the
+ *                          out_bytes of shdr_rgbe_rle_decode_batch_sizes (4 H W per file)
+ *      out_off_dev         device int64 [n_files + 1], WRITTEN: file i is out[out_off[i] .. out_off[i + 1])
+ *      workspace           device, 16-byte aligned, at least the workspace_bytes of shdr_rgbe_rle_decode_batch_sizes for the same tables
+ *      status, line        device int32 [n_files]: SHDR_RGBE_DEC_* and the failing scanline (-1 for an accepted or FALLBACK file)
+ *      consumed            device int64 [n_files]: the bytes consumed (accepted), the twin's stop offset (refused), -1 (FALLBACK)
+ *      stage_ms            NULL, or float [SHDR_RGBE_DEC_STAGES] for the device-event times of the four stages (mark and compact the line
+ *                          markers; parse every marked line; rank: rows by pointer doubling; expand) -- measurement only: the call
+ *                          then waits for them
+ * An accepted file's slot holds the host routine's pixels.  A FALLBACK file's slot is not written at all; a refused file's slot is
+ * unspecified inside its bounds.  Nothing outside a file's own slot is written on its behalf, nothing outside src is read, and a
+ * refused file does not affect the others.  Six stream-ordered launches, no global atomics -- the same input gives the same bytes --
+ * no host wait and no allocation.  Arguments are checked before anything is launched. */
+#define SHDR_RGBE_DEC_STAGES 4
+int shdr_rgbe_rle_decode_batch_sizes(const int32_t* shapes, const int64_t* src_off, int n_files, int64_t* out_bytes,
+                                     int64_t* workspace_bytes);
+int shdr_rgbe_rle_decode_batch(const uint8_t* src, int64_t src_bytes, const int64_t* src_off, const int64_t* src_off_dev,
+                               const int32_t* shapes, const int32_t* shapes_dev, int n_files, uint8_t* out, int64_t out_bytes,
+                               int64_t* out_off_dev, void* workspace, int64_t workspace_bytes, int32_t* status, int32_t* line,
+                               int64_t* consumed, void* stream, float* stage_ms);
+
 /* ---- training-set patch sampler (dataset.py:141-252; cv2.resize with the default INTER_LINEAR, see csrc/dataset.hip) ---- */
 /* HDRDataset._hdr_read_resize (dataset.py:181-202): RGBE [H0][W0][4] -> float BGR [H][W][3] (Ward's decode without +0.5,
  * channels reversed, clip(0, None)), resized by cv2's bilinear rule (half-pixel centres, replicated border). */

@@ -1858,6 +1858,82 @@ def rgbe_rle_encode(rgbe, capacity=None, stage_ms=None):
     return out, offsets
 
 
+# SHDR_RGBE_DEC_* (include/shdr.h) -> the words of shdr_rgbe_rle_decode's messages; FALLBACK is no failure (the host routine decodes)
+RGBE_DEC_OK, RGBE_DEC_TRUNCATED, RGBE_DEC_CORRUPT_RUN, RGBE_DEC_CORRUPT_LITERAL, RGBE_DEC_TRUNCATED_FLAT, RGBE_DEC_FALLBACK = range(6)
+RGBE_DEC_REASONS = {
+    RGBE_DEC_TRUNCATED: "truncated data in scanline %d",
+    RGBE_DEC_CORRUPT_RUN: "corrupt run in scanline %d",
+    RGBE_DEC_CORRUPT_LITERAL: "corrupt literal in scanline %d",
+    RGBE_DEC_TRUNCATED_FLAT: "truncated data in flat scanline %d",
+}
+
+
+def rgbe_dec_message(status, line):
+    """the text shdr_rgbe_rle_decode leaves in shdr_last_error for a file refused with (status, line)"""
+    if status not in RGBE_DEC_REASONS:
+        raise ValueError("rgbe_dec_message: status %r is no refusal" % (status,))
+    return "rgbe_rle_decode: " + RGBE_DEC_REASONS[status] % line
+
+
+def rgbe_rle_decode_host(data, w, h):
+    """scanline bytes of one Radiance file -> (pixels uint8 [h, w, 4] or None, status, line, consumed): libshdr's host twin of
+    shdr_rgbe_rle_decode (csrc/hdr_rle_dec.h, the rules the kernels run).  consumed: the bytes consumed, or for a refused file the
+    offset at which the reader stood"""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0:
+        raise ValueError("rgbe_rle_decode_host: the image is %d x %d (H x W): sizes must be positive" % (h, w))
+    out = np.zeros((h, w, 4), dtype=np.uint8)
+    st, ln, stop = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int64(-1)
+    n = lib.shdr_rgbe_rle_decode_status(_hptr(src) if src.size else None, src.size, w, h, _hptr(out), ctypes.byref(st), ctypes.byref(ln),
+                                        ctypes.byref(stop))
+    if st.value < 0:
+        raise RuntimeError("shdr_rgbe_rle_decode_status: %s" % lib.shdr_last_error().decode())
+    if st.value != RGBE_DEC_OK:
+        return None, st.value, ln.value, stop.value
+    return out, st.value, ln.value, n
+
+
+def rgbe_rle_decode(src, src_off, shapes, stage_ms=None):
+    """Radiance scanline bytes of a batch of files decoded on the device (csrc/hdr_rle_dec.hip): the pixels, refusals and consumed counts
+    of the host routine shdr_rgbe_rle_decode.  src: uint8 device tensor, the files' scanline data back to back; src_off: int64 [n + 1]
+    (host: array or list), file i is src[src_off[i]:src_off[i + 1]]; shapes: int32 [n, 2] = (H, W) (host).  Returns device tensors
+    (out uint8, out_off int64 [n + 1], status int32 [n], line int32 [n], consumed int64 [n]): file i is
+    out[out_off[i]:out_off[i + 1]].view(H, W, 4) when status[i] is 0; RGBE_DEC_FALLBACK: not decoded here (more line markers than
+    2 H + 64), its slot is untouched; any other status: refused as the host routine refuses it, in scanline line[i], the reader standing
+    at consumed[i].  Stream-ordered, no host wait.  stage_ms: a list that receives the four stages' device times (measurement: the call
+    then waits)."""
+    lib = _lib.load()
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 1):
+        raise TypeError("rgbe_rle_decode: src must be a flat uint8 device tensor")
+    src = src.contiguous()
+    shapes = np.ascontiguousarray(shapes, dtype=np.int32).reshape(-1, 2)
+    s_host = np.ascontiguousarray(src_off, dtype=np.int64).reshape(-1)
+    n = shapes.shape[0]
+    if s_host.size != n + 1:
+        raise ValueError("rgbe_rle_decode: %d shapes need %d offsets, got %d" % (n, n + 1, s_host.size))
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_rgbe_rle_decode_batch_sizes(_hptr(shapes), _hptr(s_host), n, ctypes.byref(out_b), ctypes.byref(ws_b)),
+               "shdr_rgbe_rle_decode_batch_sizes")
+    dev = src.device
+    out = torch.empty(max(out_b.value, 4), device=dev, dtype=torch.uint8)
+    ws = torch.empty(max(ws_b.value, 16), device=dev, dtype=torch.uint8)
+    out_off = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    line = torch.empty(n, device=dev, dtype=torch.int32)
+    consumed = torch.empty(n, device=dev, dtype=torch.int64)
+    s_dev = torch.from_numpy(s_host).to(dev)
+    shapes_dev = torch.from_numpy(shapes).to(dev)
+    ms = (ctypes.c_float * 4)() if stage_ms is not None else None
+    _lib.check(lib.shdr_rgbe_rle_decode_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev), _hptr(shapes),
+                                              _ptr(shapes_dev), n, _ptr(out), out_b.value, _ptr(out_off), _ptr(ws), ws_b.value,
+                                              _ptr(status), _ptr(line), _ptr(consumed), _stream(), ms), "shdr_rgbe_rle_decode_batch")
+    if stage_ms is not None:
+        stage_ms[:] = list(ms)
+    return out, out_off, status, line, consumed
+
+
 # ---------------------------------------------------------------------------
 # camera-pipeline simulator (joint_training.py:26-69), see csrc/camera.hip
 # ---------------------------------------------------------------------------

@@ -44,6 +44,7 @@ SOURCES = {
     "glue.hip": [],
     "imageio.hip": [],
     "hdr_rle.hip": [],
+    "hdr_rle_dec.hip": [],
     "metrics.hip": [],
     "camera.hip": ["-ffp-contract=off"],
     "dataset.hip": ["-ffp-contract=off"],
@@ -82,7 +83,7 @@ def build(force=False, verbose=True):
     headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
                os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
                os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "piz.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_enc.h"),
-               os.path.join(CSRC, "exr_half.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
+               os.path.join(CSRC, "exr_half.h"), os.path.join(CSRC, "hdr_rle_dec.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
     objs = []
     procs = []
     for src, extra in SOURCES.items():

@@ -5,7 +5,7 @@
     hdr, crf, invcrf, t = reader.read_batch_data()                     # device tensors [b,256,256,3], [b,1024], [b,1024], [b]
 
 Each file is read once when the dataset is built.  Radiance files: the RLE scanlines are decoded on the host (libshdr, a bounded
-thread pool), the RGBE bytes go to the device and one kernel decodes, reverses the channels to cv2's BGR and resizes the short
+thread pool; with hdr_rle="device" on the device, all files in one hdr_io.rle_decode_device), the RGBE bytes go to the device and one kernel decodes, reverses the channels to cv2's BGR and resizes the short
 side to 512 into a resident arena.  OpenEXR files (exr.py): the host inflates or run-length decodes the chunks in the same
 pool, the device undoes OpenEXR's byte predictor and one kernel converts HALF / FLOAT, clips at 0 (:185), orders the channels
 BGR and resizes into the same arena.  A second kernel computes the mean of every 512 x 512 crop.  A batch is then one launch of the
@@ -208,7 +208,7 @@ def _source_shape(item):
     """(h, w) of an item of HDRDataset"""
     if isinstance(item, (exr.Payload, exr.Stored)):
         return item.header.height, item.header.width
-    return item.shape[:2]
+    return item.shape[:2]                               # RGBE pixels, or hdr_io.Scanlines
 
 
 def resized_shape(h, w):
@@ -272,14 +272,17 @@ class HDRDataset(Dataset):
     """the file list; items are the RGBE bytes of a Radiance file or the exr.Payload of an OpenEXR one (the pixels are
     converted on the device, see PatchHDRDataset)"""
 
-    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, exr_inflate="host", exr_piz="refuse"):
+    def __init__(self, hdr_prefix, hdr_posfix_list, is_training, exr_inflate="host", exr_piz="refuse", hdr_rle="host"):
         """exr_inflate "device": ZIP / ZIPS OpenEXR files come back as exr.Stored (checked, not inflated; exr.upload_batch's input).
-        exr_piz: PIZ files are refused ("refuse"), decoded on the host ("host") or come back as exr.Stored too ("device")"""
+        exr_piz: PIZ files are refused ("refuse"), decoded on the host ("host") or come back as exr.Stored too ("device").
+        hdr_rle "device": Radiance files come back as hdr_io.Scanlines (header checked, scanlines left coded; hdr_io.rle_decode_device's
+        input)"""
         self._hdr_prefix = hdr_prefix
         self._hdr_posfix_list = list(hdr_posfix_list)
         self.is_training = is_training
         self.exr_inflate = exr.check_inflate_option("HDRDataset", exr_inflate)
         self.exr_piz = exr.check_piz_option("HDRDataset", exr_piz)
+        self.hdr_rle = hdr_io.check_decoder_option("HDRDataset", hdr_rle)
 
     def path(self, idx):
         return os.path.join(self._hdr_prefix, self._hdr_posfix_list[idx])
@@ -287,7 +290,7 @@ class HDRDataset(Dataset):
     def __getitem__(self, idx):
         path = self.path(idx)
         if not exr.is_exr(path):
-            return hdr_io.read_rgbe(path)
+            return hdr_io.read_scanlines(path) if self.hdr_rle == "device" else hdr_io.read_rgbe(path)
         return exr.read_item(path, self.exr_inflate, self.exr_piz)
 
     def __len__(self):
@@ -299,13 +302,16 @@ class PatchHDRDataset(Dataset):
     normalised to mean 0.5; training adds a random resize, 256 crop, rot90 and flips.  Every file is resident on the device."""
 
     def __init__(self, hdr_prefix, hdr_posfix_list, is_training, load_to_mem=True, device=None, seed=0, exr_inflate="host",
-                 exr_piz="refuse"):
+                 exr_piz="refuse", hdr_rle="host"):
         """load_to_mem is the reference's argument; the images are always resident (on the device).  exr_inflate: who inflates the
         ZIP / ZIPS chunks of OpenEXR files -- "host" (zlib, in the loading threads) or "device" (all files' chunks in one
         exr.upload_batch; the time moves from load_seconds["host_decode"] to load_seconds["device"]); the arena is the same.
         exr_piz: PIZ-compressed OpenEXR files are refused ("refuse", the default), decoded in the loading threads by libshdr's host
-        routine ("host") or on the device, in that same batch ("device", K.piz_decode); the arena is the same either way"""
-        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training, exr_inflate, exr_piz)
+        routine ("host") or on the device, in that same batch ("device", K.piz_decode); the arena is the same either way.
+        hdr_rle: who decodes the scanlines of Radiance files -- "host" (shdr_rgbe_rle_decode, in the loading threads, then one upload
+        of 4 B / pixel per file) or "device" (the coded bytes of all files in one upload and one hdr_io.rle_decode_device; the time
+        moves from load_seconds["host_decode"] to load_seconds["device"]); the arena is the same"""
+        self._hdr_dataset = HDRDataset(hdr_prefix, hdr_posfix_list, is_training, exr_inflate, exr_piz, hdr_rle)
         self._is_training = is_training
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.rng = np.random.default_rng(seed)          # draws of __getitem__ (the reader has its own)
@@ -336,13 +342,15 @@ class PatchHDRDataset(Dataset):
         if self._hdr_dataset.exr_inflate == "device" or any(isinstance(r, exr.Stored) for r in items):     # every OpenEXR file in one batch
             which = [i for i, r in enumerate(items) if isinstance(r, (exr.Payload, exr.Stored))]
             batched = dict(zip(which, exr.upload_batch([items[i] for i in which], self.device)))
+        coded = [i for i, r in enumerate(items) if isinstance(r, hdr_io.Scanlines)]           # hdr_rle="device": every Radiance file in one batch
+        decoded = dict(zip(coded, hdr_io.rle_decode_device([items[i] for i in coded], self.device)))
         for i, (r, (h, w)) in enumerate(zip(items, shapes)):
             out = self.arena[offsets[i]:offsets[i] + sizes[i]].view(h, w, 3)
             if isinstance(r, (exr.Payload, exr.Stored)):
                 planes, chunk_offsets = batched[i] if i in batched else exr.upload(r, self.device)
                 exr.load_resize(r, planes, chunk_offsets, out, "BGR", clip=True)
             else:
-                K.hdr_load_resize(torch.from_numpy(r).to(self.device), out)
+                K.hdr_load_resize(decoded[i] if i in decoded else torch.from_numpy(r).to(self.device), out)
         self.shapes = shapes
         self.offsets = torch.from_numpy(offsets).to(self.device)
         self.dims = torch.tensor(shapes, dtype=torch.int32).to(self.device)
@@ -425,23 +433,23 @@ def _merge(patches, tables):
     return MergeDataset([patches, CatDataset([crf, invcrf]), t])
 
 
-def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
+def get_train_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse", hdr_rle="host"):
     tables = crf_tables("train", crf_path)                     # first: a missing DoRF file fails before any file is loaded
     return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_train"), True, device=device,
-                                  exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
+                                  exr_inflate=exr_inflate, exr_piz=exr_piz, hdr_rle=hdr_rle), tables)
 
 
-def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
+def get_vali_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse", hdr_rle="host"):
     tables = crf_tables("vali", crf_path)
     posfix_list = _posfix_list(hdr_prefix, posfix_list, "i_dataset_test")
     np.random.RandomState(730).shuffle(posfix_list)
-    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device, exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
+    return _merge(PatchHDRDataset(hdr_prefix, posfix_list[:10], False, device=device, exr_inflate=exr_inflate, exr_piz=exr_piz, hdr_rle=hdr_rle), tables)
 
 
-def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse"):
+def get_i_test_dataset(hdr_prefix, posfix_list=None, crf_path=None, device=None, exr_inflate="host", exr_piz="refuse", hdr_rle="host"):
     tables = crf_tables("test", crf_path)
     return _merge(PatchHDRDataset(hdr_prefix, _posfix_list(hdr_prefix, posfix_list, "i_dataset_test"), False, device=device,
-                                  exr_inflate=exr_inflate, exr_piz=exr_piz), tables)
+                                  exr_inflate=exr_inflate, exr_piz=exr_piz, hdr_rle=hdr_rle), tables)
 
 
 # --- RandDatasetReader (dataset.py:318-363) -------------------------------------------------------------------------

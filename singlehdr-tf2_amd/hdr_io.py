@@ -124,8 +124,24 @@ def rle_decode(data, height, width):
     return rgbe
 
 
-def read_rgbe(path):
-    """Radiance picture file -> its RGBE bytes uint8 [H, W, 4] (flat and RLE scanlines, -Y +X orientation)"""
+class Scanlines:
+    """The header walk of read_rgbe without the decode: height, width and the scanline bytes of one Radiance file (`path`: where they
+    came from, for messages)"""
+
+    def __init__(self, height, width, data, path=None):
+        self.height, self.width, self.data, self.path = int(height), int(width), data, path
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 4)
+
+    def decode(self):
+        """the pixels uint8 [H, W, 4], by the host routine"""
+        return rle_decode(self.data, self.height, self.width)
+
+
+def read_scanlines(path):
+    """Radiance picture file -> Scanlines: the container is checked, the scanlines are left coded (rle_decode_device's input)"""
     with open(path, "rb") as f:
         data = f.read()
     if data.startswith(b"\x76\x2f\x31\x01"):
@@ -139,11 +155,76 @@ def read_rgbe(path):
     m = re.match(rb"-Y (\d+) \+X (\d+)", data[end + 2:nl])
     if not m:
         raise ValueError("%s: unsupported resolution line %r" % (path, data[end + 2:nl]))
-    h, w = int(m.group(1)), int(m.group(2))
+    return Scanlines(int(m.group(1)), int(m.group(2)), memoryview(data)[nl + 1:], path)
+
+
+def check_decoder_option(what, decoder):
+    """the scanline decoder of a reader: "host" (shdr_rgbe_rle_decode) or "device" (K.rgbe_rle_decode)"""
+    if decoder not in ("host", "device"):
+        raise ValueError("%s: the Radiance scanline decoder must be 'host' or 'device', got %r" % (what, decoder))
+    return decoder
+
+
+def _item_name(item, i):
+    return item.path if item.path is not None else "scanlines[%d]" % i
+
+
+def rle_decode_device(items, device=None):
+    """a list of Scanlines -> a list of uint8 device tensors [H, W, 4], rle_decode's pixels: ONE upload of all coded bytes, ONE decode
+    call (K.rgbe_rle_decode) and ONE read-back of the per-file reports.  A file with more line markers than the device decoder takes
+    (RGBE_DEC_FALLBACK) is decoded by rle_decode on the host and uploaded.  The first file of the list that the format refuses raises
+    ValueError("<path>: rgbe_rle_decode: ...") with the host route's text."""
+    items = list(items)
+    if not items:
+        return []
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    shapes = np.array([(it.height, it.width) for it in items], dtype=np.int32).reshape(-1, 2)
+    if (shapes <= 0).any():
+        bad = int(np.argmax((shapes <= 0).any(axis=1)))
+        raise ValueError("%s: rgbe_rle_decode: bad arguments" % _item_name(items[bad], bad))
+    sizes = [len(it.data) for it in items]
+    src_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    blob = np.empty(max(int(src_off[-1]), 1), dtype=np.uint8)
+    for it, a, b in zip(items, src_off[:-1], src_off[1:]):
+        blob[a:b] = np.frombuffer(it.data, dtype=np.uint8)
+    src = torch.from_numpy(blob).to(device)[:int(src_off[-1])]
+    out, out_off, status, line, _ = K.rgbe_rle_decode(src, src_off, shapes)
+    report = torch.stack([status, line]).cpu().numpy()                                        # one read-back, and the wait
+    off = np.concatenate([[0], np.cumsum(4 * shapes[:, 0].astype(np.int64) * shapes[:, 1])])
+    result = []
+    for i, it in enumerate(items):
+        st, ln = int(report[0, i]), int(report[1, i])
+        if st == K.RGBE_DEC_OK:
+            result.append(out[off[i]:off[i + 1]].view(it.height, it.width, 4))
+        elif st == K.RGBE_DEC_FALLBACK:
+            try:
+                result.append(torch.from_numpy(it.decode()).to(device))
+            except ValueError as exc:
+                raise ValueError("%s: %s" % (_item_name(it, i), exc)) from None
+        else:
+            raise ValueError("%s: %s" % (_item_name(it, i), K.rgbe_dec_message(st, ln)))
+    return result
+
+
+def read_rgbe(path, decoder="host"):
+    """Radiance picture file -> its RGBE bytes uint8 [H, W, 4] (flat and RLE scanlines, -Y +X orientation).  decoder="device": the
+    scanlines are decoded on the device (rle_decode_device) and the result is a device tensor with the same bytes"""
+    check_decoder_option("read_rgbe", decoder)
+    lines = read_scanlines(path)
+    if decoder == "device":
+        return rle_decode_device([lines])[0]
     try:
-        return rle_decode(memoryview(data)[nl + 1:], h, w)
+        return lines.decode()
     except ValueError as exc:
         raise ValueError("%s: %s" % (path, exc)) from None
+
+
+def read_rgbe_batch(paths, decoder="host", device=None):
+    """read_rgbe for a list of files: host arrays ("host"), or device tensors out of ONE rle_decode_device ("device")"""
+    check_decoder_option("read_rgbe_batch", decoder)
+    if decoder == "host":
+        return [read_rgbe(p) for p in paths]
+    return rle_decode_device([read_scanlines(p) for p in paths], device)
 
 
 def read_hdr(path):

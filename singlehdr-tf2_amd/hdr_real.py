@@ -100,14 +100,17 @@ class HdrRealFolder:
     exr_inflate="device" leaves the ZIP / ZIPS chunks of OpenEXR files to the device (exr.read_stored, then ONE exr.upload_batch for
     all of them; the same arena as with "host", where zlib inflates them one file after the other).
     exr_piz: PIZ-compressed OpenEXR files are refused ("refuse", the default), decoded by libshdr's host routine ("host") or on the
-    device in that one batch ("device", K.piz_decode); the arena is the same either way."""
+    device in that one batch ("device", K.piz_decode); the arena is the same either way.
+    hdr_rle="device" decodes the scanlines of all Radiance files in ONE hdr_io.rle_decode_device (the coded bytes are uploaded, not
+    4 B / pixel per file); "host" (the default) runs shdr_rgbe_rle_decode file by file; the arena is the same."""
 
     def __init__(self, dirpath, device=None, size=SIZE, stride=STRIDE, seed=0, rank=0, world_size=1, batch_size=BATCH_SIZE,
-                 augment=True, jpeg_decoder="pil", exr_inflate="host", exr_piz="refuse"):
+                 augment=True, jpeg_decoder="pil", exr_inflate="host", exr_piz="refuse", hdr_rle="host"):
         if jpeg_decoder not in ("pil", "device", "device_scan"):
             raise ValueError("HdrRealFolder: jpeg_decoder must be 'pil', 'device' or 'device_scan', got %r" % (jpeg_decoder,))
         exr.check_inflate_option("HdrRealFolder", exr_inflate)
         exr.check_piz_option("HdrRealFolder", exr_piz)
+        hdr_io.check_decoder_option("HdrRealFolder", hdr_rle)
         hdr_paths = sorted(p for ext in ("*.hdr", "*.exr") for p in glob.glob(os.path.join(dirpath, "HDR_gt", ext)))
         ldr_paths = sorted(glob.glob(os.path.join(dirpath, "LDR_in", "*.jpg")))
         if len(hdr_paths) != len(ldr_paths):
@@ -122,7 +125,8 @@ class HdrRealFolder:
             ldr, ldr_arena = self._decode_ldr_on_device(ldr_paths, device, "device" if jpeg_decoder == "device_scan" else "host")
         else:
             ldr = [hdr_io.read_ldr(p) for p in ldr_paths]
-        hdr = [exr.read_item(p, exr_inflate, exr_piz) if exr.is_exr(p) else hdr_io.read_rgbe(p) for p in hdr_paths]
+        read_radiance = hdr_io.read_scanlines if hdr_rle == "device" else hdr_io.read_rgbe
+        hdr = [exr.read_item(p, exr_inflate, exr_piz) if exr.is_exr(p) else read_radiance(p) for p in hdr_paths]
         self.files = list(zip(hdr_paths, ldr_paths))
         self._setup(ldr, hdr, device, size, stride, seed, rank, world_size, batch_size, augment, time.perf_counter() - t0, ldr_arena)
 
@@ -199,7 +203,7 @@ class HdrRealFolder:
         shapes = []
         for i, (l, h) in enumerate(zip(ldr, hdr)):
             hs = self._hdr_shape(h)
-            if tuple(l.shape[:2]) != hs or (not isinstance(h, (exr.Payload, exr.Stored)) and h.ndim != 3):
+            if tuple(l.shape[:2]) != hs or (not isinstance(h, (exr.Payload, exr.Stored, hdr_io.Scanlines)) and h.ndim != 3):
                 raise ValueError("HdrRealFolder: %s is %d x %d but %s is %d x %d" % (
                     self.files[i][0], hs[0], hs[1], self.files[i][1], l.shape[0], l.shape[1]))
             shapes.append(hs)
@@ -218,14 +222,16 @@ class HdrRealFolder:
         if any(isinstance(item, exr.Stored) for item in hdr):      # exr_inflate="device": every OpenEXR file in one batch
             which = [i for i, item in enumerate(hdr) if isinstance(item, (exr.Payload, exr.Stored))]
             batched = dict(zip(which, exr.upload_batch([hdr[i] for i in which], self.device)))
+        coded = [i for i, item in enumerate(hdr) if isinstance(item, hdr_io.Scanlines)]       # hdr_rle="device": one batch as well
+        decoded = dict(zip(coded, hdr_io.rle_decode_device([hdr[i] for i in coded], self.device)))
         for i, (item, (h, w)) in enumerate(zip(hdr, shapes)):
             out = self.hdr_arena[3 * offsets[i]:3 * (offsets[i] + h * w)].view(h, w, 3)
             if isinstance(item, (exr.Payload, exr.Stored)):        # HALF / FLOAT converted on the device, the file's values
                 planes, chunk_offsets = batched[i] if i in batched else exr.upload(item, self.device)
                 exr.load_resize(item, planes, chunk_offsets, out, "RGB", clip=False)
-            elif item.dtype == np.uint8 and item.shape[2] == 4:    # RGBE bytes: decoded on the device (a same-size "resize" is an
-                tmp = torch.empty_like(out)                        # exact copy), BGR -> the records' RGB
-                K.hdr_load_resize(torch.from_numpy(item).to(self.device), tmp)
+            elif i in decoded or (item.dtype == np.uint8 and item.shape[2] == 4):      # RGBE bytes: decoded on the device (a same-size
+                tmp = torch.empty_like(out)                                            # "resize" is an exact copy), BGR -> the records' RGB
+                K.hdr_load_resize(decoded[i] if i in decoded else torch.from_numpy(item).to(self.device), tmp)
                 out.copy_(K.reverse3(tmp))
             else:
                 if item.shape[2] != 3:
