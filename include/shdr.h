@@ -768,6 +768,53 @@ int shdr_piz_batch(const uint8_t* src, int64_t src_bytes, const int64_t* src_off
                    int sub_bits, void* workspace, int64_t workspace_bytes, int32_t* status, int64_t* written, int32_t* rounds,
                    void* stream, float* stage_ms);
 
+/* ---- OpenEXR PIZ chunks encoded (exr.py compression="piz", piz="host" / "device"; csrc/piz.h, csrc/piz_enc.hip) -------------- */
+/* UNPINNED AGAINST THE OPENEXR LIBRARY, LIKE THE READER: the format is restated from memory of OpenEXR 2.x and NO OpenEXR-built
+ * reader has opened a file written here.  What is pinned: tests/piz_ref.py writes the same bytes, and this library's decoders and
+ * piz_ref's read them back.
+ * The planar scanlines raw[0 .. n) of one chunk (rows 1 .. 32, n_chan 1 .. 64 channels in name order, chan_words[c] 1 for HALF and 2
+ * for FLOAT / UINT, n = 2 * width * rows * sum(chan_words) <= 2^28; host) -> its PIZ bytes in dst, WHATEVER THEIR SIZE: *written
+ * receives their number.  A caller that stores a chunk raw when coding does not shrink it (OpenEXR's rule) compares *written with n:
+ * the chunk counts as coded only if the PIZ bytes are STRICTLY fewer.  The rules (csrc/piz.h): bitmap of the values present, value 0
+ * implied; the forward LUT is the rank among them; forward wavelet per word plane (the 14-bit pair while fewer than 16385 values
+ * are present); a stretch of equal values is the value once and, from 3 repeats on, run codes of at most 255 repeats each; the
+ * optimal code of the tokens' frequencies by the two-queue method (leaves in (count, symbol) order, a leaf before an internal node
+ * of the same weight); canonical codes; the 6-bit length table with both zero-run forms, cut greedily.
+ * Returns SHDR_OK, or a negative SHDR_E_* code (see shdr_last_error) for a NULL pointer, rows outside 1 .. 32, n_chan outside
+ * 1 .. 64, words other than 1 / 2, an n that is not the shape's, or a capacity below the bytes to write (nothing is written then);
+ * shdr_piz_encode_bound returns a capacity that always suffices (-1 for a shape out of range). */
+int64_t shdr_piz_encode_bound(int width, int rows, const int32_t* chan_words, int n_chan);
+/* One wavelet pair of csrc/piz.h (host; for tests of the rules): which = 0 enc14, 1 enc16 -- (a, b) -> out = (l, h) --, 2 dec14, 3 dec16
+ * -- (l, h) -> out = (a, b); the arguments are taken mod 2^16. */
+int shdr_piz_wavelet_pair(int which, unsigned a, unsigned b, uint16_t* out);
+int shdr_piz_encode_host(const uint8_t* raw, int64_t n, int width, int rows, const int32_t* chan_words, int n_chan, uint8_t* dst,
+                         int64_t capacity, int64_t* written);
+/* The same encoder on the device for a BATCH of chunks of any widths, row counts and channel sets: chunk c is
+ * planar[chunk_off[c] .. chunk_off[c + 1]), its shape geom[c].
+ *      planar       device bytes, 2-byte aligned: the chunks' planar scanlines (what shdr_exr_pack_f32 writes with lines = 32)
+ *      chunk_off    int64 [n_chunks + 1], chunk_off[0] = 0, host array (validated: every chunk has its shape's size) and its device copy
+ *      geom, chan_words   as for shdr_piz_batch (host arrays and device copies)
+ *      pad, out, out_offsets, coded   as for shdr_deflate_huffman_batch: chunk c is stored at out[out_offsets[c] + pad ..
+ *                   out_offsets[c + 1]) -- the bytes of shdr_piz_encode_host where those are STRICTLY fewer than the chunk's
+ *                   (coded[c] = 1), else the chunk's scanline bytes -- so that shdr_exr_finish_chunks finishes the files;
+ *                   out_capacity at least the out_bytes of the _sizes call (the chunks' bytes + pad * n_chunks)
+ *      workspace    workspace_bytes of the _sizes call (about 2.5 MB per chunk + 3 bytes per input byte), 16-byte aligned
+ *      stats        NULL, or device int32 [n_chunks][SHDR_PIZ_ENC_STATS] (measurement): the symbols the chunk's code has, and the ticks
+ *                   of the device's constant-rate counter (wall_clock64) that the one-lane merge of the code lengths took
+ *      stage_ms     NULL, or float [SHDR_PIZ_ENC_STAGES]: device-event times of clear, front (bitmap, LUT, wavelet), hist, code (sort,
+ *                   merge, canonical codes, table), bits, scan, final (measurement only: the call then waits)
+ * Byte for byte the host routine's output and run to run identical: integer atomics only (LDS atomicOr for the bitmap, global atomicAdd
+ * for the per-chunk histogram, global atomicOr for the bit streams), all of them commutative.  Stream-ordered, no host wait, no
+ * allocation.  Arguments are checked before anything is launched. */
+#define SHDR_PIZ_ENC_STAGES 7
+#define SHDR_PIZ_ENC_STATS 2
+int shdr_piz_encode_batch_sizes(const int64_t* chunk_off, const int32_t* geom, const int32_t* chan_words, int n_words, int n_chunks, int pad,
+                                int64_t* out_bytes, int64_t* workspace_bytes);
+int shdr_piz_encode_batch(const uint8_t* planar, const int64_t* chunk_off, const int64_t* chunk_off_dev, const int32_t* geom,
+                          const int32_t* geom_dev, const int32_t* chan_words, const int32_t* chan_words_dev, int n_words, int n_chunks, int pad,
+                          uint8_t* out, int64_t out_capacity, int64_t* out_offsets, uint8_t* coded, void* workspace, int64_t workspace_bytes,
+                          int32_t* stats, void* stream, float* stage_ms);
+
 /* ---- OpenEXR output (exr.py encode_exr / write_exr; csrc/exr_write.hip, csrc/deflate.hip) ------------------------------ */
 /* Huffman-only zlib stream of src[0 .. n), 1 <= n <= 2^30 (host): 78 01, one final dynamic-Huffman block of literals with a
  * fixed-length header (csrc/deflate_huffman.h), the big-endian Adler-32.  zlib's inflate reads it.  Returns the stream's length,
@@ -822,7 +869,7 @@ int shdr_deflate_lz_batch(const uint8_t* data, const uint8_t* raw, const int64_t
                           void* workspace, void* stream, float* stage_ms);
 
 /* float32 images [H][W][3] -> OpenEXR scanline bytes, for a BATCH of images of different sizes in one launch.  A chunk is `lines`
- * scanlines (1: NONE / ZIPS, 16: ZIP; the last chunk of an image may hold fewer); a scanline is W samples of B, then G, then R
+ * scanlines (1: NONE / ZIPS, 16: ZIP, 32: PIZ; the last chunk of an image may hold fewer); a scanline is W samples of B, then G, then R
  * (the name-sorted order), HALF or FLOAT.  reverse_channels = 0: the pixel is R, G, B; != 0: it is B, G, R (the networks' order).
  * HALF is round to nearest even with subnormals, overflow to +-inf and NaN kept (numpy's astype(float16)); saturate != 0 first
  * turns finite values beyond +-65504 into +-65504.
@@ -841,7 +888,8 @@ int shdr_exr_pack_sizes(const int32_t* shapes, int n_images, int pixel_type, int
 int shdr_exr_pack_f32(const float* pixels, const int32_t* shapes, int n_images, int pixel_type, int lines, int reverse_channels,
                       int saturate, const int64_t* table_dev, const int64_t* chunk_off, uint8_t* planar, uint8_t* predicted,
                       void* stream);
-/* Chunk headers and offset tables of a batch of files whose chunks shdr_deflate_huffman_batch stored with pad = 8: writes
+/* Chunk headers and offset tables of a batch of files whose chunks shdr_deflate_huffman_batch (or shdr_piz_encode_batch, lines = 32)
+ * stored with pad = 8: writes
  * int32 y, int32 size in front of every chunk at records[out_offsets[c]] and the uint64 file offset of chunk c to
  * tables[8 c]: header_len[i] + 8 * (chunks of image i) + the chunk's distance from the image's first chunk.  table_dev as
  * above; header_len: device int64 [n_images], the bytes of file i in front of its offset table. */

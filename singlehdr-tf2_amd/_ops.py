@@ -2391,6 +2391,87 @@ def piz_decode(src, src_offsets, dst_offsets, geom, chan_words, mode=None, sub_b
 
 
 # ---------------------------------------------------------------------------
+# OpenEXR PIZ chunks encoded (exr.py compression="piz"), see csrc/piz.h and csrc/piz_enc.hip.  UNPINNED against the OpenEXR library,
+# like the decoder: no OpenEXR-built reader has opened what these write
+# ---------------------------------------------------------------------------
+PIZ_ENC_STAGES = 7                                    # SHDR_PIZ_ENC_STAGES
+PIZ_ENC_STATS = 2                                     # SHDR_PIZ_ENC_STATS
+PIZ_ENC_STAGE_NAMES = ("clear", "front", "hist", "code", "bits", "scan", "final")
+
+
+def piz_encode_host(raw, width, rows, chan_words):
+    """the planar scanline bytes of one chunk -> its PIZ bytes (libshdr's host encoder, csrc/piz.h: the rules the kernels run; byte
+    for byte tests/piz_ref.py's encode_chunk).  chan_words: 1 per HALF channel, 2 per FLOAT / UINT channel, in name order.  The bytes
+    are returned whatever their size: a chunk counts as coded only if len(result) < len(raw).  ValueError for a shape out of range
+    or a size that is not the shape's."""
+    lib = _lib.load()
+    src = np.frombuffer(raw, dtype=np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, dtype=np.uint8)
+    words = np.ascontiguousarray(chan_words, dtype=np.int32)
+    bound = lib.shdr_piz_encode_bound(int(width), int(rows), _hptr(words) if words.size else None, words.size)
+    if bound < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    out = np.empty(bound, dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    rc = lib.shdr_piz_encode_host(src.ctypes.data if src.size else None, src.size, int(width), int(rows), _hptr(words), words.size,
+                                  _hptr(out), out.size, ctypes.byref(n))
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n.value].tobytes()
+
+
+def piz_encode(planar, chunk_off, geom, chan_words, pad=0, front=0, stage_ms=None, chunk_off_dev=None, shape_dev=None, out=None, stats=False):
+    """a batch of chunks PIZ-coded on the device (csrc/piz_enc.hip): byte for byte what piz_encode_host writes, and the same bytes on
+    every run.  planar: uint8 device tensor, the chunks' planar scanlines (exr_pack(lines=32).planar); chunk_off: int64 [n + 1] (host
+    array or tensor), chunk c is planar[chunk_off[c]:chunk_off[c + 1]]; geom: int32 [n, 4] host array (width, rows, first entry and
+    number of entries in chan_words) and chan_words: int32 host array, as for piz_decode (shape_dev: their device copies).  Returns
+    (bytes, out_offsets int64 [n + 1], coded uint8 [n]) on the device as deflate_huffman does: chunk c is stored at
+    bytes[front + out_offsets[c] + pad : front + out_offsets[c + 1]] -- its PIZ bytes where coded[c], else (they would not be strictly
+    fewer) its scanline bytes as they are.  pad: bytes left free in front of every stored chunk; front: bytes left free in front of all
+    of them; out: a uint8 device tensor to store into (default: a new one, not cleared), at least front + the chunks' bytes + pad per
+    chunk.  Stream-ordered, no host wait.  stage_ms: a list that receives the device times of PIZ_ENC_STAGE_NAMES (measurement: the
+    call then waits).  stats=True (measurement): a fourth result, int32 [n, PIZ_ENC_STATS] on the device -- the symbols of every chunk's
+    code and the ticks of the device's constant-rate counter that the one-lane merge of its code lengths took."""
+    lib = _lib.load()
+    planar = _chk(planar, "planar", torch.uint8)
+    off_host, off_dev = _offsets_pair("piz_encode", "chunk_off", chunk_off, chunk_off_dev)
+    n = off_host.size - 1
+    geom = np.ascontiguousarray(geom, dtype=np.int32)
+    words = np.ascontiguousarray(chan_words, dtype=np.int32)
+    if planar.dim() != 1 or n < 1 or int(off_host[-1]) > planar.numel() or geom.shape != (n, 4) or words.ndim != 1:
+        raise ValueError("piz_encode: expected planar [size], chunk_off [n_chunks + 1] that ends within it, geom [n_chunks, 4] and chan_words [n]")
+    out_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.shdr_piz_encode_batch_sizes(_hptr(off_host), _hptr(geom), _hptr(words), words.size, n, int(pad), ctypes.byref(out_b),
+                                               ctypes.byref(ws_b)), "shdr_piz_encode_batch_sizes")
+    dev = planar.device
+    if off_dev is None:
+        off_dev = torch.from_numpy(off_host).to(dev)
+    if shape_dev is None:
+        both = torch.from_numpy(np.concatenate([geom.reshape(-1), words])).to(dev)
+        geom_dev, words_dev = both[:4 * n], both[4 * n:]
+    else:
+        geom_dev, words_dev = _chk(shape_dev[0], "geom_dev", torch.int32), _chk(shape_dev[1], "chan_words_dev", torch.int32)
+        if geom_dev.numel() != 4 * n or words_dev.numel() != words.size:
+            raise ValueError("piz_encode: shape_dev is not a copy of geom and chan_words")
+    front = int(front)
+    if out is None:
+        out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
+    else:
+        out = _chk(out, "out", torch.uint8)
+        if out.dim() != 1 or out.numel() < front + out_b.value:
+            raise ValueError("piz_encode: out holds %d bytes, %d are needed" % (out.numel(), front + out_b.value))
+    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    coded = torch.empty(n, device=dev, dtype=torch.uint8)
+    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    stats_dev = torch.empty((n, PIZ_ENC_STATS), device=dev, dtype=torch.int32) if stats else None
+    with _stage_times(stage_ms, PIZ_ENC_STAGES) as ms:
+        _lib.check(lib.shdr_piz_encode_batch(_ptr(planar), _hptr(off_host), _ptr(off_dev), _hptr(geom), _ptr(geom_dev), _hptr(words),
+                                             _ptr(words_dev), words.size, n, int(pad), out.data_ptr() + front, out_b.value, _ptr(out_offsets),
+                                             _ptr(coded), _ptr(ws), ws.numel(), _ptr(stats_dev) if stats else None, _stream(), ms),
+                   "shdr_piz_encode_batch")
+    return (out, out_offsets, coded, stats_dev) if stats else (out, out_offsets, coded)
+
+
+# ---------------------------------------------------------------------------
 # JPEG scan regions unstuffed and laid out (jpeg.plan_device), see csrc/jpeg_scan.h and csrc/jpeg_scan.hip
 # ---------------------------------------------------------------------------
 JPEG_SCAN_IMAGE_BYTES, JPEG_SCAN_REPORT_BYTES = 40, 32          # shdr_jpeg_scan_image, shdr_jpeg_scan_report
@@ -2727,7 +2808,7 @@ pixel, H * 2^32 + W of every image; table_dev: its device copy); shapes: host in
 
 def exr_pack(images, pixel_type=EXR_HALF, lines=16, reverse_channels=False, saturate=True, predict=True):
     """float32 images -> OpenEXR scanline bytes on the device, one launch for the whole batch (csrc/exr_write.hip).  images: one
-    [H, W, 3], one [N, H, W, 3] or a list of [H, W, 3] device tensors.  Every chunk (`lines` scanlines: 16 for ZIP, 1 for ZIPS / NONE)
+    [H, W, 3], one [N, H, W, 3] or a list of [H, W, 3] device tensors.  Every chunk (`lines` scanlines: 32 for PIZ, 16 for ZIP, 1 for ZIPS / NONE)
     holds per scanline W samples of B, then G, then R, HALF (numpy's astype(float16); saturate: finite values beyond +-65504 become
     +-65504 first) or FLOAT.  reverse_channels: channel 0 of the input is blue (the networks' order).  predict: also the interleaved,
     delta-coded bytes of every chunk, which ZIP / ZIPS deflate.  Returns an ExrPacked."""
@@ -2752,7 +2833,7 @@ def exr_pack(images, pixel_type=EXR_HALF, lines=16, reverse_channels=False, satu
 
 
 def exr_finish_chunks(out, out_offsets, packed, header_len):
-    """chunk headers (int32 y, int32 size) and uint64 offset tables into `out` of deflate_huffman(..., pad=8, front=8 * n_chunks):
+    """chunk headers (int32 y, int32 size) and uint64 offset tables into `out` of deflate_huffman / piz_encode(..., pad=8, front=8 * n_chunks):
     the tables of all images fill the front, image after image; header_len: the bytes of every file in front of its table"""
     lib = _lib.load()
     n, n_chunks = packed.shapes.shape[0], packed.chunk_off.size - 1

@@ -54,6 +54,7 @@ SOURCES = {
     "deflate_lz.hip": [],
     "inflate.hip": [],
     "piz.hip": [],
+    "piz_enc.hip": [],
     "hdr_real.hip": ["-ffp-contract=off"],
     "jpeg.hip": ["-ffp-contract=off"],
     "jpeg_scan.hip": [],

@@ -103,7 +103,7 @@ int check_shapes(const char* what, const int32_t* shapes, int n, int pixel_type,
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "%s: the number of images must be positive, got %d", what, n);
   SHDR_REQUIRE(pixel_type == SHDR_EXR_HALF || pixel_type == SHDR_EXR_FLOAT, SHDR_E_SHAPE, "%s: pixel type %d is neither HALF (1) nor FLOAT (2)",
                what, pixel_type);
-  SHDR_REQUIRE(lines == 1 || lines == 16, SHDR_E_SHAPE, "%s: a chunk holds 1 or 16 scanlines, got %d", what, lines);
+  SHDR_REQUIRE(lines == 1 || lines == 16 || lines == 32, SHDR_E_SHAPE, "%s: a chunk holds 1, 16 or 32 scanlines, got %d", what, lines);
   const int64_t sample = pixel_type == SHDR_EXR_HALF ? 2 : 4;
   int64_t c = 0, b = 0, p = 0;
   for (int i = 0; i < n; ++i) {
@@ -176,7 +176,7 @@ extern "C" int shdr_exr_finish_chunks(uint8_t* records, uint8_t* tables, const i
   SHDR_REQUIRE(records && tables && out_offsets && table_dev && header_len, SHDR_E_NULL, "%s: null pointer", what);
   SHDR_REQUIRE(n_images > 0 && n_chunks > 0 && n_chunks < ((int64_t)1 << 31), SHDR_E_SHAPE, "%s: %d images, %lld chunks", what, n_images,
                (long long)n_chunks);
-  SHDR_REQUIRE(lines == 1 || lines == 16, SHDR_E_SHAPE, "%s: a chunk holds 1 or 16 scanlines, got %d", what, lines);
+  SHDR_REQUIRE(lines == 1 || lines == 16 || lines == 32, SHDR_E_SHAPE, "%s: a chunk holds 1, 16 or 32 scanlines, got %d", what, lines);
   hipLaunchKernelGGL(exr_finish_kernel, dim3((unsigned)((n_chunks + kThreads - 1) / kThreads)), dim3(kThreads), 0, S(stream), records, tables,
                      out_offsets, table_dev, header_len, n_images, n_chunks, lines);
   return shdr::check_launch(what);

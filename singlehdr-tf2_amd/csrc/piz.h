@@ -1,7 +1,9 @@
-// OpenEXR PIZ chunks decoded: the rules of the format, shared by the host routine shdr_piz_decode_host and the device kernels
-// (csrc/piz.hip), so that both run the same checks and end in the same status.  Plain C++: also compiled without HIP.
+// OpenEXR PIZ chunks decoded and, further down, encoded: the rules of the format, shared by the host routines shdr_piz_decode_host /
+// shdr_piz_encode_host and the device kernels (csrc/piz.hip, csrc/piz_enc.hip), so that both sides run the same checks, end in the same
+// status and write the same bytes.  Plain C++: also compiled without HIP.
 //
-// Restated from memory of OpenEXR 2.x; UNPINNED: no OpenEXR-written file has been read (there is no OpenEXR library to compare with).
+// Restated from memory of OpenEXR 2.x; UNPINNED, reader and writer: no OpenEXR-written file has been read and no OpenEXR-built reader
+// has opened a file written by these rules (there is no OpenEXR library to compare with).
 //
 // A chunk (little-endian): u16 minNonZero, u16 maxNonZero, bitmap[min .. max] of an 8192-byte bitmap (if min <= max), i32 length, then
 // `length` bytes of Huffman block: u32 im, iM, tableLength (ignored), nBits, reserved; the packed code-length table of symbols im .. iM
@@ -19,7 +21,10 @@
 // Work is bounded: every token consumes at least one bit, every read is clamped to the chunk, every write is checked against the number
 // of values the chunk must hold; a chunk ends in a Status whatever its bytes are.
 #pragma once
+#include <assert.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #ifndef SHDR_HD
 #if defined(__HIPCC__)
@@ -429,6 +434,333 @@ inline int decode_host(const uint8_t* src, int64_t n, int width, int rows, const
     chan_off += (int64_t)width * words;
   }
   return kOk;
+}
+
+// ---- the encoder: the forward rules, shared by shdr_piz_encode_host and the kernels of csrc/piz_enc.hip ---------------------------------
+// UNPINNED like the decoder: no OpenEXR-built reader has opened what this writes.  The reference is tests/piz_ref.py, byte for byte.
+//
+// bitmap of the 16-bit values present (value 0 implied: its bit is not stored) -> forward LUT = rank among the present values ->
+// forward wavelet per word plane -> the chunk's value sequence (channel after channel) -> tokens: a stretch of L equal values is the
+// value once and, if L - 1 >= 3, run codes of at most 255 each, else the value L times -> optimal code of the tokens' frequencies
+// (the run code iM = max value + 1 counts 1 + run tokens), two-queue method -> canonical codes -> packed table -> bit stream.
+constexpr int kMinRun = 3;                                       // repeats from which a stretch is written with run codes
+constexpr int kMaxRun = 255;                                     // repeats per run code
+constexpr int kTableZeros = 261;                                 // zero lengths per long table token (63, z - 6)
+constexpr int kBitmapWords = kBitmapBytes / 4;
+constexpr int64_t kEncodeFixed = 4 + kBitmapBytes + 4 + 20 + (6 * (int64_t)kSymbols + 7) / 8;   // everything but the code words
+
+SHDR_HD inline void enc14(uint16_t a, uint16_t b, uint16_t& l, uint16_t& h) {
+  const int as = (int16_t)a, bs = (int16_t)b;
+  const int16_t hs = (int16_t)(as - bs);
+  const int hi = hs;
+  l = (uint16_t)(int16_t)(as - (hi & 1) - (hi >> 1));
+  h = (uint16_t)hs;
+}
+SHDR_HD inline void enc16(uint16_t a, uint16_t b, uint16_t& l, uint16_t& h) {
+  const int hh = ((int)a - (int)b + 0x8000) & 0xFFFF;
+  l = (uint16_t)(((int)b + (hh >> 1)) & 0xFFFF);
+  h = (uint16_t)hh;
+}
+template <bool W14>
+SHDR_HD inline void enc(uint16_t a, uint16_t b, uint16_t& l, uint16_t& h) {
+  if (W14) enc14(a, b, l, h);
+  else enc16(a, b, l, h);
+}
+template <bool W14>
+SHDR_HD inline void enc_quad(uint16_t& A, uint16_t& B, uint16_t& C, uint16_t& D) {
+  uint16_t i00, i01, i10, i11;
+  enc<W14>(A, B, i00, i01);
+  enc<W14>(C, D, i10, i11);
+  enc<W14>(i00, i10, A, C);
+  enc<W14>(i01, i11, B, D);
+}
+
+// the whole plane in place: the decoder's level schedule walked from the finest level to the coarsest
+template <bool W14>
+inline void wav_encode(uint16_t* in, int nx, int64_t sx, int ny, int64_t sy) {
+  const int n = nx < ny ? nx : ny;
+  for (int p = 1, p2 = 2; p2 <= n; p = p2, p2 <<= 1) {
+    int y = 0, x = 0;
+    for (; y <= ny - p2; y += p2) {
+      for (x = 0; x <= nx - p2; x += p2) {
+        uint16_t* q = in + y * sy + x * sx;
+        enc_quad<W14>(q[0], q[p * sx], q[p * sy], q[p * sy + p * sx]);
+      }
+      if (nx & p) {
+        uint16_t* q = in + y * sy + x * sx;
+        enc<W14>(q[0], q[p * sy], q[0], q[p * sy]);
+      }
+    }
+    if (ny & p) {
+      for (x = 0; x <= nx - p2; x += p2) {
+        uint16_t* q = in + y * sy + x * sx;
+        enc<W14>(q[0], q[p * sx], q[0], q[p * sx]);
+      }
+    }
+  }
+}
+
+// the forward LUT: words[2048] is the bitmap with bit 0 set, before[i] the bits set in words[0 .. i)
+SHDR_HD inline uint32_t lut_rank(const uint32_t* words, const uint32_t* before, uint32_t v) {
+  return before[v >> 5] + (uint32_t)__builtin_popcount(words[v >> 5] & ((1u << (v & 31)) - 1u));
+}
+
+// a stretch of L >= 1 equal values: how often the value itself is written, and how many run codes follow
+SHDR_HD inline void stretch_tokens(uint32_t L, uint32_t& literals, uint32_t& runs) {
+  const uint32_t rep = L - 1;
+  if (rep >= (uint32_t)kMinRun) {
+    literals = 1;
+    runs = (rep + kMaxRun - 1) / kMaxRun;
+  } else {
+    literals = L;
+    runs = 0;
+  }
+}
+SHDR_HD inline uint64_t stretch_bits(uint32_t L, uint32_t len, uint32_t run_len) {
+  uint32_t lit, runs;
+  stretch_tokens(L, lit, runs);
+  return (uint64_t)lit * len + (uint64_t)runs * (run_len + 8);
+}
+// Sink: put(value < 2^bits, bits <= 58)
+template <class Sink>
+SHDR_HD inline void put_stretch(Sink& s, uint32_t L, uint64_t code, uint32_t len, uint64_t run_code, uint32_t run_len) {
+  uint32_t lit, runs;
+  stretch_tokens(L, lit, runs);
+  for (uint32_t i = 0; i < lit; ++i) s.put(code, (int)len);
+  for (uint32_t rep = L - 1; runs; --runs) {
+    const uint32_t k = rep < (uint32_t)kMaxRun ? rep : (uint32_t)kMaxRun;
+    s.put(run_code, (int)run_len);
+    s.put(k, 8);
+    rep -= k;
+  }
+}
+
+// the code-length table: a maximal stretch of Z zero lengths is cut greedily -- 261 at a time as (63, z - 6), a rest of 6 or more the
+// same way, a rest of 2 .. 5 as 59 + z - 2, a rest of 1 as a literal 0; a stretch of L equal non-zero lengths is L literals
+SHDR_HD inline uint32_t table_stretch_bits(uint32_t l, uint32_t L) {
+  if (l) return 6 * L;
+  const uint32_t r = L % (uint32_t)kTableZeros;
+  return 14 * (L / (uint32_t)kTableZeros) + (r >= 6 ? 14u : r >= 1 ? 6u : 0u);
+}
+template <class Sink>
+SHDR_HD inline void put_table_stretch(Sink& s, uint32_t l, uint32_t L) {
+  if (l) {
+    for (uint32_t i = 0; i < L; ++i) s.put(l, 6);
+    return;
+  }
+  while (L >= 6) {
+    const uint32_t z = L < (uint32_t)kTableZeros ? L : (uint32_t)kTableZeros;
+    s.put((63u << 8) | (z - 6), 14);
+    L -= z;
+  }
+  if (L >= 2) s.put(59 + L - 2, 6);
+  else if (L == 1) s.put(0, 6);
+}
+
+// An MSB-first bit stream gathered into 32-bit words; Out::word(i, w): OR the big-endian word w into bytes 4 i .. 4 i + 3 of a cleared
+// stream (the first and the last word of a writer are shared with its neighbours).  Starts at any bit.
+template <class Out>
+struct BitSink {
+  Out out;
+  uint64_t acc;
+  int64_t index;
+  int cnt;                                                       // bits of acc that are the word's so far: < 32 between calls
+  SHDR_HD BitSink(Out o, uint64_t bit) : out(o), acc(0), index((int64_t)(bit >> 5)), cnt((int)(bit & 31)) {}
+  SHDR_HD void put32(uint32_t v, int n) {
+    acc = (acc << n) | v;
+    cnt += n;
+    if (cnt >= 32) {
+      cnt -= 32;
+      out.word(index++, (uint32_t)(acc >> cnt));
+      acc &= ((uint64_t)1 << cnt) - 1;
+    }
+  }
+  SHDR_HD void put(uint64_t v, int n) {
+    if (n > 32) {
+      put32((uint32_t)(v >> 32), n - 32);
+      put32((uint32_t)v, 32);
+    } else if (n > 0) {
+      put32((uint32_t)v, n);
+    }
+  }
+  SHDR_HD void flush() {
+    if (cnt) out.word(index, (uint32_t)(acc << (32 - cnt)));
+    cnt = 0;
+  }
+};
+
+// The optimal code by the two-queue method.  weight[0 .. n): the leaves' counts in (count, symbol) order, n >= 2; internal nodes
+// queue up in creation order (their weights never decrease); on equal weight the leaf is taken first.  Node i < n is leaf i, node
+// n + k the k-th internal node, node 2 n - 2 the root.  made[n - 1] and parent[2 n - 1] are scratch / result.
+SHDR_HD inline void huff_merge(const uint32_t* weight, uint32_t n, uint32_t* made, uint32_t* parent) {
+  uint32_t leaf = 0, head = 0;
+  for (uint32_t k = 0; k + 1 < n; ++k) {
+    uint32_t sum = 0;
+    for (int pick = 0; pick < 2; ++pick) {
+      if (leaf < n && (head >= k || weight[leaf] <= made[head])) {
+        sum += weight[leaf];
+        parent[leaf++] = n + k;
+      } else {
+        sum += made[head];
+        parent[n + head++] = n + k;
+      }
+    }
+    made[k] = sum;
+  }
+}
+SHDR_HD inline uint32_t huff_depth(const uint32_t* parent, uint32_t n, uint32_t node) {
+  uint32_t d = 0;
+  for (; node != 2 * n - 2; node = parent[node]) ++d;
+  return d;
+}
+
+// bytes that hold any chunk of `values` values: the fixed parts at their largest, and at most 17 + 8 bits per value (an optimal code
+// of at most 65537 symbols spends no more than 17 bits per token on average, and a run code's count covers at least 3 values)
+SHDR_HD inline int64_t encode_bound(int64_t values) { return kEncodeFixed + 4 * values; }
+
+// ---- the host encoder: the twin that judges the kernels ---------------------------------------------------------------------------
+struct HostOut {
+  uint8_t* p;
+  void word(int64_t i, uint32_t w) {
+    for (int k = 0; k < 4; ++k)
+      if (const uint8_t b = (uint8_t)(w >> (24 - 8 * k))) p[4 * i + k] |= b;
+  }
+};
+
+struct EncWork {                              // the caller's scratch
+  uint32_t* words;                            // [kBitmapWords]
+  uint32_t* before;                           // [kBitmapWords]
+  uint16_t* values;                           // [the chunk's values]
+  uint32_t* freq;                             // [kSymbols]
+  uint64_t* keys;                             // [kSymbols]
+  uint32_t* weight;                           // [kSymbols]
+  uint32_t* made;                             // [kSymbols]
+  uint32_t* parent;                           // [2 * kSymbols]
+  uint8_t* lens;                              // [kSymbols]
+  uint64_t* code;                             // [kSymbols]
+};
+
+// raw[0 .. 2 * values): the planar scanlines of the chunk -> dst: the PIZ bytes, whatever their size.  Returns their number, or -2 when
+// capacity is less than that (nothing is written then).
+inline int64_t encode_host(const uint8_t* raw, int width, int rows, const int32_t* chan_words, int n_chan, uint8_t* dst, int64_t capacity,
+                           EncWork& w) {
+  const int64_t nv = chunk_values(width, rows, chan_words, n_chan);
+  // bitmap, LUT
+  for (int i = 0; i < kBitmapWords; ++i) w.words[i] = 0;
+  for (int64_t i = 0; i < nv; ++i) {
+    const uint32_t v = rd16(raw + 2 * i);
+    w.words[v >> 5] |= 1u << (v & 31);
+  }
+  w.words[0] &= ~1u;                                             // value 0 is implied
+  uint32_t lo = kBitmapBytes - 1, hi = 0;
+  for (int i = kBitmapBytes - 1; i >= 0; --i)
+    if ((w.words[i >> 2] >> (8 * (i & 3))) & 255u) lo = (uint32_t)i;
+  for (int i = 0; i < kBitmapBytes; ++i)
+    if ((w.words[i >> 2] >> (8 * (i & 3))) & 255u) hi = (uint32_t)i;
+  const int64_t bm = lo <= hi ? (int64_t)(hi - lo + 1) : 0;
+  const int64_t size = 4 + bm;
+  w.words[0] |= 1u;
+  uint32_t present = 0;
+  for (int i = 0; i < kBitmapWords; ++i) {
+    w.before[i] = present;
+    present += (uint32_t)__builtin_popcount(w.words[i]);
+  }
+  const uint32_t max_value = present - 1;
+  // values: LUT, then the wavelet per channel and word plane
+  int64_t row_words = 0;
+  for (int ch = 0; ch < n_chan; ++ch) row_words += (int64_t)width * chan_words[ch];
+  uint16_t* base = w.values;
+  int64_t chan_off = 0;
+  for (int ch = 0; ch < n_chan; ++ch) {
+    const int words = chan_words[ch];
+    for (int y = 0; y < rows; ++y)
+      for (int64_t i = 0; i < (int64_t)width * words; ++i)
+        base[(int64_t)y * width * words + i] = (uint16_t)lut_rank(w.words, w.before, rd16(raw + 2 * (y * row_words + chan_off + i)));
+    for (int j = 0; j < words; ++j) {
+      if (max_value < 16384u) wav_encode<true>(base + j, width, words, rows, (int64_t)width * words);
+      else wav_encode<false>(base + j, width, words, rows, (int64_t)width * words);
+    }
+    base += (int64_t)width * rows * words;
+    chan_off += (int64_t)width * words;
+  }
+  // frequencies of the tokens
+  for (int s = 0; s < kSymbols; ++s) w.freq[s] = 0;
+  uint32_t im = 65535, top = 0, run_tokens = 0;
+  for (int64_t i = 0; i < nv;) {
+    const uint16_t v = w.values[i];
+    int64_t j = i + 1;
+    while (j < nv && w.values[j] == v) ++j;
+    uint32_t lit, runs;
+    stretch_tokens((uint32_t)(j - i), lit, runs);
+    w.freq[v] += lit;
+    run_tokens += runs;
+    if (v < im) im = v;
+    if (v > top) top = v;
+    i = j;
+  }
+  const uint32_t iM = top + 1;
+  w.freq[iM] = 1 + run_tokens;
+  // code lengths
+  uint32_t n = 0;
+  for (uint32_t s = im; s <= iM; ++s)
+    if (w.freq[s]) w.keys[n++] = ((uint64_t)w.freq[s] << 17) | s;
+  std::sort(w.keys, w.keys + n);                                 // (count, symbol)
+  for (uint32_t i = 0; i < n; ++i) w.weight[i] = (uint32_t)(w.keys[i] >> 17);
+  huff_merge(w.weight, n, w.made, w.parent);
+  Canon c;
+  for (int l = 0; l <= kMaxLen; ++l) c.count[l] = 0;
+  for (int s = 0; s < kSymbols; ++s) w.lens[s] = 0;
+  uint64_t n_bits = 8 * (uint64_t)run_tokens;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t d = huff_depth(w.parent, n, i);
+    assert(d >= 1 && d <= (uint32_t)kMaxLen);                    // fewer than 2^27 values: a depth of 41 already needs more weight
+    w.lens[w.keys[i] & 0x1FFFFu] = (uint8_t)d;
+    ++c.count[d];
+    n_bits += (uint64_t)d * w.weight[i];
+  }
+  n_bits -= w.lens[iM];                                          // the run code counts one more than it is written
+  make_canon(c);
+  for (uint32_t s = im; s <= iM; ++s)
+    if (const int l = w.lens[s]) w.code[s] = c.first[l]++;
+  // the table's size, then everything is known
+  uint32_t table_bits = 0;
+  for (uint32_t s = im; s <= iM;) {
+    uint32_t e = s + 1;
+    while (e <= iM && w.lens[e] == w.lens[s]) ++e;
+    table_bits += table_stretch_bits(w.lens[s], e - s);
+    s = e;
+  }
+  const int64_t table_bytes = (table_bits + 7) >> 3, data_bytes = (int64_t)((n_bits + 7) >> 3);
+  const int64_t block = 20 + table_bytes + data_bytes;
+  if (size + 4 + block > capacity) return -2;
+  dst[0] = (uint8_t)lo; dst[1] = (uint8_t)(lo >> 8); dst[2] = (uint8_t)hi; dst[3] = (uint8_t)(hi >> 8);
+  for (int64_t i = 0; i < bm; ++i) {
+    const uint32_t k = lo + (uint32_t)i;
+    dst[4 + i] = (uint8_t)((w.words[k >> 2] >> (8 * (k & 3))) & (k ? 0xFFu : 0xFEu));
+  }
+  uint8_t* p = dst + size;
+  const uint32_t head[6] = {(uint32_t)block, im, iM, (uint32_t)table_bytes, (uint32_t)n_bits, 0u};
+  for (int k = 0; k < 6; ++k)
+    for (int b = 0; b < 4; ++b) *p++ = (uint8_t)(head[k] >> (8 * b));
+  for (int64_t i = 0; i < table_bytes + data_bytes; ++i) p[i] = 0;
+  BitSink<HostOut> table(HostOut{p}, 0);
+  for (uint32_t s = im; s <= iM;) {
+    uint32_t e = s + 1;
+    while (e <= iM && w.lens[e] == w.lens[s]) ++e;
+    put_table_stretch(table, w.lens[s], e - s);
+    s = e;
+  }
+  table.flush();
+  BitSink<HostOut> data(HostOut{p + table_bytes}, 0);
+  for (int64_t i = 0; i < nv;) {
+    const uint16_t v = w.values[i];
+    int64_t j = i + 1;
+    while (j < nv && w.values[j] == v) ++j;
+    put_stretch(data, (uint32_t)(j - i), w.code[v], w.lens[v], w.code[iM], w.lens[iM]);
+    i = j;
+  }
+  data.flush();
+  return size + 4 + block;
 }
 
 }  // namespace shdr_piz

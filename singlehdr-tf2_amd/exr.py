@@ -515,15 +515,23 @@ def file_header(height, width, pixel_type, compression):
             + _attr(b"screenWindowWidth", b"float", struct.pack("<f", 1.0)) + b"\0")
 
 
-def _write_options(what, pixel_type, compression, encoder):
+def _write_options(what, pixel_type, compression, encoder, piz="refuse"):
     if pixel_type not in PIXEL_TYPES:
         raise ValueError("%s: pixel type %r is not supported ('half' or 'float')" % (what, pixel_type))
-    if compression not in WRITE_COMPRESSIONS:
-        raise ValueError("%s: %s compression is not supported ('none', 'zips' and 'zip' are)" % (
-            what, compression.upper() if isinstance(compression, str) else repr(compression)))
+    check_piz_option(what, piz)
+    if compression == "piz" and piz != "refuse":                        # asked for by name: piz="host" or "device"
+        comp = PIZ_COMPRESSION
+    elif compression not in WRITE_COMPRESSIONS:
+        raise ValueError("%s: %s compression is not supported ('none', 'zips' and 'zip' are%s)" % (
+            what, compression.upper() if isinstance(compression, str) else repr(compression),
+            "; 'piz' with piz='host' or 'device'" if compression == "piz" else ""))
+    elif piz != "refuse":
+        raise ValueError("%s: piz=%r goes with compression='piz' only, got %r" % (what, piz, compression))
+    else:
+        comp = WRITE_COMPRESSIONS[compression]
     if encoder not in ("host", "device", "device_lz"):
         raise ValueError("%s: encoder must be 'host', 'device' or 'device_lz', got %r" % (what, encoder))
-    return PIXEL_TYPES[pixel_type], WRITE_COMPRESSIONS[compression]
+    return PIXEL_TYPES[pixel_type], comp
 
 
 def _on_device(images, what):
@@ -549,25 +557,49 @@ def _assemble(header, lines, stored):
     return header + struct.pack("<%dQ" % n, *table) + b"".join(parts)
 
 
-def encode_exr(images, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False):
+def _piz_geometry(packed, ptype):
+    """(geom int32 [n_chunks, 4], chan_words) of the packed batch's chunks for K.piz_encode: B, G, R of one pixel type"""
+    words = PIZ_WORDS[ptype]
+    first = packed.table[0]
+    geom = np.zeros((packed.chunk_off.size - 1, 4), dtype=np.int32)
+    for i, (h, w) in enumerate(packed.shapes):
+        a, b = int(first[i]), int(first[i + 1])
+        geom[a:b, 0] = w
+        geom[a:b, 1] = np.minimum(packed.lines, int(h) - np.arange(b - a) * packed.lines)
+    geom[:, 3] = 3
+    return geom, [words] * 3
+
+
+def encode_exr(images, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False, piz="refuse"):
     """float32 images -> a list of OpenEXR files as `bytes`, one per image.  images: one [H, W, 3], one [N, H, W, 3] or a list of
     [H, W, 3] of different sizes, device tensors (float32 host arrays are uploaded).  pixel_type "half" (numpy's astype(float16);
-    saturate: finite values beyond +-65504 become +-65504 instead of inf) or "float"; compression "none", "zips" or "zip";
-    reverse_channels: channel 0 is blue (HdrReconstructor.reconstruct_device's order).  encoder: who deflates ZIP / ZIPS chunks --
-    "host": zlib.compress per chunk in a thread pool; "device": the Huffman-only encoder of csrc/deflate.hip (larger files, no host
-    deflate, one copy of the finished bytes); "device_lz": the same route with the LZ77 encoder of csrc/deflate_lz.hip (matches
-    from a chainless hash table and runs: files between the two).  The whole batch is packed, predicted and (device) coded in one
-    call each."""
-    ptype, comp = _write_options("encode_exr", pixel_type, compression, encoder)
-    lines = LINES_PER_CHUNK[comp]
-    packed = K.exr_pack(_on_device(images, "encode_exr"), ptype, lines, reverse_channels, saturate, predict=comp != NO_COMPRESSION)
+    saturate: finite values beyond +-65504 become +-65504 instead of inf) or "float"; compression "none", "zips", "zip" or -- only
+    together with piz="host" / "device" -- "piz"; reverse_channels: channel 0 is blue (HdrReconstructor.reconstruct_device's order).
+    encoder: who deflates ZIP / ZIPS chunks -- "host": zlib.compress per chunk in a thread pool; "device": the Huffman-only encoder
+    of csrc/deflate.hip (larger files, no host deflate, one copy of the finished bytes); "device_lz": the same route with the LZ77
+    encoder of csrc/deflate_lz.hip (matches from a chainless hash table and runs: files between the two).  piz: who codes PIZ chunks
+    (32 scanlines each) -- "refuse" (the default: compression="piz" is a ValueError, as it always was), "host": libshdr's host
+    encoder per chunk in the thread pool, "device": K.piz_encode (csrc/piz_enc.hip) and one copy of the finished bytes; both write the
+    same files, and `encoder` plays no part in them.  THE PIZ WRITER IS UNPINNED AGAINST THE OPENEXR LIBRARY, like the PIZ reader: no
+    OpenEXR-built reader has opened these files (tests/piz_ref.py writes the same bytes, and this package's readers read them back).
+    The whole batch is packed, predicted and (device) coded in one call each."""
+    ptype, comp = _write_options("encode_exr", pixel_type, compression, encoder, piz)
+    lines = LINES_PER_CHUNK_PIZ[comp]
+    packed = K.exr_pack(_on_device(images, "encode_exr"), ptype, lines, reverse_channels, saturate,
+                        predict=comp not in (NO_COMPRESSION, PIZ_COMPRESSION))
     headers = [file_header(int(h), int(w), ptype, comp) for h, w in packed.shapes]
     first, chunk_off = packed.table[0], packed.chunk_off
     n_chunks = chunk_off.size - 1
-    if comp != NO_COMPRESSION and encoder != "host":
-        deflate = K.deflate_lz if encoder == "device_lz" else K.deflate_huffman
-        out, out_offsets, _ = deflate(packed.predicted, chunk_off, raw=packed.planar, pad=8, front=8 * n_chunks,
-                                      offsets_dev=packed.chunk_off_dev)
+    on_device = piz == "device" if comp == PIZ_COMPRESSION else comp != NO_COMPRESSION and encoder != "host"
+    if on_device:
+        if comp == PIZ_COMPRESSION:
+            geom, words = _piz_geometry(packed, ptype)
+            out, out_offsets, _ = K.piz_encode(packed.planar, chunk_off, geom, words, pad=8, front=8 * n_chunks,
+                                               chunk_off_dev=packed.chunk_off_dev)
+        else:
+            deflate = K.deflate_lz if encoder == "device_lz" else K.deflate_huffman
+            out, out_offsets, _ = deflate(packed.predicted, chunk_off, raw=packed.planar, pad=8, front=8 * n_chunks,
+                                          offsets_dev=packed.chunk_off_dev)
         K.exr_finish_chunks(out, out_offsets, packed, [len(h) for h in headers])
         off = out_offsets.cpu().numpy()
         blob = memoryview(out[:8 * n_chunks + int(off[-1])].cpu().numpy())          # sliced without copies, joined once per file
@@ -578,10 +610,17 @@ def encode_exr(images, pixel_type="half", compression="zip", encoder="host", sat
         planar = packed.planar.cpu().numpy()
         stored = [planar[a:b] for a, b in bounds]
     else:
-        predicted = packed.predicted.cpu().numpy()
-        with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_DEFLATE_THREADS, n_chunks)) as pool:
-            stored = list(pool.map(zlib.compress, [predicted[a:b] for a, b in bounds]))
         planar = None
+        if comp == PIZ_COMPRESSION:
+            planar = packed.planar.cpu().numpy()
+            geom, words = _piz_geometry(packed, ptype)
+            jobs = [(planar[a:b], int(g[0]), int(g[1])) for (a, b), g in zip(bounds, geom)]
+            with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_DEFLATE_THREADS, n_chunks)) as pool:
+                stored = list(pool.map(lambda j: K.piz_encode_host(j[0], j[1], j[2], words), jobs))
+        else:
+            predicted = packed.predicted.cpu().numpy()
+            with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_DEFLATE_THREADS, n_chunks)) as pool:
+                stored = list(pool.map(zlib.compress, [predicted[a:b] for a, b in bounds]))
         for c, (a, b) in enumerate(bounds):
             if len(stored[c]) >= b - a:                                   # does not shrink: the scanline bytes as they are
                 if planar is None:
@@ -590,10 +629,10 @@ def encode_exr(images, pixel_type="half", compression="zip", encoder="host", sat
     return [_assemble(headers[i], lines, stored[int(first[i]):int(first[i + 1])]) for i in range(len(headers))]
 
 
-def write_exr(path, image, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False):
+def write_exr(path, image, pixel_type="half", compression="zip", encoder="host", saturate=True, reverse_channels=False, piz="refuse"):
     """one float32 image [H, W, 3] -> an OpenEXR file (encode_exr)"""
     if getattr(image, "ndim", 0) != 3:
         raise ValueError("write_exr: expected one image [H, W, 3], got shape %s" % (tuple(getattr(image, "shape", ())),))
-    data = encode_exr([image], pixel_type, compression, encoder, saturate, reverse_channels)[0]
+    data = encode_exr([image], pixel_type, compression, encoder, saturate, reverse_channels, piz)[0]
     with open(path, "wb") as f:
         f.write(data)

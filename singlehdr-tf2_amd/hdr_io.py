@@ -81,7 +81,8 @@ def _check_format(output_format, what):
 
 
 def _exr_options(encoder, exr_options):
-    """encode_exr's keyword arguments for the file loop: the estimate is in the networks' channel order"""
+    """encode_exr's keyword arguments for the file loop: the estimate is in the networks' channel order.  exr_options passes through
+    as it is, compression="piz" with piz="host" / "device" included"""
     opts = dict(encoder=encoder)
     opts.update(exr_options or {})
     opts["reverse_channels"] = True
@@ -334,7 +335,9 @@ class HdrReconstructor:
         the coded bytes (write_hdr: the same file).
         output_format: "hdr" writes a Radiance file; "exr" writes the float estimate as OpenEXR without the RGBE conversion
         (exr.encode_exr with `exr_options`, a dict of its keyword arguments such as pixel_type or compression; `encoder` then says
-        who deflates, and "device_lz", the device encoder with LZ77 matches, is a third choice that only this format has)"""
+        who deflates, and "device_lz", the device encoder with LZ77 matches, is a third choice that only this format has.
+        exr_options=dict(compression="piz", piz="device") -- or piz="host" -- writes PIZ-compressed files, for which `encoder` plays
+        no part; the PIZ writer is unpinned against the OpenEXR library, see exr.encode_exr)"""
         _check_encoder(encoder, "reconstruct_file", output_format)
         _check_format(output_format, "reconstruct_file")
         if preview_path is not None:
@@ -353,7 +356,8 @@ class HdrReconstructor:
         batched scanline-RLE launch sequence and brought back in one copy (encoder="device"), then the files are written.
         encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
         4 B per pixel.  output_format="exr": the float estimates of the whole list go through ONE exr.encode_exr call, whatever the
-        encoder"""
+        encoder (and whatever the compression: exr_options=dict(compression="piz", piz="device") codes every chunk of every file in
+        one K.piz_encode call)"""
         _check_encoder(encoder, "reconstruct_files", output_format)
         _check_format(output_format, "reconstruct_files")
         ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
