@@ -1849,12 +1849,11 @@ def rgbe_rle_encode(rgbe, capacity=None, stage_ms=None):
     ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
     shapes_dev = torch.from_numpy(shapes).to(dev)
     args = (_ptr(flat), _hptr(shapes), _ptr(shapes_dev), n, _ptr(out), cap, _ptr(offsets), _ptr(ws), _stream())
-    if stage_ms is None:
-        _lib.check(lib.shdr_rgbe_rle_encode_batch(*args), "shdr_rgbe_rle_encode_batch")
-    else:
-        ms = (ctypes.c_float * 4)()
-        _lib.check(lib.shdr_rgbe_rle_encode_batch_timed(*args, ms), "shdr_rgbe_rle_encode_batch_timed")
-        stage_ms[:] = list(ms)
+    with _stage_times(stage_ms, 4) as ms:
+        if ms is None:
+            _lib.check(lib.shdr_rgbe_rle_encode_batch(*args), "shdr_rgbe_rle_encode_batch")
+        else:
+            _lib.check(lib.shdr_rgbe_rle_encode_batch_timed(*args, ms), "shdr_rgbe_rle_encode_batch_timed")
     return out, offsets
 
 
@@ -1925,12 +1924,10 @@ def rgbe_rle_decode(src, src_off, shapes, stage_ms=None):
     consumed = torch.empty(n, device=dev, dtype=torch.int64)
     s_dev = torch.from_numpy(s_host).to(dev)
     shapes_dev = torch.from_numpy(shapes).to(dev)
-    ms = (ctypes.c_float * 4)() if stage_ms is not None else None
-    _lib.check(lib.shdr_rgbe_rle_decode_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev), _hptr(shapes),
-                                              _ptr(shapes_dev), n, _ptr(out), out_b.value, _ptr(out_off), _ptr(ws), ws_b.value,
-                                              _ptr(status), _ptr(line), _ptr(consumed), _stream(), ms), "shdr_rgbe_rle_decode_batch")
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
+    with _stage_times(stage_ms, 4) as ms:
+        _lib.check(lib.shdr_rgbe_rle_decode_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev), _hptr(shapes),
+                                                  _ptr(shapes_dev), n, _ptr(out), out_b.value, _ptr(out_off), _ptr(ws), ws_b.value,
+                                                  _ptr(status), _ptr(line), _ptr(consumed), _stream(), ms), "shdr_rgbe_rle_decode_batch")
     return out, out_off, status, line, consumed
 
 
@@ -2105,6 +2102,62 @@ class _stage_times:
         return False
 
 
+def _slot_batch(what, src, src_offsets, dst_offsets, src_offsets_dev, dst_offsets_dev, dst, mode, sizes):
+    """inflate and piz_decode: chunk c of src fills slot c of dst.  The checks and buffers of both: src, the two offset tables with
+    their device copies, dst (made if None), mode, and the per-chunk status and written.  sizes(src, s_host, d_host, n) refuses tables
+    whose shapes do not fit and returns the library's (src bytes, dst bytes).  Returns (src, (s_host, s_dev), (d_host, d_dev), dst, mode,
+    status, written)."""
+    src = _chk(src, "src", torch.uint8)
+    s_host, s_dev = _offsets_pair(what, "src_offsets", src_offsets, src_offsets_dev)
+    d_host, d_dev = _offsets_pair(what, "dst_offsets", dst_offsets, dst_offsets_dev)
+    n = s_host.size - 1
+    src_b, dst_b = sizes(src, s_host, d_host, n)
+    if src_b > src.numel():
+        raise ValueError("%s: src_offsets end at %d, src holds %d bytes" % (what, src_b, src.numel()))
+    dev = src.device
+    if dst is None:
+        dst = torch.empty(dst_b, device=dev, dtype=torch.uint8)
+    else:
+        dst = _chk(dst, "dst", torch.uint8)
+        if dst.dim() != 1 or dst.numel() < dst_b:
+            raise ValueError("%s: dst_offsets end at %d, dst holds %d bytes" % (what, dst_b, dst.numel()))
+    if mode is not None:
+        mode = _chk(mode, "mode", torch.uint8)
+        if mode.numel() != n:
+            raise ValueError("%s: mode must be uint8 [n_chunks]" % what)
+    if s_dev is None:
+        s_dev = torch.from_numpy(s_host).to(dev)
+    if d_dev is None:
+        d_dev = torch.from_numpy(d_host).to(dev)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    written = torch.empty(n, device=dev, dtype=torch.int64)
+    return src, (s_host, s_dev), (d_host, d_dev), dst, mode, status, written
+
+
+def _shape_tables(what, geom, chan_words, shape_dev, n, dev):
+    """piz_decode and piz_encode: (geom, chan_words) on the device -- the caller's copies shape_dev, checked, or one upload of both"""
+    if shape_dev is None:
+        both = torch.from_numpy(np.concatenate([geom.reshape(-1), chan_words])).to(dev)
+        return both[:4 * n], both[4 * n:]
+    geom_dev, words_dev = _chk(shape_dev[0], "geom_dev", torch.int32), _chk(shape_dev[1], "chan_words_dev", torch.int32)
+    if geom_dev.numel() != 4 * n or words_dev.numel() != chan_words.size:
+        raise ValueError("%s: shape_dev is not a copy of geom and chan_words" % what)
+    return geom_dev, words_dev
+
+
+def _store_buffers(what, out, front, out_bytes, ws_bytes, n, dev):
+    """the deflate encoders and piz_encode: (out, out_offsets, coded, workspace) of a call that stores n chunks of at most out_bytes
+    behind `front` free bytes; out: the caller's buffer, checked, or None for a new one (not cleared)"""
+    if out is None:
+        out = torch.empty(front + out_bytes, device=dev, dtype=torch.uint8)
+    else:
+        out = _chk(out, "out", torch.uint8)
+        if out.dim() != 1 or out.numel() < front + out_bytes:
+            raise ValueError("%s: out holds %d bytes, %d are needed" % (what, out.numel(), front + out_bytes))
+    return (out, torch.empty(n + 1, device=dev, dtype=torch.int64), torch.empty(n, device=dev, dtype=torch.uint8),
+            torch.empty(ws_bytes, device=dev, dtype=torch.uint8))
+
+
 # ---------------------------------------------------------------------------
 # OpenEXR output (exr.py encode_exr), see csrc/exr_write.hip and csrc/deflate.hip
 # ---------------------------------------------------------------------------
@@ -2157,10 +2210,7 @@ def _deflate_batch(what, sizes_fn_name, batch_fn_name, data, offsets, raw, pad, 
     if off_dev is None:
         off_dev = torch.from_numpy(off_host).to(dev)
     front = int(front)
-    out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
-    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
-    coded = torch.empty(n, device=dev, dtype=torch.uint8)
-    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    out, out_offsets, coded, ws = _store_buffers(what, None, front, out_b.value, ws_b.value, n, dev)
     with _stage_times(stage_ms, 3) as ms:
         _lib.check(getattr(lib, batch_fn_name)(_ptr(data), _ptr(raw) if raw is not None else None, _hptr(off_host), _ptr(off_dev), n, int(pad),
                                                out.data_ptr() + front, out_b.value, _ptr(out_offsets), _ptr(coded), _ptr(ws), _stream(), ms),
@@ -2257,34 +2307,18 @@ def inflate(src, src_offsets, dst_offsets, mode=None, stage_ms=None, src_offsets
     `written` are left as they were.  Stream-ordered, no host wait.  stage_ms: a list that receives the launch's device time
     (measurement: the call then waits)."""
     lib = _lib.load()
-    src = _chk(src, "src", torch.uint8)
-    s_host, s_dev = _offsets_pair("inflate", "src_offsets", src_offsets, src_offsets_dev)
-    d_host, d_dev = _offsets_pair("inflate", "dst_offsets", dst_offsets, dst_offsets_dev)
+
+    def sizes(src, s_host, d_host, n):
+        if src.dim() != 1 or d_host.size != n + 1:
+            raise ValueError("inflate: expected src [size] and two offset tables [n_chunks + 1]")
+        src_b, dst_b = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(lib.shdr_inflate_batch_sizes(_hptr(s_host), _hptr(d_host), n, ctypes.byref(src_b), ctypes.byref(dst_b)),
+                   "shdr_inflate_batch_sizes")
+        return src_b.value, dst_b.value
+
+    src, (s_host, s_dev), (d_host, d_dev), dst, mode, status, written = _slot_batch(
+        "inflate", src, src_offsets, dst_offsets, src_offsets_dev, dst_offsets_dev, dst, mode, sizes)
     n = s_host.size - 1
-    if src.dim() != 1 or d_host.size != n + 1:
-        raise ValueError("inflate: expected src [size] and two offset tables [n_chunks + 1]")
-    src_b, dst_b = ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(lib.shdr_inflate_batch_sizes(_hptr(s_host), _hptr(d_host), n, ctypes.byref(src_b), ctypes.byref(dst_b)),
-               "shdr_inflate_batch_sizes")
-    if src_b.value > src.numel():
-        raise ValueError("inflate: src_offsets end at %d, src holds %d bytes" % (src_b.value, src.numel()))
-    dev = src.device
-    if dst is None:
-        dst = torch.empty(dst_b.value, device=dev, dtype=torch.uint8)
-    else:
-        dst = _chk(dst, "dst", torch.uint8)
-        if dst.dim() != 1 or dst.numel() < dst_b.value:
-            raise ValueError("inflate: dst_offsets end at %d, dst holds %d bytes" % (dst_b.value, dst.numel()))
-    if mode is not None:
-        mode = _chk(mode, "mode", torch.uint8)
-        if mode.numel() != n:
-            raise ValueError("inflate: mode must be uint8 [n_chunks]")
-    if s_dev is None:
-        s_dev = torch.from_numpy(s_host).to(dev)
-    if d_dev is None:
-        d_dev = torch.from_numpy(d_host).to(dev)
-    status = torch.empty(n, device=dev, dtype=torch.int32)
-    written = torch.empty(n, device=dev, dtype=torch.int64)
     with _stage_times(stage_ms, 1) as ms:
         _lib.check(lib.shdr_inflate_batch(_ptr(src) if src.numel() else None, src.numel(), _hptr(s_host), _ptr(s_dev),
                                           _ptr(dst) if dst.numel() else None, dst.numel(), _hptr(d_host), _ptr(d_dev),
@@ -2341,44 +2375,23 @@ def piz_decode(src, src_offsets, dst_offsets, geom, chan_words, mode=None, sub_b
     subsequences that round 0, 1, ... decoded (round 0: all of them).  Stream-ordered, no host wait.
     stage_ms: a list that receives the two launches' device times (measurement: the call then waits)."""
     lib = _lib.load()
-    src = _chk(src, "src", torch.uint8)
-    s_host, s_dev = _offsets_pair("piz_decode", "src_offsets", src_offsets, src_offsets_dev)
-    d_host, d_dev = _offsets_pair("piz_decode", "dst_offsets", dst_offsets, dst_offsets_dev)
-    n = s_host.size - 1
     geom = np.ascontiguousarray(geom, dtype=np.int32)
     words = np.ascontiguousarray(chan_words, dtype=np.int32)
-    if src.dim() != 1 or d_host.size != n + 1 or geom.shape != (n, 4) or words.ndim != 1:
-        raise ValueError("piz_decode: expected src [size], two offset tables [n_chunks + 1], geom [n_chunks, 4] and chan_words [n]")
     sub = 0 if sub_bits is None else int(sub_bits)
-    src_b, dst_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(lib.shdr_piz_batch_sizes(_hptr(s_host), _hptr(d_host), _hptr(geom), _hptr(words), words.size, n, sub, ctypes.byref(src_b),
-                                        ctypes.byref(dst_b), ctypes.byref(ws_b)), "shdr_piz_batch_sizes")
-    if src_b.value > src.numel():
-        raise ValueError("piz_decode: src_offsets end at %d, src holds %d bytes" % (src_b.value, src.numel()))
-    dev = src.device
-    if dst is None:
-        dst = torch.empty(dst_b.value, device=dev, dtype=torch.uint8)
-    else:
-        dst = _chk(dst, "dst", torch.uint8)
-        if dst.dim() != 1 or dst.numel() < dst_b.value:
-            raise ValueError("piz_decode: dst_offsets end at %d, dst holds %d bytes" % (dst_b.value, dst.numel()))
-    if mode is not None:
-        mode = _chk(mode, "mode", torch.uint8)
-        if mode.numel() != n:
-            raise ValueError("piz_decode: mode must be uint8 [n_chunks]")
-    if s_dev is None:
-        s_dev = torch.from_numpy(s_host).to(dev)
-    if d_dev is None:
-        d_dev = torch.from_numpy(d_host).to(dev)
-    if shape_dev is None:
-        both = torch.from_numpy(np.concatenate([geom.reshape(-1), words])).to(dev)
-        geom_dev, words_dev = both[:4 * n], both[4 * n:]
-    else:
-        geom_dev, words_dev = _chk(shape_dev[0], "geom_dev", torch.int32), _chk(shape_dev[1], "chan_words_dev", torch.int32)
-        if geom_dev.numel() != 4 * n or words_dev.numel() != words.size:
-            raise ValueError("piz_decode: shape_dev is not a copy of geom and chan_words")
-    status = torch.empty(n, device=dev, dtype=torch.int32)
-    written = torch.empty(n, device=dev, dtype=torch.int64)
+    ws_b = ctypes.c_int64(0)
+
+    def sizes(src, s_host, d_host, n):
+        if src.dim() != 1 or d_host.size != n + 1 or geom.shape != (n, 4) or words.ndim != 1:
+            raise ValueError("piz_decode: expected src [size], two offset tables [n_chunks + 1], geom [n_chunks, 4] and chan_words [n]")
+        src_b, dst_b = ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(lib.shdr_piz_batch_sizes(_hptr(s_host), _hptr(d_host), _hptr(geom), _hptr(words), words.size, n, sub, ctypes.byref(src_b),
+                                            ctypes.byref(dst_b), ctypes.byref(ws_b)), "shdr_piz_batch_sizes")
+        return src_b.value, dst_b.value
+
+    src, (s_host, s_dev), (d_host, d_dev), dst, mode, status, written = _slot_batch(
+        "piz_decode", src, src_offsets, dst_offsets, src_offsets_dev, dst_offsets_dev, dst, mode, sizes)
+    n, dev = s_host.size - 1, src.device
+    geom_dev, words_dev = _shape_tables("piz_decode", geom, words, shape_dev, n, dev)
     rounds_dev = torch.empty((n, PIZ_ROUND_STATS), device=dev, dtype=torch.int32) if rounds else None
     ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
     with _stage_times(stage_ms, 2) as ms:
@@ -2445,23 +2458,9 @@ def piz_encode(planar, chunk_off, geom, chan_words, pad=0, front=0, stage_ms=Non
     dev = planar.device
     if off_dev is None:
         off_dev = torch.from_numpy(off_host).to(dev)
-    if shape_dev is None:
-        both = torch.from_numpy(np.concatenate([geom.reshape(-1), words])).to(dev)
-        geom_dev, words_dev = both[:4 * n], both[4 * n:]
-    else:
-        geom_dev, words_dev = _chk(shape_dev[0], "geom_dev", torch.int32), _chk(shape_dev[1], "chan_words_dev", torch.int32)
-        if geom_dev.numel() != 4 * n or words_dev.numel() != words.size:
-            raise ValueError("piz_encode: shape_dev is not a copy of geom and chan_words")
+    geom_dev, words_dev = _shape_tables("piz_encode", geom, words, shape_dev, n, dev)
     front = int(front)
-    if out is None:
-        out = torch.empty(front + out_b.value, device=dev, dtype=torch.uint8)
-    else:
-        out = _chk(out, "out", torch.uint8)
-        if out.dim() != 1 or out.numel() < front + out_b.value:
-            raise ValueError("piz_encode: out holds %d bytes, %d are needed" % (out.numel(), front + out_b.value))
-    out_offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
-    coded = torch.empty(n, device=dev, dtype=torch.uint8)
-    ws = torch.empty(ws_b.value, device=dev, dtype=torch.uint8)
+    out, out_offsets, coded, ws = _store_buffers("piz_encode", out, front, out_b.value, ws_b.value, n, dev)
     stats_dev = torch.empty((n, PIZ_ENC_STATS), device=dev, dtype=torch.int32) if stats else None
     with _stage_times(stage_ms, PIZ_ENC_STAGES) as ms:
         _lib.check(lib.shdr_piz_encode_batch(_ptr(planar), _hptr(off_host), _ptr(off_dev), _hptr(geom), _ptr(geom_dev), _hptr(words),

@@ -5,6 +5,7 @@
 hipcc cross-compiles for gfx950 without a GPU.  The shared object lands next
 to this file (git-ignored, but it travels to the GPU box with the snapshot).
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -81,10 +82,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     hipcc = _hipcc()
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(CSRC, "shdr_internal.h"), os.path.join(CSRC, "linear_resize.h"), os.path.join(CSRC, "jpeg_int.h"), os.path.join(CSRC, "deflate_huffman.h"),
-               os.path.join(CSRC, "deflate_lz.h"), os.path.join(CSRC, "deflate_batch.h"),
-               os.path.join(CSRC, "inflate.h"), os.path.join(CSRC, "piz.h"), os.path.join(CSRC, "jpeg_scan.h"), os.path.join(CSRC, "jpeg_enc.h"),
-               os.path.join(CSRC, "exr_half.h"), os.path.join(CSRC, "hdr_rle_dec.h"), os.path.join(INCLUDE, "shdr.h"), __file__]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "shdr.h"), __file__]    # every header: none is forgotten
     objs = []
     procs = []
     for src, extra in SOURCES.items():

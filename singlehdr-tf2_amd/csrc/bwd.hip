@@ -812,7 +812,6 @@ int nhwc4(const char* op, const void* a, const void* b, int N, int H, int W, int
   SHDR_REQUIRE(shdr::aligned16(a) && shdr::aligned16(b), SHDR_E_ALIGN, "%s: tensors must be 16-byte aligned", op);
   return SHDR_OK;
 }
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int reduce_grid(long npix, int C) {
   int CL = 1;
   while (CL < C && CL < 256) CL <<= 1;
@@ -847,7 +846,7 @@ inline void launch_bn_reduce(hipStream_t st, const float* a, const float* x, con
 extern "C" int shdr_act_bwd_f32(const float* dy, const float* y, float* dx, int64_t n, int act, void* stream) {
   SHDR_REQUIRE(dy && y && dx, SHDR_E_NULL, "act_bwd: null pointer");
   SHDR_REQUIRE(n > 0 && act >= 0 && act <= 3, SHDR_E_SHAPE, "act_bwd: bad arguments");
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), dy, y, dx, (long)n, act);
+  hipLaunchKernelGGL(act_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), dy, y, dx, (long)n, act);
   return shdr::check_launch("act_bwd");
 }
 extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act,
@@ -872,24 +871,24 @@ extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz,
     SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "act_bwd_bias: ws must be 16-byte aligned");
     const int rows = nquads >= (1L << 22) ? shdr::kBiasMaxBlocks : cap;        // <= kBiasMaxBlocks rows of C floats: the workspace
     if (grid > rows) grid = rows;
-    hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, S(stream), dy, y, dz, db, ws, nquads, Q, act);
-    shdr::launch_col_fold(ws, db, grid, C, S(stream));
+    hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, shdr::stream_of(stream), dy, y, dz, db, ws, nquads, Q, act);
+    shdr::launch_col_fold(ws, db, grid, C, shdr::stream_of(stream));
     return shdr::check_launch("act_bwd_bias");
   }
   if (grid > cap) grid = cap;
-  hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, S(stream), dy, y, dz, db, (float*)nullptr, nquads, Q, act);
+  hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, shdr::stream_of(stream), dy, y, dz, db, (float*)nullptr, nquads, Q, act);
   return shdr::check_launch("act_bwd_bias");
 }
 extern "C" int shdr_clip_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, float lo, float hi, void* stream) {
   SHDR_REQUIRE(dy && x && dx, SHDR_E_NULL, "clip_bwd: null pointer");
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "clip_bwd: n must be positive");
-  hipLaunchKernelGGL(clip_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), dy, x, dx, (long)n, lo, hi);
+  hipLaunchKernelGGL(clip_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), dy, x, dx, (long)n, lo, hi);
   return shdr::check_launch("clip_bwd");
 }
 extern "C" int shdr_add_ranged_f32(const float* a, const float* b, float* y, int64_t n, float* y_range, void* stream) {
   SHDR_REQUIRE(a && b && y, SHDR_E_NULL, "add: null pointer");
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "add: n must be positive");
-  hipLaunchKernelGGL(add_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), a, b, y, (long)n, reinterpret_cast<unsigned*>(y_range));
+  hipLaunchKernelGGL(add_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), a, b, y, (long)n, reinterpret_cast<unsigned*>(y_range));
   return shdr::check_launch("add");
 }
 extern "C" int shdr_add_f32(const float* a, const float* b, float* y, int64_t n, void* stream) {
@@ -897,7 +896,7 @@ extern "C" int shdr_add_f32(const float* a, const float* b, float* y, int64_t n,
 }
 extern "C" int shdr_avgpool2_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = nhwc4("avgpool2_bwd", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
                      dy, dx, N, H, W, C);
   return shdr::check_launch("avgpool2_bwd");
 }
@@ -907,7 +906,7 @@ extern "C" int shdr_maxpool2_bwd_f32(const float* x, const float* dy, float* dx,
   SHDR_REQUIRE(shdr::aligned16(dy), SHDR_E_ALIGN, "maxpool2_bwd: dy must be 16-byte aligned");
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_bwd: H, W must be even");
   hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
-                     S(stream), x, dy, dx, N, H, W, C);
+                     shdr::stream_of(stream), x, dy, dx, N, H, W, C);
   return shdr::check_launch("maxpool2_bwd");
 }
 extern "C" int shdr_maxpool3s2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int H, int W, int C,
@@ -918,13 +917,13 @@ extern "C" int shdr_maxpool3s2_bwd_f32(const float* x, const float* y, const flo
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
                      x, y, dy, dx, N, H, W, C, Ho, Wo, pt, pl);
   return shdr::check_launch("maxpool3s2_bwd");
 }
 extern "C" int shdr_resize2x_bwd_ranged_f32(const float* dy, float* dx, int N, int H, int W, int C, float* dx_range, void* stream) {
   if (int rc = nhwc4("resize2x_bwd", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(resize2x_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
                      dy, dx, N, H, W, C, reinterpret_cast<unsigned*>(dx_range));
   return shdr::check_launch("resize2x_bwd");
 }
@@ -934,12 +933,12 @@ extern "C" int shdr_resize2x_bwd_f32(const float* dy, float* dx, int N, int H, i
 extern "C" int shdr_gap_bwd_f32(const float* dy, float* dx, int N, int HW, int C, void* stream) {
   if (int rc = nhwc4("gap_bwd", dy, dx, N, HW, 1, C)) return rc;
   const long tq = (long)N * HW * (C / 4);
-  hipLaunchKernelGGL(gap_bwd_kernel, dim3(shdr::stream_grid(tq)), dim3(256), 0, S(stream), dy, dx, tq, HW, C);
+  hipLaunchKernelGGL(gap_bwd_kernel, dim3(shdr::stream_grid(tq)), dim3(256), 0, shdr::stream_of(stream), dy, dx, tq, HW, C);
   return shdr::check_launch("gap_bwd");
 }
 extern "C" int shdr_upsample_zero2_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = nhwc4("upsample_zero2", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(upsample_zero2_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(upsample_zero2_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
                      dy, dx, N, H, W, C);
   return shdr::check_launch("upsample_zero2");
 }
@@ -949,7 +948,7 @@ extern "C" int shdr_bn_stats_f32(const float* x, double* ws, float* mean, float*
   SHDR_REQUIRE(x && ws && mean && var, SHDR_E_NULL, "bn_stats: null pointer");
   SHDR_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), SHDR_E_NULL, "bn_stats: moving stats come in pairs");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bn_stats: bad shape");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce(st, x, nullptr, nullptr, nullptr, ws, (long)npix, C, 0);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var,
                      (long)npix, C, momentum);
@@ -959,7 +958,7 @@ extern "C" int shdr_bn_train_apply_ranged_f32(const float* x, const float* mean,
                                               float* y, int64_t npix, int C, float eps, int relu, float* y_range, void* stream) {
   SHDR_REQUIRE(x && mean && var && gamma && beta && y, SHDR_E_NULL, "bn_train_apply: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bn_train_apply: bad shape");
-  hipLaunchKernelGGL(bn_train_apply_kernel, dim3(shdr::stream_grid(npix * C)), dim3(256), 0, S(stream), x, mean, var,
+  hipLaunchKernelGGL(bn_train_apply_kernel, dim3(shdr::stream_grid(npix * C)), dim3(256), 0, shdr::stream_of(stream), x, mean, var,
                      gamma, beta, y, (long)npix * C, C, eps, relu, reinterpret_cast<unsigned*>(y_range));
   return shdr::check_launch("bn_train_apply");
 }
@@ -972,7 +971,7 @@ extern "C" int shdr_bn_bwd_ranged_f32(const float* dy, const float* x, const flo
                                       int C, float eps, float* dx_range, void* stream) {
   SHDR_REQUIRE(dy && x && mean && var && gamma && ws && dgamma && dbeta && dx, SHDR_E_NULL, "bn_bwd: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bn_bwd: bad shape");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce(st, dy, x, y_relu, mean, ws, (long)npix, C, 1);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
   const int Q = C / 4;
@@ -999,14 +998,14 @@ extern "C" int shdr_invcrf_decode_bwd_f32(const float* dinv, const float* feat, 
                                           float* dfeat, float* dwfc, float* dbfc, int B, int F, int K, void* stream) {
   SHDR_REQUIRE(dinv && feat && wfc && table && dfeat && dwfc && dbfc, SHDR_E_NULL, "invcrf_decode_bwd: null pointer");
   SHDR_REQUIRE(B > 0 && F > 0 && K > 0, SHDR_E_SHAPE, "invcrf_decode_bwd: bad shape");
-  hipLaunchKernelGGL(invcrf_decode_bwd_kernel, dim3(B), dim3(256), 0, S(stream), dinv, feat, wfc, table, dfeat, dwfc,
+  hipLaunchKernelGGL(invcrf_decode_bwd_kernel, dim3(B), dim3(256), 0, shdr::stream_of(stream), dinv, feat, wfc, table, dfeat, dwfc,
                      dbfc, F, K);
   return shdr::check_launch("invcrf_decode_bwd");
 }
 extern "C" int shdr_increase_bwd_f32(const float* rf, const float* dout, float* drf, int B, int K, void* stream) {
   SHDR_REQUIRE(rf && dout && drf, SHDR_E_NULL, "increase_bwd: null pointer");
   SHDR_REQUIRE(B > 0 && K >= 2 && K <= 4096, SHDR_E_SHAPE, "increase_bwd: need 2 <= K <= 4096");
-  hipLaunchKernelGGL(increase_bwd_kernel, dim3(B), dim3(256), (size_t)2 * (K - 1) * sizeof(float), S(stream), rf, dout,
+  hipLaunchKernelGGL(increase_bwd_kernel, dim3(B), dim3(256), (size_t)2 * (K - 1) * sizeof(float), shdr::stream_of(stream), rf, dout,
                      drf, K);
   return shdr::check_launch("increase_bwd");
 }
@@ -1016,7 +1015,7 @@ extern "C" int shdr_apply_rf_bwd_f32(const float* x, const float* rf, const floa
   SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_batch > 0 && K >= 2 && K <= 8192, SHDR_E_SHAPE, "apply_rf_bwd: bad shape");
   int gx = shdr::stream_grid(n_per_batch);
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(apply_rf_bwd_kernel, dim3(gx, B), dim3(256), (size_t)2 * K * sizeof(float), S(stream), x, rf, dy,
+  hipLaunchKernelGGL(apply_rf_bwd_kernel, dim3(gx, B), dim3(256), (size_t)2 * K * sizeof(float), shdr::stream_of(stream), x, rf, dy,
                      drf, dx, (long)n_per_batch, K);
   return shdr::check_launch("apply_rf_bwd");
 }
@@ -1024,7 +1023,7 @@ extern "C" int shdr_apply_rf_bwd_f32(const float* x, const float* rf, const floa
 extern "C" int shdr_diff_loss_f32(const float* a, const float* b, float* out, int B, int64_t n_per_sample, int mode, void* stream) {
   SHDR_REQUIRE(a && b && out, SHDR_E_NULL, "diff_loss: null pointer");
   SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_sample > 0 && (mode == 0 || mode == 1), SHDR_E_SHAPE, "diff_loss: bad arguments");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "diff_loss: memset");
   int gx = shdr::stream_grid(n_per_sample);
   if (gx > 128) gx = 128;
@@ -1035,14 +1034,14 @@ extern "C" int shdr_diff_loss_bwd_f32(const float* a, const float* b, const floa
                                       int64_t n_per_sample, int mode, int accumulate, void* stream) {
   SHDR_REQUIRE(a && b && g && da, SHDR_E_NULL, "diff_loss_bwd: null pointer");
   SHDR_REQUIRE(B > 0 && n_per_sample > 0 && (mode == 0 || mode == 1), SHDR_E_SHAPE, "diff_loss_bwd: bad arguments");
-  hipLaunchKernelGGL(diff_loss_bwd_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, S(stream), a, b, g,
+  hipLaunchKernelGGL(diff_loss_bwd_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, shdr::stream_of(stream), a, b, g,
                      da, (long)n_per_sample, B, mode, accumulate);
   return shdr::check_launch("diff_loss_bwd");
 }
 extern "C" int shdr_tv_loss_f32(const float* y, float* out, int N, int H, int W, int C, void* stream) {
   SHDR_REQUIRE(y && out, SHDR_E_NULL, "tv_loss: null pointer");
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "tv_loss: bad shape");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (hipMemsetAsync(out, 0, sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "tv_loss: memset");
   int gx = shdr::stream_grid((long)N * H * W * C);
   if (gx > 512) gx = 512;
@@ -1052,39 +1051,39 @@ extern "C" int shdr_tv_loss_f32(const float* y, float* out, int N, int H, int W,
 extern "C" int shdr_tv_loss_bwd_f32(const float* y, const float* g, float* dy, int N, int H, int W, int C, int accumulate, void* stream) {
   SHDR_REQUIRE(y && g && dy, SHDR_E_NULL, "tv_loss_bwd: null pointer");
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "tv_loss_bwd: bad shape");
-  hipLaunchKernelGGL(tv_loss_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * C)), dim3(256), 0, S(stream), y, g, dy,
+  hipLaunchKernelGGL(tv_loss_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * C)), dim3(256), 0, shdr::stream_of(stream), y, g, dy,
                      N, H, W, C, accumulate);
   return shdr::check_launch("tv_loss_bwd");
 }
 extern "C" int shdr_logc_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   SHDR_REQUIRE(dy && x && dx, SHDR_E_NULL, "logc_bwd: null pointer");
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "logc_bwd: n must be positive");
-  hipLaunchKernelGGL(logc_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), dy, x, dx, (long)n);
+  hipLaunchKernelGGL(logc_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), dy, x, dx, (long)n);
   return shdr::check_launch("logc_bwd");
 }
 extern "C" int shdr_alpha_mask_f32(const float* x, float* alpha, int64_t npix, float thr, void* stream) {
   SHDR_REQUIRE(x && alpha, SHDR_E_NULL, "alpha_mask: null pointer");
   SHDR_REQUIRE(npix > 0 && thr > 0.f, SHDR_E_SHAPE, "alpha_mask: bad arguments");
-  hipLaunchKernelGGL(alpha_mask_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), x, alpha, (long)npix, thr);
+  hipLaunchKernelGGL(alpha_mask_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), x, alpha, (long)npix, thr);
   return shdr::check_launch("alpha_mask");
 }
 extern "C" int shdr_alpha_blend_bwd_f32(const float* dA, const float* alpha, float* dhal, int64_t npix, void* stream) {
   SHDR_REQUIRE(dA && alpha && dhal, SHDR_E_NULL, "alpha_blend_bwd: null pointer");
   SHDR_REQUIRE(npix > 0, SHDR_E_SHAPE, "alpha_blend_bwd: npix must be positive");
-  hipLaunchKernelGGL(alpha_blend_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), dA, alpha, dhal, (long)npix);
+  hipLaunchKernelGGL(alpha_blend_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), dA, alpha, dhal, (long)npix);
   return shdr::check_launch("alpha_blend_bwd");
 }
 extern "C" int shdr_vgg_preprocess_bwd_f32(const float* dy, float* dx, int64_t npix, int in_channels, void* stream) {
   SHDR_REQUIRE(dy && dx, SHDR_E_NULL, "vgg_preprocess_bwd: null pointer");
   SHDR_REQUIRE(npix > 0 && (in_channels == 3 || in_channels == 4), SHDR_E_SHAPE, "vgg_preprocess_bwd: bad arguments");
-  hipLaunchKernelGGL(vgg_preprocess_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), dy, dx, (long)npix, in_channels);
+  hipLaunchKernelGGL(vgg_preprocess_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), dy, dx, (long)npix, in_channels);
   return shdr::check_launch("vgg_preprocess_bwd");
 }
 extern "C" int shdr_adam_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1, float beta2,
                              float eps, float grad_scale, void* stream) {
   SHDR_REQUIRE(p && g && m && v, SHDR_E_NULL, "adam: null pointer");
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "adam: n must be positive");
-  hipLaunchKernelGGL(adam_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), p, g, m, v, (long)n, lr_t, beta1,
+  hipLaunchKernelGGL(adam_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), p, g, m, v, (long)n, lr_t, beta1,
                      beta2, eps, grad_scale);
   return shdr::check_launch("adam");
 }

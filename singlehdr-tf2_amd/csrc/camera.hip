@@ -191,8 +191,6 @@ __global__ void loss_mask_kernel(const int* __restrict__ counts, float* __restri
   if (n < N) mask[n] = ((float)counts[2 * n] > 32768.0f || (float)counts[2 * n + 1] > 32768.0f) ? 0.0f : 1.0f;
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" int shdr_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]) {
@@ -207,7 +205,7 @@ extern "C" int shdr_camera_expose_f32(const float* hdr, const float* t, float* h
   SHDR_REQUIRE(hdr && t && hdr_t && clipped, SHDR_E_NULL, "camera_expose: null pointer");
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0, SHDR_E_SHAPE, "camera_expose: non-positive dimension");
   const long per = (long)H * W * 3;
-  hipLaunchKernelGGL(camera_expose_kernel, dim3(shdr::stream_grid((long)N * per)), dim3(256), 0, S(stream), hdr, t, hdr_t,
+  hipLaunchKernelGGL(camera_expose_kernel, dim3(shdr::stream_grid((long)N * per)), dim3(256), 0, shdr::stream_of(stream), hdr, t, hdr_t,
                      clipped, N, per, (uint32_t)seed, (uint32_t)(seed >> 32));
   return shdr::check_launch("camera_expose");
 }
@@ -217,7 +215,7 @@ extern "C" int shdr_jpeg_round_trip_f32(const float* ldr, const int32_t* quality
   SHDR_REQUIRE(ldr && quality && jpeg && ws_planes && ws_counts, SHDR_E_NULL, "jpeg_round_trip: null pointer");
   SHDR_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0 && H / 16 <= 65535, SHDR_E_SHAPE,
                "jpeg_round_trip: need whole 16x16 MCUs (H %% 16 == W %% 16 == 0), got %dx%d", H, W);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const size_t npix = (size_t)N * H * W;
   uint8_t* yp = ws_planes;
   uint8_t* cbp = yp + npix;

@@ -17,7 +17,6 @@ extern "C" int shdr_conv2d_x3n_prepare_filter_premax_f32(const shdr_conv2d_desc*
 
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the Winograd form a 3x3 / stride-1 / SAME layer takes (measured on MI355X, tools/wino_bench.py): the one-kernel fused form beats
@@ -184,7 +183,7 @@ extern "C" int shdr_conv2d_prepare_filter_f32(const shdr_conv2d_desc* d, int has
   if (plan == SHDR_PLAN_WINOGRAD_PLANES) return shdr_winograd_filter_f32(w, prepared, Ct, d->Cout, stream);
   const long total = (long)d->KH * d->KW * Ct * d->Cout;
   const float sc = d->C2 > 0 ? d->x2_scale : 1.0f;
-  hipLaunchKernelGGL(fold_x2_scale_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), w, prepared, total, Ct, d->C1, d->Cout, sc);
+  hipLaunchKernelGGL(fold_x2_scale_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), w, prepared, total, Ct, d->C1, d->Cout, sc);
   return shdr::check_launch("prepare_filter");
 }
 
@@ -230,7 +229,7 @@ static int measure_missing_ranges(const shdr_conv2d_desc* d, int has_residual, c
   SHDR_REQUIRE(workspace && shdr::aligned16(workspace), SHDR_E_NULL,
                "conv2d_fwd_prepared: a split-operand layer without x ranges needs shdr_conv2d_workspace_bytes_f32 bytes of workspace");
   float* slots = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + shdr_conv2d_workspace_bytes_f32(d, has_residual) - kRangeScratch);
-  if (hipMemsetAsync(slots, 0, 2 * sizeof(float), S(stream)) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_fwd_prepared: memset failed");
+  if (hipMemsetAsync(slots, 0, 2 * sizeof(float), shdr::stream_of(stream)) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_fwd_prepared: memset failed");
   const bool lowres = d->prologue == SHDR_PROLOGUE_BILINEAR2X;
   const int64_t npix = (int64_t)d->N * (lowres ? d->H / 2 : d->H) * (lowres ? d->W / 2 : d->W);
   if (!x1_range) {
@@ -402,7 +401,7 @@ extern "C" int shdr_conv2d_dgrad_ranged_f32(const shdr_conv2d_desc* d, int which
   const DgradGeom g = dgrad_geom(d, which);
   char* ws = reinterpret_cast<char*>(workspace);
   float* wt = reinterpret_cast<float*>(ws + g.off_wt);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const int Ct = d->C1 + d->C2;
   const float scale = which ? d->x2_scale : 1.0f;
   // the split-operand plans pack wt next: its maximum comes out of this pass (header slot 0 of the packed filter)

@@ -21,8 +21,6 @@ using shdr::linear::linear_taps;
 
 constexpr int kWin = 512;          // PatchHDRDataset's crop side (dataset.py:216-219)
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // Ward's RGBE -> float, as hdr_io.rgbe_decode: byte * 2^(e - 136), e == 0 -> 0; channel c of the result is the file's 2 - c
 // (cv2.imread's BGR; the [:,:,::-1] and np.flip(hdr, -1) of dataset.py:183-184 cancel), clip(0, None) (:185) is the identity
 __device__ __forceinline__ float3 rgbe_bgr(uchar4 p) {
@@ -146,7 +144,7 @@ extern "C" int shdr_hdr_load_resize_f32(const uint8_t* rgbe, float* y, int H0, i
   SHDR_REQUIRE(H0 > 0 && W0 > 0 && H > 0 && W > 0, SHDR_E_SHAPE, "hdr_load_resize: non-positive dimension");
   SHDR_REQUIRE((reinterpret_cast<uintptr_t>(rgbe) & 3u) == 0, SHDR_E_ALIGN, "hdr_load_resize: rgbe must be 4-byte aligned");
   const long total = (long)H * W;
-  hipLaunchKernelGGL(hdr_load_resize_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream),
+  hipLaunchKernelGGL(hdr_load_resize_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream),
                      reinterpret_cast<const uchar4*>(rgbe), y, H0, W0, H, W, 1.0 / ((double)H / H0), 1.0 / ((double)W / W0));
   return shdr::check_launch("hdr_load_resize");
 }
@@ -155,11 +153,11 @@ extern "C" int shdr_hdr_window_means_f32(const float* arena, const int64_t* offs
                                          float* means, void* stream) {
   SHDR_REQUIRE(arena && offsets && dims && partials && means, SHDR_E_NULL, "hdr_window_means: null pointer");
   SHDR_REQUIRE(n_files > 0 && n_files < (1 << 30), SHDR_E_SHAPE, "hdr_window_means: %d files", n_files);
-  hipLaunchKernelGGL(hdr_window_partials_kernel, dim3(2 * n_files, kMeanBlocks), dim3(256), 0, S(stream), arena, offsets, dims,
+  hipLaunchKernelGGL(hdr_window_partials_kernel, dim3(2 * n_files, kMeanBlocks), dim3(256), 0, shdr::stream_of(stream), arena, offsets, dims,
                      partials);
   int rc = shdr::check_launch("hdr_window_means");
   if (rc != SHDR_OK) return rc;
-  hipLaunchKernelGGL(hdr_window_fold_kernel, dim3(2 * n_files), dim3(kMeanBlocks), 0, S(stream), partials, means);
+  hipLaunchKernelGGL(hdr_window_fold_kernel, dim3(2 * n_files), dim3(kMeanBlocks), 0, shdr::stream_of(stream), partials, means);
   return shdr::check_launch("hdr_window_means");
 }
 
@@ -169,7 +167,7 @@ extern "C" int shdr_hdr_patch_sample_f32(const float* arena, const int64_t* offs
   SHDR_REQUIRE(N > 0 && N <= 65535 && n_files > 0 && param_stride >= 7, SHDR_E_SHAPE,
                "hdr_patch_sample: N %d, n_files %d, param_stride %d", N, n_files, param_stride);
   SHDR_REQUIRE(P > 0 && P % 16 == 0 && P <= kWin * 4, SHDR_E_SHAPE, "hdr_patch_sample: P %d must be a multiple of 16", P);
-  hipLaunchKernelGGL(hdr_patch_sample_kernel, dim3(P / 16, P / 16, N), dim3(256), 0, S(stream), arena, offsets, dims, means,
+  hipLaunchKernelGGL(hdr_patch_sample_kernel, dim3(P / 16, P / 16, N), dim3(256), 0, shdr::stream_of(stream), arena, offsets, dims, means,
                      params, param_stride, n_files, P, y);
   return shdr::check_launch("hdr_patch_sample");
 }

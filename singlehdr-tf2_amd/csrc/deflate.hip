@@ -70,8 +70,8 @@ __global__ __launch_bounds__(kThreads) void deflate_stats_kernel(const uint8_t* 
   __shared__ HuffWork work;
   __shared__ uint64_t part[4];
   const int64_t c = blockIdx.x;
-  int64_t lo, n;
-  chunk_range(offsets, c, total, lo, n);
+  const shdr::Span span = shdr::clamped_span(offsets, c, total, kMaxChunk);
+  const int64_t lo = span.lo, n = span.n;
   const int tid = threadIdx.x, wave = tid >> 6;
   for (int i = tid; i < 4 * 256; i += kThreads) (&hist[0][0])[i] = 0;
   __syncthreads();

@@ -1,10 +1,11 @@
 // The batched device encoder behind shdr_deflate_huffman_batch (csrc/deflate.hip) and shdr_deflate_lz_batch (csrc/deflate_lz.hip): all
 // of it that does not depend on what a symbol is.  Each of the two files brings the front of its pass 1, two __global__ entry points
 // and a `Codec`: a struct with kTokens, kPass1Threads, kDeposits, kSyms, kSymbolsAtBit, kTileWords, items, build_lengths, build_codes
-// and thread_bits (HuffCodec, LzCodec).  Here are the workspace, the end of pass 1 (finish_pass1), pass 2 (deflate_scan_kernel), the
+// and thread_bits (HuffCodec, LzCodec).  Here are the workspace, the end of pass 1 (finish_pass1), pass 2 (deflate_scan_kernel, over scan_array of batch.h), the
 // body of pass 3 (write_chunk) and the host side (batch_sizes, run_batch).  Every translation unit gets its own copy.
 #pragma once
 #include "shdr_internal.h"
+#include "batch.h"
 #include "deflate_huffman.h"
 
 namespace shdr_deflate_batch {
@@ -18,9 +19,8 @@ constexpr int kThreads = 256;                                    // of a writer 
 constexpr int kPerThread = 4;
 constexpr int kTile = kThreads * kPerThread;                     // items per tile of the writers (shdr.h: SHDR_DEFLATE_TILE, _LZ_TILE)
 
-inline constexpr int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 template <class Codec>
-constexpr int kLenStride = (int)align16(Codec::kSyms);           // bytes per chunk of the stored code lengths
+constexpr int kLenStride = (int)shdr::align16(Codec::kSyms);         // bytes per chunk of the stored code lengths
 
 struct Workspace {                                               // carved out of the caller's workspace, every part 16-byte aligned
   uint8_t* lens;                                                 // [C][kLenStride]
@@ -32,25 +32,14 @@ struct Workspace {                                               // carved out o
 };
 inline Workspace carve(void* ws, int64_t c, int len_stride, int64_t n_tokens) {
   Workspace w;
-  char* p = static_cast<char*>(ws);
-  int64_t o = 0;
-  w.lens = reinterpret_cast<uint8_t*>(p + o);    o += (int64_t)len_stride * c;
-  w.bits = reinterpret_cast<int64_t*>(p + o);    o += align16(8 * c);
-  w.sizes = reinterpret_cast<int64_t*>(p + o);   o += align16(8 * c);
-  w.adler = reinterpret_cast<uint32_t*>(p + o);  o += align16(4 * c);
-  w.tokens = reinterpret_cast<uint32_t*>(p + o); o += align16(4 * n_tokens);
-  w.bytes = o;
+  shdr::Carver cut(ws);
+  w.lens = cut.take<uint8_t>((int64_t)len_stride * c);           // (the stride is a multiple of 16)
+  w.bits = cut.take<int64_t>(c);
+  w.sizes = cut.take<int64_t>(c);
+  w.adler = cut.take<uint32_t>(c);
+  w.tokens = cut.take<uint32_t>(n_tokens);
+  w.bytes = cut.bytes();
   return w;
-}
-
-// chunk c of the batch, clamped into the data: [lo, lo + n)
-__device__ __forceinline__ void chunk_range(const int64_t* __restrict__ offsets, int64_t c, int64_t total, int64_t& lo, int64_t& n) {
-  int64_t a = offsets[c], b = offsets[c + 1];
-  a = a < 0 ? 0 : a > total ? total : a;
-  b = b < a ? a : b > total ? total : b;
-  if (b - a > kMaxChunk) b = a + kMaxChunk;
-  lo = a;
-  n = b - a;
 }
 
 // The end of pass 1 for chunk c of n bytes, by all `threads` threads of its block (this one is `tid`): freq (LDS) holds the counts
@@ -74,30 +63,9 @@ __device__ __forceinline__ void finish_pass1(const uint32_t* freq, uint8_t* len,
 
 // out_offsets[c] = sum of the sizes before c, out_offsets[C] = the total.  One block.
 __global__ __launch_bounds__(1024) void deflate_scan_kernel(const int64_t* __restrict__ sizes, int64_t count, int64_t* __restrict__ out_offsets) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < count; base += 1024) {
-    const int64_t r = base + threadIdx.x;
-    const int64_t v = r < count ? sizes[r] : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int64_t before = carry_s;
-    for (int w = 0; w < wave; ++w) before += part[w];
-    if (r < count) out_offsets[r] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out_offsets[count] = carry_s;
+  const int64_t all = shdr::scan_array<1024, 1>(
+      count, [&](int64_t c) { return sizes[c]; }, [&](int64_t c, int64_t before) { out_offsets[c] = before; });
+  if (threadIdx.x == 0) out_offsets[count] = all;
 }
 
 // Pass 3 for chunk blockIdx.x, by a block of kThreads: the header, then tiles of kTile items (+ end-of-block behind the last).  The
@@ -117,8 +85,8 @@ __device__ __forceinline__ void write_chunk(const Item* __restrict__ items, cons
   __shared__ uint32_t words[Codec::kTileWords];
   __shared__ int wave_bits[4];
   const int64_t c = blockIdx.x;
-  int64_t lo, n;
-  chunk_range(offsets, c, total, lo, n);
+  const shdr::Span span = shdr::clamped_span(offsets, c, total, kMaxChunk);
+  const int64_t lo = span.lo, n = span.n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t at = out_offsets[c] + pad, end = out_offsets[c + 1];
   if (at < 0 || end > capacity || end < at) return;              // never with the sizes the host checked
@@ -146,12 +114,7 @@ __device__ __forceinline__ void write_chunk(const Item* __restrict__ items, cons
     Codec::thread_bits(src, n, base + (int64_t)tid * kPerThread, len, code, v, nbk);
 #pragma unroll
     for (int k = 0; k < Codec::kDeposits; ++k) nb += nbk[k];
-    int incl = nb;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
+    const int incl = shdr::wave_scan(nb);                        // (not block_scan: the barrier below also covers `words`)
     if (lane == 63) wave_bits[wave] = incl;
     __syncthreads();                                             // words are cleared, wave_bits are written
     int before = 0;
@@ -233,7 +196,7 @@ int run_batch(const char* what, Pass1 pass1, Write write, const uint8_t* data, c
   SHDR_REQUIRE(shdr::aligned16(workspace), SHDR_E_ALIGN, "%s: workspace must be 16-byte aligned", what);
   SHDR_REQUIRE(out_capacity >= bound, SHDR_E_SHAPE, "%s: output buffer too small (%lld < %lld)", what, (long long)out_capacity, (long long)bound);
   const Workspace w = carve(workspace, n_chunks, kLenStride<Codec>, Codec::kTokens ? total : 0);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_DEFLATE_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(pass1, dim3((unsigned)n_chunks), dim3(Codec::kPass1Threads), 0, st, data, offsets_dev, total, pad, w, coded);
   timer.mark();

@@ -115,8 +115,8 @@ __global__ __launch_bounds__(kGroup) void deflate_lz_parse_kernel(const uint8_t*
   __shared__ uint64_t stage64[kWindow / 8 + 1];                  // a window of the chunk and the 2 bytes behind it
   uint8_t* stage = reinterpret_cast<uint8_t*>(stage64);
   const int64_t c = blockIdx.x;
-  int64_t lo, n;
-  chunk_range(offsets, c, total, lo, n);
+  const shdr::Span span = shdr::clamped_span(offsets, c, total, kMaxChunk);
+  const int64_t lo = span.lo, n = span.n;
   const int lane = threadIdx.x;
   for (int i = lane; i < kHashSlots; i += kGroup) table[i] = 0;
   for (int i = lane; i < kAllSyms; i += kGroup) freq[i] = i == 256 ? 1u : 0u;

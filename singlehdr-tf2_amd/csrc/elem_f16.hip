@@ -43,8 +43,6 @@ __device__ __forceinline__ V8 ld8f(const float* p) {          // 8 consecutive f
   return r;
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // e -> (n, h, w, o) of a [N, Hd, Wd, 8*O] tensor; 32-bit divisions while the index fits (see pool.hip)
 #define DECODE8(e, O, Wd, Hd, o, w, h, n)                              \
   int o, w, h;                                                          \
@@ -794,18 +792,18 @@ typedef hf* HM;
 
 extern "C" int shdr_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream) {
   SHDR_REQUIRE(x && y && n > 0, SHDR_E_NULL, "cast: bad arguments");
-  hipLaunchKernelGGL(cast_f32_f16_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), x, HM_(y), (long)n);
+  hipLaunchKernelGGL(cast_f32_f16_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), x, HM_(y), (long)n);
   return shdr::check_launch("cast_f32_to_f16");
 }
 extern "C" int shdr_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream) {
   SHDR_REQUIRE(x && y && n > 0, SHDR_E_NULL, "cast: bad arguments");
-  hipLaunchKernelGGL(cast_f16_f32_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, S(stream), H_(x), y, (long)n);
+  hipLaunchKernelGGL(cast_f16_f32_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), H_(x), y, (long)n);
   return shdr::check_launch("cast_f16_to_f32");
 }
 extern "C" int shdr_pad_channels_f32_to_f16(const float* x, void* y, int64_t npix, int Cin, int Cout, void* stream) {
   SHDR_REQUIRE(x && y, SHDR_E_NULL, "pad_channels: null pointer");
   SHDR_REQUIRE(npix > 0 && Cin > 0 && Cout >= Cin, SHDR_E_SHAPE, "pad_channels: need Cout >= Cin > 0");
-  hipLaunchKernelGGL((pad_cast_kernel<float, hf>), dim3(shdr::stream_grid(npix * Cout)), dim3(256), 0, S(stream), x, HM_(y), (long)npix, Cin, Cout);
+  hipLaunchKernelGGL((pad_cast_kernel<float, hf>), dim3(shdr::stream_grid(npix * Cout)), dim3(256), 0, shdr::stream_of(stream), x, HM_(y), (long)npix, Cin, Cout);
   return shdr::check_launch("pad_channels_f32_to_f16");
 }
 extern "C" int shdr_pack3_f16(const float* s0, const float* s1, const float* s2, const float* s3, int nsrc, void* y, int out_channels,
@@ -818,7 +816,7 @@ extern "C" int shdr_pack3_f16(const float* s0, const float* s1, const float* s2,
   const float* s[4] = {s0, s1, s2, s3};
   for (int i = 0; i < nsrc; ++i) SHDR_REQUIRE(s[i], SHDR_E_NULL, "pack3_f16: source %d is null", i);
   Src4 src{{s0, s1, s2, s3}};
-  hipLaunchKernelGGL(pack3_h_kernel, dim3(shdr::stream_grid(npix * (out_channels / 8))), dim3(256), 0, S(stream), src, nsrc, HM_(y),
+  hipLaunchKernelGGL(pack3_h_kernel, dim3(shdr::stream_grid(npix * (out_channels / 8))), dim3(256), 0, shdr::stream_of(stream), src, nsrc, HM_(y),
                      out_channels, (long)npix, vgg_preprocess);
   return shdr::check_launch("pack3_f16");
 }
@@ -829,7 +827,7 @@ extern "C" int shdr_unpack3_f16(const void* y, float* o0, float* o1, float* o2, 
   float* o[4] = {o0, o1, o2, o3};
   for (int i = 0; i < nout; ++i) SHDR_REQUIRE(o[i], SHDR_E_NULL, "unpack3_f16: output %d is null", i);
   Dst4 dst{{o0, o1, o2, o3}};
-  hipLaunchKernelGGL(unpack3_h_kernel, dim3(shdr::stream_grid(npix * 3 * nout)), dim3(256), 0, S(stream), H_(y), dst, nout, channels,
+  hipLaunchKernelGGL(unpack3_h_kernel, dim3(shdr::stream_grid(npix * 3 * nout)), dim3(256), 0, shdr::stream_of(stream), H_(y), dst, nout, channels,
                      (long)npix, vgg_preprocess_bwd);
   return shdr::check_launch("unpack3_f16");
 }
@@ -845,40 +843,40 @@ extern "C" int shdr_act_bwd_bias_f16(const void* dy, const void* y, void* dz, fl
   const int cap = db && !rows ? (nvec >= (1L << 23) ? 512 : 256) : 2048;
   int grid = octet_grid(nvec, O, cap);
   if (rows && grid > shdr::kBiasMaxBlocks) grid = octet_grid(nvec, O, shdr::kBiasMaxBlocks / 2);       // the rounding up to the octet unit stays below the row count
-  hipLaunchKernelGGL(act_bwd_bias_h_kernel, dim3(grid), dim3(256), db ? 8 * O * sizeof(float) : 0, S(stream), H_(dy),
+  hipLaunchKernelGGL(act_bwd_bias_h_kernel, dim3(grid), dim3(256), db ? 8 * O * sizeof(float) : 0, shdr::stream_of(stream), H_(dy),
                      H_(y), HM_(dz), db, rows ? ws : (float*)nullptr, nvec, O, act);
-  if (rows) shdr::launch_col_fold(ws, db, grid, C, S(stream));
+  if (rows) shdr::launch_col_fold(ws, db, grid, C, shdr::stream_of(stream));
   return shdr::check_launch("act_bwd_bias_f16");
 }
 extern "C" int shdr_add_f16(const void* a, const void* b, void* y, int64_t n, int relu, void* stream) {
   SHDR_REQUIRE(a && b && y, SHDR_E_NULL, "add_f16: null pointer");
   SHDR_REQUIRE(n > 0 && n % 8 == 0, SHDR_E_SHAPE, "add_f16: n must be a positive multiple of 8");
   SHDR_REQUIRE(shdr::aligned16(a) && shdr::aligned16(b) && shdr::aligned16(y), SHDR_E_ALIGN, "add_f16: tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(add_h_kernel, dim3(shdr::stream_grid(n / 8)), dim3(256), 0, S(stream), H_(a), H_(b), HM_(y), (long)(n / 8), relu);
+  hipLaunchKernelGGL(add_h_kernel, dim3(shdr::stream_grid(n / 8)), dim3(256), 0, shdr::stream_of(stream), H_(a), H_(b), HM_(y), (long)(n / 8), relu);
   return shdr::check_launch("add_f16");
 }
 extern "C" int shdr_avgpool2_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("avgpool2_f16", x, y, N, H, W, C)) return rc;
   SHDR_REQUIRE(H >= 2 && W >= 2, SHDR_E_SHAPE, "avgpool2_f16: H, W must be >= 2");
-  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, S(stream), H_(x), HM_(y), N, H, W, C, 0);
+  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C, 0);
   return shdr::check_launch("avgpool2_f16");
 }
 extern "C" int shdr_maxpool2_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("maxpool2_f16", x, y, N, H, W, C)) return rc;
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_f16: H, W must be even");
-  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, S(stream), H_(x), HM_(y), N, H, W, C, 1);
+  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C, 1);
   return shdr::check_launch("maxpool2_f16");
 }
 extern "C" int shdr_avgpool2_bwd_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("avgpool2_bwd_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(avgpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, S(stream), H_(dy), HM_(dx), N, H, W, C);
+  hipLaunchKernelGGL(avgpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
   return shdr::check_launch("avgpool2_bwd_f16");
 }
 extern "C" int shdr_maxpool2_bwd_f16(const void* x, const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("maxpool2_bwd_f16", x, dx, N, H, W, C)) return rc;
   SHDR_REQUIRE(dy && shdr::aligned16(dy), SHDR_E_NULL, "maxpool2_bwd_f16: dy null or unaligned");
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_bwd_f16: H, W must be even");
-  hipLaunchKernelGGL(maxpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, S(stream), H_(x),
+  hipLaunchKernelGGL(maxpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x),
                      H_(dy), HM_(dx), N, H, W, C);
   return shdr::check_launch("maxpool2_bwd_f16");
 }
@@ -887,7 +885,7 @@ extern "C" int shdr_maxpool3s2_fwd_f16(const void* x, void* y, int N, int H, int
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_h_kernel, dim3(shdr::stream_grid((long)N * Ho * Wo * (C / 8))), dim3(256), 0, S(stream), H_(x), HM_(y), N, H,
+  hipLaunchKernelGGL(maxpool3s2_h_kernel, dim3(shdr::stream_grid((long)N * Ho * Wo * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H,
                      W, C, Ho, Wo, pt, pl);
   return shdr::check_launch("maxpool3s2_f16");
 }
@@ -898,34 +896,34 @@ extern "C" int shdr_maxpool3s2_bwd_f16(const void* x, const void* y, const void*
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, S(stream), H_(x), H_(y),
+  hipLaunchKernelGGL(maxpool3s2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), H_(y),
                      H_(dy), HM_(dx), N, H, W, C, Ho, Wo, pt, pl);
   return shdr::check_launch("maxpool3s2_bwd_f16");
 }
 extern "C" int shdr_resize2x_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("resize2x_f16", x, y, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, S(stream), H_(x), HM_(y), N, H, W, C);
+  hipLaunchKernelGGL(resize2x_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C);
   return shdr::check_launch("resize2x_f16");
 }
 extern "C" int shdr_resize2x_bwd_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("resize2x_bwd_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, S(stream), H_(dy), HM_(dx), N, H, W, C);
+  hipLaunchKernelGGL(resize2x_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
   return shdr::check_launch("resize2x_bwd_f16");
 }
 extern "C" int shdr_upsample_zero2_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
   if (int rc = chk8("upsample_zero2_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(upsample_zero2_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, S(stream), H_(dy), HM_(dx), N, H, W, C);
+  hipLaunchKernelGGL(upsample_zero2_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
   return shdr::check_launch("upsample_zero2_f16");
 }
 extern "C" int shdr_gap_fwd_f16(const void* x, float* y, int N, int HW, int C, void* stream) {
   if (int rc = chk8("gap_f16", x, y, N, HW, 1, C)) return rc;
-  hipLaunchKernelGGL(gap_h_kernel, dim3((C + 127) / 128, N), dim3(256), 0, S(stream), H_(x), y, HW, C);
+  hipLaunchKernelGGL(gap_h_kernel, dim3((C + 127) / 128, N), dim3(256), 0, shdr::stream_of(stream), H_(x), y, HW, C);
   return shdr::check_launch("gap_f16");
 }
 extern "C" int shdr_gap_bwd_f16(const float* dy, void* dx, int N, int HW, int C, void* stream) {
   if (int rc = chk8("gap_bwd_f16", dy, dx, N, HW, 1, C)) return rc;
   const long tv = (long)N * HW * (C / 8);
-  hipLaunchKernelGGL(gap_bwd_h_kernel, dim3(shdr::stream_grid(tv)), dim3(256), 0, S(stream), dy, HM_(dx), tv, HW, C);
+  hipLaunchKernelGGL(gap_bwd_h_kernel, dim3(shdr::stream_grid(tv)), dim3(256), 0, shdr::stream_of(stream), dy, HM_(dx), tv, HW, C);
   return shdr::check_launch("gap_bwd_f16");
 }
 namespace {
@@ -946,7 +944,7 @@ extern "C" int shdr_bn_stats_f16(const void* x, double* ws, float* mean, float* 
   SHDR_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), SHDR_E_NULL, "bn_stats_f16: moving stats come in pairs");
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_stats_f16: bad shape (C %% 8 == 0)");
   SHDR_REQUIRE(shdr::aligned16(x), SHDR_E_ALIGN, "bn_stats_f16: x must be 16-byte aligned");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce_h(st, H_(x), nullptr, nullptr, nullptr, ws, (long)npix, C, 0);
   hipLaunchKernelGGL(bn_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var, (long)npix, C, momentum);
   return shdr::check_launch("bn_stats_f16");
@@ -957,7 +955,7 @@ extern "C" int shdr_bn_train_apply_f16(const void* x, const float* mean, const f
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_train_apply_f16: bad shape (C %% 8 == 0)");
   SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(y), SHDR_E_ALIGN, "bn_train_apply_f16: x and y must be 16-byte aligned");
   const long nvec = (long)npix * (C / 8);
-  hipLaunchKernelGGL(bn_apply_h_kernel, dim3(octet_grid(nvec, C / 8, 2048)), dim3(256), 0, S(stream), H_(x), (HP) nullptr, (HP) nullptr, mean, var,
+  hipLaunchKernelGGL(bn_apply_h_kernel, dim3(octet_grid(nvec, C / 8, 2048)), dim3(256), 0, shdr::stream_of(stream), H_(x), (HP) nullptr, (HP) nullptr, mean, var,
                      gamma, beta, (const double*)nullptr, HM_(y), nvec, (long)npix, C, eps, relu, 0);
   return shdr::check_launch("bn_train_apply_f16");
 }
@@ -967,7 +965,7 @@ extern "C" int shdr_bn_bwd_f16(const void* dy, const void* x, const void* y_relu
   SHDR_REQUIRE(npix > 0 && C > 0 && C % 8 == 0, SHDR_E_SHAPE, "bn_bwd_f16: bad shape (C %% 8 == 0)");
   SHDR_REQUIRE(shdr::aligned16(dy) && shdr::aligned16(x) && (!y_relu || shdr::aligned16(y_relu)) && shdr::aligned16(dx) && shdr::aligned16(mean),
                SHDR_E_ALIGN, "bn_bwd_f16: dy, x, y_relu, dx and mean (read as float4) must be 16-byte aligned");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce_h(st, H_(dy), H_(x), H_(y_relu), mean, ws, (long)npix, C, 1);
   hipLaunchKernelGGL(bn_bwd_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
   const long nvec = (long)npix * (C / 8);
@@ -984,13 +982,13 @@ extern "C" int shdr_lin_frontend_fwd_f16(const float* img, void* y, int N, int H
   // 6 blocks per group: one leading-octet block + five histogram blocks (5 * 256 threads = a multiple of the 10 histogram octets)
   long groups = ((long)N * H * W * 12 + 6 * 256 - 1) / (6 * 256);
   groups = groups < 1 ? 1 : (groups > 342 ? 342 : groups);
-  hipLaunchKernelGGL(lin_frontend_h_kernel, dim3((unsigned)(6 * groups)), dim3(256), 0, S(stream), img, HM_(y), N, H, W, y_channels);
+  hipLaunchKernelGGL(lin_frontend_h_kernel, dim3((unsigned)(6 * groups)), dim3(256), 0, shdr::stream_of(stream), img, HM_(y), N, H, W, y_channels);
   return shdr::check_launch("lin_frontend_f16");
 }
 extern "C" int shdr_lin_frontend_bwd_f16(const float* img, const void* dF, float* dimg, int N, int H, int W, int y_channels, void* stream) {
   SHDR_REQUIRE(img && dF && dimg, SHDR_E_NULL, "lin_frontend_bwd_f16: null pointer");
   SHDR_REQUIRE(N > 0 && H >= 2 && W >= 2 && y_channels >= 93, SHDR_E_SHAPE, "lin_frontend_bwd_f16: bad shape");
-  hipLaunchKernelGGL(lin_frontend_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * 3)), dim3(256), 0, S(stream), img, H_(dF), dimg, N, H, W,
+  hipLaunchKernelGGL(lin_frontend_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * 3)), dim3(256), 0, shdr::stream_of(stream), img, H_(dF), dimg, N, H, W,
                      y_channels);
   return shdr::check_launch("lin_frontend_bwd_f16");
 }

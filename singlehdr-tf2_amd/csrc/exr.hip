@@ -17,29 +17,20 @@
 //     copies, as cv2.resize makes them: a zero-weight tap would turn a neighbouring inf into NaN and -0 into +0.
 // Compiled with -ffp-contract=off.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "linear_resize.h"
 
 namespace {
 
 using shdr::linear::bilinear3;
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kThreads = 256;
 constexpr int kPairs = 8;                        // pairs per thread and step: a step writes 4 KiB of a chunk
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t n = __shfl_up(v, d, 64);
-    if (lane >= d) v += n;
-  }
-  return v;
-}
-
+// (block_scan of batch.h would add the lanes' prefixes, which nobody reads here: only the wave-level part is shared)
 __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  v = wave_incl_scan(v, lane);
+  v = shdr::wave_scan(v);
   if (lane == 63) lds[wid] = v;
   __syncthreads();
   const uint32_t s = lds[0] + lds[1] + lds[2] + lds[3];
@@ -54,10 +45,10 @@ __global__ __launch_bounds__(kThreads) void exr_unpredict_kernel(const uint8_t* 
                                                                  const uint8_t* __restrict__ coded) {
   __shared__ uint32_t lds[2][4];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int64_t lo = min(max(chunk_off[c], (int64_t)0), size);          // the host checked the table; clamp regardless
-  const int64_t n = min(max(chunk_off[c + 1], lo), size) - lo;
-  const uint8_t* d = src + lo;
-  uint8_t* o = dst + lo;
+  const shdr::Span span = shdr::clamped_span(chunk_off, c, size);         // the host checked the table; clamp regardless
+  const int64_t n = span.n;
+  const uint8_t* d = src + span.lo;
+  uint8_t* o = dst + span.lo;
   if (!coded[c]) {
     for (int64_t i = tid; i < n; i += kThreads) o[i] = d[i];
     return;
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void exr_unpredict_kernel(const uint8_t* 
       a[j] = sa;
       b[j] = sb;
     }
-    const uint32_t ia = wave_incl_scan(sa, lane), ib = wave_incl_scan(sb, lane);
+    const uint32_t ia = shdr::wave_scan(sa), ib = shdr::wave_scan(sb);      // (two scans under ONE pair of barriers: no block_scan)
     if (lane == 63) {
       lds[0][wid] = ia;
       lds[1][wid] = ib;
@@ -158,7 +149,7 @@ extern "C" int shdr_exr_unpredict_u8(const uint8_t* payload, uint8_t* out, int64
   SHDR_REQUIRE(payload && out && chunk_off && coded, SHDR_E_NULL, "exr_unpredict: null pointer");
   SHDR_REQUIRE(size > 0 && n_chunks > 0 && n_chunks < (1 << 30), SHDR_E_SHAPE, "exr_unpredict: size %lld, %d chunks",
                (long long)size, n_chunks);
-  hipLaunchKernelGGL(exr_unpredict_kernel, dim3(n_chunks), dim3(kThreads), 0, S(stream), payload, out, size, chunk_off, coded);
+  hipLaunchKernelGGL(exr_unpredict_kernel, dim3(n_chunks), dim3(kThreads), 0, shdr::stream_of(stream), payload, out, size, chunk_off, coded);
   return shdr::check_launch("exr_unpredict");
 }
 
@@ -183,7 +174,7 @@ extern "C" int shdr_exr_load_resize_f32(const uint8_t* planes, int64_t size, con
     ch.type[i] = chan_type[i];
   }
   const long total = (long)H * W;
-  hipLaunchKernelGGL(exr_load_resize_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), planes, size, chunk_off,
+  hipLaunchKernelGGL(exr_load_resize_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), planes, size, chunk_off,
                      lines, row_bytes, ch, H0, W0, H, W, 1.0 / ((double)H / H0), 1.0 / ((double)W / W0), clip, y);
   return shdr::check_launch("exr_load_resize");
 }

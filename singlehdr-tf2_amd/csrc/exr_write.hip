@@ -8,14 +8,13 @@
 // read three times (once for the planar byte, twice for the predicted one) and the vector L1 / L2 serve the repeats.
 // HALF conversion: exr_half.h, integer arithmetic, no floating-point contraction or rounding mode involved.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "exr_half.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int64_t kMaxSide = 1 << 20, kMaxPixels = (int64_t)1 << 28;      // exr.py's reader refuses larger data windows
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 struct Pack {
   const float* pixels;
@@ -41,11 +40,7 @@ __global__ __launch_bounds__(kThreads) void exr_pack_kernel(const float* __restr
                                                             uint8_t* __restrict__ predicted) {
   const int64_t c = blockIdx.x;
   const int64_t* chunk0 = table;
-  int lo = 0, hi = n_img;                                        // the image of this chunk: the last i with chunk0[i] <= c
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (chunk0[mid] <= c) lo = mid; else hi = mid;
-  }
+  const int lo = (int)shdr::last_le(chunk0, n_img, c);           // the image of this chunk
   const int64_t hw = table[2 * (n_img + 1) + lo];
   const int H = (int)(hw >> 32), W = (int)(hw & 0xffffffff);
   Pack p;
@@ -86,11 +81,7 @@ __global__ __launch_bounds__(kThreads) void exr_finish_kernel(uint8_t* __restric
                                                               const int64_t* __restrict__ header_len, int n_img, int64_t n_chunks, int lines) {
   const int64_t c = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (c >= n_chunks) return;
-  int lo = 0, hi = n_img;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (table[mid] <= c) lo = mid; else hi = mid;
-  }
+  const int lo = (int)shdr::last_le(table, n_img, c);
   const int64_t c0 = table[lo], c1 = table[lo + 1];
   const int64_t at = out_offsets[c], size = out_offsets[c + 1] - at - 8;
   store_le(records + at, (uint64_t)(uint32_t)((c - c0) * lines), 4);
@@ -165,7 +156,7 @@ extern "C" int shdr_exr_pack_f32(const float* pixels, const int32_t* shapes, int
   SHDR_REQUIRE((reinterpret_cast<uintptr_t>(pixels) & 3u) == 0, SHDR_E_ALIGN, "%s: pixels must be 4-byte aligned", what);
   SHDR_REQUIRE((reinterpret_cast<uintptr_t>(table_dev) & 7u) == 0 && (reinterpret_cast<uintptr_t>(chunk_off) & 7u) == 0, SHDR_E_ALIGN,
                "%s: table_dev and chunk_off must be 8-byte aligned", what);
-  hipLaunchKernelGGL(exr_pack_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, S(stream), pixels, table_dev, n_images, chunks, total, npix,
+  hipLaunchKernelGGL(exr_pack_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, shdr::stream_of(stream), pixels, table_dev, n_images, chunks, total, npix,
                      lines, pixel_type == SHDR_EXR_HALF ? 1 : 2, reverse_channels, saturate, chunk_off, planar, predicted);
   return shdr::check_launch(what);
 }
@@ -177,7 +168,7 @@ extern "C" int shdr_exr_finish_chunks(uint8_t* records, uint8_t* tables, const i
   SHDR_REQUIRE(n_images > 0 && n_chunks > 0 && n_chunks < ((int64_t)1 << 31), SHDR_E_SHAPE, "%s: %d images, %lld chunks", what, n_images,
                (long long)n_chunks);
   SHDR_REQUIRE(lines == 1 || lines == 16 || lines == 32, SHDR_E_SHAPE, "%s: a chunk holds 1, 16 or 32 scanlines, got %d", what, lines);
-  hipLaunchKernelGGL(exr_finish_kernel, dim3((unsigned)((n_chunks + kThreads - 1) / kThreads)), dim3(kThreads), 0, S(stream), records, tables,
+  hipLaunchKernelGGL(exr_finish_kernel, dim3((unsigned)((n_chunks + kThreads - 1) / kThreads)), dim3(kThreads), 0, shdr::stream_of(stream), records, tables,
                      out_offsets, table_dev, header_len, n_images, n_chunks, lines);
   return shdr::check_launch(what);
 }

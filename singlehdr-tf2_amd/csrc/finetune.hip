@@ -139,15 +139,13 @@ __global__ __launch_bounds__(256) void mean_norm_bwd_kernel(const float* __restr
   }
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" int shdr_lin_frontend_bwd_f32(const float* img, const float* dF, float* dimg, int N, int H, int W, int y_channels,
                                          void* stream) {
   SHDR_REQUIRE(img && dF && dimg, SHDR_E_NULL, "lin_frontend_bwd: null pointer");
   SHDR_REQUIRE(N > 0 && H >= 2 && W >= 2 && y_channels >= 93, SHDR_E_SHAPE, "lin_frontend_bwd: bad shape");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const long npix = (long)N * H * W;
   if (hipMemsetAsync(dimg, 0, sizeof(float) * 3 * npix, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "lin_frontend_bwd: memset");
   hipLaunchKernelGGL(lin_frontend_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, st, img, dF, dimg, N, H, W, y_channels);
@@ -158,7 +156,7 @@ extern "C" int shdr_alpha_blend_full_bwd_f32(const float* b, const float* hal, c
                                              int64_t npix, float thr, void* stream) {
   SHDR_REQUIRE(b && hal && dA && dB && dhal, SHDR_E_NULL, "alpha_blend_full_bwd: null pointer");
   SHDR_REQUIRE(npix > 0 && thr > 0.f, SHDR_E_SHAPE, "alpha_blend_full_bwd: bad arguments");
-  hipLaunchKernelGGL(alpha_blend_full_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), b, hal, dA, dB, dhal,
+  hipLaunchKernelGGL(alpha_blend_full_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), b, hal, dA, dB, dhal,
                      (long)npix, thr);
   return shdr::check_launch("alpha_blend_full_bwd");
 }
@@ -170,7 +168,7 @@ extern "C" int shdr_unpack3_f32(const float* y, float* o0, float* o1, float* o2,
   float* o[4] = {o0, o1, o2, o3};
   for (int i = 0; i < nout; ++i) SHDR_REQUIRE(o[i], SHDR_E_NULL, "unpack3: output %d is null", i);
   Unpack3Args ua{{o0, o1, o2, o3}};
-  hipLaunchKernelGGL(unpack3_kernel, dim3(shdr::stream_grid(npix * 3 * nout)), dim3(256), 0, S(stream), y, ua, nout, channels,
+  hipLaunchKernelGGL(unpack3_kernel, dim3(shdr::stream_grid(npix * 3 * nout)), dim3(256), 0, shdr::stream_of(stream), y, ua, nout, channels,
                      (long)npix);
   return shdr::check_launch("unpack3");
 }
@@ -178,7 +176,7 @@ extern "C" int shdr_unpack3_f32(const float* y, float* o0, float* o1, float* o2,
 extern "C" int shdr_sample_dot_f32(const float* a, const float* b, float* out, int B, int64_t n_per_sample, void* stream) {
   SHDR_REQUIRE(a && out, SHDR_E_NULL, "sample_dot: null pointer");
   SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_sample > 0, SHDR_E_SHAPE, "sample_dot: bad shape");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "sample_dot: memset");
   int gx = shdr::stream_grid(n_per_sample);
   if (gx > 128) gx = 128;
@@ -190,7 +188,7 @@ extern "C" int shdr_mean_norm_fwd_f32(const float* r, const float* sum, float* o
                                       float target, void* stream) {
   SHDR_REQUIRE(r && sum && out, SHDR_E_NULL, "mean_norm_fwd: null pointer");
   SHDR_REQUIRE(B > 0 && n_per_sample > 0, SHDR_E_SHAPE, "mean_norm_fwd: bad shape");
-  hipLaunchKernelGGL(mean_norm_apply_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, S(stream), r, sum, out,
+  hipLaunchKernelGGL(mean_norm_apply_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, shdr::stream_of(stream), r, sum, out,
                      (long)n_per_sample, B, eps, target);
   return shdr::check_launch("mean_norm_fwd");
 }
@@ -199,7 +197,7 @@ extern "C" int shdr_mean_norm_bwd_f32(const float* g, const float* sum, const fl
                                       int64_t n_per_sample, float eps, float target, void* stream) {
   SHDR_REQUIRE(g && sum && gdot && dr, SHDR_E_NULL, "mean_norm_bwd: null pointer");
   SHDR_REQUIRE(B > 0 && n_per_sample > 0, SHDR_E_SHAPE, "mean_norm_bwd: bad shape");
-  hipLaunchKernelGGL(mean_norm_bwd_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, S(stream), g, sum, gdot, dr,
+  hipLaunchKernelGGL(mean_norm_bwd_kernel, dim3(shdr::stream_grid(n_per_sample * B)), dim3(256), 0, shdr::stream_of(stream), g, sum, gdot, dr,
                      (long)n_per_sample, B, eps, target);
   return shdr::check_launch("mean_norm_bwd");
 }

@@ -13,8 +13,6 @@
 
 namespace {
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int kMaxSize = 16384;          // size * size stays an int
 
 // ---- (a) -----------------------------------------------------------------------------------------------------------
@@ -152,7 +150,7 @@ extern "C" int shdr_pair_patch_stats(const uint8_t* ldr, const float* hdr, int64
     const int rc = check_patch("pair_patch_stats", images_host, n_images, patches_host, p, size, arena_pixels);
     if (rc != SHDR_OK) return rc;
   }
-  hipLaunchKernelGGL(pair_patch_stats_kernel, dim3(n_patches), dim3(256), 0, S(stream), ldr, hdr, images, patches, size, count, mean);
+  hipLaunchKernelGGL(pair_patch_stats_kernel, dim3(n_patches), dim3(256), 0, shdr::stream_of(stream), ldr, hdr, images, patches, size, count, mean);
   return shdr::check_launch("pair_patch_stats");
 }
 
@@ -175,7 +173,7 @@ extern "C" int shdr_pair_patch_gather_f32(const uint8_t* ldr, const float* hdr, 
     if (rc != SHDR_OK) return rc;
   }
   const int tiles = (size + kT - 1) / kT;
-  hipLaunchKernelGGL(pair_patch_gather_kernel, dim3(tiles, tiles, b), dim3(256), 0, S(stream), ldr, hdr, images, patches, mean, samples,
+  hipLaunchKernelGGL(pair_patch_gather_kernel, dim3(tiles, tiles, b), dim3(256), 0, shdr::stream_of(stream), ldr, hdr, images, patches, mean, samples,
                      size, out_ldr, out_hdr);
   return shdr::check_launch("pair_patch_gather");
 }

@@ -27,15 +27,16 @@
 // which the vector L1 serves after the first touch, so HBM sees the pixels once per pass.  LDS holds only the 80-position window
 // (64 + 1 back + 6 ahead, rounded) of each wave, 1.25 KB per block, at any width.
 #include "shdr_internal.h"
+#include "batch.h"
 
 namespace {
+
+using shdr::wave_scan;
 
 constexpr int kMaxRun = 127, kMinRun = 4, kMaxLiteral = 128;
 constexpr int kWin = 80;                       // window of a wave: positions base - 1 .. base + 78
 constexpr int kMaxWidth = 1 << 28;             // 4 * W fits an int32 with room
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 inline bool rle_width(int w) { return w >= 8 && w <= 32767; }
 
 struct RleWorkspace {                          // carved out of the caller's workspace, every part 16-byte aligned
@@ -48,13 +49,12 @@ struct RleWorkspace {                          // carved out of the caller's wor
 };
 inline RleWorkspace carve(void* ws, int64_t n, int64_t rows) {
   RleWorkspace w;
-  char* p = static_cast<char*>(ws);
-  int64_t o = 0;
-  w.rowstart = reinterpret_cast<int64_t*>(p + o); o += align16(8 * (n + 1));
-  w.pixoff = reinterpret_cast<int64_t*>(p + o);   o += align16(8 * (n + 1));
-  w.sizes = reinterpret_cast<int32_t*>(p + o);    o += 16 * rows;
-  w.rowoff = reinterpret_cast<int64_t*>(p + o);   o += align16(8 * (rows + 1));
-  w.bytes = o;
+  shdr::Carver cut(ws);
+  w.rowstart = cut.take<int64_t>(n + 1);
+  w.pixoff = cut.take<int64_t>(n + 1);
+  w.sizes = cut.take<int32_t>(4 * rows);
+  w.rowoff = cut.take<int64_t>(rows + 1);
+  w.bytes = cut.bytes();
   return w;
 }
 
@@ -71,23 +71,6 @@ __global__ void rle_setup_kernel(const int32_t* __restrict__ shapes, int n, int6
   pixoff[n] = p;
 }
 
-__device__ __forceinline__ int wave_scan_max(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(v, off, 64);
-    if (lane >= off) v = max(v, t);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_scan_add(int v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  return v;
-}
-
 // One block per row of the batch, wave c codes component c.  WRITE = false: sizes[row][c]; WRITE = true: the bytes at rowoff[row].
 template <bool WRITE>
 __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restrict__ pixels, const int32_t* __restrict__ shapes, int n_img,
@@ -96,11 +79,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restric
                                                        uint8_t* __restrict__ out, int64_t capacity) {
   __shared__ int win[4][kWin];
   const int64_t row = blockIdx.x;
-  int lo = 0, hi = n_img;                                        // the image of this row: the last n with rowstart[n] <= row
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (rowstart[mid] <= row) lo = mid; else hi = mid;
-  }
+  const int lo = (int)shdr::last_le(rowstart, n_img, row);       // the image of this row
   const int W = shapes[2 * lo + 1];
   const uint32_t* line = pixels + pixoff[lo] + (row - rowstart[lo]) * (int64_t)W;
   const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -151,7 +130,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restric
     // scan 1: (head of the stretch of x) * 2 + (that stretch has >= 4 bytes)
     const bool lh0 = D[1] >= 0 && D[1] == D[2] && D[1] == D[3] && D[1] == D[4];
     int key = hd[0] ? x * 2 + (lh0 ? 1 : 0) : -1;
-    key = max(wave_scan_max(key, lane), carry_key);
+    key = max(wave_scan(key, shdr::maximum()), carry_key);
     carry_key = __shfl(key, 63, 64);
     const int s0 = key >> 1;
     int sk = s0;
@@ -173,7 +152,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restric
     const bool prev_short = lane == 0 ? carry_short != 0 : ((shmask >> (lane - 1)) & 1ull) != 0;
     carry_short = (int)(shmask >> 63);
     int g = sh[0] && !prev_short ? x : -1;
-    g = max(wave_scan_max(g, lane), carry_gap);
+    g = max(wave_scan(g, shdr::maximum()), carry_gap);
     carry_gap = __shfl(g, 63, 64);
     const int rel = x - g;
     // a gap that is one run of 2 or 3 bytes
@@ -189,7 +168,7 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restric
     else if (!sh[0]) contrib = run_last ? 2 : 0;
     else if (tok) contrib = gap_last ? 2 : 0;
     else contrib = 1 + (chunk == 0 ? 1 : 0);
-    const int incl = wave_scan_add(contrib, lane);
+    const int incl = wave_scan(contrib);
     const int p = carry_p + incl - contrib;
     carry_p += __shfl(incl, 63, 64);
     if constexpr (WRITE) {
@@ -216,35 +195,15 @@ __global__ __launch_bounds__(256) void rle_rows_kernel(const uint32_t* __restric
 // R is the number of scanlines of the batch, a few thousand.
 __global__ __launch_bounds__(1024) void rle_scan_kernel(const int32_t* __restrict__ sizes, int64_t rows, int64_t* __restrict__ rowoff,
                                                         const int64_t* __restrict__ rowstart, int n_img, int64_t* __restrict__ offsets) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < rows; base += 1024) {
-    const int64_t r = base + threadIdx.x;
-    int64_t v = 0;
-    if (r < rows) {
-      const int4 sz = *reinterpret_cast<const int4*>(sizes + 4 * r);
-      v = (int64_t)sz.x + sz.y + sz.z + sz.w;
-    }
-    int64_t incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int64_t before = carry_s;
-    for (int w = 0; w < wave; ++w) before += part[w];
-    if (r < rows) rowoff[r] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) rowoff[rows] = carry_s;
-  __syncthreads();                                               // the block's own global writes are visible to it after the barrier
+  const int64_t all = shdr::scan_array<1024, 1>(
+      rows,
+      [&](int64_t r) {
+        const int4 sz = *reinterpret_cast<const int4*>(sizes + 4 * r);
+        return (int64_t)sz.x + sz.y + sz.z + sz.w;
+      },
+      [&](int64_t r, int64_t before) { rowoff[r] = before; });
+  if (threadIdx.x == 0) rowoff[rows] = all;
+  __syncthreads();                                              // the block's own global writes are visible to it after the barrier
   for (int n = threadIdx.x; n <= n_img; n += 1024) offsets[n] = rowoff[rowstart[n]];
 }
 
@@ -290,7 +249,7 @@ int encode_batch(const uint8_t* rgbe, const int32_t* shapes, const int32_t* shap
   SHDR_REQUIRE(out_capacity >= bound, SHDR_E_SHAPE, "%s: output buffer too small (%lld < %lld)", what, (long long)out_capacity,
                (long long)bound);
   const RleWorkspace w = carve(workspace, n_images, rows);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const uint32_t* px = reinterpret_cast<const uint32_t*>(rgbe);
   shdr::StageTimer<SHDR_RLE_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(rle_setup_kernel, dim3(1), dim3(64), 0, st, shapes_dev, n_images, w.rowstart, w.pixoff);

@@ -25,6 +25,7 @@
 //   4  expand    dec_expand_kernel, one workgroup per row of the batch, wave c expands component c: the interleaved pixels of an x-tile of
 //                2048 are assembled in LDS and stored as whole dwords; flat rows are a copy.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "hdr_rle_dec.h"
 
 namespace {
@@ -45,8 +46,6 @@ constexpr int kMaxFiles = 65535;               // a grid dimension
 constexpr int kNone = -1;
 constexpr int kSat = 1 << 30;                  // line counts saturate here
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 __host__ __device__ inline int64_t cap_of(int h, int w) { return rle_width(w) ? 2 * (int64_t)h + 64 : 0; }
 __host__ __device__ inline int64_t chunks_of(int64_t size, int w) { return rle_width(w) ? (size + kChunk - 1) / kChunk : 0; }
 
@@ -72,13 +71,11 @@ struct DecWorkspace {                          // carved out of the caller's wor
 };
 inline DecWorkspace carve(void* ws, int64_t n, int64_t rows, int64_t nodes, int64_t chunks) {
   DecWorkspace w;
-  char* p = static_cast<char*>(ws);
-  int64_t o = 0;
-  auto i64 = [&](int64_t count) { int64_t* r = reinterpret_cast<int64_t*>(p + o); o += align16(8 * count); return r; };
-  auto i32 = [&](int64_t count) { int32_t* r = reinterpret_cast<int32_t*>(p + o); o += align16(4 * count); return r; };
-  w.rowstart = i64(n + 1);
-  w.nodeoff = i64(n + 1);
-  w.chunkoff = i64(n + 1);
+  shdr::Carver cut(ws);
+  auto i32 = [&](int64_t count) { return cut.take<int32_t>(count); };
+  w.rowstart = cut.take<int64_t>(n + 1);
+  w.nodeoff = cut.take<int64_t>(n + 1);
+  w.chunkoff = cut.take<int64_t>(n + 1);
   w.ncand = i32(n);
   w.chunkcnt = i32(chunks);
   w.n_pos = i32(nodes); w.n_end = i32(nodes); w.n_fail = i32(nodes); w.n_rel = i32(nodes); w.n_stop = i32(nodes);
@@ -86,28 +83,11 @@ inline DecWorkspace carve(void* ws, int64_t n, int64_t rows, int64_t nodes, int6
   w.n_next[0] = i32(nodes); w.n_next[1] = i32(nodes); w.n_len[0] = i32(nodes); w.n_len[1] = i32(nodes);
   w.n_comp = i32(4 * nodes);
   w.rowdesc = i32(2 * rows);
-  w.bytes = o;
+  w.bytes = cut.bytes();
   return w;
 }
 
-// the file's bytes inside the buffer, whatever the device copy of the table holds
-struct FileSpan { int64_t base, size; };
-__device__ __forceinline__ FileSpan file_span(const int64_t* src_off, int f, int64_t src_bytes) {
-  int64_t a = src_off[f], b = src_off[f + 1];
-  a = a < 0 ? 0 : a > src_bytes ? src_bytes : a;
-  b = b < a ? a : b > src_bytes ? src_bytes : b;
-  if (b - a > 0x7fffffff) b = a + 0x7fffffff;
-  return FileSpan{a, b - a};
-}
-
-__device__ __forceinline__ int find_file(const int64_t* start, int n, int64_t v) {     // the last f with start[f] <= v
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (start[mid] <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+constexpr int64_t kMaxFileBytes = 0x7fffffff;  // the cap of a file's clamped_span: offsets inside a file are int32
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -126,7 +106,7 @@ __global__ void dec_setup_kernel(const int32_t* __restrict__ shapes, const int64
     ncand[i] = 0;
     r += h;
     nd += cap_of(h, w) + 1;
-    ch += chunks_of(file_span(src_off, i, src_bytes).size, w);
+    ch += chunks_of(shdr::clamped_span(src_off, i, src_bytes, kMaxFileBytes).n, w);
     o += 4 * (int64_t)h * w;
   }
   rowstart[n] = r; nodeoff[n] = nd; chunkoff[n] = ch; out_off[n] = o;
@@ -164,9 +144,9 @@ __global__ __launch_bounds__(256) void dec_count_kernel(const uint8_t* __restric
   const int f = blockIdx.y;
   const int64_t chunk = blockIdx.x;
   if (chunk >= chunkoff[f + 1] - chunkoff[f]) return;
-  const FileSpan fs = file_span(src_off, f, src_bytes);
+  const shdr::Span fs = shdr::clamped_span(src_off, f, src_bytes, kMaxFileBytes);
   const int w = shapes[2 * f + 1];
-  const int c = scan_markers(src + fs.base, fs.size, chunk * kChunk + (int64_t)threadIdx.x * kChunkPerThread, w, [](int64_t, int) {});
+  const int c = scan_markers(src + fs.lo, fs.n, chunk * kChunk + (int64_t)threadIdx.x * kChunkPerThread, w, [](int64_t, int) {});
   const int total = block_sum_256(c, part);
   if (threadIdx.x == 0) chunkcnt[chunkoff[f] + chunk] = total;
 }
@@ -180,7 +160,7 @@ __global__ __launch_bounds__(256) void dec_compact_kernel(const uint8_t* __restr
   const int f = blockIdx.y;
   const int64_t chunk = blockIdx.x, nch = chunkoff[f + 1] - chunkoff[f];
   if (chunk >= nch) return;
-  const FileSpan fs = file_span(src_off, f, src_bytes);
+  const shdr::Span fs = shdr::clamped_span(src_off, f, src_bytes, kMaxFileBytes);
   const int h = shapes[2 * f], w = shapes[2 * f + 1];
   const int64_t cap = cap_of(h, w);
   const int32_t* cnt = chunkcnt + chunkoff[f];
@@ -195,22 +175,17 @@ __global__ __launch_bounds__(256) void dec_compact_kernel(const uint8_t* __restr
   const int total = block_sum_256((int)all, part);
   if (chunk == 0 && threadIdx.x == 0) ncand[f] = total;
   if (total > cap) return;                                                // FALLBACK: the list is not needed
-  const uint8_t* data = src + fs.base;
+  const uint8_t* data = src + fs.lo;
   const int64_t p0 = chunk * kChunk + (int64_t)threadIdx.x * kChunkPerThread;
-  const int mine = scan_markers(data, fs.size, p0, w, [](int64_t, int) {});
+  const int mine = scan_markers(data, fs.n, p0, w, [](int64_t, int) {});
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
+  const int incl = shdr::wave_scan(mine);                                 // (not block_scan: wave_base is read once, no barrier behind it)
   if (lane == 63) wave_base[wave] = incl;
   __syncthreads();
   int at = base + incl - mine;
   for (int k = 0; k < wave; ++k) at += wave_base[k];
   int32_t* list = n_pos + nodeoff[f] + 1;                                 // node 0 is the virtual one
-  if (mine) scan_markers(data, fs.size, p0, w, [&](int64_t p, int k) {
+  if (mine) scan_markers(data, fs.n, p0, w, [&](int64_t p, int k) {
     if (at + k < cap) list[at + k] = (int32_t)p;
   });
 }
@@ -258,22 +233,22 @@ __global__ __launch_bounds__(64) void dec_parse_kernel(const uint8_t* __restrict
                                                        int32_t* __restrict__ n_len, int32_t* __restrict__ n_comp) {
   __shared__ uint4 window[kWindow / 16];
   const int64_t node = blockIdx.x;
-  const int f = find_file(nodeoff, n_files, node);
+  const int f = (int)shdr::last_le(nodeoff, n_files, node);
   const int k = (int)(node - nodeoff[f]);
   const int h = shapes[2 * f], w = shapes[2 * f + 1];
   const int64_t cap = cap_of(h, w);
   const int m = ncand[f];
   if (m > cap || k > m) return;                                           // FALLBACK, or a slot no candidate fills
-  const FileSpan fs = file_span(src_off, f, src_bytes);
+  const shdr::Span fs = shdr::clamped_span(src_off, f, src_bytes, kMaxFileBytes);
   const int lane = threadIdx.x;
   const int32_t* list = n_pos + nodeoff[f] + 1;
   int own = 0, fail = 0, rel = 0;
   int64_t e = 0, stop = 0;
   if (k > 0) {
     own = 1;
-    WaveWindow read(src, src_bytes, fs.base, reinterpret_cast<uint8_t*>(window), lane);
+    WaveWindow read(src, src_bytes, fs.lo, reinterpret_cast<uint8_t*>(window), lane);
     Line l;
-    parse_line(read, fs.size, list[k - 1], w, &l);
+    parse_line(read, fs.n, list[k - 1], w, &l);
     if (lane == 0) *reinterpret_cast<int4*>(n_comp + 4 * node) = make_int4((int)l.comp[0], (int)l.comp[1], (int)l.comp[2], (int)l.comp[3]);
     if (l.status != kOk) {
       fail = l.status; stop = l.stop;
@@ -291,11 +266,11 @@ __global__ __launch_bounds__(64) void dec_parse_kernel(const uint8_t* __restrict
         next = idx + 1;
         break;
       }
-      if (fs.size - e < step) {
+      if (fs.n - e < step) {
         fail = kTruncatedFlat; rel = own + flat; stop = e;
         break;
       }
-      int64_t steps = (fs.size - e) / step;                               // whole flat lines left, at least one
+      int64_t steps = (fs.n - e) / step;                               // whole flat lines left, at least one
       if (idx < m) {
         const int64_t want = (list[idx] - e + step - 1) / step;           // as many as reach the next candidate
         if (want < steps) steps = want;
@@ -407,7 +382,7 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const uint8_t* __restri
   __shared__ uint32_t tile[kTile];
   __shared__ uint4 window[4][kWindow / 16];
   const int64_t grow = blockIdx.x;
-  const int f = find_file(rowstart, n_files, grow);
+  const int f = (int)shdr::last_le(rowstart, n_files, grow);
   const int w = shapes[2 * f + 1];
   const int64_t row = grow - rowstart[f];
   const int2 d = reinterpret_cast<const int2*>(rowdesc)[grow];
@@ -415,11 +390,11 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const uint8_t* __restri
   const int64_t at = out_off[f] + row * 4 * (int64_t)w;
   if (at < 0 || at + 4 * (int64_t)w > out_bytes) return;                  // never with the tables the host checked
   uint32_t* dst = reinterpret_cast<uint32_t*>(out + at);
-  const FileSpan fs = file_span(src_off, f, src_bytes);
-  const uint8_t* data = src + fs.base;
+  const shdr::Span fs = shdr::clamped_span(src_off, f, src_bytes, kMaxFileBytes);
+  const uint8_t* data = src + fs.lo;
   if (d.y < 0) {                                                          // flat: a copy, the source at any alignment
     const int64_t p = d.x;
-    if (p + 4 * (int64_t)w > fs.size) return;
+    if (p + 4 * (int64_t)w > fs.n) return;
     for (int x = threadIdx.x; x < w; x += 256) {
       const uint8_t* q = data + p + 4 * (int64_t)x;
       dst[x] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
@@ -427,7 +402,7 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const uint8_t* __restri
     return;
   }
   const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  WaveWindow read(src, src_bytes, fs.base, reinterpret_cast<uint8_t*>(window[c]), lane);
+  WaveWindow read(src, src_bytes, fs.lo, reinterpret_cast<uint8_t*>(window[c]), lane);
   uint8_t* bytes = reinterpret_cast<uint8_t*>(tile);
   int64_t pos = n_comp[4 * (nodeoff[f] + d.y) + c];
   int x = 0;
@@ -437,7 +412,7 @@ __global__ __launch_bounds__(256) void dec_expand_kernel(const uint8_t* __restri
       int len = 0;
       bool run = false;
       int64_t next = pos;
-      if (pos < 0 || pos >= fs.size || packet_step(read(pos), pos, fs.size, x, w, &len, &run, &next) != kOk) {
+      if (pos < 0 || pos >= fs.n || packet_step(read(pos), pos, fs.n, x, w, &len, &run, &next) != kOk) {
         x = w;                                                            // (the parser accepted this line: not reached)
         break;
       }
@@ -530,7 +505,7 @@ extern "C" int shdr_rgbe_rle_decode_batch(const uint8_t* src, int64_t src_bytes,
                    (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && shdr::aligned16(workspace),
                SHDR_E_ALIGN, "%s: the offset tables and `consumed` must be 8-byte aligned, `status`, `line`, the shape table and out 4-byte, the workspace 16-byte",
                what);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_RGBE_DEC_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(dec_setup_kernel, dim3(1), dim3(64), 0, st, shapes_dev, src_off_dev, src_bytes, n_files, w.rowstart, w.nodeoff,
                      w.chunkoff, w.ncand, out_off_dev);

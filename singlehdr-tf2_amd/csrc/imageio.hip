@@ -107,14 +107,12 @@ __global__ __launch_bounds__(256) void rgbe_encode_kernel(const float* __restric
   }
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" int shdr_u8_to_unit_f32(const uint8_t* x, float* y, int64_t npix, int reverse_channels, void* stream) {
   SHDR_REQUIRE(x && y, SHDR_E_NULL, "u8_to_unit: null pointer");
   SHDR_REQUIRE(npix > 0, SHDR_E_SHAPE, "u8_to_unit: npix must be positive");
-  hipLaunchKernelGGL(u8_to_unit_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), x, y, (long)npix, reverse_channels);
+  hipLaunchKernelGGL(u8_to_unit_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), x, y, (long)npix, reverse_channels);
   return shdr::check_launch("u8_to_unit");
 }
 
@@ -122,7 +120,7 @@ extern "C" int shdr_resize_cubic_f32(const float* x, float* y, int N, int H, int
   SHDR_REQUIRE(x && y, SHDR_E_NULL, "resize_cubic: null pointer");
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, SHDR_E_SHAPE, "resize_cubic: non-positive dimension");
   const long total = (long)N * Ho * Wo * C;
-  hipLaunchKernelGGL(resize_cubic_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), x, y, N, H, W, C, Ho, Wo,
+  hipLaunchKernelGGL(resize_cubic_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), x, y, N, H, W, C, Ho, Wo,
                      1.0 / ((double)Ho / H), 1.0 / ((double)Wo / W));
   return shdr::check_launch("resize_cubic");
 }
@@ -132,7 +130,7 @@ extern "C" int shdr_pad_symmetric_f32(const float* x, float* y, int N, int H, in
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "pad_symmetric: non-positive dimension");
   SHDR_REQUIRE(pad >= 0 && pad <= H && pad <= W, SHDR_E_SHAPE, "pad_symmetric: pad %d exceeds the image %dx%d", pad, H, W);
   const long total = (long)N * (H + 2 * pad) * (W + 2 * pad) * C;
-  hipLaunchKernelGGL(pad_symmetric_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), x, y, N, H, W, C, pad);
+  hipLaunchKernelGGL(pad_symmetric_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), x, y, N, H, W, C, pad);
   return shdr::check_launch("pad_symmetric");
 }
 
@@ -140,7 +138,7 @@ extern "C" int shdr_rgbe_encode_f32(const float* x, uint8_t* y, int64_t npix, in
   SHDR_REQUIRE(x && y, SHDR_E_NULL, "rgbe_encode: null pointer");
   SHDR_REQUIRE(npix > 0, SHDR_E_SHAPE, "rgbe_encode: npix must be positive");
   SHDR_REQUIRE((reinterpret_cast<uintptr_t>(y) & 3u) == 0, SHDR_E_ALIGN, "rgbe_encode: y must be 4-byte aligned");
-  hipLaunchKernelGGL(rgbe_encode_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), x, y, (long)npix, reverse_channels);
+  hipLaunchKernelGGL(rgbe_encode_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), x, y, (long)npix, reverse_channels);
   return shdr::check_launch("rgbe_encode");
 }
 
@@ -175,7 +173,7 @@ extern "C" int shdr_flip_rot90_f32(const float* x, float* y, const int32_t* flip
                                    float divisor, void* stream) {
   SHDR_REQUIRE(x && y && flip && rot, SHDR_E_NULL, "flip_rot90: null pointer");
   SHDR_REQUIRE(N > 0 && side > 0 && C > 0 && divisor != 0.0f, SHDR_E_SHAPE, "flip_rot90: bad shape (square images only)");
-  hipLaunchKernelGGL(flip_rot90_kernel, dim3(shdr::stream_grid((long)N * side * side * C)), dim3(256), 0, S(stream), x, y, flip,
+  hipLaunchKernelGGL(flip_rot90_kernel, dim3(shdr::stream_grid((long)N * side * side * C)), dim3(256), 0, shdr::stream_of(stream), x, y, flip,
                      rot, N, side, C, divisor);
   return shdr::check_launch("flip_rot90");
 }

@@ -18,6 +18,7 @@
 //     s1 = 1 + A and s2 = N + N A - B (mod 65521) once N is known.  Matches never read global memory.
 // LDS: ring 32 KiB + window 2 KiB + tables 4.5 KiB: four workgroups per CU.  Deterministic, no atomics, no host wait, no allocation.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "inflate.h"
 
 namespace {
@@ -27,8 +28,6 @@ using namespace shdr_inflate;
 constexpr int kLanes = 64;
 constexpr int kRing = kWindow;                                   // bytes; a power of two
 constexpr int kInWords = 512;                                    // dwords of the staged stream window
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ int64_t rfl64(int64_t v) {
@@ -162,16 +161,6 @@ struct DeviceIo {
   }
 };
 
-// [off[c], off[c + 1]) clamped into [0, total] and to kMaxChunk bytes
-__device__ __forceinline__ void chunk_range(const int64_t* __restrict__ off, int64_t c, int64_t total, int64_t& lo, int64_t& n) {
-  int64_t a = off[c], b = off[c + 1];
-  a = a < 0 ? 0 : a > total ? total : a;
-  b = b < a ? a : b > total ? total : b;
-  if (b - a > kMaxChunk) b = a + kMaxChunk;
-  lo = rfl64(a);
-  n = rfl64(b - a);
-}
-
 __global__ __launch_bounds__(kLanes) void inflate_kernel(const uint8_t* __restrict__ src, int64_t src_bytes, const int64_t* __restrict__ src_off,
                                                          uint8_t* __restrict__ dst, int64_t dst_bytes, const int64_t* __restrict__ dst_off,
                                                          const uint8_t* __restrict__ mode, int32_t* __restrict__ status,
@@ -181,9 +170,8 @@ __global__ __launch_bounds__(kLanes) void inflate_kernel(const uint8_t* __restri
   __shared__ Tables tables;
   const int64_t c = blockIdx.x;
   const int ln = threadIdx.x;
-  int64_t slo, n, dlo, cap;
-  chunk_range(src_off, c, src_bytes, slo, n);
-  chunk_range(dst_off, c, dst_bytes, dlo, cap);
+  const shdr::Span from = shdr::clamped_span(src_off, c, src_bytes, kMaxChunk), slot = shdr::clamped_span(dst_off, c, dst_bytes, kMaxChunk);
+  const int64_t slo = rfl64(from.lo), n = rfl64(from.n), dlo = rfl64(slot.lo), cap = rfl64(slot.n);
   const uint32_t m = mode ? rfl(mode[c]) : 1u;
   int st;
   int64_t wrote = 0;
@@ -251,7 +239,7 @@ extern "C" int shdr_inflate_batch(const uint8_t* src, int64_t src_bytes, const i
   SHDR_REQUIRE((reinterpret_cast<uintptr_t>(src_off_dev) & 7u) == 0 && (reinterpret_cast<uintptr_t>(dst_off_dev) & 7u) == 0 &&
                    (reinterpret_cast<uintptr_t>(written) & 7u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0,
                SHDR_E_ALIGN, "%s: the offset tables and `written` must be 8-byte aligned, `status` 4-byte aligned", what);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_INFLATE_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)n_chunks), dim3(kLanes), 0, st, src, src_bytes, src_off_dev, dst, dst_bytes, dst_off_dev,
                      mode, status, written);

@@ -27,6 +27,7 @@
 // No atomics anywhere: the same bytes give the same bits.  Every stream read is clamped to its segment, every coefficient write
 // to its image's blocks; an image whose stream is damaged gets an error code and garbage pixels, its neighbours are untouched.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "jpeg_int.h"
 
 namespace {
@@ -287,21 +288,6 @@ __global__ __launch_bounds__(WG) void jpeg_sync_kernel(const uint32_t* __restric
 
 // ---------------------------------------------------------------- inclusive scan: out[i] + partial[i / SCAN_CHUNK]
 // (the sums are unsigned: the DC sums of a batch wrap around by design, only differences of two of them are used)
-__device__ __forceinline__ uint32_t block_scan_incl(uint32_t v, uint32_t* wsum) {        // 256 threads; returns the inclusive sum up to this thread
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)v, off, 64);
-    if (lane >= off) v += u;
-  }
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  uint32_t base = 0;
-  for (int k = 0; k < wave; ++k) base += wsum[k];
-  __syncthreads();
-  return v + base;
-}
-
 __global__ __launch_bounds__(WG) void scan_local_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
                                                         int32_t* __restrict__ partial, long n) {
   __shared__ uint32_t wsum[4];
@@ -310,29 +296,17 @@ __global__ __launch_bounds__(WG) void scan_local_kernel(const int32_t* __restric
 #pragma unroll
   for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? (uint32_t)in[i0 + k] : 0u;
   v[1] += v[0]; v[2] += v[1]; v[3] += v[2];
-  const uint32_t incl = block_scan_incl(v[3], wsum);
-  const uint32_t base = incl - v[3];
+  const uint32_t base = shdr::block_scan<WG>(v[3], wsum);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (i0 + k < n) out[i0 + k] = (int32_t)(v[k] + base);
-  if (threadIdx.x == WG - 1) partial[blockIdx.x] = (int32_t)incl;
+  if (threadIdx.x == WG - 1) partial[blockIdx.x] = (int32_t)(base + v[3]);
 }
 
 // one workgroup: partial[] -> its exclusive prefix sum, in place
 __global__ __launch_bounds__(WG) void scan_partials_kernel(int32_t* __restrict__ partial, long n) {
-  __shared__ uint32_t wsum[4];
-  __shared__ uint32_t total;
-  uint32_t run = 0;
-  for (long i0 = 0; i0 < n; i0 += WG) {
-    const long i = i0 + threadIdx.x;
-    const uint32_t v = i < n ? (uint32_t)partial[i] : 0u;
-    const uint32_t incl = block_scan_incl(v, wsum);
-    if (i < n) partial[i] = (int32_t)(run + incl - v);
-    if (threadIdx.x == WG - 1) total = incl;
-    __syncthreads();
-    run += total;
-    __syncthreads();
-  }
+  shdr::scan_array<WG, 1>(
+      n, [&](int64_t i) { return (uint32_t)partial[i]; }, [&](int64_t i, uint32_t before) { partial[i] = (int32_t)before; });
 }
 
 __device__ __forceinline__ uint32_t scanned(const int32_t* __restrict__ out, const int32_t* __restrict__ partial, long i) {
@@ -528,7 +502,6 @@ __global__ __launch_bounds__(WG) void jpeg_finish_kernel(const shdr_jpeg_image* 
   }
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 
 struct Workspace {             // byte offsets into the caller's workspace
@@ -714,8 +687,8 @@ extern "C" int shdr_jpeg_entropy_decode(const shdr_jpeg_batch* batch, int16_t* c
   if (int rc = validate(batch)) return rc;
   SHDR_REQUIRE(coef && errors && workspace, SHDR_E_NULL, "jpeg_entropy_decode: null pointer");
   SHDR_REQUIRE(shdr::aligned16(workspace), SHDR_E_ALIGN, "jpeg_entropy_decode: the workspace must be 16-byte aligned");
-  Stages stages(batch->stage_ms, S(stream));
-  return entropy_dispatch(batch, coef, errors, workspace, S(stream), stages);
+  Stages stages(batch->stage_ms, shdr::stream_of(stream));
+  return entropy_dispatch(batch, coef, errors, workspace, shdr::stream_of(stream), stages);
 }
 
 extern "C" int shdr_jpeg_decode_u8(const shdr_jpeg_batch* batch, int16_t* coef, uint8_t* out, int32_t* errors, void* workspace,
@@ -723,7 +696,7 @@ extern "C" int shdr_jpeg_decode_u8(const shdr_jpeg_batch* batch, int16_t* coef, 
   if (int rc = validate(batch)) return rc;
   SHDR_REQUIRE(coef && out && errors && workspace, SHDR_E_NULL, "jpeg_decode_u8: null pointer");
   SHDR_REQUIRE(shdr::aligned16(workspace), SHDR_E_ALIGN, "jpeg_decode_u8: the workspace must be 16-byte aligned");
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   Stages stages(batch->stage_ms, st);
   if (int rc = entropy_dispatch(batch, coef, errors, workspace, st, stages)) return rc;
   const Workspace w = layout(batch->n_sub, batch->n_blocks, batch->plane_bytes);
@@ -748,8 +721,8 @@ extern "C" int shdr_jpeg_sync_rounds(const void* workspace, int64_t n_sub, int64
   SHDR_REQUIRE(workspace && rounds, SHDR_E_NULL, "jpeg_sync_rounds: null pointer");
   SHDR_REQUIRE(n_sub > 0 && n_sub % WG == 0 && n_blocks > 0 && plane_bytes >= 0, SHDR_E_SHAPE, "jpeg_sync_rounds: bad sizes");
   const Workspace w = layout(n_sub, n_blocks, plane_bytes);
-  hipError_t e = hipMemcpyAsync(rounds, static_cast<const char*>(workspace) + w.settle, (size_t)n_sub * 4, hipMemcpyDeviceToHost, S(stream));
-  if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
+  hipError_t e = hipMemcpyAsync(rounds, static_cast<const char*>(workspace) + w.settle, (size_t)n_sub * 4, hipMemcpyDeviceToHost, shdr::stream_of(stream));
+  if (e == hipSuccess) e = hipStreamSynchronize(shdr::stream_of(stream));
   if (e != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "jpeg_sync_rounds: %s", hipGetErrorString(e));
   return SHDR_OK;
 }

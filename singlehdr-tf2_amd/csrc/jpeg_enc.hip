@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include "shdr_internal.h"
+#include "batch.h"
 #include "jpeg_enc.h"
 
 namespace {
@@ -42,9 +43,6 @@ constexpr int kStageWords = 672;                                  // LDS window 
                                                                   // a marker per word (segments start on words), and the alignment
 
 __device__ const CodeTables d_codes = kCodes;
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct EncWorkspace {                          // carved out of the caller's workspace, every part 16-byte aligned
   int64_t *mcu0, *blk0, *seg0, *pix0;          // [N + 1] first MCU, block, segment and pixel of image n among all of the batch
@@ -63,38 +61,26 @@ struct EncWorkspace {                          // carved out of the caller's wor
 };
 inline EncWorkspace carve(void* ws, int64_t n, int64_t blocks, int64_t segs) {
   EncWorkspace w;
-  char* p = static_cast<char*>(ws);
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) { char* q = p + o; o += align16(bytes); return q; };
-  w.mcu0 = reinterpret_cast<int64_t*>(take(8 * (n + 1)));
-  w.blk0 = reinterpret_cast<int64_t*>(take(8 * (n + 1)));
-  w.seg0 = reinterpret_cast<int64_t*>(take(8 * (n + 1)));
-  w.pix0 = reinterpret_cast<int64_t*>(take(8 * (n + 1)));
-  w.coef = reinterpret_cast<int16_t*>(take(128 * blocks));
-  w.bits = reinterpret_cast<int32_t*>(take(4 * blocks));
-  w.bitpos = reinterpret_cast<int64_t*>(take(8 * (blocks + 1)));
-  w.segword = reinterpret_cast<int64_t*>(take(8 * (segs + 1)));
-  w.segbytes = reinterpret_cast<int32_t*>(take(4 * segs));
-  w.segff = reinterpret_cast<int64_t*>(take(8 * segs));
-  w.segsize = reinterpret_cast<int64_t*>(take(8 * segs));
-  w.segout = reinterpret_cast<int64_t*>(take(8 * (segs + 1)));
+  shdr::Carver cut(ws);
+  w.mcu0 = cut.take<int64_t>(n + 1);
+  w.blk0 = cut.take<int64_t>(n + 1);
+  w.seg0 = cut.take<int64_t>(n + 1);
+  w.pix0 = cut.take<int64_t>(n + 1);
+  w.coef = cut.take<int16_t>(64 * blocks);
+  w.bits = cut.take<int32_t>(blocks);
+  w.bitpos = cut.take<int64_t>(blocks + 1);
+  w.segword = cut.take<int64_t>(segs + 1);
+  w.segbytes = cut.take<int32_t>(segs);
+  w.segff = cut.take<int64_t>(segs);
+  w.segsize = cut.take<int64_t>(segs);
+  w.segout = cut.take<int64_t>(segs + 1);
   w.arena_words = blocks * kBlockWords + segs + 2;
   w.ff_tiles = (w.arena_words * 4 + kFfTile - 1) / kFfTile;
-  w.arena = reinterpret_cast<uint32_t*>(take(4 * w.ff_tiles * (kFfTile / 4)));          // whole tiles: the count reads them whole
-  w.ffcnt = reinterpret_cast<int32_t*>(take(4 * w.ff_tiles));
-  w.ffscan = reinterpret_cast<int64_t*>(take(8 * (w.ff_tiles + 1)));
-  w.bytes = o;
+  w.arena = cut.take<uint32_t>(w.ff_tiles * (kFfTile / 4));      // whole tiles: the count reads them whole
+  w.ffcnt = cut.take<int32_t>(w.ff_tiles);
+  w.ffscan = cut.take<int64_t>(w.ff_tiles + 1);
+  w.bytes = cut.bytes();
   return w;
-}
-
-// the last i in [0, n) with a[i] <= v (a[0] <= v is given)
-__device__ __forceinline__ int find_last_le(const int64_t* __restrict__ a, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] <= v) lo = mid; else hi = mid;
-  }
-  return (int)lo;
 }
 
 __global__ void enc_setup_kernel(const Image* __restrict__ images, int n, int64_t* __restrict__ mcu0, int64_t* __restrict__ blk0,
@@ -124,7 +110,7 @@ __global__ __launch_bounds__(64) void enc_transform_kernel(const T* __restrict__
   __shared__ __align__(16) int16_t zq[6][64];   // quantised, zig-zag order
   const int lane = threadIdx.x;
   const int64_t m = blockIdx.x;
-  const int i = find_last_le(mcu0, n, m);
+  const int i = (int)shdr::last_le(mcu0, n, m);
   const Image im = images[i];
   const Geometry g = geometry(im);
   const int ml = (int)(m - mcu0[i]);
@@ -197,7 +183,7 @@ struct BlockInfo {
 __device__ __forceinline__ BlockInfo block_info(int64_t b, const Image* __restrict__ images, int n, const int64_t* __restrict__ blk0,
                                                 const int64_t* __restrict__ seg0, const int16_t* __restrict__ coef) {
   BlockInfo r;
-  r.image = find_last_le(blk0, n, b);
+  r.image = (int)shdr::last_le(blk0, n, b);
   const Image im = images[r.image];
   const Geometry g = geometry(im);
   r.local = b - blk0[r.image];
@@ -228,38 +214,9 @@ __global__ __launch_bounds__(256) void enc_bits_kernel(const int16_t* __restrict
 // out[i] = sum of in[0 .. i), out[n] = the total.  One block.
 template <typename T>
 __global__ __launch_bounds__(1024) void enc_scan_kernel(const T* __restrict__ in, int64_t n, int64_t* __restrict__ out) {
-  __shared__ int64_t part[16];
-  __shared__ int64_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < n; base += 4096) {
-    const int64_t i0 = base + 4 * (int64_t)threadIdx.x;
-    int64_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i0 + k < n ? (int64_t)in[i0 + k] : 0;
-    const int64_t mine = v[0] + v[1] + v[2] + v[3];
-    int64_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t t = __shfl_up(incl, off, 64);
-      if (lane >= off) incl += t;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int64_t before = carry_s;
-    for (int w = 0; w < wave; ++w) before += part[w];
-    int64_t run = before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (i0 + k < n) out[i0 + k] = run;
-      run += v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[n] = carry_s;
+  const int64_t all = shdr::scan_array<1024, 4>(
+      n, [&](int64_t i) { return (int64_t)in[i]; }, [&](int64_t i, int64_t before) { out[i] = before; });
+  if (threadIdx.x == 0) out[n] = all;
 }
 
 // one lane per segment of the batch (+ one for the end of the arena)
@@ -273,7 +230,7 @@ __global__ __launch_bounds__(256) void enc_segments_kernel(const Image* __restri
     segword[s] = (bitpos[blk0[n]] >> 5) + nseg;
     return;
   }
-  const int i = find_last_le(seg0, n, s);
+  const int i = (int)shdr::last_le(seg0, n, s);
   const Image im = images[i];
   const Geometry g = geometry(im);
   const int64_t fb = blk0[i] + segment_first_block(g, im.restart, s - seg0[i]);
@@ -377,7 +334,7 @@ __global__ __launch_bounds__(256) void enc_sizes_kernel(const Image* __restrict_
                                                         int64_t* __restrict__ segsize) {
   const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (s >= seg0[n]) return;
-  const int i = find_last_le(seg0, n, s);
+  const int i = (int)shdr::last_le(seg0, n, s);
   const int64_t p0 = segword[s] * 4;
   const int64_t f0 = ff_before(p0, arena, ffscan), f1 = ff_before(p0 + segbytes[s], arena, ffscan);
   segff[s] = f0;
@@ -406,12 +363,7 @@ __global__ __launch_bounds__(256) void enc_final_kernel(const Image* __restrict_
   const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const uint32_t v = w < words ? arena[w] : 0u;
   const int mine = ff_bytes(v);
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += t;
-  }
+  const int incl = shdr::wave_scan(mine);                          // (not block_scan: the barrier below also covers the cleared window)
   if (lane == 63) part[wave] = incl;
   if (threadIdx.x == 0) first_s = ~0ull;
   for (int k = threadIdx.x; k < kStageWords; k += 256) stage[k] = owned[k] = 0u;
@@ -423,8 +375,8 @@ __global__ __launch_bounds__(256) void enc_final_kernel(const Image* __restrict_
   int64_t s = 0, j0 = 0, nb = 0, dst = 0;
   int i = 0;
   if (active) {
-    s = find_last_le(segword, nseg, w);
-    i = find_last_le(seg0, n, s);
+    s = shdr::last_le(segword, nseg, w);
+    i = (int)shdr::last_le(seg0, n, s);
     j0 = (w - segword[s]) * 4;
     nb = segbytes[s];
     active = status[i] == kOk && j0 < nb;                          // (not an image that was refused, not a gap word)
@@ -590,7 +542,7 @@ extern "C" int shdr_jpeg_encode_batch(const void* pixels, int pixel_type, const 
                  "%s: header %d is not what shdr_jpeg_encode_header_host composes for the image", what, i);
   }
   const EncWorkspace w = carve(workspace, n_images, blocks, segs);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_JPEG_ENC_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(enc_setup_kernel, dim3(1), dim3(64), 0, st, im_dev, n_images, w.mcu0, w.blk0, w.seg0, w.pix0, status);
   if (pixel_type == SHDR_JPEG_ENC_U8)
@@ -617,7 +569,7 @@ extern "C" int shdr_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_
                (long long)blocks);
   SHDR_REQUIRE(out_capacity >= bound, SHDR_E_SHAPE, "%s: output buffer too small (%lld < %lld)", what, (long long)out_capacity, (long long)bound);
   const EncWorkspace w = carve(workspace, n_images, blocks, segs);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_JPEG_ENC_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(enc_setup_kernel, dim3(1), dim3(64), 0, st, im_dev, n_images, w.mcu0, w.blk0, w.seg0, w.pix0, status);
   timer.mark();

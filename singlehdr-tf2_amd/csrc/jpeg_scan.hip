@@ -18,6 +18,7 @@
 // whatever the bytes are: a file with more markers than its header implies is counted and writes nothing outside its slots.
 // atomicMin on the ends and a store of 1 to the fill flag are the only cross-tile writes: the same input gives the same bits.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "jpeg_scan.h"
 
 namespace {
@@ -29,8 +30,6 @@ static_assert(kTile == WG * 16 && kScanChunk == WG, "a lane owns 16 bytes of a t
 static_assert(sizeof(Image) == sizeof(shdr_jpeg_scan_image) && sizeof(Report) == sizeof(shdr_jpeg_scan_report), "mirrors of shdr.h");
 constexpr int64_t kNoEnd = INT64_MAX;
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 struct Workspace {                                               // every part starts on a multiple of 16
   int64_t* end;                                                  // [n_images] kNoEnd or the end
@@ -44,17 +43,16 @@ struct Workspace {                                               // every part s
 };
 Workspace carve(void* base, int n_images, int64_t n_tiles) {
   const int64_t m = n_tiles + 1, chunks = (m + kScanChunk - 1) / kScanChunk;
-  char* p = static_cast<char*>(base);
-  int64_t o = 0;
+  shdr::Carver cut(base);
   Workspace w;
-  w.end = reinterpret_cast<int64_t*>(p + o);        o += up16(8 * (int64_t)n_images);
-  w.fill = reinterpret_cast<int32_t*>(p + o);       o += up16(4 * (int64_t)n_images);
-  w.tile_count = reinterpret_cast<uint32_t*>(p + o); o += up16(4 * n_tiles);
-  w.pre_kept = reinterpret_cast<int64_t*>(p + o);   o += up16(8 * m);
-  w.pre_rst = reinterpret_cast<int64_t*>(p + o);    o += up16(8 * m);
-  w.part_kept = reinterpret_cast<int64_t*>(p + o);  o += up16(8 * chunks);
-  w.part_rst = reinterpret_cast<int64_t*>(p + o);   o += up16(8 * chunks);
-  w.bytes = o;
+  w.end = cut.take<int64_t>(n_images);
+  w.fill = cut.take<int32_t>(n_images);
+  w.tile_count = cut.take<uint32_t>(n_tiles);
+  w.pre_kept = cut.take<int64_t>(m);
+  w.pre_rst = cut.take<int64_t>(m);
+  w.part_kept = cut.take<int64_t>(chunks);
+  w.part_rst = cut.take<int64_t>(chunks);
+  w.bytes = cut.bytes();
   return w;
 }
 
@@ -111,22 +109,6 @@ __device__ __forceinline__ Lane load_lane(const uint8_t* __restrict__ src, const
 __device__ __forceinline__ uint32_t before(const Lane& L, int64_t end) {
   const int64_t k = end - L.p0;
   return k <= 0 ? 0u : k >= 16 ? 0xFFFFu : (1u << k) - 1u;
-}
-
-// 256 threads: the inclusive sum up to this thread (jpeg.hip block_scan_incl, on 64-bit values)
-__device__ __forceinline__ uint64_t block_scan_incl(uint64_t v, uint64_t* wsum) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, off, 64);
-    if (lane >= off) v += u;
-  }
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  uint64_t base = 0;
-  for (int k = 0; k < wave; ++k) base += wsum[k];
-  __syncthreads();
-  return v + base;
 }
 
 __global__ __launch_bounds__(WG) void init_kernel(int64_t* __restrict__ end, int32_t* __restrict__ fill, int n_images) {
@@ -198,38 +180,32 @@ __global__ __launch_bounds__(WG) void prefix_local_kernel(const uint32_t* __rest
   const int64_t t = (int64_t)blockIdx.x * kScanChunk + threadIdx.x;
   const uint32_t c = t < n_tiles ? tile_count[t] : 0u;
   const uint64_t k = c & 0xFFFFu, r = c >> 16;
-  const uint64_t ik = block_scan_incl(k, wsum), ir = block_scan_incl(r, wsum);
+  const uint64_t ek = shdr::block_scan<WG>(k, wsum), er = shdr::block_scan<WG>(r, wsum);
   if (t <= n_tiles) {
-    pre_kept[t] = (int64_t)(ik - k);
-    pre_rst[t] = (int64_t)(ir - r);
+    pre_kept[t] = (int64_t)ek;
+    pre_rst[t] = (int64_t)er;
   }
   if (threadIdx.x == WG - 1) {
-    part_kept[blockIdx.x] = (int64_t)ik;
-    part_rst[blockIdx.x] = (int64_t)ir;
+    part_kept[blockIdx.x] = (int64_t)(ek + k);
+    part_rst[blockIdx.x] = (int64_t)(er + r);
   }
 }
 
 // one workgroup: the chunk totals -> their exclusive prefix sums, in place
 __global__ __launch_bounds__(WG) void prefix_partials_kernel(int64_t* __restrict__ part_kept, int64_t* __restrict__ part_rst, int64_t chunks) {
   __shared__ uint64_t wsum[WG / 64];
-  __shared__ uint64_t total[2];
   uint64_t run_k = 0, run_r = 0;
-  for (int64_t i0 = 0; i0 < chunks; i0 += WG) {
+  for (int64_t i0 = 0; i0 < chunks; i0 += WG) {                  // (not scan_array: both arrays in one walk, one LDS array)
     const int64_t i = i0 + threadIdx.x;
     const uint64_t k = i < chunks ? (uint64_t)part_kept[i] : 0u, r = i < chunks ? (uint64_t)part_rst[i] : 0u;
-    const uint64_t ik = block_scan_incl(k, wsum), ir = block_scan_incl(r, wsum);
+    uint64_t all_k, all_r;
+    const uint64_t ek = shdr::block_scan<WG>(k, wsum, all_k), er = shdr::block_scan<WG>(r, wsum, all_r);
     if (i < chunks) {
-      part_kept[i] = (int64_t)(run_k + ik - k);
-      part_rst[i] = (int64_t)(run_r + ir - r);
+      part_kept[i] = (int64_t)(run_k + ek);
+      part_rst[i] = (int64_t)(run_r + er);
     }
-    if (threadIdx.x == WG - 1) {
-      total[0] = ik;
-      total[1] = ir;
-    }
-    __syncthreads();
-    run_k += total[0];
-    run_r += total[1];
-    __syncthreads();
+    run_k += all_k;
+    run_r += all_r;
   }
 }
 
@@ -245,7 +221,7 @@ __device__ __forceinline__ Before lane_prefix(const Lane& L, uint32_t in, const 
                                               const int64_t* __restrict__ pre_rst, const int64_t* __restrict__ part_kept,
                                               const int64_t* __restrict__ part_rst, uint64_t* wsum) {
   const uint64_t c = (uint64_t)__builtin_popcount(in & ~L.dropped) | (uint64_t)__builtin_popcount(in & L.restart) << 32;
-  const uint64_t excl = block_scan_incl(c, wsum) - c;
+  const uint64_t excl = shdr::block_scan<WG>(c, wsum);
   Before b;
   b.kept = summed(pre_kept, part_kept, tile) - summed(pre_kept, part_kept, im.first_tile) + (int64_t)(excl & 0xFFFFFFFFu);
   b.rst = summed(pre_rst, part_rst, tile) - summed(pre_rst, part_rst, im.first_tile) + (int64_t)(excl >> 32);
@@ -359,7 +335,7 @@ extern "C" int shdr_jpeg_scan(const uint8_t* src, int64_t src_bytes, const shdr_
   SHDR_REQUIRE(shdr::aligned16(src) && shdr::aligned16(workspace) && (reinterpret_cast<uintptr_t>(images_dev) & 7u) == 0 &&
                    (reinterpret_cast<uintptr_t>(report) & 7u) == 0 && (reinterpret_cast<uintptr_t>(bounds) & 7u) == 0,
                SHDR_E_ALIGN, "%s: the source and the workspace must be 16-byte aligned, descriptors, report and boundaries 8-byte aligned", what);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const Workspace w = carve(workspace, n_images, n_tiles);
   const Image* im = reinterpret_cast<const Image*>(images_dev);
   const int64_t chunks = (n_tiles + 1 + kScanChunk - 1) / kScanChunk;
@@ -400,7 +376,7 @@ extern "C" int shdr_jpeg_compact(const uint8_t* src, int64_t src_bytes, const sh
   SHDR_REQUIRE(shdr::aligned16(src) && shdr::aligned16(workspace) && (reinterpret_cast<uintptr_t>(images_dev) & 7u) == 0 &&
                    (reinterpret_cast<uintptr_t>(bounds) & 7u) == 0 && (reinterpret_cast<uintptr_t>(seg_dword) & 3u) == 0,
                SHDR_E_ALIGN, "%s: the source and the workspace must be 16-byte aligned, descriptors and boundaries 8-byte, seg_dword 4-byte", what);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const Workspace w = carve(const_cast<void*>(workspace), n_images, n_tiles);
   {
     shdr::StageTimer<1> timer(stage_ms, st);                     // the whole call is the one stage

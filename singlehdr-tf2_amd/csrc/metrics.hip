@@ -313,8 +313,6 @@ __global__ __launch_bounds__(256) void tonemap_u8_kernel(const float* __restrict
   }
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 inline int moments_grid(int H, int W) {
   const int64_t g = ((int64_t)H * W * 3 + 256 * 16 - 1) / (256 * 16);           // ~16 values per thread, at most MGRID_MAX blocks
   return (int)(g < 1 ? 1 : (g > MGRID_MAX ? MGRID_MAX : g));
@@ -344,8 +342,8 @@ extern "C" int shdr_pair_moments_f32(const float* pred, const float* gt, int N, 
   const int grid = moments_grid(H, W);
   const int vec = (n_per % 4 == 0) && shdr::aligned16(pred) && shdr::aligned16(gt);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(pair_moments_kernel, dim3(grid, N), dim3(256), 0, S(stream), pred, gt, n_per, vec, part);
-  hipLaunchKernelGGL(pair_moments_final_kernel, dim3(N), dim3(64), 0, S(stream), part, grid, n_per, normalise, scale_pred, scale_gt,
+  hipLaunchKernelGGL(pair_moments_kernel, dim3(grid, N), dim3(256), 0, shdr::stream_of(stream), pred, gt, n_per, vec, part);
+  hipLaunchKernelGGL(pair_moments_final_kernel, dim3(N), dim3(64), 0, shdr::stream_of(stream), part, grid, n_per, normalise, scale_pred, scale_gt,
                      peak);
   return shdr::check_launch("pair_moments");
 }
@@ -366,9 +364,9 @@ extern "C" int shdr_hdr_metrics_f32(const float* pred, const float* gt, int N, i
   for (int k = 0; k < TAPS; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
   for (int k = 0; k < TAPS; ++k) gw.w[k] = (float)(g[k] / sum);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(hdr_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), pred, gt, H, W, tiles_x, tiles_y, mu,
+  hipLaunchKernelGGL(hdr_metrics_kernel, dim3((unsigned)blocks), dim3(256), 0, shdr::stream_of(stream), pred, gt, H, W, tiles_x, tiles_y, mu,
                      (float)(1.0 / log1p((double)mu)), scale_pred, scale_gt, peak, gw, part);
-  hipLaunchKernelGGL(hdr_metrics_final_kernel, dim3(N), dim3(256), 0, S(stream), part, tiles_y * tiles_x, H, W, peak, mse_l, mse_mu,
+  hipLaunchKernelGGL(hdr_metrics_final_kernel, dim3(N), dim3(256), 0, shdr::stream_of(stream), part, tiles_y * tiles_x, H, W, peak, mse_l, mse_mu,
                      l1_logc, ssim_mu);
   return shdr::check_launch("hdr_metrics");
 }
@@ -379,7 +377,7 @@ extern "C" int shdr_tonemap_u8_f32(const float* x, const double* scale, const do
   SHDR_REQUIRE(shape_ok(N, H, W), SHDR_E_SHAPE, "tonemap_u8: need N > 0, H >= 11, W >= 11 (got %d, %d, %d)", N, H, W);
   SHDR_REQUIRE(mu > 0.0f, SHDR_E_SHAPE, "tonemap_u8: mu must be positive");
   const int64_t npix_per = (int64_t)H * W, npix = npix_per * N;
-  hipLaunchKernelGGL(tonemap_u8_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, S(stream), x, scale, peak, y, npix_per, npix, mu,
+  hipLaunchKernelGGL(tonemap_u8_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), x, scale, peak, y, npix_per, npix, mu,
                      (float)(1.0 / log1p((double)mu)), reverse_channels);
   return shdr::check_launch("tonemap_u8");
 }

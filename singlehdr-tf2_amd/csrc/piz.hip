@@ -21,6 +21,7 @@
 // applies the LUT and writes the little-endian scanline layout into the chunk's slot.  A chunk with a status leaves its slot untouched.
 // Deterministic, no atomics, no host wait, no allocation.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "piz.h"
 
 namespace {
@@ -30,8 +31,6 @@ using namespace shdr_piz;
 constexpr int kThreads = 256;
 constexpr int kDefaultSubBits = 256;                            // measured: 256 / 1024 / 4096 / 16384 take 6.6 / 7.2 / 8.5 / 9.4 ms on 544 4K chunks
 constexpr int kSymBlock = (kSymbols + kThreads - 1) / kThreads;  // symbols per lane of the counting sort: 257
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // per-chunk workspace: what the two kernels hand over, then the tables
 struct Meta {
@@ -49,15 +48,6 @@ constexpr int kSubArrays = 7;                                    // uint32 each:
 struct Geom {                                 // int32 [4] per chunk
   int32_t width, rows, chan_first, n_chan;
 };
-
-__device__ __forceinline__ void clamp_range(const int64_t* __restrict__ off, int64_t c, int64_t total, int64_t& lo, int64_t& n) {
-  int64_t a = off[c], b = off[c + 1];
-  a = a < 0 ? 0 : a > total ? total : a;
-  b = b < a ? a : b > total ? total : b;
-  if (b - a > kMaxChunk) b = a + kMaxChunk;
-  lo = a;
-  n = b - a;
-}
 
 // the first subsequence record of chunk c: chunk c has room for (8 bytes / sub_bits) + 1 of them
 __device__ __host__ inline int64_t sub_base(int64_t src_lo, int64_t c, int sub_bits) { return 8 * src_lo / sub_bits + c; }
@@ -81,9 +71,8 @@ __global__ __launch_bounds__(kThreads) void piz_decode_kernel(const uint8_t* __r
 
   const int64_t c = blockIdx.x;
   const int t = threadIdx.x;
-  int64_t slo, n, dlo, cap;
-  clamp_range(src_off, c, src_bytes, slo, n);
-  clamp_range(dst_off, c, dst_bytes, dlo, cap);
+  const shdr::Span from = shdr::clamped_span(src_off, c, src_bytes, kMaxChunk), slot = shdr::clamped_span(dst_off, c, dst_bytes, kMaxChunk);
+  const int64_t slo = from.lo, n = from.n, dlo = slot.lo, cap = slot.n;
   uint8_t* cws = ws + c * kChunkWs;
   Meta* meta = reinterpret_cast<Meta*>(cws + kMetaAt);
   uint16_t* lut = reinterpret_cast<uint16_t*>(cws + kLutAt);
@@ -376,8 +365,8 @@ __global__ __launch_bounds__(kThreads) void piz_wavelet_kernel(const uint8_t* __
   }
   if (ch >= g.n_chan) return;
   const int words = cw[ch], j = plane;
-  int64_t dlo, cap;
-  clamp_range(dst_off, c, dst_bytes, dlo, cap);
+  const shdr::Span slot = shdr::clamped_span(dst_off, c, dst_bytes, kMaxChunk);
+  const int64_t dlo = slot.lo, cap = slot.n;
   if (2 * row_words * ny != cap) return;
   const uint16_t* tmp = reinterpret_cast<const uint16_t*>(ws + tmp_at + dlo) + value_at;
   const uint16_t* lut = reinterpret_cast<const uint16_t*>(cws + kLutAt);
@@ -523,7 +512,7 @@ extern "C" int shdr_piz_batch(const uint8_t* src, int64_t src_bytes, const int64
                    (reinterpret_cast<uintptr_t>(geom_dev) & 3u) == 0 && (reinterpret_cast<uintptr_t>(chan_words_dev) & 3u) == 0 &&
                    (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 1u) == 0,
                SHDR_E_ALIGN, "%s: the offset tables and `written` must be 8-byte aligned, `status` and the shape tables 4-byte, the workspace 16-byte, dst 2-byte", what);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   shdr::StageTimer<SHDR_PIZ_STAGES> timer(stage_ms, st);
   hipLaunchKernelGGL(piz_decode_kernel, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, src, p.src_bytes, src_off_dev, p.dst_bytes, dst_off_dev,

@@ -16,12 +16,12 @@
 //            form of the zero stretch in front of every used symbol
 //   bits     token bit lengths per lane, a scan, the chunk's size and whether it is coded; then the code words, each lane gathering
 //            its bits into 32-bit words that are OR-ed into the cleared stream (integer OR: the order of arrival does not matter)
-//   scan     out_offsets from the stored sizes (the deflate encoders' kernel)
+//   scan     out_offsets from the stored sizes (scan_array of batch.h, as the deflate encoders)
 //   final    the chunk's bytes at their final place: header, bitmap, block header, table, code words -- or the scanline bytes
 // Stream-ordered, no host wait, no allocation, integer atomics only: the same input gives the same bytes.
 #include "shdr_internal.h"
+#include "batch.h"
 #include "piz.h"
-#include "deflate_batch.h"
 
 namespace {
 
@@ -40,8 +40,7 @@ constexpr int64_t kTableBytes = ((6 * (int64_t)kSymbols + 7) / 8 + 4 + 15) & ~(i
 constexpr int64_t kZeroBytes = 4 * (int64_t)kSymPad + kSymPad + kTableBytes;     // per chunk: hist, lens, table
 static_assert(kZeroBytes % 16 == 0, "per-chunk regions keep 16-byte alignment");
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline constexpr int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+using shdr::block_scan;
 
 struct Meta {                                 // what the launches hand over, per chunk
   uint32_t ok, bm_min, bm_max, max_value, im, iM, runs, table_bits;
@@ -74,22 +73,21 @@ struct Ws {                                   // carved out of the caller's work
 };
 Ws carve(void* base, int64_t c, int64_t total) {
   Ws w;
-  uint8_t* p = static_cast<uint8_t*>(base);
-  int64_t o = 0;
-  w.zero = p + o;                                      o += c * kZeroBytes;
-  w.data = p + o;                                      o += align16(total + 8 * c + 8);
-  w.zero_bytes = o;
-  w.meta = reinterpret_cast<Meta*>(p + o);             o += 64 * c;
-  w.bitmap = reinterpret_cast<uint32_t*>(p + o);       o += 4 * (int64_t)kBitmapWords * c;
-  w.used = reinterpret_cast<uint32_t*>(p + o);         o += 4 * (int64_t)kBitmapWords * c;
-  w.keys_a = reinterpret_cast<uint64_t*>(p + o);       o += 8 * (int64_t)kSymPad * c;
-  w.keys_b = reinterpret_cast<uint64_t*>(p + o);       o += 8 * (int64_t)kSymPad * c;
-  w.parent = reinterpret_cast<uint32_t*>(p + o);       o += 8 * (int64_t)kSymPad * c;
-  w.weight = reinterpret_cast<uint32_t*>(p + o);       o += 4 * (int64_t)kSymPad * c;
-  w.made = reinterpret_cast<uint32_t*>(p + o);         o += 4 * (int64_t)kSymPad * c;
-  w.vals = reinterpret_cast<uint16_t*>(p + o);         o += align16(total);
-  w.sizes = reinterpret_cast<int64_t*>(p + o);         o += align16(8 * c);
-  w.bytes = o;
+  shdr::Carver cut(base);
+  w.zero = cut.take<uint8_t>(c * kZeroBytes);                    // a multiple of 16: data follows at once, and ONE clear
+  w.data = cut.take<uint8_t>(total + 8 * c + 8);                 // of zero_bytes covers both
+  w.zero_bytes = cut.bytes();
+  w.meta = cut.take<Meta>(c);
+  w.bitmap = cut.take<uint32_t>((int64_t)kBitmapWords * c);
+  w.used = cut.take<uint32_t>((int64_t)kBitmapWords * c);
+  w.keys_a = cut.take<uint64_t>((int64_t)kSymPad * c);
+  w.keys_b = cut.take<uint64_t>((int64_t)kSymPad * c);
+  w.parent = cut.take<uint32_t>(2 * (int64_t)kSymPad * c);
+  w.weight = cut.take<uint32_t>((int64_t)kSymPad * c);
+  w.made = cut.take<uint32_t>((int64_t)kSymPad * c);
+  w.vals = cut.take<uint16_t>((total + 1) / 2);
+  w.sizes = cut.take<int64_t>(c);
+  w.bytes = cut.bytes();
   return w;
 }
 
@@ -110,11 +108,9 @@ struct Chunk {
 };
 __device__ __forceinline__ Chunk chunk_of(const Tables& tb, int64_t c) {
   Chunk k;
-  int64_t a = tb.chunk_off[c], b = tb.chunk_off[c + 1];
-  a = a < 0 ? 0 : a > tb.total ? tb.total : a;
-  b = b < a ? a : b > tb.total ? tb.total : b;
-  k.lo = a;
-  k.n = b - a;
+  const shdr::Span span = shdr::clamped_span(tb.chunk_off, c, tb.total);
+  k.lo = span.lo;
+  k.n = span.n;
   k.width = tb.geom[4 * c];
   k.rows = tb.geom[4 * c + 1];
   const int first = tb.geom[4 * c + 2];
@@ -123,30 +119,8 @@ __device__ __forceinline__ Chunk chunk_of(const Tables& tb, int64_t c) {
   int64_t values = 0;
   if (first >= 0 && k.n_chan >= 1 && (int64_t)first + k.n_chan <= tb.n_words) values = chunk_values(k.width, k.rows, k.cw, k.n_chan);
   k.nv = (uint32_t)values;
-  k.ok = values > 0 && 2 * values == k.n && (a & 1) == 0;      // (never false with the tables the host checked)
+  k.ok = values > 0 && 2 * values == k.n && (k.lo & 1) == 0;     // (never false with the tables the host checked)
   return k;
-}
-
-// exclusive prefix sum over the block's lanes, and the total; every lane calls it; part: LDS [THREADS / 64]
-template <int THREADS, class T>
-__device__ __forceinline__ T block_scan(T v, T* part, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const T x = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += x;
-  }
-  if (lane == 63) part[wave] = incl;
-  __syncthreads();
-  T before = 0, all = 0;
-  for (int w = 0; w < THREADS / 64; ++w) {
-    if (w < wave) before += part[w];
-    all += part[w];
-  }
-  __syncthreads();                                               // part may be written again
-  total = all;
-  return before + incl - v;
 }
 
 // The stretches of equal elements of v[0 .. n), cut into one segment per lane.  summary: what a segment starts with and how many
@@ -638,6 +612,13 @@ __global__ __launch_bounds__(kCopyThreads) void piz_enc_final_kernel(const uint8
   for (int64_t i = t; i < data_bytes; i += kCopyThreads) p[i] = data[i];
 }
 
+// ---- scan: out_offsets[c] = sum of the stored sizes before c, out_offsets[C] = the total.  One block. -------------------------------
+__global__ __launch_bounds__(1024) void piz_enc_scan_kernel(const int64_t* __restrict__ sizes, int64_t count, int64_t* __restrict__ out_offsets) {
+  const int64_t all = shdr::scan_array<1024, 1>(
+      count, [&](int64_t c) { return sizes[c]; }, [&](int64_t c, int64_t before) { out_offsets[c] = before; });
+  if (threadIdx.x == 0) out_offsets[count] = all;
+}
+
 struct Plan {
   int64_t total, out_bytes, ws_bytes;
 };
@@ -753,7 +734,7 @@ extern "C" int shdr_piz_encode_batch(const uint8_t* planar, const int64_t* chunk
                (long long)workspace_bytes, (long long)p.ws_bytes);
   const Ws ws = carve(workspace, n_chunks, p.total);
   const Tables tb{chunk_off_dev, geom_dev, chan_words_dev, p.total, n_words};
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const dim3 grid((unsigned)n_chunks);
   shdr::StageTimer<SHDR_PIZ_ENC_STAGES> timer(stage_ms, st);
   if (hipMemsetAsync(ws.zero, 0, (size_t)ws.zero_bytes, st) != hipSuccess) return shdr::check_launch(what);
@@ -766,7 +747,7 @@ extern "C" int shdr_piz_encode_batch(const uint8_t* planar, const int64_t* chunk
   timer.mark();
   hipLaunchKernelGGL(piz_enc_bits_kernel, grid, dim3(kWide), 0, st, tb, ws, pad, coded);
   timer.mark();
-  hipLaunchKernelGGL(shdr_deflate_batch::deflate_scan_kernel, dim3(1), dim3(1024), 0, st, ws.sizes, (int64_t)n_chunks, out_offsets);
+  hipLaunchKernelGGL(piz_enc_scan_kernel, dim3(1), dim3(1024), 0, st, ws.sizes, (int64_t)n_chunks, out_offsets);
   timer.mark();
   hipLaunchKernelGGL(piz_enc_final_kernel, grid, dim3(kCopyThreads), 0, st, planar, tb, ws, pad, out_offsets, out, out_capacity, stats);
   timer.mark();

@@ -41,6 +41,9 @@ inline int device_slot() {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// the `void* stream` of the C ABI (include/shdr.h) as HIP's handle
+inline hipStream_t stream_of(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
 // SHDR_* environment switches (kernel-family opt-outs, tile experiments, thresholds) are read ONCE per call site and process, not on
 // every launch -- a conv launch used to walk the environment up to ten times.  shdr_config_reload() (include/shdr.h) invalidates every
 // cached value: call it after changing a switch inside a running process (the tests do).

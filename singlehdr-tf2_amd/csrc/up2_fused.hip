@@ -34,8 +34,6 @@ namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 constexpr int UF_HEADER_FLOATS = 16;                            // conv_x3.hip: the packed filter's header, [1] = 2^-S
 constexpr int UF_IMG_HALVES = 64 * 32, UF_UNIT_HALVES = 2 * UF_IMG_HALVES;      // one (slice, chunk) unit: wh, wl images [64 couts][32 channels]
 constexpr int UF_R = 8;                                         // patch rows: interior 6 x 14 of a 8 x 16 patch
@@ -462,7 +460,7 @@ extern "C" int shdr_conv2d_up2_fused_prepare_filter_f32(const shdr_conv2d_desc* 
   SHDR_REQUIRE(packed > 0, SHDR_E_SHAPE, "up2_fused_prepare_filter: the 1x1 form of this layer has no packed filter");
   float* staged = prepared + packed;
   const long total = (long)g.C1 * g.Cout;
-  hipLaunchKernelGGL(up2_fused_filter_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), w, staged, g.C1, d->Cout, g.Cout);
+  hipLaunchKernelGGL(up2_fused_filter_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), w, staged, g.C1, d->Cout, g.Cout);
   if (int rc = shdr::check_launch("up2_fused_filter")) return rc;
   return shdr_conv2d_x3_prepare_filter_f32(&g, staged, prepared, stream);
 }
@@ -490,7 +488,7 @@ extern "C" int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const fl
   a.nty = (a.h + UF_R - 3) / (UF_R - 2);
   a.ntx = (a.w + UF_COLS - 1) / UF_COLS;
   a.npatch = (int)((long)a.N * a.nty * a.ntx);
-  hipStream_t st = S(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (d->Cout == 64) return uf_launch<4, 128>(a, st);
   if (d->Cout == 32) return d->C1 <= 64 ? uf_launch<2, 64>(a, st) : uf_launch<2, 128>(a, st);
   return d->C1 <= 32 ? uf_launch<1, 32>(a, st) : uf_launch<1, 64>(a, st);

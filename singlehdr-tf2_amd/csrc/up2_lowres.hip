@@ -19,7 +19,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr size_t kRangeScratch = 256;         // tail of the workspace: the slot of an input that arrives without a range
 // z columns: 9 Cout rounded up to the blocks of launch_x3_1x1 -- 256 couts per block (each input chunk split once per 256 couts) where
@@ -240,7 +239,7 @@ extern "C" int shdr_conv2d_up2_lowres_prepare_filter_f32(const shdr_conv2d_desc*
   SHDR_REQUIRE(packed > 0, SHDR_E_SHAPE, "up2_lowres_prepare_filter: the 1x1 form of this layer has no packed filter");
   float* staged = prepared + packed;
   const long total = (long)g.C1 * g.Cout;
-  hipLaunchKernelGGL(up2_lowres_filter_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), w, staged, g.C1, d->Cout, g.Cout);
+  hipLaunchKernelGGL(up2_lowres_filter_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), w, staged, g.C1, d->Cout, g.Cout);
   if (int rc = shdr::check_launch("up2_lowres_filter")) return rc;
   return shdr_conv2d_x3_prepare_filter_f32(&g, staged, prepared, stream);
 }
@@ -267,7 +266,7 @@ extern "C" int shdr_conv2d_fwd_up2_lowres_f32(const shdr_conv2d_desc* d, const f
   float* z = reinterpret_cast<float*>(workspace);
   if (!x_range) {
     float* slot = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + shdr_conv2d_up2_lowres_workspace_bytes_f32(d) - kRangeScratch);
-    if (hipMemsetAsync(slot, 0, sizeof(float), S(stream)) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_up2_lowres: memset failed");
+    if (hipMemsetAsync(slot, 0, sizeof(float), shdr::stream_of(stream)) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_up2_lowres: memset failed");
     if (int rc = shdr_absmax_f32(x, (int64_t)g.N * g.H * g.W * g.C1, slot, stream)) return rc;
     x_range = slot;
   }
@@ -285,6 +284,6 @@ extern "C" int shdr_conv2d_fwd_up2_lowres_f32(const shdr_conv2d_desc* d, const f
   a.nseg = (a.h + a.rows - 1) / a.rows;
   const long nblk = (long)a.N * a.nseg * a.nstrip * a.ncs;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_up2_lowres: grid of %ld blocks", nblk);
-  hipLaunchKernelGGL(up2_lowres_stencil_kernel, dim3((unsigned)nblk), dim3(256), 0, S(stream), a);
+  hipLaunchKernelGGL(up2_lowres_stencil_kernel, dim3((unsigned)nblk), dim3(256), 0, shdr::stream_of(stream), a);
   return shdr::check_launch("up2_lowres_stencil_kernel");
 }

@@ -187,15 +187,13 @@ __global__ __launch_bounds__(256) void winograd_output_kernel(const WinoOutArgs 
   }
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" int shdr_winograd_filter_f32(const float* w, float* u, int Cin, int Cout, void* stream) {
   SHDR_REQUIRE(w && u, SHDR_E_NULL, "winograd_filter: null pointer");
   SHDR_REQUIRE(Cin > 0 && Cout > 0, SHDR_E_SHAPE, "winograd_filter: bad shape");
   const long cc = (long)Cin * Cout;
-  hipLaunchKernelGGL(winograd_filter_kernel, dim3(shdr::stream_grid(cc)), dim3(256), 0, S(stream), w, u, cc);
+  hipLaunchKernelGGL(winograd_filter_kernel, dim3(shdr::stream_grid(cc)), dim3(256), 0, shdr::stream_of(stream), w, u, cc);
   return shdr::check_launch("winograd_filter");
 }
 
@@ -203,7 +201,7 @@ extern "C" int shdr_winograd_filter_packed_f32(const float* w, float* up, int Ci
   SHDR_REQUIRE(w && up, SHDR_E_NULL, "winograd_filter_packed: null pointer");
   SHDR_REQUIRE(Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 64 == 0, SHDR_E_SHAPE,
                "winograd_filter_packed: need Cin %% 8 == 0 and Cout %% 64 == 0");
-  hipLaunchKernelGGL(winograd_filter_packed_kernel, dim3(shdr::stream_grid((long)Cin * Cout)), dim3(256), 0, S(stream), w, up, Cin, Cout);
+  hipLaunchKernelGGL(winograd_filter_packed_kernel, dim3(shdr::stream_grid((long)Cin * Cout)), dim3(256), 0, shdr::stream_of(stream), w, up, Cin, Cout);
   return shdr::check_launch("winograd_filter_packed");
 }
 
@@ -218,7 +216,7 @@ extern "C" int shdr_winograd_input_f32(const float* x, float* v, int N, int H, i
   SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(v), SHDR_E_ALIGN, "winograd_input: tensors must be 16-byte aligned");
   const int TH = (H + 1) / 2, TW = (W + 1) / 2;
   const long total = (long)N * TH * TW * (C / 4);
-  hipLaunchKernelGGL(winograd_input_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), x, v, N, H, W, C, TH, TW,
+  hipLaunchKernelGGL(winograd_input_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), x, v, N, H, W, C, TH, TW,
                      (long)shdr_winograd_tiles(N, H, W));
   return shdr::check_launch("winograd_input");
 }
@@ -231,6 +229,6 @@ extern "C" int shdr_winograd_output_f32(const float* m, float* y, const float* b
   SHDR_REQUIRE(shdr::aligned16(m) && shdr::aligned16(y), SHDR_E_ALIGN, "winograd_output: tensors must be 16-byte aligned");
   WinoOutArgs a{m, y, bias, scale, shift, N, H, W, C, (H + 1) / 2, (W + 1) / 2, (long)shdr_winograd_tiles(N, H, W), act1, act2};
   const long total = (long)N * a.TH * a.TW * (C / 4);
-  hipLaunchKernelGGL(winograd_output_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, S(stream), a);
+  hipLaunchKernelGGL(winograd_output_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0, shdr::stream_of(stream), a);
   return shdr::check_launch("winograd_output");
 }

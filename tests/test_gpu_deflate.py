@@ -61,6 +61,25 @@ def test_thousand_small_chunks(shdr):
     assert coded.sum() == 1100
 
 
+@pytest.mark.parametrize("pad", [0, 5])
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2049])
+def test_offsets_where_the_scan_loops(shdr, n, pad):
+    """the one-block scan of the stored sizes (scan_array of csrc/batch.h, 1024 chunks a step; PIZ encode runs the same) on batches
+    that end inside, at and one past a step: out_offsets against the host routine's sizes summed here, and every stored chunk"""
+    K = shdr._ops
+    rng = np.random.default_rng(25)
+    chunks = [rng.integers(0, 256, k, dtype=np.uint8).tobytes() for k in rng.integers(1, 4, n)]
+    host = {c: K.deflate_huffman_host(c) for c in set(chunks)}
+    stored = [host[c] if len(host[c]) < len(c) else c for c in chunks]
+    data, offsets = batch(chunks)
+    out, out_offsets, coded = K.deflate_huffman(data, offsets, pad=pad)
+    out, off, coded = out.cpu().numpy(), out_offsets.cpu().numpy(), coded.cpu().numpy()
+    assert off.tolist() == np.concatenate([[0], np.cumsum([pad + len(s) for s in stored])]).tolist()
+    assert coded.tolist() == [int(len(host[c]) < len(c)) for c in chunks]
+    for c, s in enumerate(stored):
+        assert out[off[c] + pad:off[c + 1]].tobytes() == s, c
+
+
 def test_pad_front_and_raw(shdr):
     """room in front of every chunk and of the whole output stays untouched; a chunk that is not coded is stored from `raw`"""
     K = shdr._ops

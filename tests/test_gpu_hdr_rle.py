@@ -94,6 +94,15 @@ def test_batch_of_different_sizes_and_offsets():
     assert offsets.cpu().tolist() == [0] + np.cumsum(sizes).tolist()
 
 
+def test_more_rows_than_the_scan_block_takes_in_one_step():
+    """the one-block scan of the row sizes (rle_scan_kernel over scan_array of csrc/batch.h, 1024 rows a step): 4097 + 1025 rows, so
+    the first image ends one row past a step and the batch two rows past another; bytes and per-image offsets against the host's"""
+    images = [R.family_image(4097, 8, seed=21), R.family_image(1025, 9, seed=22)]
+    _check(images)
+    data, offsets = K.rgbe_rle_encode([_dev(a) for a in images])
+    assert offsets.cpu().tolist() == [0] + np.cumsum([len(IO.rle_encode(a)) for a in images]).tolist()
+
+
 def test_two_runs_give_identical_bytes_and_offsets():
     tensors = [_dev(a) for a in _mixed_batch()]
     d1, o1 = K.rgbe_rle_encode(tensors)

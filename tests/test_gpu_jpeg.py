@@ -71,6 +71,22 @@ def test_many_subsequences_many_workgroups(jpeg, big):
     assert small.plan.images["n_wg"][0] >= 4 and np.array_equal(small.image(0).cpu().numpy(), pil)
 
 
+def test_more_scan_partials_than_one_step_of_their_block(jpeg):
+    """scan_partials_kernel (csrc/jpeg.hip, over scan_array of csrc/batch.h) takes WG = 256 partials a step, one partial per
+    SCAN_CHUNK = 1024 scanned elements: the DC sums of more than 256 * 1024 = 262144 blocks need a second step.  The smallest such
+    image has 262145 = 65 * 4033 blocks of one component: 520 x 32264 grey pixels.  Every block row has a value of its own, so the DC
+    differences are not zero where a row of 65 blocks begins, and the DC of the last block holds the sum over all partials."""
+    bw, bh = 65, 4033
+    assert bw * bh == 256 * 1024 + 1
+    rows = ((np.arange(8 * bh) // 8 * 7) % 200 + 20).astype(np.uint8)
+    data = jpeg_ref.encode(np.repeat(rows[:, None, None], 8 * bw, axis=1).repeat(3, axis=2), "grey", 75)
+    _, want = jpeg_ref.coefficients(data)
+    coef = jpeg.decode_coefficients(data)
+    assert len(coef) == len(want) == 1 and tuple(coef[0].shape) == want[0].shape == (bh, bw, 64)
+    assert len(set(want[0][:, 0, 0].tolist())) > 20 and want[0][-1, -1, 0] != 0
+    assert np.array_equal(coef[0].cpu().numpy(), want[0])
+
+
 def test_many_restart_segments(jpeg, big):
     data = _noise_file(restart_marker_blocks=5)
     hd = jpeg.parse(data)

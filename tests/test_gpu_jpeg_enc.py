@@ -87,6 +87,18 @@ def test_long_segments_and_flat_content(shdr):
     _encode_checked(K, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in imgs], desc, want)
 
 
+@pytest.mark.parametrize("restart", [0, 1])
+def test_more_blocks_than_the_scan_block_takes_in_one_step(shdr, restart):
+    """the one-block scans (enc_scan_kernel over scan_array of csrc/batch.h, 1024 lanes x 4 items = 4096 a step): a 4:2:0 image of
+    16 x 10928 pixels is 683 MCUs = 4098 blocks, two past a step, with an 8 x 8 image behind it in the same batch"""
+    K = shdr._ops
+    imgs = [R.content("noise", 16, 10928, seed=5), R.content("noise", 8, 8, seed=6)]
+    desc = K.jpeg_enc_images([a.shape[:2] for a in imgs], 75, "420", restart)
+    assert K.jpeg_encode_blocks(desc[0:1])[0] == 4098
+    want = [K.jpeg_encode_host(np.ascontiguousarray(img), desc[i:i + 1]) for i, img in enumerate(imgs)]
+    _encode_checked(K, [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in imgs], desc, want)
+
+
 def test_float_pixels_equal_the_uint8_they_round_to(shdr):
     K = shdr._ops
     g = torch.Generator().manual_seed(4)
