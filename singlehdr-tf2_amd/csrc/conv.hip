@@ -57,7 +57,7 @@ struct ConvArgs {
 };
 
 // max |y| -> the range slot, only if it exceeds what the slot holds (agent-scope load).  BLOCK: the four waves' maxima meet in LDS and
-// one thread issues the atomicMax (conv_x3.hip x3_range_out: same-address atomics execute one after the other at the memory side); the
+// one thread issues the atomicMax (split.h range_out: same-address atomics execute one after the other at the memory side); the
 // call must then be reached by every wave of the block exactly once per kernel.  Otherwise one atomicMax per wave and call.
 // `seen` = the slot's value loaded BEFORE the epilogue's stores (conv_range_seen): a load at the end of the block kept its LDS and
 // registers allocated for a round trip to the memory side, ~2 us on blocks that live 10 - 20 us.
@@ -95,11 +95,6 @@ __host__ __device__ constexpr int conv_lds_bytes() {
   return 2 * (BM * SA + BK * sb_stride(BN)) * 4;
 }
 
-// Bijective XCD-aware remap: consecutive logical ids share an XCD (and its L2).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // Epilogue shared by the MFMA kernels: lane (fi, fg) holds, per 16x16 tile, 4 consecutive
 // couts (4*fg..4*fg+3) of pixel fi.
@@ -249,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
   const int wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
 
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_dma_kernel(const ConvArgs a)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
 
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -1124,7 +1119,7 @@ extern "C" int shdr_conv2d_fwd_yrange_f32(const shdr_conv2d_desc* d, const float
     SHDR_REQUIRE((long)d->N * d->y_H * d->y_W < (1L << 31), SHDR_E_SHAPE, "conv2d: more than 2^31 output pixels");
     a.YH = d->y_H; a.YW = d->y_W; a.ys = d->y_pix_stride; a.yoh = d->y_off_h; a.yow = d->y_off_w;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   a.legacy_epilogue = SHDR_ENV("SHDR_CONV_LEGACY_EPILOGUE") != nullptr;
 
   const bool ragged = (cout_valid % 4) != 0;  // scalar epilogue: no alignment demands on y/res/bias

@@ -55,10 +55,6 @@ struct ConvHFusedArgs : ConvHArgs {
 template <bool FUSED>
 using ConvHArgsT = std::conditional_t<FUSED, ConvHFusedArgs, ConvHArgs>;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 __host__ __device__ inline int swz(int row) { return (-(row >> 2)) & 3; }
 
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -405,7 +401,7 @@ extern "C" int shdr_conv2d_pack_filter_f16(const float* w, void* wp, int KH, int
   SHDR_REQUIRE(shdr::aligned16(wp), SHDR_E_ALIGN, "pack_filter_f16: wp must be 16-byte aligned");
   const int nchunks = f16_nchunks(KH * KW, C1, C2);
   hipLaunchKernelGGL(conv_pack_filter_f16_kernel, dim3(shdr::stream_grid((long)nchunks * Cout * 4)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), w, reinterpret_cast<_Float16*>(wp), KH * KW, C1 + C2, C1, Cout, nchunks,
+                     shdr::stream_of(stream), w, reinterpret_cast<_Float16*>(wp), KH * KW, C1 + C2, C1, Cout, nchunks,
                      f16_fast(C1, C2) ? 1 : 0, C2 > 0 ? x2_scale : 1.0f);
   return shdr::check_launch("conv_pack_filter_f16");
 }
@@ -458,7 +454,7 @@ extern "C" int shdr_conv2d_fwd_f16(const shdr_conv2d_desc* d, const void* x1, co
                                    void* y, int y_is_f32, void* stream) {
   ConvHArgs a;
   if (int e = f16_setup(d, x1, x2, wp, bias, y, y_is_f32, a)) return e;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   // narrow full-resolution layers (<= 32 channels per tap, 16 / 32 couts): raw patch + resident filter in LDS (conv_f16_patch.hip)
   if (shdr_conv2d_patch_ok_f16(d) && (y_is_f32 || d->act1 != SHDR_ACT_TANH) && SHDR_ENV("SHDR_NO_PATCH") == nullptr)
     return shdr_conv2d_fwd_patch_f16(d, x1, x2, wp, bias, y, y_is_f32, stream);
@@ -490,7 +486,7 @@ extern "C" int shdr_conv2d_fwd_fused_f16(const shdr_conv2d_desc* d, const void* 
   a.f.res_f32 = residual_is_f32 ? 1 : 0;
   a.f.res_cstride = residual ? d->res_cstride : 0;
   a.f.act2 = d->act2;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   // the same kernel families as shdr_conv2d_fwd_f16, each only where its fused form takes every option of the call
   if (shdr_conv2d_patch_fused_ok_f16(d, y_is_f32) && SHDR_ENV("SHDR_NO_PATCH") == nullptr)
     return shdr_conv2d_fwd_patch_fused_f16(d, x1, x2, wp, bias, &a.f, y, stream);

@@ -39,10 +39,6 @@ struct W3FusedArgs : W3Args {
 template <bool FUSED>
 using W3ArgsT = std::conditional_t<FUSED, W3FusedArgs, W3Args>;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 __host__ __device__ inline int f4(int row) { return (-(row >> 2)) & 3; }      // filter image: rows = couts, 16-row aligned fragments
 // patch image: column-keyed slot swizzle + lane -> tile-column permutation (conv_x3.hip: a ds_read_b128 lane group = 8 lanes of one
 // channel group + 8 of its neighbour; with pcol() each set reads 8 consecutive columns -> conflict-free at every tap shift, and the
@@ -66,7 +62,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -256,7 +252,7 @@ extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1,
                                       void* stream) {
   W3Args a;
   if (int e = w3_setup(d, x1, x2, wp, bias, y, a)) return e;
-  return w3_launch<false>(a, reinterpret_cast<hipStream_t>(stream));
+  return w3_launch<false>(a, shdr::stream_of(stream));
 }
 
 // the fused form takes the folded BatchNorm (scale / shift) and act2 of the Hallucination-Net's `up` blocks (hallucination_net.py:86-89); a
@@ -272,5 +268,5 @@ extern "C" int shdr_conv2d_fwd_w3_fused_f16(const shdr_conv2d_desc* d, const voi
   W3FusedArgs a;
   if (int e = w3_setup(d, x1, x2, wp, bias, y, a)) return e;
   a.f = *f;
-  return w3_launch<true>(a, reinterpret_cast<hipStream_t>(stream));
+  return w3_launch<true>(a, shdr::stream_of(stream));
 }

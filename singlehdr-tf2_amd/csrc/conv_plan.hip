@@ -10,18 +10,15 @@
 // linearization_net.py:12-101, hallucination_net.py:47-140, refinement_net.py:8-47, vgg16.py:33-35, joint_training.py:185).
 #include <stdlib.h>
 
-#include "shdr_internal.h"
-
-extern "C" int shdr_conv2d_x3_prepare_filter_premax_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, int premax, void* stream);
-extern "C" int shdr_conv2d_x3n_prepare_filter_premax_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, int premax, void* stream);
+#include "split.h"
 
 namespace {
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+using shdr::kRangeScratch;
+using shdr::up256;
 
 // the Winograd form a 3x3 / stride-1 / SAME layer takes (measured on MI355X, tools/wino_bench.py): the one-kernel fused form beats
 // the direct kernels on every shape it accepts; the three-kernel "planes" form pays from 128 -> 256 / 256 -> 128 channels up
-constexpr int X3_HEADER_FLOATS_PUB = 16;       // header of a packed split-operand filter (conv_x3.hip)
 inline bool is_auto(int algo) { return algo == SHDR_ALGO_AUTO || algo == SHDR_ALGO_AUTO_EXACT; }
 
 int plan_of(const shdr_conv2d_desc* d, bool has_residual) {
@@ -121,8 +118,8 @@ DgradGeom dgrad_geom(const shdr_conv2d_desc* d, int which) {
            (long)d->N * d->Ho * d->Wo * g.CZ < (1L << 32) && SHDR_ENV("SHDR_NO_WINOGRAD") == nullptr;
   // ... and the split-operand fp16 kernel before it, by the rule of plan_of on the transposed convolution
   g.x3 = false;
+  shdr_conv2d_desc t{};
   if (g.wino && d->algo == SHDR_ALGO_AUTO && g.CZ % 32 == 0) {
-    shdr_conv2d_desc t{};
     t.N = d->N; t.H = d->Ho; t.W = d->Wo; t.C1 = g.CZ; t.Cout = g.CC; t.KH = 3; t.KW = 3; t.stride = 1; t.pad_t = 2 - d->pad_t; t.pad_l = 2 - d->pad_l;
     t.Ho = d->H; t.Wo = d->W; t.cout_valid = g.CC;
     g.x3 = shdr_conv2d_x3_ok_f32(&t) != 0;
@@ -140,7 +137,7 @@ DgradGeom dgrad_geom(const shdr_conv2d_desc* d, int which) {
   g.off_wt = o; o += up256(filt);
   g.off_u = o;
   if (g.x3n) o += up256((size_t)shdr_conv2d_x3n_filter_elems_f32(&tn) * sizeof(float));
-  else if (g.x3) o += up256((size_t)(X3_HEADER_FLOATS_PUB + (int64_t)9 * g.CZ * g.CC) * sizeof(float));
+  else if (g.x3) o += up256((size_t)shdr_conv2d_x3_filter_elems_f32(&t) * sizeof(float));
   else if (g.wino) o += up256((size_t)16 * g.CZ * g.CC * sizeof(float));
   g.off_dz = o; if (g.pad_dz) o += up256((size_t)d->N * d->Ho * d->Wo * g.CZ * sizeof(float));
   g.off_sub = o; if (d->stride == 2 && !(d->KH == 1 && d->KW == 1)) o += up256(filt);
@@ -207,7 +204,6 @@ inline size_t up2_bytes(const shdr_conv2d_desc* d, int plan) {
 // The split-operand plans scale their input by a power of two taken from a RANGE SLOT per source (conv_x3.hip "Range").  A caller that
 // does not know the range of a source (x1_range / x2_range = NULL) gets it measured here: one absmax pass over that source into two
 // scratch slots at the tail of the workspace.
-constexpr size_t kRangeScratch = 256;
 inline bool split_plan(int plan) { return plan == SHDR_PLAN_X3 || plan == SHDR_PLAN_X3N; }
 
 extern "C" int64_t shdr_conv2d_workspace_bytes_f32(const shdr_conv2d_desc* d, int has_residual) {
@@ -406,7 +402,7 @@ extern "C" int shdr_conv2d_dgrad_ranged_f32(const shdr_conv2d_desc* d, int which
   const float scale = which ? d->x2_scale : 1.0f;
   // the split-operand plans pack wt next: its maximum comes out of this pass (header slot 0 of the packed filter)
   unsigned* maxslot = (d->stride == 1 && (g.x3n || g.x3)) ? reinterpret_cast<unsigned*>(ws + g.off_u) : nullptr;
-  if (maxslot && hipMemsetAsync(maxslot, 0, 64, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_dgrad: memset failed");
+  if (maxslot && hipMemsetAsync(maxslot, 0, shdr::kSplitHeaderFloats * sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_dgrad: memset failed");
   long fgrid = shdr::stream_grid((long)d->KH * d->KW * g.CZ * g.CC);
   if (maxslot && fgrid > 256) fgrid = 256;                 // (every wave ends in an atomicMax on one address)
   hipLaunchKernelGGL(dgrad_filter_kernel, dim3((unsigned)fgrid), dim3(256), 0, st, w, wt, d->KH, d->KW, Ct,
@@ -428,7 +424,7 @@ extern "C" int shdr_conv2d_dgrad_ranged_f32(const shdr_conv2d_desc* d, int which
       c.algo = SHDR_ALGO_AUTO;
       if (int rc = shdr_conv2d_x3n_prepare_filter_premax_f32(&c, wt, u, 1, stream)) return rc;
       if (!dz_range) {
-        if (int rc = shdr_conv2d_x3_input_absmax_f32(dzp, (int64_t)c.N * c.H * c.W * c.C1, u, stream)) return rc;     // header slot 2, as the wide kernel
+        if (int rc = shdr_conv2d_x3_input_absmax_f32(dzp, (int64_t)c.N * c.H * c.W * c.C1, u, stream)) return rc;     // header slot kHdrInputRange, as the wide kernel
         c.prologue = SHDR_PROLOGUE_RANGE_SCALE;
       }
       return shdr_conv2d_fwd_x3n_ranged_f32(&c, dzp, nullptr, u, nullptr, nullptr, nullptr, nullptr, dx, nullptr, dz_range, nullptr, dx_range, stream);

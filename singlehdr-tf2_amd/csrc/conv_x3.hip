@@ -38,7 +38,7 @@
 
 #include <type_traits>
 
-#include "shdr_internal.h"
+#include "split.h"
 
 namespace {
 
@@ -47,7 +47,6 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
-constexpr int X3_HEADER_FLOATS = 16;                           // [0] max |w| (bits), [1] 2^-S; 64 bytes keep the images 16-byte aligned
 constexpr int BN = 64, NT = 4, MT = 4;
 constexpr int IMG_HALVES = BN * 32;                            // one filter image of a tap: [64 couts][32 channels]
 constexpr int UNIT_HALVES = 2 * IMG_HALVES;                    // wh, wl
@@ -62,14 +61,14 @@ struct X3G {
   static constexpr int PATCH_HALVES = PPIX * 32;              // one fp16 image of the patch
   static constexpr int LDS_BYTES = (2 * PATCH_HALVES + 2 * UNIT_HALVES) * 2;
   static constexpr int LDS_BYTES_UP = LDS_BYTES + LRPIX * 32 * 4;
-  static constexpr int RANGE_BYTES = 16;                       // + the waves' output maxima (x3_range_out), behind everything else
+  static constexpr int RANGE_BYTES = 16;                       // + the waves' output maxima (shdr::range_out), behind everything else
 };
 
 struct X3Args {
   const float* x1;
   const float* x2;
   const _Float16* wp;      // packed [Cout / 64][units = Ct / 32 * taps][2 images: wh, wl][64][32]
-  const float* hdr;        // packed header: hdr[1] = 2^-S
+  const float* hdr;        // packed header (split.h): hdr[kHdrInvScale] = 2^-S
   const float* bias;
   const float* scale;
   const float* shift;
@@ -92,75 +91,15 @@ struct X3Args {
   float* yproj;            // ... yproj[N,H,W,3][j] = sum_c proj[j][c] y[c] (shdr_conv2d_fwd_x3_projected_f32; Cout = 64)
 };
 
-// 2^T and 2^-T for the power of two that brings the larger of the two bounds into [2^10, 2^11); 1 for an empty, zero or non-finite bound
-__device__ __forceinline__ void x3_range_scale(const unsigned* r1, const unsigned* r2, float& xs, float& ixs) {
-  xs = 1.0f;
-  ixs = 1.0f;
-  unsigned b = r1 ? *r1 : 0u;
-  if (r2) {
-    const unsigned b2 = *r2;
-    b = b2 > b ? b2 : b;                                       // non-negative floats order like their bit patterns
-  }
-  if (b != 0u && b < 0x7f800000u) {
-    int ex;
-    frexpf(__uint_as_float(b), &ex);                           // bound in [2^(ex-1), 2^ex)
-    int T = 11 - ex;
-    T = T < -126 ? -126 : (T > 126 ? 126 : T);
-    xs = ldexpf(1.0f, T);
-    ixs = ldexpf(1.0f, -T);
-  }
-}
-// one float4 -> (fp16(v xs), fp16((v xs - fp16(v xs)) 2^11)) as two packed register pairs: v_fma_mixlo/hi_f16 multiply, round and pack in
-// one instruction, v_fma_mix_f32 forms v xs - (float)h exactly (the product is exact, the difference representable): 12 vector
-// instructions per float4 (the compiler's cast / convert / subtract / multiply / pack sequence: 19)
-__device__ __forceinline__ void x3_split4(const f32x4 v, float xs, unsigned (&h)[2], unsigned (&l)[2]) {
-  const float k2048 = 2048.0f;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float t0, t1;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h[p]) : "v"(v[2 * p]), "s"(xs));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h[p]) : "v"(v[2 * p + 1]), "s"(xs));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(v[2 * p]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(v[2 * p + 1]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l[p]) : "v"(t0), "s"(k2048));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l[p]) : "v"(t1), "s"(k2048));
-  }
-}
-// max |y| of a block -> the range slot: the waves' maxima meet in four LDS words of their own and ONE thread issues a
-// no-return atomicMax, and only when the block's maximum exceeds what the slot already holds.  Atomics execute at the memory side, one
-// after the other per address (measured ~4 ns each): one per WAVE cost the small layers of the U-Nets 15 - 35 us per launch, all of it
-// in the first round of blocks, which finish together and all still see the slot empty.
-// `seen` = the slot's value loaded at the START of the epilogue (the load's round trip to the memory side runs under the stores)
-// (NW = 8: the eight waves of conv_x3_wide_kernel, eight words)
-template <int NW = 4>
-__device__ __forceinline__ void x3_range_out(unsigned* slot, float m, int lane, int wave, unsigned seen, unsigned* lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  if (lane == 0) lds[wave] = __float_as_uint(m);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (not __syncthreads(): that would also sit out the output stores)
-  if (threadIdx.x == 0) {
-    const unsigned b01 = lds[0] > lds[1] ? lds[0] : lds[1], b23 = lds[2] > lds[3] ? lds[2] : lds[3];
-    unsigned b = b01 > b23 ? b01 : b23;                        // non-negative floats order like their bit patterns
-    if (NW == 8) {
-      const unsigned b45 = lds[4] > lds[5] ? lds[4] : lds[5], b67 = lds[6] > lds[7] ? lds[6] : lds[7];
-      const unsigned b47 = b45 > b67 ? b45 : b67;
-      b = b47 > b ? b47 : b;
-    }
-#ifndef SHDR_ABL_NO_RANGE_ATOMIC
-    if (b > seen) atomicMax(slot, b);
-#endif
-  }
-}
-
 // ---- the tile epilogue of conv_x3_kernel (NW = 4 waves, PROJ) and conv_x3_wide_kernel (NW = 8; no projected output, which needs Cout = 64).
 // The wave holds acc[MT][NT] = the MT pixel rows from oh_row0 on x the 64 couts from n0 on; the lane's tile column is ow (pc in the tile: the
-// pcol permutation), its couts the quads 4 fg of each 16; ixs = 2^-T of the input scaling; range_lds = NW words of LDS for x3_range_out.
+// pcol permutation), its couts the quads 4 fg of each 16; ixs = 2^-T of the input scaling; range_lds = NW words of LDS for shdr::range_out.
 template <int NW, bool PROJ>
 __device__ __forceinline__ void x3_tile_epilogue(const X3Args& a, f32x4 (&acc)[MT][NT], int img, int oh_row0, int ow, int pc, int fg, int n0, float ixs,
                                                  int lane, int wave, unsigned* range_lds) {
   // y = act2(affine(act1(acc * 2^-S + bias))), 16-byte stores (lane = pixel x 4 consecutive couts); the 2 x 2 pooling window of the
   // optional second output is two rows of this lane and of its neighbour lane
-  const float inv_s = a.hdr[1] * ixs;
+  const float inv_s = a.hdr[shdr::kHdrInvScale] * ixs;
   // bias / scale / shift of the lane's four cout quads are loaded ONCE, in front of the store loop: a load inside it is followed by
   // "s_waitcnt vmcnt(0)", which also sits out the round trip of the output store issued just before it -- the stores of a block went
   // out one at a time
@@ -263,14 +202,10 @@ __device__ __forceinline__ void x3_tile_epilogue(const X3Args& a, f32x4 (&acc)[M
   // (a pooled output is bounded by the same maximum).  The waves' words have LDS of their own: without a barrier after the last chunk (the
   // 1 x 1 form) wave 0 may still be reading patch pixel (0, 0) when another wave writes its maximum
   if (a.yr)
-    x3_range_out<NW>(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, range_lds);
+    shdr::range_out<NW>(a.yr, ow < a.W ? ym : 0.0f, lane, wave, yr_seen, range_lds);
 #endif
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 __host__ __device__ inline int f4(int row) { return (-(row >> 2)) & 3; }      // filter images: rows = couts, 16-row aligned fragments
 // Patch images: the 16-byte slot of channel group kg of patch column c is kg ^ sx(c).  A ds_read_b128 is served in lane groups of
 // {8 lanes of one kg, 8 lanes of kg ^ 1}; with the lane -> tile-column permutation pcol() below each set of 8 reads 8 CONSECUTIVE
@@ -316,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -395,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
                                                                // slot is a dependent scalar load: in front of them it delayed every block's first fetch)
   auto split_store = [&](int dst, const f32x4 v4) __attribute__((always_inline)) {            // one float4 -> 8 bytes in each fp16 image
     unsigned h[2], l[2];
-    x3_split4(v4, xs, h, l);
+    shdr::split4(v4, xs, h, l);
     *reinterpret_cast<uint2*>(patch_h + dst) = make_uint2(h[0], h[1]);
     *reinterpret_cast<uint2*>(patch_l + dst) = make_uint2(l[0], l[1]);
   };
@@ -536,7 +471,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   load_patch(0, Set0{});
   if (DEPTH == 2 && nch > 1) load_patch(1, Set1{});
   issue_filt(0, 0);
-  if (!MP || phase == 0) x3_range_scale(a.xr1, a.xr2, xs, ixs);
+  if (!MP || phase == 0) shdr::range_scale(a.xr1, a.xr2, xs, ixs);
   if (UP) {
     park_lr();
     __syncthreads();
@@ -672,12 +607,12 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
   constexpr int IMG = BP * 32;                                 // halves of one fp16 image of a chunk (8 KB)
   static_assert(NS * (BP / (MT1 * 16)) == 4, "four waves: NS cout slices x pixel groups");
   __shared__ __attribute__((aligned(16))) _Float16 x1sm[2 * 2 * IMG];       // [buffer][h, l][BP pixels][32], 16-byte slots swizzled by sx()
-  __shared__ unsigned x1rw[4];                                 // the waves' output maxima (x3_range_out)
+  __shared__ unsigned x1rw[4];                                 // the waves' output maxima (shdr::range_out)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slice = wave % NS, grp = wave / NS;
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n, pm = L / a.nblk_n;
   const int P0 = pm * BP, Ptot = a.N * a.H * a.W;
 
@@ -717,7 +652,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
 #pragma unroll
     for (int j = 0; j < PJ1; ++j) {
       unsigned h[2], l[2];
-      x3_split4(pr_sets[S][j], xs, h, l);
+      shdr::split4(pr_sets[S][j], xs, h, l);
       *reinterpret_cast<uint2*>(x1sm + buf * 2 * IMG + pdst + 1024 * j) = make_uint2(h[0], h[1]);
       *reinterpret_cast<uint2*>(x1sm + buf * 2 * IMG + IMG + pdst + 1024 * j) = make_uint2(l[0], l[1]);
     }
@@ -777,7 +712,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
   load_patch(0, Set0{});
   if (nch > 1) load_patch(1, Set1{});
   load_w(0, 0, f0h, f0l);
-  x3_range_scale(a.xr1, a.xr2, xs, ixs);                       // (behind the first loads: the slot is a dependent scalar load)
+  shdr::range_scale(a.xr1, a.xr2, xs, ixs);                    // (behind the first loads: the slot is a dependent scalar load)
   store_patch(0, Set0{});
   if (nch > 2) load_patch(2, Set0{});
   // chunk c: buffer c & 1 holds it; `nxt` = the register set of chunk c + 1 (split into the other buffer here, then refilled with c + 3)
@@ -799,7 +734,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
   }
 
   // ---- epilogue: conv_x3_kernel's, per 16-pixel row mi: lane = pixel P0 + grp * MT1 * 16 + 16 mi + pc x 4 consecutive couts ------------
-  const float inv_s = a.hdr[1] * ixs;
+  const float inv_s = a.hdr[shdr::kHdrInvScale] * ixs;
   const unsigned yr_seen = a.yr ? __hip_atomic_load(a.yr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   int ep0 = (pn * NS + slice) * BN;                            // first cout of the wave's slice
   asm volatile("" : "+s"(ep0));                                // (loads below the chunk loop, not hoisted above it)
@@ -846,7 +781,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_1x1_kernel(const X3Args a) {
       }
     }
   }
-  if (a.yr) x3_range_out(a.yr, ym, lane, wave, yr_seen, x1rw);
+  if (a.yr) shdr::range_out(a.yr, ym, lane, wave, yr_seen, x1rw);
 }
 
 // ---- wide 3 x 3 layers: one split per chunk for 128 couts ---------------------------------------------------------------------------
@@ -889,7 +824,7 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slice = wave >> 2, wq = wave & 3;                  // cout slice of the wave, its group of four pixel rows
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L % a.nblk_n;
   int pm = L / a.nblk_n;
   const int tx = pm % a.tiles_x;
@@ -1001,7 +936,7 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
       dst = pdst[j];
     }
     unsigned h[2], l[2];
-    x3_split4(v, xs, h, l);
+    shdr::split4(v, xs, h, l);
     *reinterpret_cast<uint2*>(patch_buf(buf) + dst) = make_uint2(h[0], h[1]);
     *reinterpret_cast<uint2*>(patch_buf(buf) + PATCH_HALVES + dst) = make_uint2(l[0], l[1]);
   };
@@ -1070,7 +1005,7 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
   load_patch(0, false);
   issue_filt(0, 0);
   issue_filt(1, 1);
-  x3_range_scale(a.xr1, a.xr2, xs, ixs);                       // (behind the first loads: the slot is a dependent scalar load)
+  shdr::range_scale(a.xr1, a.xr2, xs, ixs);                    // (behind the first loads: the slot is a dependent scalar load)
   if (UP) {
     park_lr();
     __syncthreads();
@@ -1182,7 +1117,8 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
 #undef lrs
 
 // ---- filter preparation ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void x3_absmax_kernel(const float* __restrict__ w, long n, unsigned* __restrict__ out) {
+// max |w| -> *out (bits): one atomicMax per wave, so launched with <= 64 blocks (2048 blocks took 50 us on a 9 MB filter, 64 take 6)
+__global__ __launch_bounds__(256) void split_absmax_kernel(const float* __restrict__ w, long n, unsigned* __restrict__ out) {
   float m = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
 #pragma unroll
@@ -1207,13 +1143,9 @@ __global__ __launch_bounds__(256) void x3_absmax_big_kernel(const float* __restr
 // taps of the packed filter = the sub-filter w[p0 + step * a][q0 + step * b], a < TH, b < TW, of a KWF-wide filter
 __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ w, float* __restrict__ hdr, _Float16* __restrict__ out, int Ct,
                                                       int C1, int Cout, float x2_scale, int KWF, int TH, int TW, int p0, int q0, int step) {
-  const float mx = fmaxf(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[0]) * fmaxf(1.0f, fabsf(x2_scale)), 1e-30f);
-  int ex;
-  frexpf(mx, &ex);                                             // mx = f * 2^ex, f in [0.5, 1)
-  int S = 14 - ex;                                             // max |w'| in [2^13, 2^14)
-  S = S < -100 ? -100 : (S > 100 ? 100 : S);
-  const float s = ldexpf(1.0f, S);
-  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[1] = ldexpf(1.0f, -S);
+  float inv;
+  const float s = shdr::weight_scale(hdr, x2_scale, inv);    // max |w'| in [2^13, 2^14)
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[shdr::kHdrInvScale] = inv;
   const int ntaps = TH * TW;
   const int nunits = (Ct >> 5) * ntaps;
   const long total = (long)((Cout + 63) / 64) * nunits * 64 * 32;      // (a 32-cout layer fills half of its one 64-cout slice with zeros)
@@ -1236,6 +1168,10 @@ __global__ __launch_bounds__(256) void x3_pack_kernel(const float* __restrict__ 
 
 }  // namespace
 
+void shdr::launch_split_absmax(const float* w, long n, unsigned* out, hipStream_t st) {
+  hipLaunchKernelGGL(split_absmax_kernel, dim3(shdr::stream_grid(n) < 64 ? shdr::stream_grid(n) : 64), dim3(256), 0, st, w, n, out);
+}
+
 namespace {
 
 struct X3Phase { int th, tw, p0, q0, step, bh, bw; };
@@ -1253,7 +1189,7 @@ int x3_phases(const shdr_conv2d_desc* d, X3Phase ph[4]) {
     for (int q0 = 0; q0 < 2; ++q0) ph[n++] = X3Phase{(d->KH - p0 + 1) / 2, (d->KW - q0 + 1) / 2, p0, q0, 2, p0 - d->pad_t, q0 - d->pad_l};
   return n;
 }
-inline int64_t x3_phase_floats(const X3Phase& p, int Ct, int Cout) { return X3_HEADER_FLOATS + (int64_t)p.th * p.tw * Ct * ((Cout + 63) / 64 * 64); }    // two fp16 images
+inline int64_t x3_phase_floats(const X3Phase& p, int Ct, int Cout) { return shdr::kSplitHeaderFloats + (int64_t)p.th * p.tw * Ct * ((Cout + 63) / 64 * 64); }    // two fp16 images
 
 template <bool UP, int KH, int KW, bool MP, int LOOK>
 int launch_x3_look(const X3Args& a, hipStream_t st) {
@@ -1365,9 +1301,6 @@ extern "C" int64_t shdr_conv2d_x3_filter_elems_f32(const shdr_conv2d_desc* d) {
   return total;
 }
 
-// premax: header slot 0 of the (single) phase already holds max |w| (written by the kernel that produced w: the input gradient's filter
-// transform) -- no memset, no absmax launch
-extern "C" int shdr_conv2d_x3_prepare_filter_premax_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, int premax, void* stream);
 extern "C" int shdr_conv2d_x3_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream) {
   return shdr_conv2d_x3_prepare_filter_premax_f32(d, w, prepared, 0, stream);
 }
@@ -1377,7 +1310,7 @@ extern "C" int shdr_conv2d_x3_prepare_filter_premax_f32(const shdr_conv2d_desc* 
   SHDR_REQUIRE(Ct > 0 && Ct % 32 == 0 && d->C1 % 32 == 0 && d->Cout > 0 && (d->Cout % 64 == 0 || d->Cout == 32), SHDR_E_SHAPE,
                "conv2d_x3_prepare_filter: need C %% 32 == 0, Cout %% 64 == 0 (or Cout 32)");
   SHDR_REQUIRE(shdr::aligned16(prepared), SHDR_E_ALIGN, "conv2d_x3_prepare_filter: prepared must be 16-byte aligned");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const float x2s = d->C2 > 0 ? d->x2_scale : 1.0f;
   X3Phase ph[4];
   const int n = x3_phases(d, ph);
@@ -1386,13 +1319,11 @@ extern "C" int shdr_conv2d_x3_prepare_filter_premax_f32(const shdr_conv2d_desc* 
   SHDR_REQUIRE(!premax || n == 1, SHDR_E_SHAPE, "conv2d_x3_prepare_filter: premax is for single-phase (stride-1) layers");
   for (int i = 0; i < n; ++i) {
     if (!premax) {
-      if (hipMemsetAsync(out, 0, X3_HEADER_FLOATS * sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_x3_prepare_filter: memset");
-      // <= 64 blocks: every wave ends with an atomicMax on ONE address (2048 blocks took 50 us on a 9 MB filter, this takes 6)
-      const int gmax = shdr::stream_grid(nw) < 64 ? shdr::stream_grid(nw) : 64;
-      hipLaunchKernelGGL(x3_absmax_kernel, dim3(gmax), dim3(256), 0, st, w, nw, reinterpret_cast<unsigned*>(out));
+      if (hipMemsetAsync(out, 0, shdr::kSplitHeaderFloats * sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_x3_prepare_filter: memset");
+      shdr::launch_split_absmax(w, nw, reinterpret_cast<unsigned*>(out) + shdr::kHdrMaxW, st);
     }
     const long np = (long)ph[i].th * ph[i].tw * Ct * ((d->Cout + 63) / 64 * 64);
-    hipLaunchKernelGGL(x3_pack_kernel, dim3(shdr::stream_grid(np)), dim3(256), 0, st, w, out, reinterpret_cast<_Float16*>(out + X3_HEADER_FLOATS), Ct,
+    hipLaunchKernelGGL(x3_pack_kernel, dim3(shdr::stream_grid(np)), dim3(256), 0, st, w, out, reinterpret_cast<_Float16*>(out + shdr::kSplitHeaderFloats), Ct,
                        d->C1, d->Cout, x2s, d->KW, ph[i].th, ph[i].tw, ph[i].p0, ph[i].q0, ph[i].step);
     out += x3_phase_floats(ph[i], Ct, d->Cout);
   }
@@ -1404,7 +1335,7 @@ extern "C" int shdr_conv2d_x3_prepare_filter_premax_f32(const shdr_conv2d_desc* 
 extern "C" int shdr_absmax_f32(const float* x, int64_t n, float* range, void* stream) {
   SHDR_REQUIRE(x && range, SHDR_E_NULL, "absmax: null pointer");
   SHDR_REQUIRE(n > 0, SHDR_E_SHAPE, "absmax: n must be positive");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   unsigned* slot = reinterpret_cast<unsigned*>(range);
   const int64_t n4 = shdr::aligned16(x) ? n / 4 : 0;
   if (n4 > 0) {
@@ -1412,15 +1343,15 @@ extern "C" int shdr_absmax_f32(const float* x, int64_t n, float* range, void* st
     if (grid > 1024) grid = 1024;
     hipLaunchKernelGGL(x3_absmax_big_kernel, dim3(grid), dim3(256), 0, st, x, (long)n4, slot);
   }
-  if (n - 4 * n4 > 0) hipLaunchKernelGGL(x3_absmax_kernel, dim3(n4 > 0 ? 1 : (shdr::stream_grid(n) < 64 ? shdr::stream_grid(n) : 64)), dim3(256), 0, st, x + 4 * n4, (long)(n - 4 * n4), slot);
+  if (n - 4 * n4 > 0) shdr::launch_split_absmax(x + 4 * n4, (long)(n - 4 * n4), slot, st);      // the tail (n4 > 0: at most three elements, one block)
   return shdr::check_launch("absmax");
 }
 
-// the range slot inside a prepared filter's header (slot 2): the low-level protocol of desc.prologue = SHDR_PROLOGUE_RANGE_SCALE
+// the range slot inside a prepared filter's header (kHdrInputRange): the low-level protocol of desc.prologue = SHDR_PROLOGUE_RANGE_SCALE
 extern "C" int shdr_conv2d_x3_input_absmax_f32(const float* x, int64_t n, float* prepared, void* stream) {
   SHDR_REQUIRE(x && prepared, SHDR_E_NULL, "conv2d_x3_input_absmax: null pointer");
   SHDR_REQUIRE(n > 0 && n % 4 == 0 && shdr::aligned16(x), SHDR_E_SHAPE, "conv2d_x3_input_absmax: n must be a positive multiple of 4, x 16-byte aligned");
-  return shdr_absmax_f32(x, n, prepared + 2, stream);
+  return shdr_absmax_f32(x, n, prepared + shdr::kHdrInputRange, stream);
 }
 
 static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x2, const float* prepared, const float* bias,
@@ -1460,13 +1391,13 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
   SHDR_REQUIRE(!residual || (d->stride == 1 && d->res_cstride >= d->Cout && d->res_cstride % 4 == 0 && shdr::aligned16(residual) && !y_pool && !proj), SHDR_E_SHAPE,
                "conv2d_x3: the residual takes a stride-1 layer, res_cstride >= Cout (a multiple of 4), a 16-byte aligned tensor, no pooled / projected output");
   a.res = residual; a.res_cs = d->res_cstride;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   X3Phase ph[4];
   const int n = x3_phases(d, ph);
   const int Ct = d->C1 + d->C2;
   a.hdr = prepared;
-  a.wp = reinterpret_cast<const _Float16*>(prepared + X3_HEADER_FLOATS);
-  if (rs && !x1_range) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + 2;      // the header-slot protocol (shdr_conv2d_x3_input_absmax_f32)
+  a.wp = reinterpret_cast<const _Float16*>(prepared + shdr::kSplitHeaderFloats);
+  if (rs && !x1_range) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + shdr::kHdrInputRange;      // the header-slot protocol (shdr_conv2d_x3_input_absmax_f32)
   a.in_s = ph[0].step; a.bh = ph[0].bh; a.bw = ph[0].bw;
   if (n == 4) {
     // the stride-2 stem in ONE launch: the phases' packed sub-filters share the scale 2^S (each header's maximum is taken over the whole
@@ -1476,7 +1407,7 @@ static int x3_forward(const shdr_conv2d_desc* d, const float* x1, const float* x
     for (int i = 0; i < 4; ++i) {
       SHDR_REQUIRE(ph[i].th <= 4 && ph[i].tw <= 4 && ph[i].step == ph[0].step, SHDR_E_SHAPE, "conv2d_x3: unexpected phase geometry");
       a.pth[i] = ph[i].th; a.ptw[i] = ph[i].tw; a.pbh[i] = ph[i].bh; a.pbw[i] = ph[i].bw;
-      a.pwp[i] = reinterpret_cast<const _Float16*>(pk + X3_HEADER_FLOATS);
+      a.pwp[i] = reinterpret_cast<const _Float16*>(pk + shdr::kSplitHeaderFloats);
       pk += x3_phase_floats(ph[i], Ct, d->Cout);
     }
     return launch_x3<false, 4, 4, true>(a, st);

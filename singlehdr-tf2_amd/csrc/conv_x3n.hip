@@ -12,7 +12,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "split.h"
 
 namespace {
 
@@ -21,8 +21,6 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
-
-constexpr int XN_HEADER_FLOATS = 16;                            // [0] max |w| (bits), [1] 2^-S
 
 __device__ __attribute__((aligned(16))) float g_xn_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -43,53 +41,6 @@ struct X3nArgs {
   const unsigned* xr2;
   unsigned* yr;            // range slot of the output: atomicMax of max |y| (null: not wanted)
 };
-
-// conv_x3.hip: x3_range_scale / x3_split4 / x3_range_out (the same arithmetic; kept per translation unit)
-__device__ __forceinline__ void xn_range_scale(const unsigned* r1, const unsigned* r2, float& xs, float& ixs) {
-  xs = 1.0f;
-  ixs = 1.0f;
-  unsigned b = r1 ? *r1 : 0u;
-  if (r2) {
-    const unsigned b2 = *r2;
-    b = b2 > b ? b2 : b;
-  }
-  if (b != 0u && b < 0x7f800000u) {
-    int ex;
-    frexpf(__uint_as_float(b), &ex);
-    int T = 11 - ex;
-    T = T < -126 ? -126 : (T > 126 ? 126 : T);
-    xs = ldexpf(1.0f, T);
-    ixs = ldexpf(1.0f, -T);
-  }
-}
-__device__ __forceinline__ void xn_split4(const f32x4 v, float xs, unsigned (&h)[2], unsigned (&l)[2]) {
-  const float k2048 = 2048.0f;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float t0, t1;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h[p]) : "v"(v[2 * p]), "s"(xs));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h[p]) : "v"(v[2 * p + 1]), "s"(xs));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(v[2 * p]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(v[2 * p + 1]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l[p]) : "v"(t0), "s"(k2048));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l[p]) : "v"(t1), "s"(k2048));
-  }
-}
-// max |y| of a persistent block -> the range slot: one atomicMax per BLOCK (conv_x3.hip x3_range_out: the blocks all finish together,
-// same-address atomics execute one after the other at the memory side); the waves' maxima meet in four LDS words behind the images
-__device__ __forceinline__ void xn_range_out(unsigned* slot, float m, int lane, int wave, unsigned* lds) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  if (lane == 0) lds[wave] = __float_as_uint(m);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  if (threadIdx.x == 0) {
-    const unsigned b01 = lds[0] > lds[1] ? lds[0] : lds[1], b23 = lds[2] > lds[3] ? lds[2] : lds[3];
-    const unsigned b = b01 > b23 ? b01 : b23;
-#ifndef SHDR_ABL_NO_RANGE_ATOMIC
-    if (b > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, b);
-#endif
-  }
-}
 
 struct __attribute__((packed, aligned(4))) f32x3u { float x, y, z; };      // 12 bytes at 4-byte alignment: global_load / store_dwordx3
 
@@ -118,7 +69,7 @@ struct NG {
   static constexpr int FILT_HALVES = FULL_STEPS * COUT * 32 + (HALF ? COUT * 16 : 0);      // one image
   static constexpr int FINSTR = FULL_STEPS * COUT / 16;        // filter DMA instructions per image for the full steps (16 rows of 64 bytes each)
   static constexpr int IMAGE_BYTES = (2 * FILT_HALVES + 2 * PATCH_HALVES) * 2;
-  static constexpr int LDS_BYTES = IMAGE_BYTES + 16;           // + the waves' output maxima (xn_range_out)
+  static constexpr int LDS_BYTES = IMAGE_BYTES + 16;           // + the waves' output maxima (shdr::range_out)
 };
 
 // TANH: the epilogue knows SHDR_ACT_TANH (instantiated for the 16-cout single-source layers only: shdr_conv2d_x3n_ok_f32)
@@ -244,7 +195,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
       if (pdst[j] < 0) continue;
       if (ASM_LOADS) {
         unsigned h[2], l[2];
-        xn_split4(pr[j], xs, h, l);
+        shdr::split4(pr[j], xs, h, l);
         *reinterpret_cast<uint2*>(patch_h + pdst[j]) = make_uint2(h[0], h[1]);
         *reinterpret_cast<uint2*>(patch_l + pdst[j]) = make_uint2(l[0], l[1]);
       } else {                                                 // the 7x7 image layers: compiler-scheduled split as well (0.16 vs 0.20 ms with the asm form)
@@ -295,9 +246,9 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
   int tile = blockIdx.x;
   if (tile < a.ntiles) load_patch(tile);
 #ifndef SHDR_ABL_NO_SCALE
-  xn_range_scale(a.xr1, a.xr2, xs, ixs);                     // behind the first patch loads: the slot's round trip hides under theirs
+  shdr::range_scale(a.xr1, a.xr2, xs, ixs);                     // behind the first patch loads: the slot's round trip hides under theirs
 #endif
-  const float inv_s = a.hdr[1] * ixs;
+  const float inv_s = a.hdr[shdr::kHdrInvScale] * ixs;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's pieces of the filter (LDS-DMA) have landed
   int stores_since = -1;                                        // output store instructions this wave issued after its last patch loads (-1: unknown)
   for (; tile < a.ntiles; tile += gridDim.x) {
@@ -465,7 +416,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
     }
   }
 #ifndef SHDR_ABL_NO_TAIL
-  if (a.yr) xn_range_out(a.yr, ym, lane, wave, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(nsm) + G::IMAGE_BYTES));                        // once per persistent block and wave (a pooled output has the same bound)
+  if (a.yr) shdr::range_out<4, true>(a.yr, ym, lane, wave, 0u, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(nsm) + G::IMAGE_BYTES));                        // once per persistent block and wave (a pooled output has the same bound)
 #endif
 #undef filt_h
 #undef filt_l
@@ -473,26 +424,14 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
 #undef patch_l
 }
 
-// max |w| -> hdr[0] (bits)
-__global__ __launch_bounds__(256) void x3n_absmax_kernel(const float* __restrict__ w, long n, unsigned* __restrict__ out) {
-  float m = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
-}
 // packed[image][step][co][k]: k = (tap, channel) in natural order, CT channels per tap (the source's C1 [+ C2] real ones, zero beyond),
 // zero beyond the last tap and beyond the real couts; w * x2-scale * 2^S split into wh, wl
 __global__ __launch_bounds__(256) void x3n_pack_kernel(const float* __restrict__ w, float* __restrict__ hdr, _Float16* __restrict__ out, int ntaps,
                                                        int CT, int C1, int Creal, int cout_real, int Cout_w, int COUT, int NS, float x2_scale,
                                                        int half_last) {
-  const float mx = fmaxf(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[0]) * fmaxf(1.0f, fabsf(x2_scale)), 1e-30f);
-  int ex;
-  frexpf(mx, &ex);
-  int S = 14 - ex;
-  S = S < -100 ? -100 : (S > 100 ? 100 : S);
-  const float s = ldexpf(1.0f, S);
-  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[1] = ldexpf(1.0f, -S);
+  float inv;
+  const float s = shdr::weight_scale(hdr, x2_scale, inv);
+  if (blockIdx.x == 0 && threadIdx.x == 0) hdr[shdr::kHdrInvScale] = inv;
   // half_last (NG::HALF): the last k-step holds one 16-channel tap: rows of 16 halves instead of 32
   const long full = (long)(NS - (half_last ? 1 : 0)) * COUT * 32;
   const long total = full + (half_last ? COUT * 16 : 0);
@@ -591,29 +530,26 @@ extern "C" int64_t shdr_conv2d_x3n_filter_elems_f32(const shdr_conv2d_desc* d) {
   if (!d || d->KH <= 0 || !(d->Cout == 16 || d->Cout == 32 || d->Cout == 64)) return -1;
   const int ct = ct_of(d);
   const int64_t ns = (d->KH * d->KW * ct + 31) / 32;
-  return XN_HEADER_FLOATS + ns * d->Cout * 32;               // header + two fp16 images, in floats
+  return shdr::kSplitHeaderFloats + ns * d->Cout * 32;               // header + two fp16 images, in floats
 }
 
 // w: HWIO [KH][KW][C1 + C2][cout_w] with cout_w = the filter tensor's channel count (>= cout_valid; the desc's Cout may be its padding)
-extern "C" int shdr_conv2d_x3n_prepare_filter_premax_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, int premax, void* stream);
 extern "C" int shdr_conv2d_x3n_prepare_filter_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, void* stream) {
   return shdr_conv2d_x3n_prepare_filter_premax_f32(d, w, prepared, 0, stream);
 }
-// premax: header slot 0 already holds max |w| (conv_x3.hip: shdr_conv2d_x3_prepare_filter_premax_f32)
 extern "C" int shdr_conv2d_x3n_prepare_filter_premax_f32(const shdr_conv2d_desc* d, const float* w, float* prepared, int premax, void* stream) {
   SHDR_REQUIRE(d && w && prepared, SHDR_E_NULL, "conv2d_x3n_prepare_filter: null pointer");
   SHDR_REQUIRE(shdr::aligned16(prepared), SHDR_E_ALIGN, "conv2d_x3n_prepare_filter: prepared must be 16-byte aligned");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const int ct = ct_of(d), Creal = d->C1 + d->C2, ntaps = d->KH * d->KW, ns = (ntaps * ct + 31) / 32;
   const int cv = d->cout_valid > 0 ? d->cout_valid : d->Cout;
   const long nw = (long)ntaps * Creal * d->Cout;             // the filter tensor handed over has the desc's (padded) Cout columns
   if (!premax) {
-    if (hipMemsetAsync(prepared, 0, XN_HEADER_FLOATS * sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_x3n_prepare_filter: memset");
-    hipLaunchKernelGGL(x3n_absmax_kernel, dim3(shdr::stream_grid(nw) < 64 ? shdr::stream_grid(nw) : 64), dim3(256), 0, st, w, nw,
-                       reinterpret_cast<unsigned*>(prepared));
+    if (hipMemsetAsync(prepared, 0, shdr::kSplitHeaderFloats * sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "conv2d_x3n_prepare_filter: memset");
+    shdr::launch_split_absmax(w, nw, reinterpret_cast<unsigned*>(prepared) + shdr::kHdrMaxW, st);
   }
   hipLaunchKernelGGL(x3n_pack_kernel, dim3(shdr::stream_grid((long)ns * d->Cout * 32)), dim3(256), 0, st, w, prepared,
-                     reinterpret_cast<_Float16*>(prepared + XN_HEADER_FLOATS), ntaps, ct, d->C1, Creal, cv, d->Cout, d->Cout, ns,
+                     reinterpret_cast<_Float16*>(prepared + shdr::kSplitHeaderFloats), ntaps, ct, d->C1, Creal, cv, d->Cout, d->Cout, ns,
 #ifdef SHDR_ABL_X3N_NO_HALF
                      d->C2 > 0 ? d->x2_scale : 1.0f, 0);
 #else
@@ -637,7 +573,7 @@ extern "C" int shdr_conv2d_fwd_x3n_ranged_f32(const shdr_conv2d_desc* d, const f
   X3nArgs a{};
   a.x1 = x1; a.x2 = x2;
   a.hdr = prepared;
-  a.wp = reinterpret_cast<const _Float16*>(prepared + XN_HEADER_FLOATS);
+  a.wp = reinterpret_cast<const _Float16*>(prepared + shdr::kSplitHeaderFloats);
   a.bias = bias; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
   a.yp = y_pool; a.pool_avg = d->pool == SHDR_POOL_AVG;
   a.N = d->N; a.H = d->H; a.W = d->W; a.C1 = d->C1;
@@ -648,11 +584,11 @@ extern "C" int shdr_conv2d_fwd_x3n_ranged_f32(const shdr_conv2d_desc* d, const f
   SHDR_REQUIRE(!x2 || ((x1_range == nullptr) == (x2_range == nullptr)), SHDR_E_NULL, "conv2d_x3n: give the range of both sources or of neither");
   a.xr1 = reinterpret_cast<const unsigned*>(x1_range);
   a.xr2 = reinterpret_cast<const unsigned*>(x2 ? x2_range : nullptr);
-  if (!x1_range && d->prologue == SHDR_PROLOGUE_RANGE_SCALE) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + 2;   // header-slot protocol
+  if (!x1_range && d->prologue == SHDR_PROLOGUE_RANGE_SCALE) a.xr1 = reinterpret_cast<const unsigned*>(prepared) + shdr::kHdrInputRange;   // header-slot protocol
   a.yr = reinterpret_cast<unsigned*>(y_range);
   a.cout_valid = d->cout_valid > 0 ? d->cout_valid : d->Cout;
   a.res_cs = d->res_cstride;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (d->Cout == 64) return launch_x3n<3, 8, 4, false>(a, st);
   if (d->Cout == 16) {
     if (d->KH == 3) return dispatch_ct<3, 1>(a, d, st);

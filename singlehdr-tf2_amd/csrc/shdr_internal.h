@@ -159,7 +159,14 @@ __global__ __launch_bounds__(256) static void col_fold_kernel(const float* __res
 inline void launch_col_fold(const float* ws, float* out, int g, int C, hipStream_t st) {
   hipLaunchKernelGGL(col_fold_kernel, dim3((C + 15) / 16, (g + 255) / 256), dim3(256), 0, st, ws, out, g, C);
 }
-constexpr int kBiasMaxBlocks = 2048;          // rows of the act_bwd_bias workspace (shdr_workspace_bytes(SHDR_OP_ACT_BWD_BIAS))
+// Bijective XCD-aware remap of a 1-D grid: hardware block ids go round-robin over the 8 XCDs, so consecutive LOGICAL ids -- neighbouring
+// tiles, the cout slices of one tile, the taps of one slice -- share an XCD and its L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+constexpr int kBiasMaxBlocks = 2048;         // rows of the act_bwd_bias workspace (shdr_workspace_bytes(SHDR_OP_ACT_BWD_BIAS))
 
 __device__ __forceinline__ float act_apply(float v, int act) {
   switch (act) {

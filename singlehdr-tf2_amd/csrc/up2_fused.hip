@@ -27,14 +27,16 @@
 
 #include <type_traits>
 
-#include "shdr_internal.h"
+#include "split.h"
 
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using shdr::fma4;
+using shdr::fma4v;
+using shdr::mul4;
 
-constexpr int UF_HEADER_FLOATS = 16;                            // conv_x3.hip: the packed filter's header, [1] = 2^-S
 constexpr int UF_IMG_HALVES = 64 * 32, UF_UNIT_HALVES = 2 * UF_IMG_HALVES;      // one (slice, chunk) unit: wh, wl images [64 couts][32 channels]
 constexpr int UF_R = 8;                                         // patch rows: interior 6 x 14 of a 8 x 16 patch
 constexpr int UF_COLS = 14;                                     // interior columns of the 16 lanes
@@ -48,7 +50,7 @@ constexpr int uf_stride(int CMAX) { return CMAX == 32 ? 32 : CMAX + 8; }
 struct UpFusedArgs {
   const float* x;          // [N, h, w, C1] low-res
   const _Float16* wp;      // packed 1x1 filter [9 (+ pad) slices][C1 / 32 chunks][wh, wl][64][32]
-  const float* hdr;        // hdr[1] = 2^-S
+  const float* hdr;        // hdr[kHdrInvScale] = 2^-S
   const float* bias;
   const float* scale;
   const float* shift;
@@ -61,54 +63,6 @@ struct UpFusedArgs {
   int npatch;              // N nty ntx
 };
 
-// conv_x3.hip's x3_range_scale for one source: 2^T brings the bound into [2^10, 2^11); 1 for an empty, zero or non-finite bound
-__device__ __forceinline__ void uf_range_scale(const unsigned* r, float& xs, float& ixs) {
-  xs = 1.0f;
-  ixs = 1.0f;
-  const unsigned b = r ? *r : 0u;
-  if (b != 0u && b < 0x7f800000u) {
-    int ex;
-    frexpf(__uint_as_float(b), &ex);
-    int T = 11 - ex;
-    T = T < -126 ? -126 : (T > 126 ? 126 : T);
-    xs = ldexpf(1.0f, T);
-    ixs = ldexpf(1.0f, -T);
-  }
-}
-// conv_x3.hip's x3_split4: one float4 -> (fp16(v xs), fp16((v xs - fp16(v xs)) 2^11)) as packed pairs
-__device__ __forceinline__ void uf_split4(const f32x4 v, float xs, unsigned (&h)[2], unsigned (&l)[2]) {
-  const float k2048 = 2048.0f;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float t0, t1;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h[p]) : "v"(v[2 * p]), "s"(xs));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h[p]) : "v"(v[2 * p + 1]), "s"(xs));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(v[2 * p]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(v[2 * p + 1]), "s"(xs), "v"(h[p]));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l[p]) : "v"(t0), "s"(k2048));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l[p]) : "v"(t1), "s"(k2048));
-  }
-}
-
-// explicit multiplies and fused multiply-adds, as in up2_lowres.hip
-__device__ __forceinline__ f32x4 mul4(f32x4 a, float s) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __fmul_rn(a[e], s);
-  return r;
-}
-__device__ __forceinline__ f32x4 fma4(f32x4 a, float s, f32x4 c) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a[e], s, c[e]);
-  return r;
-}
-__device__ __forceinline__ f32x4 fma4v(f32x4 a, f32x4 s, f32x4 c) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a[e], s[e], c[e]);
-  return r;
-}
 // the value of the lane one to the left / right inside the 16-lane row (DPP row_shr:1 / row_shl:1; the row's first / last lane reads zero:
 // those are the halo lanes, whose sums are not used)
 __device__ __forceinline__ f32x4 from_left(f32x4 a) {
@@ -124,10 +78,6 @@ __device__ __forceinline__ f32x4 from_right(f32x4 a) {
   return r;
 }
 
-__device__ __forceinline__ int uf_xcd_remap(int bid, int nwg) {      // conv_x3.hip: consecutive logical blocks on one XCD (one L2)
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // CW = Cout / 16 waves finish one patch (wave cw of them the couts 16 cw .. 16 cw + 15), so the four waves of a block finish PPB = 4 / CW
 // patches, each with its own pair of images in LDS; a patch past the end of the grid leaves its waves idle (they still reach every barrier).
@@ -147,7 +97,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   const int tid = PPB == 1 ? threadIdx.x : threadIdx.x & (GT - 1);        // among the threads of the patch
   _Float16* const fsm = fsm_all + ps * (2 * IMG);
   const float* const projp = CW == 4 ? a.proj : nullptr;         // the projection is the 64-cout form's
-  int L = uf_xcd_remap(blockIdx.x, gridDim.x) * PPB + ps;
+  int L = shdr::xcd_remap(blockIdx.x, gridDim.x) * PPB + ps;
   const bool patch_ok = PPB == 1 || L < a.npatch;                // wave-uniform
   if (!patch_ok) L = 0;
   const int tx_ = L % a.ntx; L /= a.ntx;
@@ -161,7 +111,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   {
     const int f4n = a.C1 >> 2, total = NPIX * f4n;
     const float* xb = a.x + (size_t)n * a.h * a.w * a.C1;
-    uf_range_scale(a.xr, xs, ixs);
+    shdr::range_scale(a.xr, nullptr, xs, ixs);
 #pragma unroll 1
     for (int id0 = patch_ok ? tid : total; id0 < total; id0 += 4 * GT) {
       f32x4 v[4];
@@ -181,7 +131,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
       for (int k = 0; k < 4; ++k) {
         if (dst[k] >= 0) {
           unsigned h[2], l[2];
-          uf_split4(v[k], xs, h, l);
+          shdr::split4(v[k], xs, h, l);
           *reinterpret_cast<uint2*>(fsm + dst[k]) = make_uint2(h[0], h[1]);
           *reinterpret_cast<uint2*>(fsm + IMG + dst[k]) = make_uint2(l[0], l[1]);
         }
@@ -197,7 +147,7 @@ __global__ __launch_bounds__(UF_THREADS, 2) void up2_fused_kernel(const UpFusedA
   // taps whose hi-res column falls outside the image drop out (up2_lowres_stencil_kernel)
   const float wl0 = j0 >= 1 ? 0.75f : 0.0f, wl1 = j0 >= 1 ? 0.25f : 0.0f;
   const float wr0 = j0 + 1 < a.w ? 0.25f : 0.0f, wr1 = j0 + 1 < a.w ? 0.75f : 0.0f;
-  const float inv_s = a.hdr[1] * ixs;
+  const float inv_s = a.hdr[shdr::kHdrInvScale] * ixs;
   const _Float16* wlane = a.wp + p * 32 + 8 * fg;                // A operand: row (lane & 15) of the wave's 16 couts, channels 8 fg .. 8 fg + 7 of the chunk
   const _Float16* xlane = fsm + p * UF_STRIDE + 8 * fg;          // B operand: patch pixel (q, p), the same channels; + 16 q UF_STRIDE, + 32 c
 
@@ -481,7 +431,7 @@ extern "C" int shdr_conv2d_fwd_up2_fused_f32(const shdr_conv2d_desc* d, const fl
                    (!scale || (shdr::aligned16(scale) && shdr::aligned16(shift))) && (!proj || shdr::aligned16(proj)),
                SHDR_E_ALIGN, "conv2d_up2_fused: tensors must be 16-byte aligned");
   UpFusedArgs a{};
-  a.x = x; a.hdr = prepared; a.wp = reinterpret_cast<const _Float16*>(prepared + UF_HEADER_FLOATS);
+  a.x = x; a.hdr = prepared; a.wp = reinterpret_cast<const _Float16*>(prepared + shdr::kSplitHeaderFloats);
   a.bias = bias; a.scale = scale; a.shift = shift; a.proj = proj; a.y = y; a.yproj = y_proj;
   a.xr = reinterpret_cast<const unsigned*>(x_range); a.yr = reinterpret_cast<unsigned*>(y_range);
   a.N = d->N; a.h = d->H / 2; a.w = d->W / 2; a.C1 = d->C1; a.act1 = d->act1; a.act2 = d->act2;

@@ -13,14 +13,18 @@
 // A/B switch SHDR_NO_UP2_LOWRES=1.
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "split.h"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-constexpr size_t kRangeScratch = 256;         // tail of the workspace: the slot of an input that arrives without a range
+using shdr::fma4;
+using shdr::fma4v;
+using shdr::kRangeScratch;
+using shdr::mul4;
+using shdr::up256;
+
 // z columns: 9 Cout rounded up to the blocks of launch_x3_1x1 -- 256 couts per block (each input chunk split once per 256 couts) where
 // that pads at most an eighth (9 x 128 = 1152 -> 1280: 128^2 x 256 -> 1152 at batch 16 0.74 -> 0.655 ms, the layer 1.09 - 1.13 -> 1.00 - 1.03),
 // else 128 (9 x 64 = 576 -> 640); SHDR_UP2_LOWRES_PAD=128|256 forces one (A/B)
@@ -61,35 +65,9 @@ struct UpLowArgs {
   int N, h, w, Cout, Cp, rows, nseg, nstrip, ncs, act1, act2;
 };
 
-// every product and sum of the pass is one of these: explicit multiplies and fused multiply-adds, so the roundings of a pixel do not depend
-// on how the compiler contracts or unrolls (the row walk is unrolled by three; its copies must agree to the bit)
-__device__ __forceinline__ f32x4 mul4(f32x4 a, float s) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __fmul_rn(a[e], s);
-  return r;
-}
-__device__ __forceinline__ f32x4 fma4(f32x4 a, float s, f32x4 c) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a[e], s, c[e]);
-  return r;
-}
-__device__ __forceinline__ f32x4 fma4v(f32x4 a, f32x4 s, f32x4 c) {
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a[e], s[e], c[e]);
-  return r;
-}
-
-__device__ __forceinline__ int ul_xcd_remap(int bid, int nwg) {      // conv_x3.hip: consecutive logical blocks on one XCD (one L2)
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 __global__ __launch_bounds__(256, 2) void up2_lowres_stencil_kernel(const UpLowArgs a) {
   const int tid = threadIdx.x;
-  int L = ul_xcd_remap(blockIdx.x, gridDim.x);
+  int L = shdr::xcd_remap(blockIdx.x, gridDim.x);
   const int cs = L % a.ncs; L /= a.ncs;
   const int strip = L % a.nstrip; L /= a.nstrip;
   const int seg = L % a.nseg;

@@ -39,10 +39,6 @@ struct WgradHArgs {
 
 constexpr int PK = 32;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 template <int T>
 __host__ __device__ constexpr int win_swz(int p) {
@@ -78,7 +74,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void wgrad_f16_kernel(c
   // 1-D grid, XCD-aware: consecutive logical ids share an XCD (and its L2), and the taps of one (tile, pixel slice) are consecutive --
   // the nine blocks that stream the same X / dZ slice fetch it into ONE L2 instead of eight
   const int ntaps = a.KH * a.KW;
-  int t = xcd_remap(blockIdx.x, gridDim.x);
+  int t = shdr::xcd_remap(blockIdx.x, gridDim.x);
   const int tap = t % ntaps; t /= ntaps;
   const int tn = t % a.tiles_n; t /= a.tiles_n;
   const int tm = t % a.tiles_m; t /= a.tiles_m;
@@ -354,7 +350,7 @@ extern "C" int shdr_conv2d_wgrad_f16(const shdr_conv2d_desc* d, const void* x, i
   a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo;
   a.npix = d->N * d->Ho * d->Wo;
   a.x_scale = which ? d->x2_scale : 1.0f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   // 256-wide tiles (8 waves, one block per CU) halve the L2 -> LDS traffic per flop of the widest layers
   long min256 = 4096;
   if (const char* e = SHDR_ENV("SHDR_WGRAD_256_MIN_PIXELS")) min256 = atol(e);

@@ -18,7 +18,7 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "split.h"
 
 namespace {
 
@@ -47,45 +47,21 @@ struct WgradXArgs {
 
 constexpr int PK = 32;
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 template <int T>
 __host__ __device__ constexpr int win_swz(int p) {
   return T >= 128 ? ((p & 3) | (((p >> 3) & 1) << 2)) : T == 64 ? (((p >> 1) & 1) | (((p >> 3) & 1) << 1)) : T == 32 ? ((p >> 3) & 1) : 0;
 }
-// exponent T of the power of two that brings the bound in the slot to [2^10, 2^11) (0 for an empty, zero or non-finite slot) -- the ONE
-// place the split pass and the kernel take it from
-__device__ __forceinline__ int range_exponent(const unsigned* slot) {
-  const unsigned b = slot ? *slot : 0u;
-  if (b == 0u || b >= 0x7f800000u) return 0;
-  int ex;
-  frexpf(__uint_as_float(b), &ex);
-  const int T = 11 - ex;
-  return T < -126 ? -126 : (T > 126 ? 126 : T);
-}
-
 // x -> (fp16(x 2^T), fp16((x 2^T - high) 2^11)), 8 elements (two 16-byte stores) per thread and iteration
 __global__ __launch_bounds__(256) void x3_split_planes_kernel(const float* __restrict__ x, long n8, const unsigned* __restrict__ slot,
                                                               _Float16* __restrict__ hi, _Float16* __restrict__ lo) {
-  const float s = ldexpf(1.0f, range_exponent(slot)), k2048 = 2048.0f;
+  const float s = ldexpf(1.0f, shdr::range_exponent(slot));
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
     const f32x4 a = reinterpret_cast<const f32x4*>(x)[2 * i], b = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const float v0 = p < 2 ? a[2 * p] : b[2 * p - 4], v1 = p < 2 ? a[2 * p + 1] : b[2 * p - 3];
-      float t0, t1;
-      asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h[p]) : "v"(v0), "s"(s));
-      asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h[p]) : "v"(v1), "s"(s));
-      asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(t0) : "v"(v0), "s"(s), "v"(h[p]));
-      asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(t1) : "v"(v1), "s"(s), "v"(h[p]));
-      asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l[p]) : "v"(t0), "s"(k2048));
-      asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l[p]) : "v"(t1), "s"(k2048));
-    }
-    reinterpret_cast<uint4*>(hi)[i] = make_uint4(h[0], h[1], h[2], h[3]);
-    reinterpret_cast<uint4*>(lo)[i] = make_uint4(l[0], l[1], l[2], l[3]);
+    unsigned h[2][2], l[2][2];
+    shdr::split4(a, s, h[0], l[0]);
+    shdr::split4(b, s, h[1], l[1]);
+    reinterpret_cast<uint4*>(hi)[i] = make_uint4(h[0][0], h[0][1], h[1][0], h[1][1]);
+    reinterpret_cast<uint4*>(lo)[i] = make_uint4(l[0][0], l[0][1], l[1][0], l[1][1]);
   }
 }
 
@@ -106,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int ntaps = a.KH * a.KW;
-  int t = xcd_remap(blockIdx.x, gridDim.x);
+  int t = shdr::xcd_remap(blockIdx.x, gridDim.x);
   const int tap = t % ntaps; t /= ntaps;
   const int tn = t % a.tiles_n; t /= a.tiles_n;
   const int tm = t % a.tiles_m; t /= a.tiles_m;
@@ -234,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
   }
 
   // D[ci][co]: lane holds column co = lane & 15 of rows ci = 4 * (lane >> 4) + e; dW += x_scale 2^-(Tx+Tz) (hi + 2^-11 lo)
-  const float sc = a.x_scale * ldexpf(1.0f, -range_exponent(a.xr)) * ldexpf(1.0f, -range_exponent(a.zr));
+  const float sc = a.x_scale * ldexpf(1.0f, -shdr::range_exponent(a.xr)) * ldexpf(1.0f, -shdr::range_exponent(a.zr));
   const int fi = lane & 15, fg = lane >> 4;
   float* out = a.dw + ((size_t)tap * a.Ct + a.ci_off) * a.Cout;
 #pragma unroll
@@ -281,7 +257,7 @@ extern "C" int shdr_x3_split_planes_f32(const float* x, int64_t n, const float* 
   SHDR_REQUIRE(x && range && hi && lo, SHDR_E_NULL, "x3_split_planes: null pointer");
   SHDR_REQUIRE(n > 0 && n % 8 == 0 && shdr::aligned16(x) && shdr::aligned16(hi) && shdr::aligned16(lo), SHDR_E_ALIGN,
                "x3_split_planes: n must be a positive multiple of 8, pointers 16-byte aligned");
-  hipLaunchKernelGGL(x3_split_planes_kernel, dim3(shdr::stream_grid(n / 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, (long)(n / 8),
+  hipLaunchKernelGGL(x3_split_planes_kernel, dim3(shdr::stream_grid(n / 8)), dim3(256), 0, shdr::stream_of(stream), x, (long)(n / 8),
                      reinterpret_cast<const unsigned*>(range), reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo));
   return shdr::check_launch("x3_split_planes");
 }
@@ -316,7 +292,7 @@ extern "C" int shdr_conv2d_wgrad_x3_f32(const shdr_conv2d_desc* d, const void* x
   a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo;
   a.npix = d->N * d->Ho * d->Wo;
   a.x_scale = which ? d->x2_scale : 1.0f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if ((a.Cx % 128 == 0 || a.Cx % 128 > 64) && a.Cz % 128 == 0) return launch_wgrad_x3<128, 128>(a, st);
   // (96 channels -- the stem of the Linearization-Net: ONE 128-row tile with a quarter of its rows zero, 1.93 ms at 32 x 256^2 against 2.81
   //  on two 64-row tiles and 3.0 on the exact fp32 kernel, split passes included)

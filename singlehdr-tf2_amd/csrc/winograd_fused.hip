@@ -77,10 +77,6 @@ struct WF {
   static constexpr int LDS_BYTES = (EPI_FLOATS > PIPE_FLOATS ? EPI_FLOATS : PIPE_FLOATS) * 4;
 };
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 // UP = true (R = 1): tf.image.resize(x, 2x, BILINEAR) fused in front of the convolution (hallucination_net.py:86,
 // dequantization_net.py:25): the block stages the LOW-RES patch (6 x 10 pixels per 8-channel chunk, a third of the bytes) by
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(512, (R == 1 ? 4 : 2)) void winograd_fused_kernel(c
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
+  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
   const int pn = L / a.nblk_m;
   int pm = L - pn * a.nblk_m;
   const int tx = pm % a.tiles_x;
@@ -463,7 +459,7 @@ extern "C" int shdr_conv2d_winograd_fused2_f32(const float* x, const float* x2, 
   a.x = x; a.x2 = x2 ? x2 : x; a.u = u; a.bias = bias; a.scale = scale; a.shift = shift; a.y = y; a.yp = y_pool;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.C1 = C1; a.Cout = Cout;
   a.act1 = act1; a.act2 = act2;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   // The 16 x 16 tile (one block per CU, half the filter bytes per MFMA) was measured equal on wide layers and 5..10 % slower on
   // narrow ones (the kernel is not bound by the filter stream): it stays selectable for experiments only.
   const char* force = SHDR_ENV("SHDR_WINOGRAD_TILE");        // "16": the tall tile
@@ -493,5 +489,5 @@ extern "C" int shdr_conv2d_winograd_fused_up2_f32(const float* x, const float* u
   a.x = x; a.x2 = x; a.u = u; a.bias = bias; a.scale = scale; a.shift = shift; a.y = y; a.yp = nullptr;
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.C1 = Cin; a.Cout = Cout; a.Hl = H / 2; a.Wl = W / 2;
   a.act1 = act1; a.act2 = act2;
-  return launch_fused<1, true>(a, reinterpret_cast<hipStream_t>(stream));
+  return launch_fused<1, true>(a, shdr::stream_of(stream));
 }

@@ -170,7 +170,7 @@ def range_exponent(bound):
 
 
 def split_planes(x, bound):
-    """(hi, lo) fp16 planes of an fp32 tensor as csrc/wgrad_x3.hip states them: hi = fp16(x 2^T), lo = fp16(fp32(x 2^T - hi) 2^11),
+    """(hi, lo) fp16 planes of an fp32 tensor as shdr::split4 (csrc/split.h) states them: hi = fp16(x 2^T), lo = fp16(fp32(x 2^T - hi) 2^11),
     T = range_exponent(bound), every conversion round-to-nearest-even.  x 2^T is a power-of-two multiple of an fp32 number and
     x 2^T - hi is the residual of a rounding: both are exact before their own single rounding, which is what float64 gives here.
     The kernel forms both products as FMAs with a +0 addend; that shows in one place, the sign of a zero: a -0 input gives +0 planes
@@ -200,7 +200,7 @@ def wgrad_split(x, dz, khw, stride, x_bound, z_bound, x_scale=1.0):
 # the split-operand forward model (csrc/conv_x3.hip, conv_x3n.hip), for tests/test_gpu_conv_x3_exact.py
 # ---------------------------------------------------------------------------------------------------------------------------------
 def weight_exponent(w, x2_scale=1.0):
-    """S of x3_pack_kernel / x3n_pack_kernel: 14 - (frexp exponent of max(max |w| max(1, |x2_scale|), 1e-30)), the product formed in fp32;
+    """S of shdr::weight_scale (csrc/split.h; x3_pack_kernel and x3n_pack_kernel call it): 14 - (frexp exponent of max(max |w| max(1, |x2_scale|), 1e-30)), the product formed in fp32;
     clamped to +-100.  2^S brings the largest filter element to [2^13, 2^14)."""
     f = np.float32
     mx = f(np.abs(np.asarray(w, dtype=np.float32)).max(initial=f(0.0))) * max(f(1.0), abs(f(x2_scale)))
@@ -239,7 +239,7 @@ def common_lsb(*arrays):
 
 def conv_split(x, x2, w, bias, stride, x2_scale, x_bound, x2_bound=None, pad=None, out_hw=None):
     """the split-operand convolution as conv_x3_kernel / conv_x3_1x1_kernel / conv_x3n_kernel compute it, in float64:
-        T = range_exponent(the larger of the two bounds)   (x3_range_scale: ONE scale for both sources)
+        T = range_exponent(the larger of the two bounds)   (shdr::range_scale, csrc/split.h: ONE scale for both sources)
         (xh, xl) = split_planes(concat[x, x2], that bound)  (the second source enters UNSCALED: its scale lives in the filter planes)
         acc = conv(xh, wh) + conv(xl, ws) + conv(xh, wl)    (three MFMAs into one fp32 accumulator; xl wl 2^-11 is dropped)
         z   = acc 2^-(S + T) + bias

@@ -245,12 +245,15 @@ def case(name, plan, n, h, w, c1, c2, cout, k, stride=1, mode="int", epi="plain"
     return pytest.param(o, id=name)
 
 
-def reference(o):
-    """everything of a case that needs no device: operands, the model, the precondition, the expected outputs"""
+def reference(o, bounds=None):
+    """everything of a case that needs no device: operands, the model, the precondition, the expected outputs.  bounds = (x1's, x2's)
+    replaces the slot contents the operands come with (test_unusual_slot_contents)"""
     name, n, h, w, c1, c2, cout, k, stride = (o[f] for f in ("name", "n", "h", "w", "c1", "c2", "cout", "k", "stride"))
     cv = o.get("cv") or cout
     x, xb, x2, x2b, wt = operands(name, n, h, w, c1, c2, cout, k, o["mode"], o["x2s"], o.get("keep", 1.0), o.get("kmax", 2),
                                   cv if cv != cout else None)
+    if bounds is not None:
+        xb, x2b = bounds
     xin = x
     if o.get("up"):                                                      # the descriptor's H, W are the up-sampled ones
         xin = C.resize2x(x.astype(np.float32)).astype(np.float64)
@@ -847,6 +850,38 @@ def test_declared_measured_and_absent_ranges_give_the_same_output(K, lib, o, mon
     for ranges in ("declared", "measured", "none"):
         for preset in (0.0, 1.0e6):
             run_forward(K, lib, o, monkeypatch, r=r, ranges=ranges, preset=preset)
+
+
+# Unusual slot contents in front of every forward reader of a range slot (all of them take T from shdr::range_exponent, csrc/split.h; the
+# split pass of the weight gradient has test_split_planes_slots, the one-launch low-res form tests/test_gpu_up2_narrow.py): the smallest
+# int-mode case of conv_x3_kernel, its bilinear-prologue form, conv_x3_1x1_kernel, conv_x3_wide_kernel and conv_x3n_kernel under an
+# empty slot, infinity, a NaN pattern, a word with the sign bit set (all four: T = 0, the input is split as it stands), a bound that is
+# no power of two and a large one (T = 9 and -5).  A second source holds integers / x2_scale, so its slot holds bound / x2_scale as the
+# harness's own declared bounds do (the same word in both slots would push that source out of the fp16 range and fail the
+# precondition); the slots without a bound go into both as they are.  The two-source cases also take the mixed pairs, in which the
+# larger BIT PATTERN wins and the launch runs unscaled.  The precondition of `reference` holds for every pair below.
+NAN_SLOT = np.uint32(0x7FC5A5A5).view(np.float32)
+SLOT_CONTENTS = [("zero", 0.0), ("inf", np.float32(np.inf)), ("nan_bits", NAN_SLOT), ("sign_bit", -3.0), ("three", 3.0), ("large", 6.0e4)]
+SLOT_READERS = ("x3_c32_64_1x1x1_int", "x3_up_c32_64_1x1x3_int", "x1_two_32_32_scaled_256_1x3x43_int_relu", "xw_c32_128_1x1x1_int",
+                "x3n_two_k3_16_2x17x33_int_scaled")
+
+
+def slot_cases():
+    out = []
+    for o in (named(n).values[0] for n in SLOT_READERS):
+        for tag, b in SLOT_CONTENTS:
+            has_bound = bool(np.isfinite(b)) and b > 0
+            out.append(pytest.param(o, (b, (b / o["x2s"] if has_bound else b) if o["c2"] else None), id="%s-%s" % (o["name"], tag)))
+        if o["c2"]:
+            out.append(pytest.param(o, (np.float32(np.inf), 2.0), id=o["name"] + "-inf_and_two"))
+            out.append(pytest.param(o, (2.0, NAN_SLOT), id=o["name"] + "-two_and_nan_bits"))
+    return out
+
+
+@pytest.mark.parametrize("o, bounds", slot_cases())
+def test_unusual_slot_contents(K, lib, o, bounds, monkeypatch):
+    assert o["mode"] == "int"
+    run_forward(K, lib, o, monkeypatch, r=reference(o, bounds), ranges="declared")
 
 
 @pytest.mark.parametrize("o", [named(n) for n in ("x3_c64_128_3x16x17_fw_lrelu", "x1_c96_256_1x1x127_fxw_relu", "x1_c64_128_1x17x19_fxw_res",

@@ -20,7 +20,7 @@ import up2_fused_ref as U
 import up2_narrow_ref as R
 from conftest import quantised_image, rel_err
 from oracle import nets
-from test_gpu_conv_x3_exact import E_SHAPE, Slot, dev, guarded_f32, same, slot_of
+from test_gpu_conv_x3_exact import E_SHAPE, LIMIT, SLOT_CONTENTS, Slot, dev, guarded_f32, same, slot_of
 from test_gpu_up2_lowres_exact import descriptor
 from test_gpu_wgrad_f32_exact import P, guards_intact, untouched
 
@@ -71,6 +71,21 @@ def test_y_and_range_slot_exact(K, lib, o):
                         opt["scale"], opt["shift"], r["act2"], o["name"], preset)
     same(y, r["y"], o["name"] + " y")
     slot.check(r["ymax"], o["name"])
+
+
+@pytest.mark.parametrize("bound", [b for _, b in SLOT_CONTENTS], ids=[t for t, _ in SLOT_CONTENTS])
+def test_unusual_slot_contents(K, lib, bound):
+    """up2_fused_kernel's share of tests/test_gpu_conv_x3_exact.py::test_unusual_slot_contents: the smallest int-mode case under an empty
+    slot, infinity, a NaN pattern, a word with the sign bit set, a bound that is no power of two and a large one"""
+    o = R.EXACT_CASES[0]
+    assert o["mode"] == "int" and o["epi"] == "none"
+    r = R.exact_reference(o)
+    _, y_ref, gemm, stencil = C.up2_lowres(r["x"], bound, r["w"])
+    assert gemm < LIMIT and stencil < LIMIT, "%s: not exact by construction under the slot %r" % (o["name"], bound)
+    y, slot = fused_abi(K, lib, o["n"], o["h"], o["w"], o["cin"], o["cout"], dev(r["x"]), slot_of(bound), dev(r["w"]), None, r["act1"], None, None,
+                        r["act2"], o["name"])
+    same(y, y_ref, o["name"] + " y")
+    slot.check(float(np.abs(y_ref).max()), o["name"])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
