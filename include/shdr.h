@@ -1254,6 +1254,53 @@ int shdr_jpeg_encode_entropy_batch(const int16_t* coef, int64_t coef_blocks, con
                                    const shdr_jpeg_enc_image* images_dev, int n_images, uint8_t* out, int64_t out_capacity,
                                    int64_t* offsets, int32_t* status, void* workspace, void* stream, float* stage_ms);
 
+/* ---- PNG writer (csrc/png_enc.hip; the rules are csrc/png.h, shared with the host twin) -----------------------------------------
+ * Lossless 8-bit files: bit depth 8, no interlace, C = 1 grey (colour type 0), C = 3 RGB (2), C = 4 RGBA (6); H >= 1, W >= 1 and
+ * H (W C + 1) < 2^31.  No 16-bit samples, no palettes, no ancillary chunks.  A scanline is filtered with one of PNG's five predictors,
+ * the same for every row (SHDR_PNG_FILTER_NONE .. _PAETH) or per row the one whose filtered bytes, read as signed, have the smallest
+ * sum of absolute values, the lowest number on a tie (_ADAPTIVE).  The filtered stream is cut every SHDR_PNG_SEGMENT bytes into
+ * segments that are deflated on their own -- by the Huffman-only encoder or the one with LZ77 matches (shdr_deflate_*) -- and joined
+ * into ONE zlib stream as Z_SYNC_FLUSH joins them: an empty stored block behind every segment but the last, BFINAL in the last, a
+ * stored block wherever the coded segment would not be strictly fewer than n + 5 bytes, the Adler-32 of the whole stream at the end.
+ * One IDAT per segment.  Any PNG reader opens the files; they are larger than zlib level 6 makes them.
+ *
+ * Host (host memory; a negative SHDR_E_* code on failure, see shdr_last_error):
+ *      shdr_crc32            CRC-32 (IEEE, reflected 0xEDB88320: zlib's crc32) of n bytes, continuing from `crc` (0 to start)
+ *      shdr_png_filter_host  pixels uint8 [H][W][C] -> the filtered stream, H (W C + 1) bytes; returns that count
+ *      shdr_png_encode_host  the twin: pixels -> the complete file; returns its length.  A capacity of exactly that length suffices;
+ *                            with less, nothing is written.  shdr_png_encode_batch_sizes of the one image gives an upper bound
+ *
+ * Device, a BATCH of images of different sizes and channel counts in one call:
+ *      pixels      device uint8: the images' [H][W][C] pixels back to back (pixel_bytes of shdr_png_encode_batch_sizes)
+ *      images      int32 [n_images][4]: H, W, C, 0 -- as a host array, which is validated, and as the device copy of that very
+ *                  array (images_dev), which the kernels read
+ *      out         device bytes: the files back to back; out_capacity must be at least the out_bytes of
+ *                  shdr_png_encode_batch_sizes (every segment stored)
+ *      offsets     device int64 [n_images + 1]: file i is out[offsets[i] .. offsets[i + 1])
+ *      workspace   workspace_bytes of shdr_png_encode_batch_sizes (for the same `deflate`), 16-byte aligned, owned by the caller: the
+ *                  filtered streams, the segment tables and the encoder's workspace (with _LZ 4 bytes per filtered byte)
+ *      stage_ms    NULL, or [SHDR_PNG_STAGES] device-event times: tables + filter, the encoder's three launches (sizes and
+ *                  checksums, scan, blocks), framing + CRC (measurement only: the call then waits)
+ * Stream-ordered launches, no global atomics -- the same input gives the same bytes -- no host wait and no allocation.  Arguments are
+ * checked before anything is launched. */
+#define SHDR_PNG_SEGMENT 65520
+#define SHDR_PNG_STAGES 5
+#define SHDR_PNG_FILTER_NONE 0
+#define SHDR_PNG_FILTER_SUB 1
+#define SHDR_PNG_FILTER_UP 2
+#define SHDR_PNG_FILTER_AVERAGE 3
+#define SHDR_PNG_FILTER_PAETH 4
+#define SHDR_PNG_FILTER_ADAPTIVE 5
+#define SHDR_PNG_DEFLATE_HUFFMAN 0
+#define SHDR_PNG_DEFLATE_LZ 1
+uint32_t shdr_crc32(const void* data, uint64_t n, uint32_t crc);
+int64_t shdr_png_filter_host(const uint8_t* pixels, int h, int w, int c, int filter, uint8_t* out, int64_t capacity);
+int64_t shdr_png_encode_host(const uint8_t* pixels, int h, int w, int c, int filter, int deflate, uint8_t* out, int64_t capacity);
+int shdr_png_encode_batch_sizes(const int32_t* images, int n_images, int deflate, int64_t* pixel_bytes, int64_t* out_bytes,
+                                int64_t* n_segments, int64_t* workspace_bytes);
+int shdr_png_encode_batch(const uint8_t* pixels, const int32_t* images, const int32_t* images_dev, int n_images, int filter, int deflate,
+                          uint8_t* out, int64_t out_capacity, int64_t* offsets, void* workspace, void* stream, float* stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2771,6 +2771,115 @@ def jpeg_encode_entropy(coef, images, stage_ms=None, guard=0, info=None):
     return _jpeg_enc_run("shdr_jpeg_encode_entropy_batch", images, coef.device, stage_ms, guard, info, call)
 
 
+# ---------------------------------------------------------------------------
+# PNG writer (png.encode), see csrc/png_enc.hip and csrc/png.h
+# ---------------------------------------------------------------------------
+PNG_SEGMENT = 65520                                             # SHDR_PNG_SEGMENT
+PNG_FILTERS = ("none", "sub", "up", "average", "paeth", "adaptive")   # SHDR_PNG_FILTER_*: the index is the value
+PNG_DEFLATES = ("huffman", "lz")                                # SHDR_PNG_DEFLATE_*
+PNG_STAGE_NAMES = ("filter", "deflate_sizes", "deflate_scan", "deflate_blocks", "frame_crc")   # SHDR_PNG_STAGES
+
+
+def _png_options(what, filter, deflate):
+    if filter not in PNG_FILTERS:
+        raise ValueError("%s: filter must be one of %s, got %r" % (what, ", ".join(PNG_FILTERS), filter))
+    if deflate not in PNG_DEFLATES:
+        raise ValueError("%s: deflate must be 'lz' or 'huffman', got %r" % (what, deflate))
+    return PNG_FILTERS.index(filter), PNG_DEFLATES.index(deflate)
+
+
+def _png_host_image(image, what):
+    """uint8 [H, W] or [H, W, C] host array -> contiguous [H, W, C], C in (1, 3, 4), no empty dimension"""
+    a = np.asarray(image)
+    if a.dtype != np.uint8:
+        raise TypeError("%s: expected uint8 pixels, got %s" % (what, a.dtype))
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3, 4):
+        raise ValueError("%s: expected [H, W] or [H, W, C] with C = 1 (grey), 3 (RGB) or 4 (RGBA), got %s" % (what, a.shape))
+    if 0 in a.shape:
+        raise ValueError("%s: an image has no pixels: %s" % (what, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def crc32(data, crc=0):
+    """CRC-32 (IEEE: zlib.crc32) of bytes by the libshdr host routine"""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    return int(_lib.load().shdr_crc32(_hptr(src) if src.size else None, src.size, crc))
+
+
+def png_filter_host(image, filter="adaptive"):
+    """the filtered stream of one uint8 image [H, W] or [H, W, C] (bytes: per row the filter type and W C filtered bytes), by the
+    libshdr host routine (csrc/png.h)"""
+    lib = _lib.load()
+    a = _png_host_image(image, "png_filter_host")
+    f, _ = _png_options("png_filter_host", filter, "lz")
+    h, w, c = a.shape
+    out = np.empty(h * (w * c + 1), dtype=np.uint8)
+    n = lib.shdr_png_filter_host(_hptr(a), h, w, c, f, _hptr(out), out.size)
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n].tobytes()
+
+
+def png_bound(h, w, c):
+    """no PNG file of an H x W x C image is larger (every segment stored)"""
+    stream = h * (w * c + 1)
+    return 8 + 25 + 12 + 6 + stream + 17 * (-(-stream // PNG_SEGMENT))
+
+
+def png_encode_host(image, filter="adaptive", deflate="lz", capacity=None):
+    """the host twin: the complete PNG file (bytes) of one uint8 image [H, W] or [H, W, C]; capacity: the size of the destination
+    (default: png_bound), a smaller one than the file raises ValueError"""
+    lib = _lib.load()
+    a = _png_host_image(image, "png_encode_host")
+    f, d = _png_options("png_encode_host", filter, deflate)
+    h, w, c = a.shape
+    cap = png_bound(h, w, c) if capacity is None else int(capacity)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n = lib.shdr_png_encode_host(_hptr(a), h, w, c, f, d, _hptr(out), cap)
+    if n < 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    return out[:n].tobytes()
+
+
+def png_encode(pixels, shapes, filter="adaptive", deflate="lz", stage_ms=None, buffers=None):
+    """PNG files of a batch of 8-bit images, written on the device (csrc/png_enc.hip): byte for byte what png_encode_host writes.
+    pixels: uint8 device tensor, the images' [H, W, C] pixels back to back; shapes: their (H, W, C).  Returns (bytes uint8,
+    offsets int64 [n + 1]) on the device: file i is bytes[offsets[i]:offsets[i + 1]].  Stream-ordered, no host wait.  stage_ms: a
+    list that receives the device times of the PNG_STAGE_NAMES (measurement: the call then waits); buffers: a dict that keeps output
+    and workspace for the next call and grows them when needed (both are sized for the worst case; with deflate="lz" the workspace
+    holds 4 bytes per filtered byte) -- the returned bytes are then valid until that call."""
+    lib = _lib.load()
+    pixels = _chk(pixels, "pixels", torch.uint8)
+    f, d = _png_options("png_encode", filter, deflate)
+    images = np.zeros((len(shapes), 4), dtype=np.int32)
+    for i, shape in enumerate(shapes):
+        if len(shape) != 3 or shape[2] not in (1, 3, 4) or min(shape) < 1:
+            raise ValueError("png_encode: image %d is %s: expected (H, W, C) with C = 1, 3 or 4 and no empty dimension" % (i, tuple(shape)))
+        images[i, :3] = shape
+    n = images.shape[0]
+    pix_b, out_b, segs, ws_b = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = lib.shdr_png_encode_batch_sizes(_hptr(images), n, d, ctypes.byref(pix_b), ctypes.byref(out_b), ctypes.byref(segs), ctypes.byref(ws_b))
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+    if pixels.dim() != 1 or pixels.numel() != pix_b.value:
+        raise ValueError("png_encode: pixels must be the %d bytes of these shapes back to back, got %s" % (pix_b.value, tuple(pixels.shape)))
+    dev = pixels.device
+    kept = buffers.get("raw") if buffers is not None else None
+    if kept is None or kept[0].device != dev or kept[0].numel() < out_b.value or kept[1].numel() < ws_b.value:
+        kept = (torch.empty(out_b.value, device=dev, dtype=torch.uint8), torch.empty(ws_b.value, device=dev, dtype=torch.uint8))
+        if buffers is not None:
+            buffers["raw"] = kept
+    out, ws = kept[0][:out_b.value], kept[1][:ws_b.value]
+    offsets = torch.empty(n + 1, device=dev, dtype=torch.int64)
+    images_dev = torch.from_numpy(images).to(dev)
+    with _stage_times(stage_ms, len(PNG_STAGE_NAMES)) as ms:
+        _lib.check(lib.shdr_png_encode_batch(_ptr(pixels), _hptr(images), _ptr(images_dev), n, f, d, _ptr(out), out_b.value, _ptr(offsets),
+                                             _ptr(ws), _stream(), ms), "shdr_png_encode_batch")
+    return out, offsets
+
+
 EXR_HALF, EXR_FLOAT = 1, 2
 
 

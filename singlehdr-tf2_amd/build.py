@@ -60,6 +60,7 @@ SOURCES = {
     "jpeg.hip": ["-ffp-contract=off"],
     "jpeg_scan.hip": [],
     "jpeg_enc.hip": ["-ffp-contract=off"],
+    "png_enc.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]

@@ -63,7 +63,7 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* part) {
 }
 
 __global__ __launch_bounds__(kThreads) void deflate_stats_kernel(const uint8_t* __restrict__ data, const int64_t* __restrict__ offsets,
-                                                                 int64_t total, int pad, Workspace w, uint8_t* __restrict__ coded) {
+                                                                 int64_t total, Framing fr, Workspace w, uint8_t* __restrict__ coded) {
   __shared__ uint32_t hist[4][256];
   __shared__ uint32_t freq[kSyms];
   __shared__ uint8_t len[kLenStride<HuffCodec>];
@@ -86,17 +86,31 @@ __global__ __launch_bounds__(kThreads) void deflate_stats_kernel(const uint8_t* 
   s1 = block_sum_u64(s1 % kAdlerMod, part);
   s2 = block_sum_u64(s2 % kAdlerMod, part);
   for (int s = tid; s < kSyms; s += kThreads) freq[s] = s < 256 ? hist[0][s] + hist[1][s] + hist[2][s] + hist[3][s] : 1u;
-  finish_pass1<HuffCodec>(freq, len, work, tid, kThreads, c, n, pad, s1, s2, w, coded);
+  finish_pass1<HuffCodec>(freq, len, work, tid, kThreads, c, n, fr, s1, s2, w, coded);
 }
 
 __global__ __launch_bounds__(kThreads) void deflate_write_kernel(const uint8_t* __restrict__ data, const uint8_t* __restrict__ raw,
-                                                                 const int64_t* __restrict__ offsets, int64_t total, int pad, Workspace w,
+                                                                 const int64_t* __restrict__ offsets, int64_t total, Framing fr, Workspace w,
                                                                  const uint8_t* __restrict__ coded, const int64_t* __restrict__ out_offsets,
                                                                  uint8_t* __restrict__ out, int64_t capacity) {
-  write_chunk<HuffCodec>(data, raw, offsets, total, pad, w, coded, out_offsets, out, capacity);
+  write_chunk<HuffCodec>(data, raw, offsets, total, fr, w, coded, out_offsets, out, capacity);
 }
 
 }  // namespace
+
+// the same kernels over the segments of PNG images (csrc/png_enc.hip; deflate_batch.h: run_segments)
+namespace shdr_deflate_batch {
+static int64_t segments_workspace(int64_t n_chunks, int64_t total) {
+  return carve(nullptr, n_chunks, kLenStride<HuffCodec>, HuffCodec::kTokens ? total : 0).bytes;
+}
+static void segments_run(const uint8_t* data, const int64_t* offsets_dev, int64_t n_chunks, int64_t total, const uint8_t* seg_dev, uint8_t* out,
+                         int64_t out_capacity, int64_t* out_offsets, uint8_t* coded, void* workspace, hipStream_t st, const uint32_t** adler,
+                         void (*mark)(void*), void* mark_arg) {
+  run_segments<HuffCodec>(deflate_stats_kernel, deflate_write_kernel, data, offsets_dev, n_chunks, total, seg_dev, out, out_capacity, out_offsets, coded, workspace, st,
+                      adler, [&] { mark(mark_arg); });
+}
+SegmentCoder huffman_segments() { return SegmentCoder{segments_workspace, segments_run}; }
+}  // namespace shdr_deflate_batch
 
 extern "C" int64_t shdr_deflate_huffman_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity) {
   int64_t need = 0;

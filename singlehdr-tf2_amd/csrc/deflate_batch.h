@@ -3,10 +3,13 @@
 // and a `Codec`: a struct with kTokens, kPass1Threads, kDeposits, kSyms, kSymbolsAtBit, kTileWords, items, build_lengths, build_codes
 // and thread_bits (HuffCodec, LzCodec).  Here are the workspace, the end of pass 1 (finish_pass1), pass 2 (deflate_scan_kernel, over scan_array of batch.h), the
 // body of pass 3 (write_chunk) and the host side (batch_sizes, run_batch).  Every translation unit gets its own copy.
+// A second framing (Framing, run_segments) codes the segments of PNG images with the same kernels: the block without the zlib bytes,
+// BFINAL per chunk, a sync marker, stored blocks (csrc/png.h has the rules, csrc/png_enc.hip the caller).
 #pragma once
 #include "shdr_internal.h"
 #include "batch.h"
 #include "deflate_huffman.h"
+#include "png.h"
 
 namespace shdr_deflate_batch {
 namespace {                                   // internal linkage: the kernel and its host stub exist once per translation unit
@@ -30,6 +33,13 @@ struct Workspace {                                               // carved out o
   uint32_t* tokens;                                              // [n_tokens] one per input byte where the codec parses, else none
   int64_t bytes;
 };
+// How a chunk is framed.  seg == NULL: a zlib stream of its own behind `pad` free bytes, or its raw bytes (the entry points of shdr.h).
+// seg[c], a PNG segment's flags (png.h): the block alone -- no zlib bytes, BFINAL only with kLast, the sync marker behind every other
+// one -- or one stored block if that is not strictly fewer than n + 5 bytes, between seg_front and seg_back free bytes.
+struct Framing {
+  int pad;
+  const uint8_t* seg;
+};
 inline Workspace carve(void* ws, int64_t c, int len_stride, int64_t n_tokens) {
   Workspace w;
   shdr::Carver cut(ws);
@@ -47,13 +57,22 @@ inline Workspace carve(void* ws, int64_t c, int len_stride, int64_t n_tokens) {
 // bits, the checksum and the stored size: the stream if that is strictly smaller than the chunk, else the chunk.  All store the lengths.
 template <class Codec, class Work>
 __device__ __forceinline__ void finish_pass1(const uint32_t* freq, uint8_t* len, Work& work, int tid, int threads, int64_t c,
-                                             int64_t n, int pad, uint64_t s1, uint64_t s2, const Workspace& w, uint8_t* __restrict__ coded) {
+                                             int64_t n, Framing fr, uint64_t s1, uint64_t s2, const Workspace& w, uint8_t* __restrict__ coded) {
   __syncthreads();
   if (tid == 0) {
-    const int64_t bits = Codec::build_lengths(freq, len, work), stream = stream_bytes(bits);
-    const bool use = n > 0 && stream < n;
+    const int64_t bits = Codec::build_lengths(freq, len, work);
+    bool use;
+    if (fr.seg) {
+      const int flags = fr.seg[c];
+      const int64_t body = shdr_png::coded_bytes(bits - 16, flags & shdr_png::kLast);
+      use = n > 0 && shdr_png::use_coded(body, n);
+      w.sizes[c] = shdr_png::seg_front(flags) + (use ? body : n + 5) + shdr_png::seg_back(flags);
+    } else {
+      const int64_t stream = stream_bytes(bits);
+      use = n > 0 && stream < n;
+      w.sizes[c] = fr.pad + (use ? stream : n);
+    }
     w.bits[c] = bits;
-    w.sizes[c] = pad + (use ? stream : n);
     coded[c] = use ? 1 : 0;
     w.adler[c] = (uint32_t)((((uint64_t)(n % kAdlerMod) + s2) % kAdlerMod) << 16) | (uint32_t)((1 + s1) % kAdlerMod);
   }
@@ -75,7 +94,7 @@ __global__ __launch_bounds__(1024) void deflate_scan_kernel(const int64_t* __res
 // byte and the bit position carry to the next tile; then the tail and the Adler-32.  A chunk that is not coded is copied from `raw`.
 template <class Codec, class Item>
 __device__ __forceinline__ void write_chunk(const Item* __restrict__ items, const uint8_t* __restrict__ raw,
-                                            const int64_t* __restrict__ offsets, int64_t total, int pad, const Workspace& ws,
+                                            const int64_t* __restrict__ offsets, int64_t total, Framing fr, const Workspace& ws,
                                             const uint8_t* __restrict__ coded, const int64_t* __restrict__ out_offsets,
                                             uint8_t* __restrict__ out, int64_t capacity) {
   constexpr int kHeaderBytes = Codec::kSymbolsAtBit / 8 + 1;     // the bytes that hold the bits in front of the symbols
@@ -88,22 +107,37 @@ __device__ __forceinline__ void write_chunk(const Item* __restrict__ items, cons
   const shdr::Span span = shdr::clamped_span(offsets, c, total, kMaxChunk);
   const int64_t lo = span.lo, n = span.n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t at = out_offsets[c] + pad, end = out_offsets[c + 1];
+  const bool png = fr.seg != nullptr;
+  const int flags = png ? fr.seg[c] : 0;
+  const bool last = !png || (flags & shdr_png::kLast);
+  const int64_t at = out_offsets[c] + (png ? shdr_png::seg_front(flags) : fr.pad), end = out_offsets[c + 1] - (png ? shdr_png::seg_back(flags) : 0);
   if (at < 0 || end > capacity || end < at) return;              // never with the sizes the host checked
   uint8_t* dst = out + at;
-  const int64_t room = end - at;
+  int64_t room = end - at;
   if (!coded[c]) {
     const uint8_t* src = raw + lo;
+    if (png) {                                                   // one stored block
+      if (room != n + 5) return;
+      if (tid == 0) shdr_png::put_stored_header(dst, n, last);
+      dst += 5;
+      room -= 5;
+    }
     for (int64_t i = tid; i < n && i < room; i += kThreads) dst[i] = src[i];
     return;
   }
   const int64_t bits = ws.bits[c];
-  if (stream_bytes(bits) != room) return;                        // (pass 1 stored both)
+  if ((png ? shdr_png::coded_bytes(bits - 16, last) : stream_bytes(bits)) != room) return;   // (pass 1 stored both)
+  const int skip = png ? 2 : 0;                                  // the zlib bytes in front: stream byte i goes to dst[i], from `skip` on
+  dst -= skip;                                                   // (at least 8 bytes of the segment's front lie there)
+  room += skip;
   for (int s = tid; s < kLenStride<Codec>; s += kThreads) len[s] = ws.lens[c * kLenStride<Codec> + s];
   __syncthreads();
-  if (tid == 0) Codec::build_codes(len, code, hdr);
+  if (tid == 0) {
+    Codec::build_codes(len, code, hdr);
+    if (!last) hdr[2] &= 0xFEu;                                  // BFINAL
+  }
   __syncthreads();
-  for (int i = tid; i < kHeaderBytes - 1; i += kThreads) dst[i] = hdr[i];
+  for (int i = skip + tid; i < kHeaderBytes - 1; i += kThreads) dst[i] = hdr[i];
   const Item* src = items + lo;
   int64_t P = Codec::kSymbolsAtBit;                              // the stream bit of the tile's first item; the same in every thread
   uint32_t carry = hdr[kHeaderBytes - 1];                        // the bits of byte P / 8 that are already decided
@@ -145,6 +179,16 @@ __device__ __forceinline__ void write_chunk(const Item* __restrict__ items, cons
   if (tid == 0) {
     int64_t o = P >> 3;
     if ((P & 7) && o < room) dst[o++] = (uint8_t)carry;
+    if (png) {
+      if (!last && P == bits) {                                  // the empty stored block: three zero bits, the byte's rest, 00 00 FF FF
+        for (const int64_t e = (P + 3 + 7) >> 3; o < e && o < room; ++o) dst[o] = 0;
+        if (o + 4 == room) {
+          dst[o] = dst[o + 1] = 0;
+          dst[o + 2] = dst[o + 3] = 0xFF;
+        }
+      }
+      return;
+    }
     const uint32_t a = ws.adler[c];
     if (P == bits && o + 4 == room) {
       dst[o] = (uint8_t)(a >> 24); dst[o + 1] = (uint8_t)(a >> 16); dst[o + 2] = (uint8_t)(a >> 8); dst[o + 3] = (uint8_t)a;
@@ -198,15 +242,46 @@ int run_batch(const char* what, Pass1 pass1, Write write, const uint8_t* data, c
   const Workspace w = carve(workspace, n_chunks, kLenStride<Codec>, Codec::kTokens ? total : 0);
   hipStream_t st = shdr::stream_of(stream);
   shdr::StageTimer<SHDR_DEFLATE_STAGES> timer(stage_ms, st);
-  hipLaunchKernelGGL(pass1, dim3((unsigned)n_chunks), dim3(Codec::kPass1Threads), 0, st, data, offsets_dev, total, pad, w, coded);
+  hipLaunchKernelGGL(pass1, dim3((unsigned)n_chunks), dim3(Codec::kPass1Threads), 0, st, data, offsets_dev, total, Framing{pad, nullptr}, w, coded);
   timer.mark();
   hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, st, w.sizes, (int64_t)n_chunks, out_offsets);
   timer.mark();
-  hipLaunchKernelGGL(write, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, Codec::items(data, w), raw ? raw : data, offsets_dev, total, pad,
-                     w, coded, out_offsets, out, out_capacity);
+  hipLaunchKernelGGL(write, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, Codec::items(data, w), raw ? raw : data, offsets_dev, total,
+                     Framing{pad, nullptr}, w, coded, out_offsets, out, out_capacity);
   timer.mark();
   return shdr::check_launch(what);
 }
 
+// The same three launches over the segments of PNG images (csrc/png_enc.hip, which has checked every size): chunk c is
+// data[offsets_dev[c] .. offsets_dev[c + 1]), at most kPngSegment bytes, framed by seg_dev[c]; out_offsets[c] is where its front begins.
+// *adler: the workspace's Adler-32 per segment.  mark: called behind every launch.
+template <class Codec, class Pass1, class Write, class Mark>
+void run_segments(Pass1 pass1, Write write, const uint8_t* data, const int64_t* offsets_dev, int64_t n_chunks, int64_t total,
+                  const uint8_t* seg_dev, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, uint8_t* coded, void* workspace,
+                  hipStream_t st, const uint32_t** adler, Mark mark) {
+  const Workspace w = carve(workspace, n_chunks, kLenStride<Codec>, Codec::kTokens ? total : 0);
+  const Framing fr{0, seg_dev};
+  hipLaunchKernelGGL(pass1, dim3((unsigned)n_chunks), dim3(Codec::kPass1Threads), 0, st, data, offsets_dev, total, fr, w, coded);
+  mark();
+  hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, st, w.sizes, n_chunks, out_offsets);
+  mark();
+  hipLaunchKernelGGL(write, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, Codec::items(data, w), data, offsets_dev, total, fr, w, coded,
+                     out_offsets, out, out_capacity);
+  mark();
+  *adler = w.adler;
+}
+
 }  // namespace
+
+// Defined by csrc/deflate.hip (huffman_segments) and csrc/deflate_lz.hip (lz_segments) over their codecs, for csrc/png_enc.hip: the workspace that
+// run_segments takes for n_chunks segments of `total` bytes, and run_segments itself.
+struct SegmentCoder {
+  int64_t (*workspace_bytes)(int64_t n_chunks, int64_t total);
+  void (*run)(const uint8_t* data, const int64_t* offsets_dev, int64_t n_chunks, int64_t total, const uint8_t* seg_dev, uint8_t* out,
+              int64_t out_capacity, int64_t* out_offsets, uint8_t* coded, void* workspace, hipStream_t st, const uint32_t** adler,
+              void (*mark)(void*), void* mark_arg);
+};
+SegmentCoder huffman_segments();
+SegmentCoder lz_segments();
+
 }  // namespace shdr_deflate_batch

@@ -188,8 +188,9 @@ inline uint32_t adler32_host(const uint8_t* src, int64_t n) {
 }
 
 // The stream of src[0..n) into dst; returns its length, -1 for bad arguments, -2 when `capacity` is less than that length (then
-// *need, if given, receives it and nothing is written).
-inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity, int64_t* need) {
+// *need, if given, receives it and nothing is written).  *stream_bits_out, if given: the bits in front of the padding and the
+// Adler-32 (png.h cuts its segments there).
+inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity, int64_t* need, int64_t* stream_bits_out = nullptr) {
   if (!src || !dst || n < 1 || n > kMaxChunk) return -1;
   uint32_t freq[kSyms];
   uint8_t len[kSyms];
@@ -200,6 +201,7 @@ inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t 
   build_codes(len, code);
   const int64_t bits = stream_bits(freq, len), total = stream_bytes(bits);
   if (need) *need = total;
+  if (stream_bits_out) *stream_bits_out = bits;
   if (capacity < total) return -2;
   write_header(len, dst);
   BitPut b{dst, kHeaderBytes - 1, dst[kHeaderBytes - 1], kSymbolsAtBit & 7};

@@ -243,7 +243,8 @@ inline void parse_host(const uint8_t* src, int64_t n, uint32_t* tokens, uint32_t
 
 // The stream of src[0..n) into dst; returns its length, -1 for bad arguments, -2 when `capacity` is less than that length (then
 // *need, if given, receives it and nothing is written), -3 when the token scratch (4 n bytes) cannot be allocated.
-inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity, int64_t* need) {
+// *stream_bits_out: as in deflate_huffman.h.
+inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity, int64_t* need, int64_t* stream_bits_out = nullptr) {
   if (!src || !dst || n < 1 || n > kMaxChunk) return -1;
   uint32_t* tokens = new (std::nothrow) uint32_t[(size_t)n + kHashSlots];
   if (!tokens) return -3;
@@ -265,6 +266,7 @@ inline int64_t encode_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t 
   build_all_codes(len, code);
   const int64_t bits = stream_bits(freq, len), total = stream_bytes(bits);
   if (need) *need = total;
+  if (stream_bits_out) *stream_bits_out = bits;
   if (capacity < total) {
     delete[] tokens;
     return -2;

@@ -107,7 +107,7 @@ __device__ __forceinline__ uint32_t extend_in_wave(const uint8_t* __restrict__ s
 }
 
 __global__ __launch_bounds__(kGroup) void deflate_lz_parse_kernel(const uint8_t* __restrict__ data, const int64_t* __restrict__ offsets,
-                                                                  int64_t total, int pad, Workspace w, uint8_t* __restrict__ coded) {
+                                                                  int64_t total, Framing fr, Workspace w, uint8_t* __restrict__ coded) {
   __shared__ uint32_t table[kHashSlots];
   __shared__ uint32_t freq[kAllSyms];
   __shared__ uint8_t len[kLenStride<LzCodec>];
@@ -201,17 +201,31 @@ __global__ __launch_bounds__(kGroup) void deflate_lz_parse_kernel(const uint8_t*
   }
   s1 = wave_sum_u64(s1 % kAdlerMod);
   s2 = wave_sum_u64(s2 % kAdlerMod);
-  finish_pass1<LzCodec>(freq, len, work, lane, kGroup, c, n, pad, s1, s2, w, coded);
+  finish_pass1<LzCodec>(freq, len, work, lane, kGroup, c, n, fr, s1, s2, w, coded);
 }
 
 __global__ __launch_bounds__(kThreads) void deflate_lz_write_kernel(const uint32_t* __restrict__ tokens, const uint8_t* __restrict__ raw,
-                                                                    const int64_t* __restrict__ offsets, int64_t total, int pad, Workspace w,
+                                                                    const int64_t* __restrict__ offsets, int64_t total, Framing fr, Workspace w,
                                                                     const uint8_t* __restrict__ coded, const int64_t* __restrict__ out_offsets,
                                                                     uint8_t* __restrict__ out, int64_t capacity) {
-  write_chunk<LzCodec>(tokens, raw, offsets, total, pad, w, coded, out_offsets, out, capacity);
+  write_chunk<LzCodec>(tokens, raw, offsets, total, fr, w, coded, out_offsets, out, capacity);
 }
 
 }  // namespace
+
+// the same kernels over the segments of PNG images (csrc/png_enc.hip; deflate_batch.h: run_segments)
+namespace shdr_deflate_batch {
+static int64_t segments_workspace(int64_t n_chunks, int64_t total) {
+  return carve(nullptr, n_chunks, kLenStride<LzCodec>, LzCodec::kTokens ? total : 0).bytes;
+}
+static void segments_run(const uint8_t* data, const int64_t* offsets_dev, int64_t n_chunks, int64_t total, const uint8_t* seg_dev, uint8_t* out,
+                         int64_t out_capacity, int64_t* out_offsets, uint8_t* coded, void* workspace, hipStream_t st, const uint32_t** adler,
+                         void (*mark)(void*), void* mark_arg) {
+  run_segments<LzCodec>(deflate_lz_parse_kernel, deflate_lz_write_kernel, data, offsets_dev, n_chunks, total, seg_dev, out, out_capacity, out_offsets, coded, workspace, st,
+                      adler, [&] { mark(mark_arg); });
+}
+SegmentCoder lz_segments() { return SegmentCoder{segments_workspace, segments_run}; }
+}  // namespace shdr_deflate_batch
 
 extern "C" int64_t shdr_deflate_lz_host(const uint8_t* src, int64_t n, uint8_t* dst, int64_t capacity) {
   int64_t need = 0;

@@ -240,10 +240,23 @@ def rgbe_decode(rgbe):
 
 
 def _check_preview_encoder(encoder, path, what):
-    if encoder not in ("pil", "device"):
-        raise ValueError("%s: the preview encoder must be 'pil' or 'device', got %r" % (what, encoder))
-    if encoder == "device" and os.path.splitext(str(path))[1].lower() not in (".jpg", ".jpeg"):
-        raise ValueError("%s: the device encoder writes JPEG files only (.jpg / .jpeg), got %r" % (what, path))
+    if encoder not in ("pil", "device", "device_png"):
+        raise ValueError("%s: the preview encoder must be 'pil', 'device' or 'device_png', got %r" % (what, encoder))
+    ext = os.path.splitext(str(path))[1].lower()
+    if encoder == "device" and ext not in (".jpg", ".jpeg"):
+        raise ValueError("%s: the device encoder writes JPEG files only (.jpg / .jpeg; 'device_png' writes .png), got %r" % (what, path))
+    if encoder == "device_png" and ext != ".png":
+        raise ValueError("%s: the preview encoder 'device_png' writes PNG files only (.png), got %r" % (what, path))
+
+
+def _device_coder(encoder):
+    """(module, its one-file writer name) behind a device preview encoder"""
+    try:
+        from . import jpeg, png
+    except ImportError:
+        import jpeg
+        import png
+    return (png, "write_png") if encoder == "device_png" else (jpeg, "write_jpeg")
 
 
 def write_preview(path, hdr_tensor, peak=None, reverse_channels=False, encoder="pil", jpeg_options=None):
@@ -251,18 +264,16 @@ def write_preview(path, hdr_tensor, peak=None, reverse_channels=False, encoder="
     image's maximum, then a 2.2 gamma) -> an image file through PIL (the format follows the extension; PNG is lossless).
     encoder="device" (only for .jpg / .jpeg paths) codes the file on the device instead (jpeg.encode) and copies the finished bytes:
     the bytes PIL writes for the same 8-bit image and the same `jpeg_options` (quality, subsampling, restart_interval; PIL's defaults
-    where they are not given: quality 75, 4:2:0)."""
+    where they are not given: quality 75, 4:2:0).  encoder="device_png" (only for .png paths) writes a lossless PNG on the device
+    (png.encode; `jpeg_options` then holds ITS options: filter, deflate): the same pixels as PIL's file, not the same bytes."""
     if hdr_tensor.dim() != 3:
         raise ValueError("write_preview: expected one image [H, W, 3], got %s" % (tuple(hdr_tensor.shape),))
     _check_preview_encoder(encoder, path, "write_preview")
     options = dict(jpeg_options or {})
     u8 = K.tonemap_u8(hdr_tensor.contiguous(), peak, reverse_channels)
-    if encoder == "device":
-        try:
-            from . import jpeg
-        except ImportError:
-            import jpeg
-        jpeg.write_jpeg(path, u8, **options)
+    if encoder != "pil":
+        module, writer = _device_coder(encoder)
+        getattr(module, writer)(path, u8, **options)
         return
     from PIL import Image
     if "restart_interval" in options:
@@ -327,7 +338,8 @@ class HdrReconstructor:
     def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host", output_format="hdr",
                          exr_options=None, preview_encoder="pil", preview_options=None):
         """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support;
-        preview_encoder, preview_options: write_preview's encoder and jpeg_options ("device": a .jpg preview coded on the device).
+        preview_encoder, preview_options: write_preview's encoder and jpeg_options ("device": a .jpg preview coded on the device,
+        "device_png": a .png preview coded on the device).
         decoder: "pil" decodes the file on the host (read_ldr); "device" decodes baseline JPEG files on the device
         (jpeg.read_ldr_device: the same bytes, PIL for files out of its scope); "device_scan" is "device" with the scan prepared on
         the device too (unstuff="device": the end of the scan, the byte stuffing and the restart segments; the same bytes again).
@@ -351,18 +363,39 @@ class HdrReconstructor:
         if preview_path is not None:
             write_preview(preview_path, y, reverse_channels=True, encoder=preview_encoder, jpeg_options=preview_options)
 
-    def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host", output_format="hdr", exr_options=None):
+    def _write_previews(self, ys, preview_paths, preview_encoder, preview_options):
+        """the previews of a list of estimates: with a device encoder ALL of them are tone-mapped and coded in one call"""
+        if preview_encoder == "pil":
+            for dst, y in zip(preview_paths, ys):
+                write_preview(dst, y, reverse_channels=True, jpeg_options=preview_options)
+            return
+        module, _ = _device_coder(preview_encoder)
+        u8 = [K.tonemap_u8(y.contiguous(), None, True) for y in ys]
+        for dst, data in zip(preview_paths, module.encode(u8, **dict(preview_options or {}))):
+            with open(dst, "wb") as f:
+                f.write(data)
+
+    def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host", output_format="hdr", exr_options=None,
+                          preview_paths=None, preview_encoder="pil", preview_options=None):
         """reconstruct_file for a list of files: geometry and inference per image as there, then ALL results of the call coded in one
         batched scanline-RLE launch sequence and brought back in one copy (encoder="device"), then the files are written.
         encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
         4 B per pixel.  output_format="exr": the float estimates of the whole list go through ONE exr.encode_exr call, whatever the
         encoder (and whatever the compression: exr_options=dict(compression="piz", piz="device") codes every chunk of every file in
-        one K.piz_encode call)"""
+        one K.piz_encode call).  preview_paths: one 8-bit preview per file as reconstruct_file writes it; with
+        preview_encoder="device_png" (.png paths) or "device" (.jpg paths) the previews of the whole list are coded in one call."""
         _check_encoder(encoder, "reconstruct_files", output_format)
         _check_format(output_format, "reconstruct_files")
         ldr_paths, hdr_paths = list(ldr_paths), list(hdr_paths)
         if len(ldr_paths) != len(hdr_paths):
             raise ValueError("reconstruct_files: %d inputs but %d outputs" % (len(ldr_paths), len(hdr_paths)))
+        if preview_paths is not None:
+            preview_paths = list(preview_paths)
+            if len(preview_paths) != len(ldr_paths):
+                raise ValueError("reconstruct_files: %d inputs but %d previews" % (len(ldr_paths), len(preview_paths)))
+            for dst in preview_paths:
+                _check_preview_encoder(preview_encoder, dst, "reconstruct_files")
+            previews = dict(preview_encoder=preview_encoder, preview_options=preview_options)
         if decoder not in ("pil", "device", "device_scan"):
             raise ValueError("reconstruct_files: decoder must be 'pil', 'device' or 'device_scan', got %r" % (decoder,))
         if output_format == "exr":
@@ -372,26 +405,43 @@ class HdrReconstructor:
             for dst, data in zip(hdr_paths, exr.encode_exr(ys, **_exr_options(encoder, exr_options))):
                 with open(dst, "wb") as f:
                     f.write(data)
+            if preview_paths is not None:
+                self._write_previews(ys, preview_paths, **previews)
             return
-        if encoder == "host":
+        if encoder == "host" and preview_paths is None:
             for src, dst in zip(ldr_paths, hdr_paths):
                 self.reconstruct_file(src, dst, decoder=decoder)
             return
         if not ldr_paths:
             return
-        rgbe = [K.rgbe_encode(self._read_device(src, decoder, "reconstruct_files"), reverse_channels=True) for src in ldr_paths]
-        for dst, img, data in zip(hdr_paths, rgbe, rle_encode_device(rgbe)):
-            _write_scanlines(dst, img.shape[0], img.shape[1], data)
+        ys, rgbe = [], []
+        for src in ldr_paths:
+            y = self._read_device(src, decoder, "reconstruct_files")
+            rgbe.append(K.rgbe_encode(y, reverse_channels=True))
+            if preview_paths is not None:                        # the float estimates are kept only for the previews: 12 B per pixel
+                ys.append(y)
+        if encoder == "host":
+            for dst, img in zip(hdr_paths, rgbe):
+                write_hdr(dst, img.cpu().numpy(), encoder="host")
+        else:
+            for dst, img, data in zip(hdr_paths, rgbe, rle_encode_device(rgbe)):
+                _write_scanlines(dst, img.shape[0], img.shape[1], data)
+        if preview_paths is not None:
+            self._write_previews(ys, preview_paths, **previews)
 
     def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil", encoder="host", group=16,
-                        output_format="hdr", exr_options=None):
+                        output_format="hdr", exr_options=None, preview_dir=None, preview_encoder="pil", preview_options=None):
         """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder, encoder: as reconstruct_file;
         with encoder="device" the files go through reconstruct_files in groups of `group`.  output_format="exr" names the outputs
-        *.exr"""
+        *.exr.  preview_dir: also write an 8-bit preview per file there (*.png, or *.jpg with preview_encoder="device"), through
+        reconstruct_files' preview_paths"""
         _check_encoder(encoder, "reconstruct_dir", output_format)
         _check_format(output_format, "reconstruct_dir")
         fmt = dict(output_format=output_format, exr_options=exr_options)
         os.makedirs(output_dir, exist_ok=True)
+        if preview_dir is not None:
+            os.makedirs(preview_dir, exist_ok=True)
+            fmt.update(preview_encoder=preview_encoder, preview_options=preview_options)
         written = []
         paths = sorted(glob.glob(os.path.join(dataset_dir, pattern)))
         step = max(int(group), 1) if encoder != "host" else 1
@@ -399,7 +449,10 @@ class HdrReconstructor:
             start = time.perf_counter()
             part = paths[i:i + step]
             outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + "." + output_format) for path in part]        # :148-149
-            if encoder != "host":
+            if preview_dir is not None:
+                ext = ".jpg" if preview_encoder == "device" else ".png"
+                fmt["preview_paths"] = [os.path.join(preview_dir, os.path.splitext(os.path.basename(out))[0] + ext) for out in outs]
+            if encoder != "host" or preview_dir is not None:
                 self.reconstruct_files(part, outs, decoder=decoder, encoder=encoder, **fmt)
             else:
                 self.reconstruct_file(part[0], outs[0], decoder=decoder, **fmt)
