@@ -118,7 +118,7 @@ class Conv2D(Layer):
         self.kernel = self.add_weight("kernel", _glorot_uniform((k, k, in_channels, filters),
                                                                 k * k * in_channels, k * k * filters, device))
         self.bias = self.add_weight("bias", torch.zeros(filters, device=device)) if use_bias else None
-        self._padded = None  # (version, cin_pad, tensor)
+        self._padded = None  # ((version, cin_pad, cout_pad), tensor, K.Ready)
 
     def kernel_padded(self, cin_pad=None, cout_pad=None):
         """Kernel zero-padded along the input- and/or output-channel axis (cached per parameter
@@ -133,7 +133,8 @@ class Conv2D(Layer):
             pad[:, :, :k.shape[2], :k.shape[3]] = k
             pad = pad.contiguous()
             pad._shdr_const = True         # one tensor per parameter version: the library's prepared form is cached on it (_ops._prepared_filter)
-            self._padded = (key, pad)
+            self._padded = (key, pad, K.Ready(pad.device))
+        self._padded[2].wait()             # (built on the stream that asked first: K.Ready)
         return self._padded[1]
 
     def call_padded(self, x, cin_pad=None, cout_pad=None, **kw):
@@ -179,7 +180,9 @@ class BatchNormalization(Layer):
             with torch.no_grad():
                 scale = self.gamma.detach() * torch.rsqrt(self.moving_variance + BN_EPS)
                 shift = self.beta.detach() - self.moving_mean * scale
-            self._folded = (ver, scale.contiguous(), shift.contiguous())
+            scale, shift = scale.contiguous(), shift.contiguous()
+            self._folded = (ver, scale, shift, K.Ready(scale.device))
+        self._folded[3].wait()             # (built on the stream that asked first: K.Ready)
         return self._folded[1], self._folded[2]
 
     def train_apply(self, x, relu=False):

@@ -125,6 +125,47 @@ def _d(t):
 
 
 # ---------------------------------------------------------------------------
+# tensors that one stream produces once and every stream consumes (per-version caches, constant slots)
+# ---------------------------------------------------------------------------
+class Ready:
+    """Ordering of a cached tensor across streams.  The producer makes one right AFTER it has enqueued the work that writes the tensor(s):
+    an event recorded on its stream.  Every consumer calls wait() before it enqueues a reader: on another stream than the producer's it
+    waits for the event unless the event is already complete.  A complete event is dropped, so the steady state costs nothing: no launch,
+    no device-side wait, and after the first answer not even a query.  No event calls while a stream capture is open (hipEventQuery invalidates the capture;
+    GraphedInference warms the caches up first), and none for tensors that are not in device memory."""
+    __slots__ = ("stream_id", "event")
+
+    def __init__(self, device=None):
+        self.stream_id = self.event = None
+        if (device is None or device.type == "cuda") and not torch.cuda.is_current_stream_capturing():
+            self.stream_id = torch.cuda.current_stream(device).cuda_stream
+            self.event = torch.cuda.Event()
+            self.event.record(torch.cuda.current_stream(device))
+
+    def wait(self):
+        event = self.event
+        if event is None or torch.cuda.current_stream().cuda_stream == self.stream_id or torch.cuda.is_current_stream_capturing():
+            return
+        if event.query():
+            self.event = None
+        else:
+            torch.cuda.current_stream().wait_event(event)
+
+
+def _publish(t):
+    """producer side for a single tensor: the Ready travels on the tensor"""
+    t._shdr_ready = Ready(t.device)
+    return t
+
+
+def _consume(t):
+    ready = getattr(t, "_shdr_ready", None)
+    if ready is not None:
+        ready.wait()
+    return t
+
+
+# ---------------------------------------------------------------------------
 # range slots (include/shdr.h: shdr_conv2d_fwd_prepared_ranged_f32)
 # ---------------------------------------------------------------------------
 # The split-operand conv plans scale their input by a power of two taken from a RANGE SLOT: a device float holding an upper bound of
@@ -189,8 +230,8 @@ def _range_of(t):
         return slot
     slot = _CONST_SLOTS.get((t.device, b))
     if slot is None:
-        slot = _CONST_SLOTS[(t.device, b)] = torch.full((1,), b, device=t.device, dtype=torch.float32)
-    return slot
+        slot = _CONST_SLOTS[(t.device, b)] = _publish(torch.full((1,), b, device=t.device, dtype=torch.float32))
+    return _consume(slot)        # (filled on whichever stream asked first)
 
 
 def _bound_of(t):
@@ -528,22 +569,18 @@ def _is_persistent(w):
 
 def _filter_cache_get(w, attr, key):
     """Derived forms of a persistent filter (prepared / packed / fp16-packed) live ON the filter tensor in a dict
-    {key: (tensor, producing stream, ready event)} tagged with the variable's version.  Entries are dropped only when the version
+    {key: (tensor, Ready)} tagged with the variable's version.  Entries are dropped only when the version
     changes: the same weight takes different plans at different input shapes (x3 needs >= 192 blocks, x3n >= 256 tiles), and a
     captured HIP graph holds the raw pointer of the form it was captured with -- evicting one shape's form for another's would
-    leave that graph reading freed memory.  A consumer on another stream than the producer waits for the producer's event."""
+    leave that graph reading freed memory.  A consumer on another stream than the producer waits for the producer's event (Ready)."""
     store = getattr(w, attr, None)
     if store is None or store[0] != w._version:
         return None
     ent = store[1].get(key)
     if ent is None:
         return None
-    tensor, stream_id, event = ent
-    # (no event calls while a stream capture is open: hipEventQuery invalidates the capture; GraphedInference warms the caches up first)
-    if event is not None and torch.cuda.current_stream().cuda_stream != stream_id and not torch.cuda.is_current_stream_capturing() \
-            and not event.query():
-        torch.cuda.current_stream().wait_event(event)
-    return tensor
+    ent[1].wait()
+    return ent[0]
 
 
 def _filter_cache_put(w, attr, key, tensor):
@@ -551,11 +588,7 @@ def _filter_cache_put(w, attr, key, tensor):
     if store is None or store[0] != w._version:
         store = (w._version, {})
         setattr(w, attr, store)
-    event = None
-    if not torch.cuda.is_current_stream_capturing():
-        event = torch.cuda.Event()
-        event.record()
-    store[1][key] = (tensor, torch.cuda.current_stream().cuda_stream, event)
+    store[1][key] = (tensor, Ready(tensor.device))
     return tensor
 
 

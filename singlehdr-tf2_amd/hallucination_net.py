@@ -205,7 +205,9 @@ class model(Layer):
                 up_filter = wc[:, :, :64, :].contiguous()
                 up_filter._shdr_const = True
                 self._tail_proj = (key, dict(up_map=m[:64].t().contiguous(), skip_map=m[64:].t().contiguous(),
-                                             const=(sc[:3] * bc + sh[:3]).contiguous(), up_filter=up_filter, bias=bc))
+                                             const=(sc[:3] * bc + sh[:3]).contiguous(), up_filter=up_filter, bias=bc),
+                                   K.Ready(wc.device))
+        self._tail_proj[2].wait()          # (built on the stream that asked first: K.Ready)
         return self._tail_proj[1]
 
     def _tail_filter(self, c_skip):
@@ -221,5 +223,6 @@ class model(Layer):
                 wc[0, 0, :, :3] = (w1 @ w2).float()
                 bc = (b1.detach().double() @ w2 + b2.detach().double()).float().contiguous()
                 wc._shdr_const = True
-            self._tail = (key, wc, bc)
+            self._tail = (key, wc, bc, K.Ready(wc.device))
+        self._tail[3].wait()               # (built on the stream that asked first: K.Ready)
         return self._tail[1], self._tail[2]

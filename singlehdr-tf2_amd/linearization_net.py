@@ -156,8 +156,8 @@ class AEInvcrfDecodeNet(Layer):
 
     def table(self, device):
         if self._table is None or self._table.device != device:
-            self._table = load_invemor_table(device)
-        return self._table
+            self._table = K._publish(load_invemor_table(device))       # (copied on the stream that asked first: K.Ready)
+        return K._consume(self._table)
 
     def call(self, feature):
         return K.invcrf_decode(feature, self.fc.kernel, self.fc.bias, self.table(feature.device))

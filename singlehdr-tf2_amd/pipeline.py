@@ -265,6 +265,10 @@ class JointTrainStep:
         # lets the small Dequantization / Linearization kernels fill the CUs the big Hallucination kernels leave idle.
         main = torch.cuda.current_stream()
         streams = self._streams if self.multi_stream else (main, main, main)
+        # On the caller's stream, ahead of the fork: the backward pass reads `msum` there (d objective / d crf_loss) and frees it.  Made on
+        # the Hallucination stream it would go back to that stream's allocator pool, which hands memory out again without knowing of
+        # the read on the caller's stream.
+        b_glob, msum = _dp_scalars(self, mask)
         for st in streams:
             st.wait_stream(main)
 
@@ -292,7 +296,6 @@ class JointTrainStep:
             perceptual_loss = sum(K.diff_loss(fa, fb, 1) for fa, fb in zip(feats, target_feats))
             l1loss_hal = K.diff_loss(y_l1, hdr_t_gamma, 1)
             tv_loss = K.tv_loss(y_tv)                                              # batch-global scalar [1]
-            b_glob, msum = _dp_scalars(self, mask)
             # exact sharding of tv_loss * loss_mask: d/dtheta sums to (sum_all mask / G) * sum_r grad tv_r
             tv_w = mask if self.world == 1 else torch.ones_like(mask) * (msum / b_glob)
             loss_hal = (l1loss_hal + 0.001 * perceptual_loss) * mask + 0.1 * tv_loss * tv_w
