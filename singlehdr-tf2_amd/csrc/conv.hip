@@ -25,8 +25,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 struct ConvArgs {
   const float* x1;
   const float* x2;
@@ -82,7 +80,6 @@ __device__ __forceinline__ void conv_range_out(unsigned* slot, float m, unsigned
   if (b > seen) atomicMax(slot, b);
 }
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 constexpr int BK = 32;
@@ -425,9 +422,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
 // ---------------------------------------------------------------------------
 __device__ __attribute__((aligned(16))) float g_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
-typedef __attribute__((address_space(1))) const void* shdr_gptr_t;
-typedef __attribute__((address_space(3))) void* shdr_lptr_t;
-
 template <int BM, int BN>
 __host__ __device__ constexpr int conv_dma_lds_bytes() {
   constexpr int pipe = 2 * (BM * BK + BK * BN) * 4;
@@ -533,7 +527,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_dma_kernel(const ConvArgs a)
       for (int i = 0; i < AI; ++i) {
         const bool ok = (unsigned)(ihb[i] + kh) < (unsigned)a.H && (unsigned)(iwb[i] + kw) < (unsigned)a.W;
         const float* p = ok ? src + (size_t)((second ? rowoff2[i] : rowoff1[i]) + delta) : zero;
-        __builtin_amdgcn_global_load_lds((shdr_gptr_t)p, (shdr_lptr_t)(Ab + i * 8 * BK), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(Ab + i * 8 * BK), 16, 0, 0);
       }
     } else {
       krow0 = (unsigned)(nx_kc * BK);
@@ -547,7 +541,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_dma_kernel(const ConvArgs a)
         const unsigned off = (second ? rowoff2[i] : rowoff1[i]) +
                              (unsigned)((kh * a.W + kw) * (second ? a.C2 : a.C1) + (second ? t_c[i] - a.C1 : t_c[i]));
         const float* p = ok ? src + (size_t)off : zero;
-        __builtin_amdgcn_global_load_lds((shdr_gptr_t)p, (shdr_lptr_t)(Ab + i * 8 * BK), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(Ab + i * 8 * BK), 16, 0, 0);
         t_c[i] += BK;
         while (t_c[i] >= a.Ct && t_kh[i] < a.KH) {
           t_c[i] -= a.Ct;
@@ -562,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_dma_kernel(const ConvArgs a)
       for (int j = 0; j < BI; ++j) {
         const bool ok = FAST || ((int)krow0 + wk[j] < a.K);
         const float* p = ok ? wimg + (size_t)(wbase + woff[j]) : zero;
-        __builtin_amdgcn_global_load_lds((shdr_gptr_t)p, (shdr_lptr_t)(Bb + j * 256), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(Bb + j * 256), 16, 0, 0);
       }
     }
   };
@@ -928,14 +922,7 @@ int launch_mfma_dma_impl(ConvArgs& a, hipStream_t st) {
   a.nblk_m = a.N * a.tiles_y * a.tiles_x;
   a.nblk_n = a.Cout / BN;
   constexpr int lds = conv_dma_lds_bytes<BM, BN>();
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_dma_kernel<BM, BN, WM, WN, FAST, PREC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_mfma_dma_kernel<BM, BN, WM, WN, FAST, PREC>>(lds)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk <= 0 || nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_mfma_dma_kernel<BM, BN, WM, WN, FAST, PREC>), dim3((unsigned)nblk), dim3(256), lds, st, a);
@@ -950,14 +937,7 @@ int launch_mfma_impl(ConvArgs& a, hipStream_t st) {
   a.nblk_m = a.N * a.tiles_y * a.tiles_x;
   a.nblk_n = a.Cout / BN;
   constexpr int lds = conv_lds_bytes<BM, BN>();
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<BM, BN, WM, WN, FAST>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_mfma_kernel<BM, BN, WM, WN, FAST>>(lds)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk <= 0 || nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, WN, FAST>), dim3((unsigned)nblk), dim3(256), lds, st, a);
@@ -988,26 +968,11 @@ int launch_rega(ConvArgs& a, hipStream_t st) {
   a.tiles_y = (a.Ho + TH - 1) / TH;
   const long ntiles = (long)a.N * a.tiles_y * a.tiles_x;
   const int lds = a.ntaps * CT * NT * 16 * 4;
-  const int dev_slot = shdr::device_slot();
-  static int attr_lds_dev[shdr::kMaxDevices] = {};
-  int& attr_lds = attr_lds_dev[dev_slot];
-  if (lds > attr_lds) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_rega_kernel<MT, NT, CT, KK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_lds = lds;
-  }
   // persistent grid = the blocks that are actually co-resident (VGPR- or LDS-limited): a grid that is not a multiple of the
-  // residency runs its last blocks alone at low occupancy (measured: 768 blocks with 2 resident per CU cost +20 %)
-  static int occ_lds_dev[shdr::kMaxDevices] = {}, occ_dev[shdr::kMaxDevices] = {};
-  int &occ_lds = occ_lds_dev[dev_slot], &occ = occ_dev[dev_slot];     // (LDS bytes are never 0 here: 0 = not queried yet)
-  if (lds != occ_lds) {
-    int nb = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_rega_kernel<MT, NT, CT, KK>), 256, lds);
-    if (e != hipSuccess || nb < 1) nb = 1;
-    occ = nb > 8 ? 8 : nb;
-    occ_lds = lds;
-  }
+  // residency runs its last blocks alone at low occupancy (measured: 768 blocks with 2 resident per CU cost +20 %).  The LDS is the
+  // filter's size: the limit is raised when a larger one arrives, the occupancy asked again whenever it changes.
+  int occ = 1;
+  if (int e = shdr::dynamic_lds_occupancy<&conv_rega_kernel<MT, NT, CT, KK>>(256, lds, 8, occ)) return e;
   long grid = 256L * occ;
   if (const char* e = SHDR_ENV("SHDR_REGA_PER_CU")) grid = 256L * atoi(e);
   if (grid > ntiles) grid = ntiles;

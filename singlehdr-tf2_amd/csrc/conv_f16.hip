@@ -24,17 +24,9 @@
 
 #include <type_traits>
 
-#include "shdr_internal.h"
+#include "f16.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_h_zero_page[4] = {0u, 0u, 0u, 0u};
 
 struct ConvHArgs {
   const _Float16* x1;
@@ -49,14 +41,10 @@ struct ConvHArgs {
   int act1, cout_valid;
 };
 // the inference instantiations (shdr_conv2d_fwd_fused_f16) take the fused epilogue on top; the training ones keep ConvHArgs
-struct ConvHFusedArgs : ConvHArgs {
-  shdr::FusedEpiF16 f;
-};
+using ConvHFusedArgs = shdr::WithFusedEpi<ConvHArgs>;
 template <bool FUSED>
-using ConvHArgsT = std::conditional_t<FUSED, ConvHFusedArgs, ConvHArgs>;
-
-
-__host__ __device__ inline int swz(int row) { return (-(row >> 2)) & 3; }
+using ConvHArgsT = shdr::FusedArgsT<ConvHArgs, FUSED>;
+SHDR_F16_ARGS_LAYOUT(ConvHArgs, 144, 184);
 
 // ---- filter packing: fp32 HWIO [KH*KW][Ct][Cout] -> fp16 [chunk][Cout][32] in the chunk order of the conv kernel --------------
 __global__ __launch_bounds__(256) void conv_pack_filter_f16_kernel(const float* __restrict__ w, _Float16* __restrict__ wp, int ntaps,
@@ -104,15 +92,10 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
-  const int pn = L % a.nblk_n;
-  int pm = L / a.nblk_n;
-  const int tx = pm % a.tiles_x;
-  pm /= a.tiles_x;
-  const int ty = pm % a.tiles_y;
-  const int img = pm / a.tiles_y;
-  const int n0 = pn * BN, oh0 = ty * TH, ow0 = tx * 16;
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_h_zero_page);
+  const shdr::BlockTile bt = shdr::block_tile_of(blockIdx.x, a.nblk_m, a.nblk_n, a.tiles_x, a.tiles_y);
+  const int img = bt.img;
+  const int n0 = bt.pn * BN, oh0 = bt.ty * TH, ow0 = bt.tx * 16;
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   // ---- A geometry: instruction i of this wave fills tile rows (wave*AI + i)*16 .. +15; lane = (row, physical slot) -------
   int ihb[AI], iwb[AI], akg[AI];
@@ -121,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     const int r = (wave * AI + i) * 16 + (lane >> 2);
-    akg[i] = (lane & 3) ^ swz(r);                  // logical k-group fetched into physical slot lane & 3
+    akg[i] = (lane & 3) ^ row_swz(r);              // logical k-group fetched into physical slot lane & 3
     const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
     const bool ok = (oh < a.Ho) && (ow < a.Wo);
     ihb[i] = ok ? oh * a.stride - a.pad_t : -(1 << 28);
@@ -135,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     const int r = (wave * BI + j) * 16 + (lane >> 2);           // cout row of the tile
-    woff[j] = (unsigned)(n0 + r) * 32u + 8u * (unsigned)((lane & 3) ^ swz(r));
+    woff[j] = (unsigned)(n0 + r) * 32u + 8u * (unsigned)((lane & 3) ^ row_swz(r));
   }
 
   // chunk walk: scalars when FAST (tap inner, channel chunk outer); per instruction and lane otherwise
@@ -218,12 +201,12 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
     const int row = wm * MT * 16 + mi * 16 + fi;
-    a_rd[mi] = row * 32 + 8 * (fg ^ swz(row));
+    a_rd[mi] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = wn * NT * 16 + ni * 16 + fi;
-    b_rd[ni] = BM * 32 + row * 32 + 8 * (fg ^ swz(row));
+    b_rd[ni] = BM * 32 + row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   const int nstages = (a.nchunks + KC - 1) / KC;
@@ -261,6 +244,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
       const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
       if (oh >= a.Ho || ow >= a.Wo) continue;
       const size_t pix = ((size_t)img * a.Ho + oh) * a.Wo + ow;
+      // (the head steps of this kernel and of conv_f16_patch.hip stay apart: one helper for both took 1 - 2 % of the code out of the fused
+      //  instantiations here and put scratch into a 512-register instantiation there: DESIGN.md section 18, the rule for sharing)
       if constexpr (FUSED) {                                   // bias, act1 (tanh: the deq head), affine, residual, act2 per 4 couts
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni) {
@@ -279,6 +264,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
         }
         continue;
       }
+      // (the training heads stay on this scalar loop: act_apply per element compiles to another stream than the 4-vector steps)
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
@@ -293,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
     }
     return;
   }
-  constexpr int RS = BN + 8;                                   // staged row stride in halves (16-byte aligned)
+  constexpr int RS = shdr::f16_stage_stride(BN);
   _Float16* stage = hsm;                                       // the pipeline buffers are dead (last barrier passed)
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
@@ -302,35 +288,26 @@ __global__ __launch_bounds__(256, 2) void conv_f16_kernel(const ConvHArgsT<FUSED
 #pragma unroll
     for (int ni = 0; ni < NT; ++ni) {
       const int cl = wn * NT * 16 + ni * 16 + 4 * fg;
-      f32x4 v = acc[mi][ni];
-      if (a.bias) {
-        const float4 b4 = *reinterpret_cast<const float4*>(a.bias + n0 + cl);
-        v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-      }
-      f16x4 h;
       if constexpr (FUSED) {                                   // (no tanh on fp16 outputs here: shdr_conv2d_fwd_fused_f16 declines it)
-        shdr::act_apply4<0>(v, a.act1);
-        const bool in = oh < a.Ho && ow < a.Wo;
-        shdr::fused_epi4_f16<0>(v, n0 + cl, in ? ((size_t)img * a.Ho + oh) * a.Wo + ow : 0, 4, in, a.f);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) h[e] = (_Float16)v[e];
+        const bool in = oh < a.Ho && ow < a.Wo;                  // (the residual of a pixel outside the output is not read)
+        shdr::f16_stage4<true>(a, acc[mi][ni], n0, cl, in ? ((size_t)img * a.Ho + oh) * a.Wo + ow : 0, in, stage + r * RS);
       } else {
+        // Not f16_stage4: the training instantiations compile tanh into an fp16 output (the patch and w3 kernels send such layers
+        // here) and apply the activation per element; with one dispatch per 4-vector they came out 7 - 10 % shorter.
+        f32x4 v = acc[mi][ni];
+        if (a.bias) {
+          const float4 b4 = *reinterpret_cast<const float4*>(a.bias + n0 + cl);
+          v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
+        }
+        f16x4 h;
 #pragma unroll
         for (int e = 0; e < 4; ++e) h[e] = (_Float16)shdr::act_apply(v[e], a.act1);
+        *reinterpret_cast<f16x4*>(stage + r * RS + cl) = h;
       }
-      *reinterpret_cast<f16x4*>(stage + r * RS + cl) = h;
     }
   }
   __syncthreads();
-  constexpr int QR = BN / 8;                                   // 16-byte pieces per tile row
-#pragma unroll 2
-  for (int e = tid; e < BM * QR; e += 256) {
-    const int r = e / QR, q = e - r * QR;
-    const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
-    if (oh >= a.Ho || ow >= a.Wo) continue;
-    const size_t pix = ((size_t)img * a.Ho + oh) * a.Wo + ow;
-    *reinterpret_cast<f16x8*>(a.y16 + pix * a.Cout + n0 + 8 * q) = *reinterpret_cast<const f16x8*>(stage + r * RS + 8 * q);
-  }
+  shdr::f16_drain<BM, BN>(stage, a.y16, img, oh0, ow0, a.Ho, a.Wo, a.Cout, n0);
 }
 
 template <int BM, int BN, int WM, int WN, bool FAST, int KC, class A>
@@ -341,16 +318,9 @@ int launch_f16(A& a, hipStream_t st) {
   a.tiles_y = (a.Ho + TH - 1) / TH;
   a.nblk_m = a.N * a.tiles_y * a.tiles_x;
   a.nblk_n = a.Cout / BN;
-  constexpr int pipe = 2 * KC * (BM + BN) * 32 * 2, stage = BM * (BN + 8) * 2;
+  constexpr int pipe = 2 * KC * (BM + BN) * 32 * 2, stage = BM * shdr::f16_stage_stride(BN) * 2;
   constexpr int lds = pipe > stage ? pipe : stage;
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_kernel<BM, BN, WM, WN, FAST, KC, FUSED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_f16_kernel<BM, BN, WM, WN, FAST, KC, FUSED>>(lds)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk <= 0 || nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_f16: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_f16_kernel<BM, BN, WM, WN, FAST, KC, FUSED>), dim3((unsigned)nblk), dim3(256), lds, st, a);
@@ -363,23 +333,6 @@ int launch_f16_k(A& a, hipStream_t st) {
   if (a.fast) return a.nchunks >= 2 ? launch_f16<BM, BN, WM, WN, true, 2>(a, st) : launch_f16<BM, BN, WM, WN, true, 1>(a, st);
   return a.nchunks >= 2 ? launch_f16<BM, BN, WM, WN, false, 2>(a, st) : launch_f16<BM, BN, WM, WN, false, 1>(a, st);
 }
-
-extern "C" int shdr_conv2d_patch_ok_f16(const shdr_conv2d_desc* d);
-extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
-                                         void* y, int y_is_f32, void* stream);
-
-extern "C" int shdr_conv2d_w3_ok_f16(const shdr_conv2d_desc* d);
-extern "C" int shdr_conv2d_fwd_w3_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y,
-                                      void* stream);
-
-// the fused inference forms of the two specialised kernels (shdr_conv2d_fwd_fused_f16 dispatches to them when their predicate takes
-// every fused option of the call; the general kernel runs the layer otherwise)
-extern "C" int shdr_conv2d_patch_fused_ok_f16(const shdr_conv2d_desc* d, int y_is_f32);
-extern "C" int shdr_conv2d_fwd_patch_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
-                                               const shdr::FusedEpiF16* f, void* y, void* stream);
-extern "C" int shdr_conv2d_w3_fused_ok_f16(const shdr_conv2d_desc* d, int has_residual);
-extern "C" int shdr_conv2d_fwd_w3_fused_f16(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias,
-                                            const shdr::FusedEpiF16* f, void* y, void* stream);
 
 inline bool f16_fast(int C1, int C2) { return ((C1 + C2) % 32 == 0) && (C2 == 0 || C1 % 32 == 0); }
 inline int f16_nchunks(int ntaps, int C1, int C2) {
@@ -410,11 +363,12 @@ namespace {
 // the checks and kernel arguments shared by shdr_conv2d_fwd_f16 and shdr_conv2d_fwd_fused_f16
 int f16_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, int y_is_f32,
               ConvHArgs& a) {
-  SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_f16: null desc/x1/wp/y");
+  const shdr::F16FwdPointers ptr{"conv2d_f16", d, x1, x2, wp, bias, y};
+  if (int e = ptr.given()) return e;
   SHDR_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C1 > 0 && d->C2 >= 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 &&
                    d->stride > 0 && d->Ho > 0 && d->Wo > 0,
                SHDR_E_SHAPE, "conv2d_f16: non-positive dimension");
-  SHDR_REQUIRE((d->C2 == 0) == (x2 == nullptr), SHDR_E_NULL, "conv2d_f16: x2 must be given iff C2 > 0");
+  if (int e = ptr.x2_iff_c2()) return e;
   SHDR_REQUIRE(d->C1 % 8 == 0 && d->C2 % 8 == 0 && d->Cout % 16 == 0, SHDR_E_SHAPE,
                "conv2d_f16: need C1 %% 8 == 0, C2 %% 8 == 0 (16-byte channel groups) and Cout %% 16 == 0, got %d+%d -> %d", d->C1,
                d->C2, d->Cout);
@@ -427,9 +381,7 @@ int f16_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const v
   SHDR_REQUIRE(y_is_f32 || cout_valid == d->Cout, SHDR_E_SHAPE, "conv2d_f16: an fp16 output stores every channel (cout_valid == Cout)");
   SHDR_REQUIRE((long)d->N * d->H * d->W * (d->C1 > d->C2 ? d->C1 : d->C2) < (1L << 32) && (long)d->N * d->Ho * d->Wo < (1L << 31),
                SHDR_E_SHAPE, "conv2d_f16: tensor with more than 2^32 elements");
-  SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) &&
-                   (!bias || shdr::aligned16(bias)),
-               SHDR_E_ALIGN, "conv2d_f16: tensors must be 16-byte aligned");
+  if (int e = ptr.aligned()) return e;
   a = ConvHArgs{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2);

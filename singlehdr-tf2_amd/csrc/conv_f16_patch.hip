@@ -13,17 +13,9 @@
 
 #include <type_traits>
 
-#include "shdr_internal.h"
+#include "f16.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_p_zero_page[4] = {0u, 0u, 0u, 0u};
 
 struct PatchArgs {
   const _Float16* x1;
@@ -35,13 +27,10 @@ struct PatchArgs {
   int N, H, W, Cout, tiles_x, tiles_y, ntiles, act1, cout_valid;
 };
 // the inference instantiations (fp32 heads with the fused epilogue: shdr_conv2d_fwd_patch_fused_f16); the training ones keep PatchArgs
-struct PatchFusedArgs : PatchArgs {
-  shdr::FusedEpiF16 f;
-};
+using PatchFusedArgs = shdr::WithFusedEpi<PatchArgs>;
 template <bool FUSED>
-using PatchArgsT = std::conditional_t<FUSED, PatchFusedArgs, PatchArgs>;
-
-__host__ __device__ inline int pswz(int row) { return (-(row >> 2)) & 3; }
+using PatchArgsT = shdr::FusedArgsT<PatchArgs, FUSED>;
+SHDR_F16_ARGS_LAYOUT(PatchArgs, 88, 128);
 
 template <int KK, int CT, int NT, bool TWO>
 struct PG {
@@ -73,13 +62,13 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FU
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_p_zero_page);
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   // ---- filter -> LDS, once per block (rows of 64 bytes, physical slot = k-group ^ swz(row)) ----------------------------------
   for (int j = wave; j < G::FINSTR; j += 4) {
     const int r = j * 16 + (lane >> 2);                        // row = step * COUT + cout
     const int co = r % G::COUT;
-    const _Float16* p = a.wp + (size_t)r * 32 + 8 * ((lane & 3) ^ pswz(co));
+    const _Float16* p = a.wp + (size_t)r * 32 + 8 * ((lane & 3) ^ row_swz(co));
     __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(filt + j * 512), 16, 0, 0);
   }
 
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FU
     } else {
       pix = piece / (CT / 8);
       cg = piece - pix * (CT / 8);
-      if (CT == 32) cg ^= pswz(pix);                           // 64-byte pixels: the b128 bank swizzle, applied on the source side
+      if (CT == 32) cg ^= row_swz(pix);                        // 64-byte pixels: the b128 bank swizzle, applied on the source side
     }
     psrc[j] = src;
     ppy[j] = pix / G::PW;
@@ -139,7 +128,7 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FU
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = ni * 16 + fi;
-    b_rd[ni] = row * 32 + 8 * (fg ^ pswz(row));
+    b_rd[ni] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   // the bias is the same for every tile of the persistent block: loaded once (inside the epilogue each load is followed by
@@ -189,7 +178,7 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FU
         int ad = a_base[mi] + toff;
         if (!TWO && CT == 32) {                                // undo the source-side swizzle of the 64-byte pixel
           const int pix = ad >> 5;
-          ad = (pix << 5) + 8 * (cgl ^ pswz(pix));
+          ad = (pix << 5) + 8 * (cgl ^ row_swz(pix));
         }
         pa[mi] = *reinterpret_cast<const f16x8*>(P + ad);
       }
@@ -218,6 +207,8 @@ __global__ __launch_bounds__(256) void conv_f16_patch_kernel(const PatchArgsT<FU
         const int co = ni * 16 + 4 * fg;
         f32x4 v = acc[mi][ni];
         if (FUSED || a.y32) {                                    // the fp32 heads (tanh lives here only: shdr_internal.h act_apply4)
+          // (the head steps of this kernel and of conv_f16.hip stay apart: one helper for both put scratch into the 7x7 / 32-channel
+          //  instantiation here and took 1 - 2 % of the code out of the fused ones there: DESIGN.md section 18, the rule for sharing)
           if (co >= a.cout_valid) continue;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -250,19 +241,9 @@ int launch_patch(A& a, hipStream_t st) {
   if constexpr (lds > 160 * 1024) {
     return shdr::fail(SHDR_E_SHAPE, "conv2d_patch_f16: filter + patches (%d bytes) do not fit the LDS", lds);
   } else {
-  const int dev_slot = shdr::device_slot();
-  static bool attr_done[shdr::kMaxDevices] = {};
-  static int occ[shdr::kMaxDevices] = {};
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int nb = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>), 256, lds);
-    occ[dev_slot] = (e != hipSuccess || nb < 1) ? 1 : (nb > 4 ? 4 : nb);
-    attr_done[dev_slot] = true;
-  }
-  long grid = 256L * occ[dev_slot];
+  int occ = 1;
+  if (int e = shdr::dynamic_lds_occupancy<&conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>>(256, lds, 4, occ)) return e;
+  long grid = 256L * occ;
   if (grid > a.ntiles) grid = a.ntiles;
   hipLaunchKernelGGL((conv_f16_patch_kernel<KK, CT, NT, TWO, FUSED>), dim3((unsigned)grid), dim3(256), lds, st, a);
   return shdr::check_launch("conv_f16_patch_kernel");
@@ -296,15 +277,15 @@ namespace {
 // the checks and kernel arguments shared by shdr_conv2d_fwd_patch_f16 and shdr_conv2d_fwd_patch_fused_f16
 int patch_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, int y_is_f32,
                 PatchArgs& a) {
-  SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_patch_f16: null desc/x1/wp/y");
+  const shdr::F16FwdPointers ptr{"conv2d_patch_f16", d, x1, x2, wp, bias, y};
+  if (int e = ptr.given()) return e;
   SHDR_REQUIRE(shdr_conv2d_patch_ok_f16(d), SHDR_E_SHAPE, "conv2d_patch_f16: layer shape not taken by the patch kernel");
   SHDR_REQUIRE(y_is_f32 || d->act1 != SHDR_ACT_TANH, SHDR_E_SHAPE, "conv2d_patch_f16: tanh is compiled into the fp32-output (head) path only");
-  SHDR_REQUIRE((d->C2 == 0) == (x2 == nullptr), SHDR_E_NULL, "conv2d_patch_f16: x2 must be given iff C2 > 0");
+  if (int e = ptr.x2_iff_c2()) return e;
   const int cout_valid = d->cout_valid > 0 ? d->cout_valid : d->Cout;
   SHDR_REQUIRE(cout_valid <= d->Cout && (y_is_f32 || cout_valid == d->Cout), SHDR_E_SHAPE, "conv2d_patch_f16: bad cout_valid");
   SHDR_REQUIRE((long)d->N * d->H * d->W * 32 < (1L << 32), SHDR_E_SHAPE, "conv2d_patch_f16: tensor too large");
-  SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) && (!bias || shdr::aligned16(bias)),
-               SHDR_E_ALIGN, "conv2d_patch_f16: tensors must be 16-byte aligned");
+  if (int e = ptr.aligned()) return e;
   a = PatchArgs{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2);
@@ -326,7 +307,7 @@ extern "C" int shdr_conv2d_fwd_patch_f16(const shdr_conv2d_desc* d, const void* 
                                          void* y, int y_is_f32, void* stream) {
   PatchArgs a;
   if (int e = patch_setup(d, x1, x2, wp, bias, y, y_is_f32, a)) return e;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   if (d->Cout == 16) {
     if (d->KH == 3) return dispatch_ct<3, 1>(a, d->C1, d->C2, st);
     if (d->KH == 5) return dispatch_ct<5, 1>(a, d->C1, d->C2, st);
@@ -351,5 +332,5 @@ extern "C" int shdr_conv2d_fwd_patch_fused_f16(const shdr_conv2d_desc* d, const 
   PatchFusedArgs a;
   if (int e = patch_setup(d, x1, x2, wp, bias, y, 1, a)) return e;
   a.f = *f;
-  return dispatch_ct<3, 1>(a, d->C1, d->C2, reinterpret_cast<hipStream_t>(stream));
+  return dispatch_ct<3, 1>(a, d->C1, d->C2, shdr::stream_of(stream));
 }

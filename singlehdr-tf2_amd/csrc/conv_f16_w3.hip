@@ -12,17 +12,9 @@
 
 #include <type_traits>
 
-#include "shdr_internal.h"
+#include "f16.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_w3_zero_page[4] = {0u, 0u, 0u, 0u};
 
 struct W3Args {
   const _Float16* x1;
@@ -33,13 +25,11 @@ struct W3Args {
   int N, H, W, C1, C2, Cout, tiles_x, tiles_y, nblk_m, nblk_n, act1;
 };
 // the inference instantiation (folded BatchNorm + second activation: shdr_conv2d_fwd_w3_fused_f16); the training one keeps W3Args
-struct W3FusedArgs : W3Args {
-  shdr::FusedEpiF16 f;
-};
+using W3FusedArgs = shdr::WithFusedEpi<W3Args>;
 template <bool FUSED>
-using W3ArgsT = std::conditional_t<FUSED, W3FusedArgs, W3Args>;
+using W3ArgsT = shdr::FusedArgsT<W3Args, FUSED>;
+SHDR_F16_ARGS_LAYOUT(W3Args, 88, 128);
 
-__host__ __device__ inline int f4(int row) { return (-(row >> 2)) & 3; }      // filter image: rows = couts, 16-row aligned fragments
 // patch image: column-keyed slot swizzle + lane -> tile-column permutation (conv_x3.hip: a ds_read_b128 lane group = 8 lanes of one
 // channel group + 8 of its neighbour; with pcol() each set reads 8 consecutive columns -> conflict-free at every tap shift, and the
 // operand address is a per-lane column term + a scalar row term)
@@ -62,15 +52,10 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = shdr::xcd_remap(blockIdx.x, a.nblk_m * a.nblk_n);
-  const int pn = L % a.nblk_n;
-  int pm = L / a.nblk_n;
-  const int tx = pm % a.tiles_x;
-  pm /= a.tiles_x;
-  const int ty = pm % a.tiles_y;
-  const int img = pm / a.tiles_y;
-  const int n0 = pn * BN, oh0 = ty * 16, ow0 = tx * 16;
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_w3_zero_page);
+  const shdr::BlockTile bt = shdr::block_tile_of(blockIdx.x, a.nblk_m, a.nblk_n, a.tiles_x, a.tiles_y);
+  const int img = bt.img;
+  const int n0 = bt.pn * BN, oh0 = bt.ty * 16, ow0 = bt.tx * 16;
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   // ---- patch DMA geometry (fixed per block): piece -> (patch pixel, physical slot) -------------------------------------------
   unsigned poff1[PJ], poff2[PJ];
@@ -93,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
   for (int j = 0; j < FJ; ++j) {
     const int R = (wave * FJ + j) * 16 + (lane >> 2);
     const int kw = R >> 6, co = R & 63;
-    foff[j] = (unsigned)(kw * a.Cout + n0 + co) * 32u + 8u * (unsigned)((lane & 3) ^ f4(co));
+    foff[j] = (unsigned)(kw * a.Cout + n0 + co) * 32u + 8u * (unsigned)((lane & 3) ^ row_swz(co));
   }
   const int nch = (a.C1 + a.C2) >> 5;
   const int nunits = nch * 3;
@@ -129,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = ni * 16 + fi;
-    b_rd[ni] = row * 32 + 8 * (fg ^ f4(row));
+    b_rd[ni] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   dma_patch(0, 0);
@@ -160,8 +145,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
   }
   __syncthreads();
 
-  // ---- epilogue: bias + activation in fp32 -> fp16 through LDS -> 16-byte row-contiguous stores (as conv_f16.hip) ----------------
-  constexpr int RS = BN + 8;
+  // ---- epilogue: bias + activation in fp32 -> fp16 through LDS -> 16-byte row-contiguous stores (f16.h) ---------------------------------
+  constexpr int RS = shdr::f16_stage_stride(BN);
   _Float16* stage = wsm;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
@@ -169,29 +154,11 @@ __global__ __launch_bounds__(256, 2) void conv_f16_w3_kernel(const W3ArgsT<FUSED
 #pragma unroll
     for (int ni = 0; ni < NT; ++ni) {
       const int cl = ni * 16 + 4 * fg;
-      f32x4 v = acc[mi][ni];
-      if (a.bias) {
-        const float4 b4 = *reinterpret_cast<const float4*>(a.bias + n0 + cl);
-        v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-      }
-      shdr::act_apply4<0>(v, a.act1);                      // (no tanh here: shdr_conv2d_w3_ok_f16; shdr_internal.h act_apply4)
-      if constexpr (FUSED) shdr::fused_epi4_f16<0>(v, n0 + cl, 0, 4, false, a.f);   // affine, act2 (no residual: w3_fused_ok)
-      f16x4 h;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) h[e] = (_Float16)v[e];
-      *reinterpret_cast<f16x4*>(stage + r * RS + cl) = h;
+      shdr::f16_stage4<FUSED>(a, acc[mi][ni], n0, cl, 0, false, stage + r * RS);     // (no residual: w3_fused_ok)
     }
   }
   __syncthreads();
-  constexpr int QR = BN / 8;
-#pragma unroll 2
-  for (int e = tid; e < 256 * QR; e += 256) {
-    const int r = e / QR, q = e - r * QR;
-    const int oh = oh0 + (r >> 4), ow = ow0 + (r & 15);
-    if (oh >= a.H || ow >= a.W) continue;
-    const size_t pix = ((size_t)img * a.H + oh) * a.W + ow;
-    *reinterpret_cast<f16x8*>(a.y + pix * a.Cout + n0 + 8 * q) = *reinterpret_cast<const f16x8*>(stage + r * RS + 8 * q);
-  }
+  shdr::f16_drain<256, BN>(stage, a.y, img, oh0, ow0, a.H, a.W, a.Cout, n0);
 }
 
 }  // namespace
@@ -211,12 +178,12 @@ extern "C" int shdr_conv2d_w3_ok_f16(const shdr_conv2d_desc* d) {
 namespace {
 // the checks and kernel arguments shared by shdr_conv2d_fwd_w3_f16 and shdr_conv2d_fwd_w3_fused_f16
 int w3_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const void* wp, const float* bias, void* y, W3Args& a) {
-  SHDR_REQUIRE(d && x1 && wp && y, SHDR_E_NULL, "conv2d_w3_f16: null desc/x1/wp/y");
+  const shdr::F16FwdPointers ptr{"conv2d_w3_f16", d, x1, x2, wp, bias, y};
+  if (int e = ptr.given()) return e;
   SHDR_REQUIRE(shdr_conv2d_w3_ok_f16(d), SHDR_E_SHAPE, "conv2d_w3_f16: layer shape not taken by this kernel");
-  SHDR_REQUIRE((d->C2 == 0) == (x2 == nullptr), SHDR_E_NULL, "conv2d_w3_f16: x2 must be given iff C2 > 0");
+  if (int e = ptr.x2_iff_c2()) return e;
   SHDR_REQUIRE((long)d->N * d->H * d->W * (d->C1 > d->C2 ? d->C1 : d->C2) < (1L << 32), SHDR_E_SHAPE, "conv2d_w3_f16: tensor too large");
-  SHDR_REQUIRE(shdr::aligned16(x1) && (!x2 || shdr::aligned16(x2)) && shdr::aligned16(wp) && shdr::aligned16(y) && (!bias || shdr::aligned16(bias)),
-               SHDR_E_ALIGN, "conv2d_w3_f16: tensors must be 16-byte aligned");
+  if (int e = ptr.aligned()) return e;
   a = W3Args{};
   a.x1 = reinterpret_cast<const _Float16*>(x1);
   a.x2 = reinterpret_cast<const _Float16*>(x2 ? x2 : x1);
@@ -234,13 +201,7 @@ int w3_setup(const shdr_conv2d_desc* d, const void* x1, const void* x2, const vo
 
 template <bool FUSED>
 int w3_launch(const W3ArgsT<FUSED>& a, hipStream_t st) {
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16_w3_kernel<FUSED>), hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS_BYTES);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_f16_w3_kernel<FUSED>>(W3_LDS_BYTES)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_w3_f16: grid of %ld blocks", nblk);
   hipLaunchKernelGGL(conv_f16_w3_kernel<FUSED>, dim3((unsigned)nblk), dim3(256), W3_LDS_BYTES, st, a);

@@ -42,9 +42,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 constexpr int BN = 64, NT = 4, MT = 4;
@@ -206,7 +203,7 @@ __device__ __forceinline__ void x3_tile_epilogue(const X3Args& a, f32x4 (&acc)[M
 #endif
 }
 
-__host__ __device__ inline int f4(int row) { return (-(row >> 2)) & 3; }      // filter images: rows = couts, 16-row aligned fragments
+// (filter images: rows = couts, 16-row aligned fragments, slots swizzled by row_swz)
 // Patch images: the 16-byte slot of channel group kg of patch column c is kg ^ sx(c).  A ds_read_b128 is served in lane groups of
 // {8 lanes of one kg, 8 lanes of kg ^ 1}; with the lane -> tile-column permutation pcol() below each set of 8 reads 8 CONSECUTIVE
 // columns, so (column mod 8, kg) -- and with it (64-byte quarter, slot) -- is distinct for every tap shift: conflict-free at any
@@ -397,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
   for (int j = 0; j < FJ; ++j) {
     const int p = tid + 256 * j;
     const int im = p >> 8, co = (p & 255) >> 2, slot = p & 3;
-    fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ f4(co));
+    fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ row_swz(co));
   }
   // LOOK = 2: units alternate between two register slots.  The slot of a unit has to be a compile-time constant (a slot chosen by a branch
   // on the unit's parity left the compiler free to keep it in other registers on either side and to copy a load in flight), so the nine
@@ -453,7 +450,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const X3Args a) {
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = ni * 16 + fi;
-    b_rd[ni] = row * 32 + 8 * (fg ^ f4(row));
+    b_rd[ni] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   int kh_n = KH, kw_n = KW;                                    // taps of the phase (MP)
@@ -950,7 +947,7 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
   for (int j = 0; j < FJ; ++j) {
     const int p = ht + 256 * j;
     const int im = p >> 8, co = (p & 255) >> 2, slot = p & 3;
-    fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ f4(co));
+    fdst[j] = im * IMG_HALVES + co * 32 + 8 * (slot ^ row_swz(co));
   }
   u32x4 fr[2][FJ];
 #pragma unroll
@@ -998,7 +995,7 @@ __global__ __launch_bounds__(XW_THREADS, 2) void conv_x3_wide_kernel(const X3Arg
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = ni * 16 + fi;
-    b_rd[ni] = row * 32 + 8 * (fg ^ f4(row));
+    b_rd[ni] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   static_assert(NT == MT, "one filter fragment pair of the next tap is read in front of each MFMA group");
@@ -1194,13 +1191,7 @@ inline int64_t x3_phase_floats(const X3Phase& p, int Ct, int Cout) { return shdr
 template <bool UP, int KH, int KW, bool MP, int LOOK>
 int launch_x3_look(const X3Args& a, hipStream_t st) {
   constexpr int lds = (UP ? X3G<KH, KW>::LDS_BYTES_UP : X3G<KH, KW>::LDS_BYTES) + X3G<KH, KW>::RANGE_BYTES;
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<UP, KH, KW, MP, LOOK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_x3_kernel<UP, KH, KW, MP, LOOK>>(lds)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_x3_kernel<UP, KH, KW, MP, LOOK>), dim3((unsigned)nblk), dim3(256), lds, st, a);
@@ -1239,13 +1230,7 @@ int launch_x3_wide(const X3Args& a0, hipStream_t st) {
   X3Args a = a0;
   a.nblk_n = a.Cout / XW_BN;
   constexpr int lds = XWG::LDS_BYTES + (UP ? XWG::LR_BYTES : 0) + XWG::RANGE_BYTES;
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_wide_kernel<UP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&conv_x3_wide_kernel<UP>>(lds)) return e;
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "conv2d_x3: grid of %ld blocks", nblk);
   hipLaunchKernelGGL((conv_x3_wide_kernel<UP>), dim3((unsigned)nblk), dim3(XW_THREADS), lds, st, a);

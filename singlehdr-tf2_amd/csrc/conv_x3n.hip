@@ -16,12 +16,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __attribute__((aligned(16))) float g_xn_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
 struct X3nArgs {
@@ -43,8 +37,6 @@ struct X3nArgs {
 };
 
 struct __attribute__((packed, aligned(4))) f32x3u { float x, y, z; };      // 12 bytes at 4-byte alignment: global_load / store_dwordx3
-
-__host__ __device__ inline int pswz(int row) { return (-(row >> 2)) & 3; }
 
 template <int KK, int CT, int NT, bool TWO>
 struct NG {
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
     const int img = j >= G::FINSTR, jj = j - img * G::FINSTR;
     const int r = jj * 16 + (lane >> 2);                       // row = step * COUT + cout of image img
     const int co = r % G::COUT;
-    const _Float16* p = a.wp + img * G::FILT_HALVES + (size_t)r * 32 + 8 * ((lane & 3) ^ pswz(co));
+    const _Float16* p = a.wp + img * G::FILT_HALVES + (size_t)r * 32 + 8 * ((lane & 3) ^ row_swz(co));
     __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(nsm + img * G::FILT_HALVES + jj * 512), 16, 0, 0);
   }
   if (G::HALF && wave < 2) {                                   // the 32-byte rows of the last k-step: two lanes per row, one (partial) instruction per image
@@ -115,7 +107,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
     const int co = lane >> 1;
     if (co < G::COUT) {
       const int base = wave * G::FILT_HALVES + G::FULL_STEPS * G::COUT * 32;
-      const _Float16* p = a.wp + base + co * 16 + 8 * ((lane & 1) ^ (pswz(co) & 1));
+      const _Float16* p = a.wp + base + co * 16 + 8 * ((lane & 1) ^ (row_swz(co) & 1));
       __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(nsm + base), 16, 0, 0);
     }
   }
@@ -142,7 +134,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
       pdst[j] = ok ? src * G::PP * 16 + pix * 16 + 4 * c4 : -1;
       pch[j] = ok ? (src << 16) | (4 * c4) : -1;
     } else {
-      const int cg = (CT == 32) ? ((c4 >> 1) ^ pswz(pix)) : (c4 >> 1);       // 64-byte pixels: the b128 bank swizzle
+      const int cg = (CT == 32) ? ((c4 >> 1) ^ row_swz(pix)) : (c4 >> 1);       // 64-byte pixels: the b128 bank swizzle
       pdst[j] = ok ? pix * CT + 8 * cg + 4 * (c4 & 1) : -1;
       pch[j] = (ok && 4 * c4 < a.C1) ? 4 * c4 : -1;            // channels beyond the source's (3 -> 4, 9 -> 12 padded inputs) are zero
     }
@@ -228,7 +220,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
 #pragma unroll
   for (int ni = 0; ni < NT; ++ni) {
     const int row = ni * 16 + fi;
-    b_rd[ni] = row * 32 + 8 * (fg ^ pswz(row));
+    b_rd[ni] = row * 32 + 8 * (fg ^ row_swz(row));
   }
 
   // Workgroup barriers of the tile loop order LDS traffic only: __syncthreads() also fences global memory (s_waitcnt vmcnt(0)), i.e.
@@ -287,7 +279,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
         int bo = s * G::COUT * 32 + b_rd[ni];
         if (last_half) {                                         // 16-half rows; the lanes of the absent tap alias the real one's (finite) weights
           const int row = ni * 16 + fi;
-          bo = s * G::COUT * 32 + row * 16 + 8 * ((fg & 1) ^ (pswz(row) & 1));
+          bo = s * G::COUT * 32 + row * 16 + 8 * ((fg & 1) ^ (row_swz(row) & 1));
         }
         wh[ni] = *reinterpret_cast<const f16x8*>(filt_h + bo);
         wl[ni] = *reinterpret_cast<const f16x8*>(filt_l + bo);
@@ -298,7 +290,7 @@ __global__ __launch_bounds__(256, (x3n_min_waves<KK, CT, NT>(TANH))) void conv_x
         int ad = a_base[mi] + toff;
         if (!TWO && CT == 32) {                                // undo the swizzle of the 64-byte pixel
           const int pix = ad >> 5;
-          ad = (pix << 5) + 8 * (cgl ^ pswz(pix));
+          ad = (pix << 5) + 8 * (cgl ^ row_swz(pix));
         }
         ph[mi] = *reinterpret_cast<const f16x8*>(patch_h + ad);
         pl[mi] = *reinterpret_cast<const f16x8*>(patch_l + ad);
@@ -463,18 +455,9 @@ int launch_x3n(X3nArgs& a, hipStream_t st) {
   if constexpr (lds > 160 * 1024) {
     return shdr::fail(SHDR_E_SHAPE, "conv2d_x3n: filter + patch (%d bytes) do not fit the LDS", lds);
   } else {
-    const int dev_slot = shdr::device_slot();
-    static bool attr_done[shdr::kMaxDevices] = {};
-    static int occ[shdr::kMaxDevices] = {};
-    if (!attr_done[dev_slot]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3n_kernel<KK, CT, NT, TWO, TANH>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-      int nb = 0;
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&conv_x3n_kernel<KK, CT, NT, TWO, TANH>), 256, lds);
-      occ[dev_slot] = (e != hipSuccess || nb < 1) ? 1 : (nb > 4 ? 4 : nb);
-      attr_done[dev_slot] = true;
-    }
-    long grid = 256L * occ[dev_slot];
+    int occ = 1;
+    if (int e = shdr::dynamic_lds_occupancy<&conv_x3n_kernel<KK, CT, NT, TWO, TANH>>(256, lds, 4, occ)) return e;
+    long grid = 256L * occ;
     if (grid > a.ntiles) grid = a.ntiles;
     hipLaunchKernelGGL((conv_x3n_kernel<KK, CT, NT, TWO, TANH>), dim3((unsigned)grid), dim3(256), lds, st, a);
     return shdr::check_launch("conv_x3n_kernel");

@@ -8,6 +8,18 @@
 
 #include "shdr.h"
 
+// ---- MFMA / LDS-DMA vocabulary of the matrix-pipe kernels: the vector operands and the address spaces of global_load_lds ----------------
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+typedef __attribute__((__vector_size__(4 * sizeof(short)))) short sv4;      // one ds_read_b64_tr_b16
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+typedef __attribute__((address_space(3))) sv4* lsv4_t;
+// Images with 64-byte rows (32 halves: one MFMA k-chunk of a pixel or of a cout): physical 16-byte slot = k-group ^ row_swz(row),
+// conflict-free for the four 16-lane groups of a ds_read_b128; applied on the SOURCE address of the LDS-DMA.
+__host__ __device__ inline int row_swz(int row) { return (-(row >> 2)) & 3; }
+
 namespace shdr {
 
 // thread-local last-error message, returned by shdr_last_error()
@@ -38,6 +50,10 @@ inline int device_slot() {
   if (hipGetDevice(&d) != hipSuccess) d = 0;
   return d & (kMaxDevices - 1);
 }
+
+// The 16 zero bytes that an out-of-image LDS-DMA piece reads instead of the tensor.  Internal linkage: the library is built without
+// relocatable device code, so every translation unit that stages with LDS-DMA carries its own instance (and the others none).
+static __device__ __attribute__((aligned(16))) unsigned zero_page[4] = {0u, 0u, 0u, 0u};
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -120,6 +136,51 @@ inline long block_slots(KernelT kernel, int threads, size_t lds) {
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || cus < 1 || occ < 1)
     return 0;
   return (long)cus * occ;
+}
+// The launch set-up that HIP keeps per (kernel, device), done once per pair: the kernel is the template argument, so every instantiation
+// has its own memo and a launch site is one call.  Each returns SHDR_OK or SHDR_E_ARCH with the runtime's message; none makes a HIP call
+// beyond hipGetDevice once the pair is set up.
+// The dynamic-LDS limit: one hipFuncSetAttribute per size needed -- a kernel launched with one size sets it once, one whose size depends
+// on the layer raises it whenever a larger size arrives.
+template <auto Kernel>
+inline int dynamic_lds(int lds) {
+  static int set_dev[kMaxDevices] = {};
+  int& set = set_dev[device_slot()];
+  if (lds > set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    set = lds;
+  }
+  return SHDR_OK;
+}
+// ... and the kernel's block slots (the split-K weight gradients); a failed query is an error named after `who`
+template <auto Kernel>
+inline int dynamic_lds_slots(int threads, int lds, const char* who, long& slots) {
+  static long slots_dev[kMaxDevices] = {};
+  long& s = slots_dev[device_slot()];
+  if (s == 0) {
+    if (int e = dynamic_lds<Kernel>(lds)) return e;
+    s = block_slots(Kernel, threads, lds);
+    if (s == 0) return fail(SHDR_E_ARCH, "%s: occupancy query failed", who);
+  }
+  slots = s;
+  return SHDR_OK;
+}
+// ... and the kernel's blocks per CU at that size, 1 .. cap (the persistent grids), asked again when the size changes; a failed query
+// counts as 1
+template <auto Kernel>
+inline int dynamic_lds_occupancy(int threads, int lds, int cap, int& occ) {
+  static int occ_dev[kMaxDevices] = {}, lds_dev[kMaxDevices] = {};     // (LDS bytes are never 0 here: 0 = not queried yet)
+  const int slot = device_slot();
+  if (lds != lds_dev[slot]) {
+    if (int e = dynamic_lds<Kernel>(lds)) return e;
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(Kernel), threads, lds);
+    occ_dev[slot] = (e != hipSuccess || nb < 1) ? 1 : (nb > cap ? cap : nb);
+    lds_dev[slot] = lds;
+  }
+  occ = occ_dev[slot];
+  return SHDR_OK;
 }
 // slices (of `units` work items, at least `min_slice` each) per tile so that tiles x slices fills `rounds` rounds of the slots
 inline long slice_for_rounds(long slots, long tiles, long units, long min_slice) {

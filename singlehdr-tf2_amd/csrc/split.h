@@ -15,8 +15,6 @@ extern "C" int shdr_conv2d_x3n_prepare_filter_premax_f32(const shdr_conv2d_desc*
 
 namespace shdr {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 // ---- the packed filter's header: 16 floats in front of the fp16 images (64 bytes keep the images 16-byte aligned) -------------------------
 constexpr int kSplitHeaderFloats = 16;
 constexpr int kHdrMaxW = 0;          // max |w| (bits)

@@ -31,8 +31,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using shdr::fma4;
 using shdr::fma4v;
 using shdr::mul4;
@@ -356,13 +354,7 @@ template <int CW, int CMAX>
 int uf_launch(const UpFusedArgs& a, hipStream_t st) {
   constexpr int lds = uf_lds_bytes(UF_R, CW, CMAX), PPB = 4 / CW;
   static_assert(lds <= 160 * 1024 - 64, "the patch images of a block must fit the CU's LDS");
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&up2_fused_kernel<UF_R, CW, CMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&up2_fused_kernel<UF_R, CW, CMAX>>(lds)) return e;
   const long nblk = ((long)a.npatch + PPB - 1) / PPB;
   hipLaunchKernelGGL((up2_fused_kernel<UF_R, CW, CMAX>), dim3((unsigned)nblk), dim3(UF_THREADS), lds, st, a);
   return shdr::check_launch("up2_fused_kernel");

@@ -22,11 +22,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __attribute__((aligned(16))) float g_wg_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -455,18 +451,11 @@ int launch_wgrad_prec(WgradArgs& a, hipStream_t st) {
   a.tiles_m = (a.Cx + BMc - 1) / BMc;
   a.tiles_n = (a.Cout + BNc - 1) / BNc;
   constexpr int lds = 2 * PK * (BMc + BNc) * 4;
-  static long slots_of[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (slots_of[dev_slot] == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_mfma_kernel<BMc, BNc, WM, WN, PREC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    slots_of[dev_slot] = shdr::block_slots(wgrad_mfma_kernel<BMc, BNc, WM, WN, PREC>, 256, lds);
-    if (slots_of[dev_slot] == 0) return shdr::fail(SHDR_E_ARCH, "wgrad: occupancy query failed");
-  }
+  long slots = 0;
+  if (int e = shdr::dynamic_lds_slots<&wgrad_mfma_kernel<BMc, BNc, WM, WN, PREC>>(256, lds, "wgrad", slots)) return e;
   // pixel slices: one round of the chip's block slots, at least 1024 pixels per slice to bound the atomics
   const long tiles = (long)a.KH * a.KW * a.tiles_m * a.tiles_n;
-  long slice = shdr::slice_for_rounds(slots_of[dev_slot], tiles, a.npix, 1024);
+  long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
   if (SHDR_ENV("SHDR_WGRAD_LEGACY_GRID")) {
     const long want = (256L * 8 + tiles - 1) / tiles;
     slice = (a.npix + want - 1) / want;
@@ -527,7 +516,7 @@ extern "C" int shdr_conv2d_wgrad_f32(const shdr_conv2d_desc* d, const float* x, 
   a.Ho = d->Ho; a.Wo = d->Wo;
   a.npix = d->N * d->Ho * d->Wo;
   a.x_scale = which ? d->x2_scale : 1.0f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st = shdr::stream_of(stream);
   const bool mfma_ok = (a.Cx % 16 == 0) && (a.Cout % 16 == 0) && shdr::aligned16(x) && shdr::aligned16(dz);
   a.prec = (d->algo == SHDR_ALGO_MFMA_F16 || d->algo == SHDR_ALGO_AUTO_F16) ? 1
            : (d->algo == SHDR_ALGO_MFMA_BF16 || d->algo == SHDR_ALGO_AUTO_BF16) ? 2 : 0;
@@ -563,7 +552,7 @@ extern "C" int shdr_filter_transform_f32(const float* w, float* wt, int KH, int 
                SHDR_E_SHAPE, "filter_transform: bad shape");
   const long total = (long)KH * KW * Cout * c_count;
   hipLaunchKernelGGL(filter_transform_kernel, dim3(shdr::stream_grid(total)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), w, wt, KH, KW, Cin, Cout, c_begin, c_count, scale);
+                     shdr::stream_of(stream), w, wt, KH, KW, Cin, Cout, c_begin, c_count, scale);
   return shdr::check_launch("filter_transform");
 }
 
@@ -576,7 +565,7 @@ extern "C" int shdr_bias_grad_f32(const float* dz, float* db, int64_t npix, int 
   long g = (npix + (long)PL * 64 - 1) / ((long)PL * 64);
   if (g < 1) g = 1;
   if (g > 1024) g = 1024;
-  hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)g), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dz,
+  hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)g), dim3(256), 0, shdr::stream_of(stream), dz,
                      db, (long)npix, C);
   return shdr::check_launch("bias_grad");
 }

@@ -14,18 +14,12 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "f16.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short sv4;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) sv4* lsv4_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_wh_zero_page[4] = {0u, 0u, 0u, 0u};
+using shdr::Frag;
+using shdr::win_swz;
 
 struct WgradHArgs {
   const _Float16* x;   // [N,H,W,Cx]
@@ -38,12 +32,6 @@ struct WgradHArgs {
 };
 
 constexpr int PK = 32;
-
-
-template <int T>
-__host__ __device__ constexpr int win_swz(int p) {
-  return T >= 128 ? ((p & 3) | (((p >> 3) & 1) << 2)) : T == 64 ? (((p >> 1) & 1) | (((p >> 3) & 1) << 1)) : T == 32 ? ((p >> 3) & 1) : 0;
-}
 
 constexpr int pick_wm(int tm, int tn) { return (tm >= 2 && (tn >= 2 || tm >= 4)) ? (tn >= 2 ? 2 : 4) : (tm >= 2 && tn == 1 ? (tm >= 4 ? 4 : 2) : 1); }
 
@@ -85,7 +73,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void wgrad_f16_kernel(c
   const int p_end = min(p_begin + a.slice, a.npix);
   const int nchunks = (p_end - p_begin + PK - 1) / PK;
   const int nstages = (nchunks + KC - 1) / KC;
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_wh_zero_page);
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   // lane -> (pixel of the chunk, logical 16-byte piece) of each DMA instruction
   int xp[XI], xc[XI], zp[ZI], zc[ZI];
@@ -175,10 +163,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void wgrad_f16_kernel(c
       z_rd[h][ni] = PK * CI_T + row * CO_T + 16 * (w ^ win_swz<CO_T>(row)) + 4 * pp;
     }
   }
-  union Frag {
-    sv4 h[2];
-    f16x8 v;
-  };
 
   dma_stage(0);
   __syncthreads();
@@ -243,6 +227,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 4 ? 2 : 1) void wgrad_f16_kernel(c
   }
 
   // D[ci][co]: lane holds column co = lane & 15 of rows ci = 4 * (lane >> 4) + e; one wave instruction adds 4 rows x 64 bytes
+  // (the same loop is in wgrad_f16_alltaps.hip and wgrad_x3.hip, on purpose: see the all-taps kernel)
   if (computing) {
     const int fi = lane & 15, fg = lane >> 4;
     float* out = a.dw + ((size_t)tap * a.Ct + a.ci_off) * a.Cout;
@@ -271,20 +256,8 @@ int launch_wgrad_f16(WgradHArgs& a, hipStream_t st) {
   // block slots (CUs x the kernel's occupancy) -- ONE round unless SHDR_WGRAD_ROUNDS says otherwise:
   // one round of 252 blocks ran the 256 x 256 tile at 821-950 TFLOP/s where four rounds of 1008 ran at 676-843, and a grid of
   // 1029 blocks on 512 slots (the 7x7 stem) spent a third of its time in a round of 5 blocks.
-  static long slots_of[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (slots_of[dev_slot] == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f16_kernel<CI_T, CO_T, KC, NWV, WM_>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wgrad_f16_kernel<CI_T, CO_T, KC, NWV, WM_>, NWV * 64, lds) != hipSuccess ||
-        cus < 1 || occ < 1)
-      return shdr::fail(SHDR_E_ARCH, "wgrad_f16: occupancy query failed");
-    slots_of[dev_slot] = (long)cus * occ;
-  }
-  const long slots = slots_of[dev_slot];
+  long slots = 0;
+  if (int e = shdr::dynamic_lds_slots<&wgrad_f16_kernel<CI_T, CO_T, KC, NWV, WM_>>(NWV * 64, lds, "wgrad_f16", slots)) return e;
   int rounds = 1;
   if (const char* e = SHDR_ENV("SHDR_WGRAD_ROUNDS")) rounds = atoi(e);
   long slice = a.npix;
@@ -315,13 +288,10 @@ int dispatch_co(WgradHArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int shdr_conv2d_wgrad_alltaps_ok_f16(const shdr_conv2d_desc* d, int which, int dz_channels);
-extern "C" int shdr_conv2d_wgrad_alltaps_f16(const shdr_conv2d_desc* d, const void* x, int which, const void* dz, int dz_channels,
-                                             int c1_rows, int c2_rows, float* dw, void* stream);
-
 extern "C" int shdr_conv2d_wgrad_f16(const shdr_conv2d_desc* d, const void* x, int which, const void* dz, int dz_channels, int c1_rows,
                                      int c2_rows, float* dw, void* stream) {
-  SHDR_REQUIRE(d && x && dz && dw, SHDR_E_NULL, "wgrad_f16: null pointer");
+  const shdr::F16WgradPointers ptr{"wgrad_f16", d, x, dz, dw};
+  if (int e = ptr.given()) return e;
   SHDR_REQUIRE(which == 0 || (which == 1 && d->C2 > 0), SHDR_E_SHAPE, "wgrad_f16: `which` selects x1 (0) or x2 (1)");
   SHDR_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C1 > 0 && d->C2 >= 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 &&
                    d->Ho > 0 && d->Wo > 0,
@@ -334,22 +304,14 @@ extern "C" int shdr_conv2d_wgrad_f16(const shdr_conv2d_desc* d, const void* x, i
                "wgrad_f16: channels per pixel must be multiples of 8 (x %d, dz %d >= %d)", Cx, dz_channels, cout);
   SHDR_REQUIRE((long)d->N * d->Ho * d->Wo < (1L << 31) && (long)d->N * d->H * d->W * Cx < (1L << 32), SHDR_E_SHAPE,
                "wgrad_f16: tensor too large");
-  SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(dz), SHDR_E_ALIGN, "wgrad_f16: tensors must be 16-byte aligned");
+  if (int e = ptr.aligned()) return e;
   // stride-1 layers with many pixels: every tap from one staged strip (wgrad_f16_alltaps.hip)
   if (shdr_conv2d_wgrad_alltaps_ok_f16(d, which, dz_channels) && SHDR_ENV("SHDR_NO_ALLTAPS") == nullptr)
     return shdr_conv2d_wgrad_alltaps_f16(d, x, which, dz, dz_channels, c1_rows, c2_rows, dw, stream);
   WgradHArgs a{};
-  a.x = reinterpret_cast<const _Float16*>(x);
-  a.dz = reinterpret_cast<const _Float16*>(dz);
-  a.dw = dw;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cx = Cx; a.Cz = dz_channels;
-  a.Ct = c1_rows + c2_rows;
-  a.ci_off = which ? c1_rows : 0;
-  a.ci_valid = which ? c2_rows : c1_rows;
-  a.Cout = d->Cout; a.co_valid = cout;
+  shdr::f16_wgrad_fill(a, d, x, which, dz, dz_channels, c1_rows, c2_rows, dw);
   a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.Ho = d->Ho; a.Wo = d->Wo;
   a.npix = d->N * d->Ho * d->Wo;
-  a.x_scale = which ? d->x2_scale : 1.0f;
   hipStream_t st = shdr::stream_of(stream);
   // 256-wide tiles (8 waves, one block per CU) halve the L2 -> LDS traffic per flop of the widest layers
   long min256 = 4096;

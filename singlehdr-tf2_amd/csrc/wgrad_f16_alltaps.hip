@@ -16,18 +16,12 @@
 #include <type_traits>
 #include <utility>
 
-#include "shdr_internal.h"
+#include "f16.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short sv4;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) sv4* lsv4_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_wa_zero_page[4] = {0u, 0u, 0u, 0u};
+using shdr::Frag;
+using shdr::win_swz;
 
 struct WgradAArgs {
   const _Float16* x;   // [N,H,W,Cx]
@@ -38,11 +32,6 @@ struct WgradAArgs {
   int ci_valid, co_valid;
   float x_scale;
 };
-
-template <int T>
-__host__ __device__ constexpr int wswz(int p) {
-  return T >= 128 ? ((p & 3) | (((p >> 3) & 1) << 2)) : T == 64 ? (((p >> 1) & 1) | (((p >> 3) & 1) << 1)) : T == 32 ? ((p >> 3) & 1) : 0;
-}
 
 template <int KK, int CI_T, int CO_T, int MODE>
 struct AG {
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
   const int ci0 = tm * CI_T, co0 = tn * CO_T;
   const int s_begin = blockIdx.y * a.slice;
   const int s_end = min(s_begin + a.slice, a.nsegs);
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_wa_zero_page);
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   // ---- DMA geometry: piece -> (strip row, strip pixel, logical 16-byte piece) -------------------------------------------------
   // Segments run DOWN a 32-pixel column (consecutive segments of a block share KK - 1 of their KK strip rows, which the XCD's L2
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
     const int r = pix / G::SW, sp = pix - r * G::SW;
     xrp[j] = r - PAD;
     xsp[j] = sp - PAD;
-    xc[j] = 8 * ((((pq >> 1) ^ wswz<CI_T>(sp)) << 1) | (pq & 1));
+    xc[j] = 8 * ((((pq >> 1) ^ win_swz<CI_T>(sp)) << 1) | (pq & 1));
     xok[j] = xok[j] && ci0 + xc[j] < a.Cx;
   }
 #pragma unroll
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
     zok[j] = piece < G::Z_PIECES;
     zp[j] = piece / G::ZP;
     const int pq = piece - zp[j] * G::ZP;
-    zc[j] = 8 * ((((pq >> 1) ^ wswz<CO_T>(zp[j])) << 1) | (pq & 1));
+    zc[j] = 8 * ((((pq >> 1) ^ win_swz<CO_T>(zp[j])) << 1) | (pq & 1));
     zok[j] = zok[j] && co0 + zc[j] < a.Cz;
   }
   // element offsets modulo 2^32 (the host checks N*H*W*C < 2^32; rows above the image wrap and are never dereferenced)
@@ -186,10 +175,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
   // transposed reads (wgrad_f16.hip): lane = (k-group g, row q, piece pp) -> pixel 8g + 4h + q of the segment
   const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
   const int wm = MODE ? (wave >> 1) : 0, wn = MODE ? (wave & 1) : 0;
-  union Frag {
-    sv4 h[2];
-    f16x8 v;
-  };
   // LDS byte addresses inside a stage.  The reads are inline asm: the compiler orders every LDS read it knows of behind ALL
   // LDS-DMA writes in flight (s_waitcnt vmcnt(0) -- it cannot tell the ring's buffers apart), which would drain the ring once per
   // segment; hidden in asm their completion is the counted "s_waitcnt lgkmcnt" + register fence in front of each MFMA group.
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
     const int row = 8 * g + 4 * h + q;
 #pragma unroll
     for (int ni = 0; ni < NT; ++ni)
-      z_rd[h][ni] = lds0 + 2u * (unsigned)(G::X_HALVES + row * CO_T + 16 * ((wn * NT + ni) ^ wswz<CO_T>(row)) + 4 * pp);
+      z_rd[h][ni] = lds0 + 2u * (unsigned)(G::X_HALVES + row * CO_T + 16 * ((wn * NT + ni) ^ win_swz<CO_T>(row)) + 4 * pp);
 #pragma unroll
     for (int i = 0; i < XR; ++i) {
       const int tap = MODE ? i : min(4 * i + wave, G::NTAPS - 1);
@@ -211,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
       const int sp = row + kw;                                        // strip pixel of this lane's row
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi)
-        x_rd[i][h][mi] = lds0 + 2u * (unsigned)((kh * G::SW + sp) * CI_T + 16 * ((wm * MT + mi) ^ wswz<CI_T>(sp)) + 4 * pp);
+        x_rd[i][h][mi] = lds0 + 2u * (unsigned)((kh * G::SW + sp) * CI_T + 16 * ((wm * MT + mi) ^ win_swz<CI_T>(sp)) + 4 * pp);
     }
   }
 
@@ -289,7 +274,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16_alltaps_kernel(const WgradAA
   }
   __builtin_amdgcn_s_waitcnt(vmcnt_only(0));                          // the re-fetched tail segments land before the block's LDS is released
 
-  // D[ci][co]: lane holds column co = lane & 15 of rows ci = 4 * (lane >> 4) + e
+  // D[ci][co]: lane holds column co = lane & 15 of rows ci = 4 * (lane >> 4) + e.  (This loop is also in wgrad_f16.hip and, on hi / lo
+  // accumulators, in wgrad_x3.hip: through one helper it compiled to another stream in all three -- 3 - 11 % shorter here -- and the
+  // per-tap kernel's wide layers measured 1 - 2 % slower, so each kernel keeps its copy.)
   const int fi = lane & 15, fg = lane >> 4;
 #pragma unroll
   for (int t = 0; t < G::TAPS_W; ++t) {
@@ -320,25 +307,9 @@ int launch_alltaps(WgradAArgs& a, hipStream_t st) {
   a.nsegs = a.N * a.H * a.segs_x;
   // segment slices: ONE round of the chip's block slots (CUs x occupancy; wgrad_f16.hip has the measurements), at least 32
   // segments (1024 pixels) per block so that the KK^2 x CI_T x CO_T atomics of a block stay cheap
-  static long slots_of[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (slots_of[dev_slot] == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_f16_alltaps_kernel<KK, CI_T, CO_T, MODE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int dev = 0, cus = 0, occ = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wgrad_f16_alltaps_kernel<KK, CI_T, CO_T, MODE>, 256, G::LDS_BYTES) != hipSuccess ||
-        cus < 1 || occ < 1)
-      return shdr::fail(SHDR_E_ARCH, "wgrad_f16_alltaps: occupancy query failed");
-    slots_of[dev_slot] = (long)cus * occ;
-  }
-  long rounds = 1;
-  if (const char* e = SHDR_ENV("SHDR_WGRAD_ROUNDS")) rounds = atol(e) > 0 ? atol(e) : 1;
-  long want = slots_of[dev_slot] * rounds / tiles;
-  if (want < 1) want = 1;
-  long slice = (a.nsegs + want - 1) / want;
-  if (slice < 32) slice = 32;
+  long slots = 0;
+  if (int e = shdr::dynamic_lds_slots<&wgrad_f16_alltaps_kernel<KK, CI_T, CO_T, MODE>>(256, G::LDS_BYTES, "wgrad_f16_alltaps", slots)) return e;
+  const long slice = shdr::slice_for_rounds(slots, tiles, a.nsegs, 32);
   a.slice = (int)slice;
   const long nslices = (a.nsegs + slice - 1) / slice;
   if (nslices > 65535) return shdr::fail(SHDR_E_SHAPE, "wgrad_f16_alltaps: grid too large");
@@ -363,25 +334,18 @@ extern "C" int shdr_conv2d_wgrad_alltaps_ok_f16(const shdr_conv2d_desc* d, int w
 
 extern "C" int shdr_conv2d_wgrad_alltaps_f16(const shdr_conv2d_desc* d, const void* x, int which, const void* dz, int dz_channels,
                                              int c1_rows, int c2_rows, float* dw, void* stream) {
-  SHDR_REQUIRE(d && x && dz && dw, SHDR_E_NULL, "wgrad_f16_alltaps: null pointer");
+  const shdr::F16WgradPointers ptr{"wgrad_f16_alltaps", d, x, dz, dw};
+  if (int e = ptr.given()) return e;
   SHDR_REQUIRE(shdr_conv2d_wgrad_alltaps_ok_f16(d, which, dz_channels), SHDR_E_SHAPE, "wgrad_f16_alltaps: layer not taken by this kernel");
   const int Cx = which ? d->C2 : d->C1;
   const int cout = d->cout_valid > 0 ? d->cout_valid : d->Cout;
   SHDR_REQUIRE(c1_rows > 0 && c1_rows <= d->C1 && c2_rows >= 0 && c2_rows <= d->C2 && cout <= d->Cout && cout <= dz_channels, SHDR_E_SHAPE,
                "wgrad_f16_alltaps: bad row / column counts");
   SHDR_REQUIRE((long)d->N * d->H * d->W * (Cx > dz_channels ? Cx : dz_channels) < (1L << 32), SHDR_E_SHAPE, "wgrad_f16_alltaps: tensor too large");
-  SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(dz), SHDR_E_ALIGN, "wgrad_f16_alltaps: tensors must be 16-byte aligned");
+  if (int e = ptr.aligned()) return e;
   WgradAArgs a{};
-  a.x = reinterpret_cast<const _Float16*>(x);
-  a.dz = reinterpret_cast<const _Float16*>(dz);
-  a.dw = dw;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cx = Cx; a.Cz = dz_channels;
-  a.Ct = c1_rows + c2_rows;
-  a.ci_off = which ? c1_rows : 0;
-  a.ci_valid = which ? c2_rows : c1_rows;
-  a.Cout = d->Cout; a.co_valid = cout;
-  a.x_scale = which ? d->x2_scale : 1.0f;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  shdr::f16_wgrad_fill(a, d, x, which, dz, dz_channels, c1_rows, c2_rows, dw);
+  hipStream_t st = shdr::stream_of(stream);
   const int cz = dz_channels;
   if (d->KH == 7) return launch_alltaps<7, 16, 16, 0>(a, st);
   if (d->KH == 5) {

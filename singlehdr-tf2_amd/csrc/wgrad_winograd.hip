@@ -20,10 +20,6 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __attribute__((aligned(16))) float g_ww_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
 struct WinoWgradArgs {
@@ -242,7 +238,7 @@ extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, f
   SHDR_REQUIRE((long)N * H * W * Cx < (1L << 32) && (long)N * H * W * Cout < (1L << 32), SHDR_E_SHAPE,
                "wgrad_winograd: tensor with more than 2^32 elements");
   // du is scratch of this call: zeroed here, in stream order (the caller hands over uninitialised memory)
-  if (hipMemsetAsync(du, 0, sizeof(float) * 16 * (size_t)Cx * Cout, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+  if (hipMemsetAsync(du, 0, sizeof(float) * 16 * (size_t)Cx * Cout, shdr::stream_of(stream)) != hipSuccess)
     return shdr::fail(SHDR_E_LAUNCH, "wgrad_winograd: memset of the dU scratch failed");
   WinoWgradArgs a{};
   a.x = x; a.dz = dz; a.du = du;
@@ -254,19 +250,12 @@ extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, f
   // spills (measured 10 % slower even without the pipeline)
   a.tiles_m = Cx / 32;
   a.tiles_n = Cout / 64;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  static long slots_of[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (slots_of[dev_slot] == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_winograd_kernel<2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, WW<2>::LDS_BYTES);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    slots_of[dev_slot] = shdr::block_slots(wgrad_winograd_kernel<2>, 256, WW<2>::LDS_BYTES);
-    if (slots_of[dev_slot] == 0) return shdr::fail(SHDR_E_ARCH, "wgrad_winograd: occupancy query failed");
-  }
+  hipStream_t st = shdr::stream_of(stream);
+  long slots = 0;
+  if (int e = shdr::dynamic_lds_slots<&wgrad_winograd_kernel<2>>(256, WW<2>::LDS_BYTES, "wgrad_winograd", slots)) return e;
   // unit slices: one round of the chip's block slots, >= 32 units (256 tiles) per block to bound the atomics
   const long tiles = (long)a.tiles_m * a.tiles_n;
-  long slice = shdr::slice_for_rounds(slots_of[dev_slot], tiles, a.units, 32);
+  long slice = shdr::slice_for_rounds(slots, tiles, a.units, 32);
   if (SHDR_ENV("SHDR_WGRAD_LEGACY_GRID")) {
     const long want = (768 + tiles - 1) / tiles;
     slice = (a.units + want - 1) / want;

@@ -18,18 +18,13 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
+#include "f16.h"
 #include "split.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-typedef __attribute__((__vector_size__(4 * sizeof(short)))) short sv4;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef __attribute__((address_space(3))) sv4* lsv4_t;
-
-__device__ __attribute__((aligned(16))) unsigned g_wx_zero_page[4] = {0u, 0u, 0u, 0u};
+using shdr::Frag;
+using shdr::win_swz;
 
 struct WgradXArgs {
   const _Float16* xh;  // [N,H,W,Cx] high plane of X 2^Tx
@@ -47,10 +42,6 @@ struct WgradXArgs {
 
 constexpr int PK = 32;
 
-template <int T>
-__host__ __device__ constexpr int win_swz(int p) {
-  return T >= 128 ? ((p & 3) | (((p >> 3) & 1) << 2)) : T == 64 ? (((p >> 1) & 1) | (((p >> 3) & 1) << 1)) : T == 32 ? ((p >> 3) & 1) : 0;
-}
 // x -> (fp16(x 2^T), fp16((x 2^T - high) 2^11)), 8 elements (two 16-byte stores) per thread and iteration
 __global__ __launch_bounds__(256) void x3_split_planes_kernel(const float* __restrict__ x, long n8, const unsigned* __restrict__ slot,
                                                               _Float16* __restrict__ hi, _Float16* __restrict__ lo) {
@@ -92,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
   const int p_begin = slice_id * a.slice;
   const int p_end = min(p_begin + a.slice, a.npix);
   const int nchunks = (p_end - p_begin + PK - 1) / PK;
-  const _Float16* zero = reinterpret_cast<const _Float16*>(g_wx_zero_page);
+  const _Float16* zero = reinterpret_cast<const _Float16*>(shdr::zero_page);
 
   int xp[XI], xc[XI], zp[ZI], zc[ZI];
 #pragma unroll
@@ -165,10 +156,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
 #pragma unroll
     for (int ni = 0; ni < NT; ++ni) z_rd[h][ni] = row * CO_T + 16 * ((wn * NT + ni) ^ win_swz<CO_T>(row)) + 4 * pp;
   }
-  union Frag {
-    sv4 h[2];
-    f16x8 v;
-  };
   auto rd = [&](const _Float16* img, int o0, int o1) __attribute__((always_inline)) {
     Frag f;
     f.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lsv4_t)(img + o0));
@@ -210,6 +197,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
   }
 
   // D[ci][co]: lane holds column co = lane & 15 of rows ci = 4 * (lane >> 4) + e; dW += x_scale 2^-(Tx+Tz) (hi + 2^-11 lo)
+  // (the loop of wgrad_f16.hip and wgrad_f16_alltaps.hip, kept apart on purpose: see the all-taps kernel)
   const float sc = a.x_scale * ldexpf(1.0f, -shdr::range_exponent(a.xr)) * ldexpf(1.0f, -shdr::range_exponent(a.zr));
   const int fi = lane & 15, fg = lane >> 4;
   float* out = a.dw + ((size_t)tap * a.Ct + a.ci_off) * a.Cout;
@@ -232,16 +220,10 @@ int launch_wgrad_x3(WgradXArgs& a, hipStream_t st) {
   a.tiles_m = (a.Cx + CI_T - 1) / CI_T;
   a.tiles_n = (a.Cz + CO_T - 1) / CO_T;
   const long tiles = (long)a.KH * a.KW * a.tiles_m * a.tiles_n;
-  static long slots_of[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (slots_of[dev_slot] == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_x3_kernel<CI_T, CO_T>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    slots_of[dev_slot] = shdr::block_slots(wgrad_x3_kernel<CI_T, CO_T>, 256, lds);
-    if (slots_of[dev_slot] < 1) return shdr::fail(SHDR_E_ARCH, "wgrad_x3: occupancy query failed");
-  }
+  long slots = 0;
+  if (int e = shdr::dynamic_lds_slots<&wgrad_x3_kernel<CI_T, CO_T>>(256, lds, "wgrad_x3", slots)) return e;
   // one round of the chip's block slots (wgrad_f16.hip: every block pays a DMA prologue and a tile of atomics)
-  long slice = shdr::slice_for_rounds(slots_of[dev_slot], tiles, a.npix, 1024);
+  long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
   slice = (slice + PK - 1) / PK * PK;
   a.slice = (int)slice;
   const long nslices = (a.npix + slice - 1) / slice;

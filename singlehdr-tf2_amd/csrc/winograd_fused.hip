@@ -34,10 +34,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 __device__ __attribute__((aligned(16))) float g_wf_zero_page[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -426,14 +423,7 @@ int launch_fused(WinoFusedArgs& a, hipStream_t st) {
   const long nblk = (long)a.nblk_m * a.nblk_n;
   if (nblk <= 0 || nblk > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "winograd_fused: grid of %ld blocks", nblk);
   static_assert(!UP || WF<R>::PIPE_FLOATS + 5 * 8 * 256 <= WF<R>::LDS_BYTES / 4, "the low-res ring lives inside the epilogue overlay");
-  static bool attr_done[shdr::kMaxDevices] = {};
-  const int dev_slot = shdr::device_slot();
-  if (!attr_done[dev_slot]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_fused_kernel<R, UP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, WF<R>::LDS_BYTES);
-    if (e != hipSuccess) return shdr::fail(SHDR_E_ARCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_done[dev_slot] = true;
-  }
+  if (int e = shdr::dynamic_lds<&winograd_fused_kernel<R, UP>>(WF<R>::LDS_BYTES)) return e;
   hipLaunchKernelGGL((winograd_fused_kernel<R, UP>), dim3((unsigned)nblk), dim3(512), WF<R>::LDS_BYTES, st, a);
   return shdr::check_launch("winograd_fused_kernel");
 }
