@@ -1301,6 +1301,77 @@ int shdr_png_encode_batch_sizes(const int32_t* images, int n_images, int deflate
 int shdr_png_encode_batch(const uint8_t* pixels, const int32_t* images, const int32_t* images_dev, int n_images, int filter, int deflate,
                           uint8_t* out, int64_t out_capacity, int64_t* offsets, void* workspace, void* stream, float* stage_ms);
 
+/* ---- gain maps (csrc/gainmap.hip; the rules are csrc/gainmap.h, shared with the host twins) ----------------------------------------
+ * The arithmetic of Ultra HDR v1 / Adobe hdrgm gain-map files, in both directions (the container is ultrahdr.py).  ENCODE: an SDR image
+ * uint8 [H][W][3] RGB and an HDR image float32 [H][W][3] (reverse_channels: its channel 2 is red) -> a map uint8 [h][w][3] with
+ * h = ceil(H / f), w = ceil(W / f), f in {1, 2, 4, 8}, and one shdr_gainmap_meta.  Per channel a cell holds
+ * g = log2((mean of s hdr + 1/64) / (mean of sRGB-linear sdr + 1/64)) clamped to [lo, hi], coded as rint(255 (g - min) / (max - min)),
+ * min and max those of the image (max at least min + 2^-10).  HDR values are sanitised first (NaN, negatives -> 0, +inf -> FLT_MAX).
+ * s is scales[i], or with scales NULL the exposure alignment exp2(mean log2 Y_sdr - mean log2 max(Y_hdr, 2^-20)) over the pixels whose
+ * SDR bytes all lie in [16, 239] (count of them in the meta record; none: s = 1), summed in float64 in a fixed tree.  log2 and exp2
+ * are polynomials of the header, so the device bits are the host twin's bits.  APPLY: out = max((lin(sdr) + offset_sdr) exp2(L weight)
+ * - offset_hdr, 0), L = min (1 - r) + max r, r the map (1 or 3 channels) sampled bilinearly at (x + 0.5) / f - 0.5, through
+ * exp2(log2(r) / gamma) when gamma != 1.
+ *
+ * Both directions take a BATCH of images of different sizes out of flat arenas (sdr uint8 [arena_pixels][3], hdr / out float32
+ * [arena_pixels][3], image i starting at pixel pix_off) through one descriptor table: a host array, which is validated before anything
+ * is launched (an image that leaves its arena, a factor outside the set, an empty image and derived fields that are not what the
+ * *_sizes call writes are refused), and the device copy of that very array, which the kernels read.
+ *      shdr_gainmap_encode_sizes  fills the derived fields of the descriptors; the bytes of all maps back to back (image i's map
+ *                                 starts at byte 3 cell_off) and of the workspace
+ *      shdr_gainmap_encode        three stream-ordered launches: alignment statistics (with scales given: only the clearing of the
+ *                                 min / max slots), cells (g as fp32 into the workspace, min / max by integer atomics on ordered bits),
+ *                                 quantise (maps and meta records).  maps: map_capacity bytes, meta: meta_capacity records, both on the
+ *                                 device; workspace 16-byte aligned, owned by the caller; stage_ms NULL or [SHDR_GAINMAP_STAGES]
+ *      shdr_gainmap_encode_host   the twin, host memory: the same bits
+ *      shdr_gainmap_apply_sizes   fills block0 of the descriptors; the launch's blocks
+ *      shdr_gainmap_apply         one launch; out: out_capacity PIXELS, image i at pixel pix_off as in the sdr arena
+ *      shdr_gainmap_apply_host    the twin
+ *      shdr_gainmap_math_host     y[i] = log2 (op 0) or exp2 (op 1) of x[i] by the header's polynomials; op 2: y[0 .. n) = the sRGB table (n <= 256)
+ * A destination smaller than needed is refused and nothing is written.  No host wait, no allocation on the device routes. */
+#define SHDR_GAINMAP_CELLS_PER_BLOCK 1024
+#define SHDR_GAINMAP_PIXELS_PER_BLOCK 1024
+#define SHDR_GAINMAP_STAGES 3
+typedef struct shdr_gainmap_image {
+  int64_t pix_off;                            /* first pixel of the image in both arenas */
+  int64_t cell_off;                           /* derived: map cells of the images before this one */
+  int32_t height, width;                      /* 1 .. 65535 */
+  int32_t factor;                             /* 1, 2, 4 or 8 */
+  int32_t stat_block0, cell_block0;           /* derived: the image's first block of the statistics and of the cell launch */
+  int32_t reserved;
+} shdr_gainmap_image;
+typedef struct shdr_gainmap_meta {
+  float gain_min, gain_max;                   /* GainMapMin, GainMapMax (log2) */
+  float scale;                                /* s */
+  int32_t reserved;
+  int64_t count;                              /* pixels that took part in the alignment; 0 with scales given */
+} shdr_gainmap_meta;
+typedef struct shdr_gainmap_apply_image {
+  int64_t pix_off;                            /* first pixel in the sdr arena and in out */
+  int64_t map_off;                            /* first byte of the map */
+  int32_t height, width, map_height, map_width;
+  int32_t factor;                             /* 1 .. 64; map_height = ceil(height / factor), map_width likewise */
+  int32_t map_channels;                       /* 1 or 3 */
+  float gain_min, gain_max, gamma, offset_sdr, offset_hdr, weight;
+  int32_t block0;                             /* derived: the image's first block */
+  int32_t reserved;
+} shdr_gainmap_apply_image;
+int shdr_gainmap_math_host(int op, const float* x, int64_t n, float* y);
+int shdr_gainmap_encode_sizes(shdr_gainmap_image* images, int n_images, int64_t* map_bytes, int64_t* workspace_bytes);
+int shdr_gainmap_encode_host(const uint8_t* sdr, const float* hdr, int64_t arena_pixels, const shdr_gainmap_image* images, int n_images,
+                             const float* scales, float lo, float hi, int reverse_channels, uint8_t* maps, int64_t map_capacity,
+                             shdr_gainmap_meta* meta, int64_t meta_capacity);
+int shdr_gainmap_encode(const uint8_t* sdr, const float* hdr, int64_t arena_pixels, const shdr_gainmap_image* images,
+                        const shdr_gainmap_image* images_dev, int n_images, const float* scales, const float* scales_dev, float lo, float hi,
+                        int reverse_channels, uint8_t* maps, int64_t map_capacity, shdr_gainmap_meta* meta, int64_t meta_capacity,
+                        void* workspace, void* stream, float* stage_ms);
+int shdr_gainmap_apply_sizes(shdr_gainmap_apply_image* images, int n_images, int64_t* n_blocks);
+int shdr_gainmap_apply_host(const uint8_t* sdr, int64_t arena_pixels, const uint8_t* maps, int64_t map_bytes,
+                            const shdr_gainmap_apply_image* images, int n_images, float* out, int64_t out_capacity);
+int shdr_gainmap_apply(const uint8_t* sdr, int64_t arena_pixels, const uint8_t* maps, int64_t map_bytes,
+                       const shdr_gainmap_apply_image* images, const shdr_gainmap_apply_image* images_dev, int n_images, float* out,
+                       int64_t out_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

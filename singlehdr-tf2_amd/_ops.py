@@ -3131,3 +3131,200 @@ def tonemap_u8(x, peak=None, reverse_channels=False, mu=5000.0):
     _lib.check(lib.shdr_tonemap_u8_f32(_ptr(x4), None, _ptr(peak), _ptr(y), n, h, w, float(mu), int(reverse_channels), _stream()),
                "shdr_tonemap_u8_f32")
     return y
+
+
+# ---------------------------------------------------------------------------
+# gain maps (ultrahdr.py), see csrc/gainmap.hip and csrc/gainmap.h
+# ---------------------------------------------------------------------------
+GAINMAP_FACTORS = (1, 2, 4, 8)
+GAINMAP_STAGE_NAMES = ("statistics", "cells", "quantise")       # SHDR_GAINMAP_STAGES
+GAINMAP_GUARD = 0xA5                                            # what the guard bytes of gainmap_encode / gainmap_apply(..., guard=) hold
+GAINMAP_OFFSET = 0.015625                                       # OffsetSDR = OffsetHDR of every map written here
+GAINMAP_IMAGE_DTYPE = np.dtype([("pix_off", np.int64), ("cell_off", np.int64), ("height", np.int32), ("width", np.int32),
+                                ("factor", np.int32), ("stat_block0", np.int32), ("cell_block0", np.int32),
+                                ("reserved", np.int32)])       # shdr_gainmap_image
+GAINMAP_META_DTYPE = np.dtype([("gain_min", np.float32), ("gain_max", np.float32), ("scale", np.float32), ("reserved", np.int32),
+                               ("count", np.int64)])            # shdr_gainmap_meta
+GAINMAP_APPLY_DTYPE = np.dtype([("pix_off", np.int64), ("map_off", np.int64), ("height", np.int32), ("width", np.int32),
+                                ("map_height", np.int32), ("map_width", np.int32), ("factor", np.int32), ("map_channels", np.int32),
+                                ("gain_min", np.float32), ("gain_max", np.float32), ("gamma", np.float32), ("offset_sdr", np.float32),
+                                ("offset_hdr", np.float32), ("weight", np.float32), ("block0", np.int32),
+                                ("reserved", np.int32)])        # shdr_gainmap_apply_image
+assert GAINMAP_IMAGE_DTYPE.itemsize == 40 and GAINMAP_META_DTYPE.itemsize == 24 and GAINMAP_APPLY_DTYPE.itemsize == 72
+
+
+def _gainmap_fail(lib, rc):
+    if rc != 0:
+        raise ValueError(lib.shdr_last_error().decode())
+
+
+def gainmap_math_host(op, x=None):
+    """the polynomials and the table of csrc/gainmap.h on the host: op "log2" | "exp2" of a float32 array, or "srgb": the 256 entries"""
+    lib = _lib.load()
+    if op == "srgb":
+        y = np.empty(256, dtype=np.float32)
+        _gainmap_fail(lib, lib.shdr_gainmap_math_host(2, None, 256, _hptr(y)))
+        return y
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    _gainmap_fail(lib, lib.shdr_gainmap_math_host({"log2": 0, "exp2": 1}[op], _hptr(x), x.size, _hptr(y)))
+    return y
+
+
+def gainmap_images(shapes, factor=4):
+    """(descriptors GAINMAP_IMAGE_DTYPE [n], bytes of all maps, bytes of the workspace) of images of `shapes` [(H, W)] that lie back to
+    back in the arenas; factor: one value or one per image.  ValueError for a shape or factor outside the scope."""
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    factors = list(factor) if isinstance(factor, (list, tuple, np.ndarray)) else [factor] * len(shapes)
+    if len(factors) != len(shapes):
+        raise ValueError("gainmap_images: %d factors for %d images" % (len(factors), len(shapes)))
+    images = np.zeros(len(shapes), dtype=GAINMAP_IMAGE_DTYPE)
+    pix = 0
+    for i, (shape, f) in enumerate(zip(shapes, factors)):
+        if len(shape) != 2:
+            raise ValueError("gainmap_images: image %d is %s: expected (H, W)" % (i, shape))
+        images[i]["pix_off"], images[i]["height"], images[i]["width"], images[i]["factor"] = pix, shape[0], shape[1], int(f)
+        pix += max(shape[0], 0) * max(shape[1], 0)
+    return (images,) + gainmap_sizes(images)
+
+
+def gainmap_sizes(images):
+    """fills the derived fields of descriptors (in place); returns (bytes of all maps, bytes of the workspace)"""
+    lib = _lib.load()
+    if images.dtype != GAINMAP_IMAGE_DTYPE or images.ndim != 1 or not images.flags.c_contiguous:
+        raise ValueError("gainmap_sizes: expected descriptors of GAINMAP_IMAGE_DTYPE")
+    map_b, ws_b = ctypes.c_int64(0), ctypes.c_int64(0)
+    _gainmap_fail(lib, lib.shdr_gainmap_encode_sizes(_hptr(images), images.size, ctypes.byref(map_b), ctypes.byref(ws_b)))
+    return map_b.value, ws_b.value
+
+
+def _gainmap_encode_args(what, images, scales, log2_range):
+    images = np.ascontiguousarray(images)
+    if images.dtype != GAINMAP_IMAGE_DTYPE or images.ndim != 1:
+        raise ValueError("%s: expected descriptors of GAINMAP_IMAGE_DTYPE (gainmap_images)" % what)
+    if scales is not None:
+        scales = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+        if scales.size != images.size:
+            raise ValueError("%s: %d scales for %d images" % (what, scales.size, images.size))
+    lo, hi = (float(v) for v in log2_range)
+    return images, scales, lo, hi
+
+
+def gainmap_encode_host(sdr, hdr, images, scales=None, log2_range=(-4.0, 8.0), reverse_channels=False, map_capacity=None, meta_capacity=None):
+    """the host twin of gainmap_encode: sdr uint8 / hdr float32 host arenas [arena_pixels, 3] -> (maps uint8 [map bytes], meta
+    GAINMAP_META_DTYPE [n]).  map_capacity, meta_capacity: the sizes of the destinations (default: what is needed); a smaller one
+    raises ValueError and nothing is written."""
+    lib = _lib.load()
+    images, scales, lo, hi = _gainmap_encode_args("gainmap_encode_host", images, scales, log2_range)
+    sdr, hdr = np.ascontiguousarray(sdr), np.ascontiguousarray(hdr)
+    if sdr.dtype != np.uint8 or hdr.dtype != np.float32 or sdr.size != hdr.size or sdr.size % 3:
+        raise ValueError("gainmap_encode_host: the arenas must hold the same pixels, uint8 and float32 [arena_pixels, 3]")
+    need = int(sum(3 * (-(-int(im["height"]) // max(int(im["factor"]), 1))) * (-(-int(im["width"]) // max(int(im["factor"]), 1))) for im in images))
+    map_cap = need if map_capacity is None else int(map_capacity)
+    meta_cap = images.size if meta_capacity is None else int(meta_capacity)
+    maps = np.full(max(map_cap, 1), GAINMAP_GUARD, dtype=np.uint8)
+    meta = np.zeros(max(meta_cap, 1), dtype=GAINMAP_META_DTYPE)
+    _gainmap_fail(lib, lib.shdr_gainmap_encode_host(_hptr(sdr), _hptr(hdr), sdr.size // 3, _hptr(images), images.size,
+                                                   None if scales is None else _hptr(scales), lo, hi, int(bool(reverse_channels)),
+                                                   _hptr(maps), map_cap, _hptr(meta), meta_cap))
+    return maps[:need], meta[:images.size]
+
+
+def _guarded(size, guard, dev):
+    """(raw, inner): `size` bytes with `guard` bytes of GAINMAP_GUARD on both sides (a multiple of 16: the inner part stays aligned)"""
+    if not guard:
+        raw = torch.empty(max(size, 1), device=dev, dtype=torch.uint8)
+        return raw, raw[:size]
+    raw = torch.full((size + 2 * guard,), GAINMAP_GUARD, device=dev, dtype=torch.uint8)
+    return raw, raw[guard:guard + size]
+
+
+def gainmap_encode(sdr, hdr, images, scales=None, log2_range=(-4.0, 8.0), reverse_channels=False, stage_ms=None, guard=0, info=None):
+    """Gain maps of a batch of SDR / HDR pairs on the device (csrc/gainmap.hip): bit for bit what gainmap_encode_host computes.
+    sdr uint8 / hdr float32 device arenas [arena_pixels, 3] (flat), images: descriptors (gainmap_images), scales: one fixed exposure
+    scale per image, or None for the alignment of include/shdr.h.  Returns (maps uint8 [map bytes], meta uint8 [24 n]: the records of
+    GAINMAP_META_DTYPE) on the device; image i's map starts at byte 3 images[i]["cell_off"].  Three stream-ordered launches, no host
+    wait.  stage_ms: receives the device times of GAINMAP_STAGE_NAMES; guard: bytes of GAINMAP_GUARD around maps, meta and
+    workspace, returned through `info` (a dict).  A descriptor that libshdr refuses raises ValueError before anything is launched."""
+    lib = _lib.load()
+    sdr, hdr = _chk(sdr, "sdr", torch.uint8), _chk(hdr, "hdr")
+    if sdr.numel() != hdr.numel() or sdr.numel() % 3 or sdr.device != hdr.device:
+        raise ValueError("gainmap_encode: the arenas must hold the same pixels, uint8 and float32 [arena_pixels, 3], on one device")
+    images, scales, lo, hi = _gainmap_encode_args("gainmap_encode", images, scales, log2_range)
+    dev = sdr.device
+    derived = images.copy()
+    map_b, ws_b = gainmap_sizes(derived)                           # refuses shapes and factors; the derived fields are checked by the call
+    guard = (int(guard) + 15) // 16 * 16
+    maps_raw, maps = _guarded(map_b, guard, dev)
+    meta_raw, meta = _guarded(24 * images.size, guard, dev)
+    ws_raw, ws = _guarded(ws_b, guard, dev)
+    images_dev = torch.from_numpy(images.view(np.uint8).copy()).to(dev)
+    scales_dev = None if scales is None else torch.from_numpy(scales).to(dev)
+    with _stage_times(stage_ms, len(GAINMAP_STAGE_NAMES)) as ms:
+        _gainmap_fail(lib, lib.shdr_gainmap_encode(_ptr(sdr), _ptr(hdr), sdr.numel() // 3, _hptr(images), _ptr(images_dev), images.size,
+                                                  None if scales is None else _hptr(scales), _ptr(scales_dev), lo, hi,
+                                                  int(bool(reverse_channels)), _ptr(maps), map_b, _ptr(meta), images.size, _ptr(ws),
+                                                  _stream(), ms))
+    if info is not None:
+        info.update(maps_raw=maps_raw, meta_raw=meta_raw, workspace_raw=ws_raw, guard=guard, map_bytes=map_b, workspace_bytes=ws_b)
+    return maps, meta
+
+
+def gainmap_apply_images(items):
+    """descriptors GAINMAP_APPLY_DTYPE [n] of images whose SDR pixels and maps lie back to back.  items: dicts with height, width, factor,
+    map_channels, gain_min, gain_max and optionally gamma (1), offset_sdr, offset_hdr (1 / 64), weight (1).  Returns (descriptors,
+    blocks of the launch); ValueError for what libshdr refuses."""
+    lib = _lib.load()
+    images = np.zeros(len(items), dtype=GAINMAP_APPLY_DTYPE)
+    pix = off = 0
+    for i, it in enumerate(items):
+        h, w, f, mc = (int(it[k]) for k in ("height", "width", "factor", "map_channels"))
+        mh, mw = -(-h // max(f, 1)), -(-w // max(f, 1))
+        images[i] = (pix, off, h, w, mh, mw, f, mc, it["gain_min"], it["gain_max"], it.get("gamma", 1.0), it.get("offset_sdr", GAINMAP_OFFSET),
+                     it.get("offset_hdr", GAINMAP_OFFSET), it.get("weight", 1.0), 0, 0)
+        pix += max(h, 0) * max(w, 0)
+        off += max(mh * mw * mc, 0)
+    blocks = ctypes.c_int64(0)
+    _gainmap_fail(lib, lib.shdr_gainmap_apply_sizes(_hptr(images), images.size, ctypes.byref(blocks)))
+    return images, blocks.value
+
+
+def _gainmap_apply_args(what, images):
+    images = np.ascontiguousarray(images)
+    if images.dtype != GAINMAP_APPLY_DTYPE or images.ndim != 1:
+        raise ValueError("%s: expected descriptors of GAINMAP_APPLY_DTYPE (gainmap_apply_images)" % what)
+    return images
+
+
+def gainmap_apply_host(sdr, maps, images, out_capacity=None):
+    """the host twin of gainmap_apply: sdr uint8 [arena_pixels, 3], maps uint8 (flat) -> float32 [arena_pixels, 3]; out_capacity: the
+    destination's size in pixels (default: the arena's)"""
+    lib = _lib.load()
+    images = _gainmap_apply_args("gainmap_apply_host", images)
+    sdr, maps = np.ascontiguousarray(sdr), np.ascontiguousarray(maps)
+    if sdr.dtype != np.uint8 or maps.dtype != np.uint8 or sdr.size % 3:
+        raise ValueError("gainmap_apply_host: expected uint8 pixels [arena_pixels, 3] and uint8 maps")
+    cap = sdr.size // 3 if out_capacity is None else int(out_capacity)
+    out = np.zeros((max(cap, 1), 3), dtype=np.float32)
+    _gainmap_fail(lib, lib.shdr_gainmap_apply_host(_hptr(sdr), sdr.size // 3, _hptr(maps), maps.size, _hptr(images), images.size, _hptr(out), cap))
+    return out[:cap]
+
+
+def gainmap_apply(sdr, maps, images, guard=0, info=None):
+    """HDR pixels of a batch of SDR images and their gain maps, one launch (csrc/gainmap.hip): bit for bit gainmap_apply_host.  sdr
+    uint8 device arena [arena_pixels, 3], maps uint8 device bytes, images: descriptors (gainmap_apply_images).  Returns float32
+    [arena_pixels, 3] on the device.  guard: bytes of GAINMAP_GUARD around the output, returned through `info`."""
+    lib = _lib.load()
+    images = _gainmap_apply_args("gainmap_apply", images)
+    sdr, maps = _chk(sdr, "sdr", torch.uint8), _chk(maps, "maps", torch.uint8)
+    if sdr.numel() % 3 or sdr.device != maps.device:
+        raise ValueError("gainmap_apply: expected uint8 pixels [arena_pixels, 3] and the maps on one device")
+    pixels = sdr.numel() // 3
+    guard = (int(guard) + 15) // 16 * 16
+    out_raw, out = _guarded(12 * pixels, guard, sdr.device)
+    images_dev = torch.from_numpy(images.view(np.uint8).copy()).to(sdr.device)
+    _gainmap_fail(lib, lib.shdr_gainmap_apply(_ptr(sdr), pixels, _ptr(maps), maps.numel(), _hptr(images), _ptr(images_dev), images.size,
+                                             _ptr(out), pixels, _stream()))
+    if info is not None:
+        info.update(out_raw=out_raw, guard=guard)
+    return out.view(torch.float32).view(pixels, 3)

@@ -61,6 +61,7 @@ SOURCES = {
     "jpeg_scan.hip": [],
     "jpeg_enc.hip": ["-ffp-contract=off"],
     "png_enc.hip": [],
+    "gainmap.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + INCLUDE, "-I" + CSRC,
           "-Wall", "-Wno-unused-function"]

@@ -10,7 +10,8 @@ decode (PIL) and the file write are host work; the uint8 image goes to the devic
 instead of 12) come back -- every step in between is a libshdr kernel (csrc/imageio.hip).  With encoder="device" the scanline
 RLE runs on the device too (csrc/hdr_rle.hip, the host routine's bytes) and only the coded bytes come back; reconstruct_files
 does that for a whole list of files in one batched encode and one copy.  output_format="exr" stores the float estimate as OpenEXR
-instead (exr.encode_exr: HALF or FLOAT, ZIP by default) -- RGBE keeps an 8-bit mantissa, about 1 % steps.
+instead (exr.encode_exr: HALF or FLOAT, ZIP by default) -- RGBE keeps an 8-bit mantissa, about 1 % steps.  output_format="ultrahdr"
+stores it as a gain-map JPEG (ultrahdr.encode): the input photograph with a log2 gain map behind it, which browsers and phones show as HDR.
 cv2 is not installed in this image, so cv2's behaviour is restated: INTER_CUBIC = a -0.75 bicubic
 with replicated borders, '.hdr' = Radiance RGBE with adaptive scanline RLE and the `-Y h +X w` orientation.
 """
@@ -76,8 +77,8 @@ def _check_encoder(encoder, what, output_format="hdr"):
 
 
 def _check_format(output_format, what):
-    if output_format not in ("hdr", "exr"):
-        raise ValueError("%s: output_format must be 'hdr' or 'exr', got %r" % (what, output_format))
+    if output_format not in ("hdr", "exr", "ultrahdr"):
+        raise ValueError("%s: output_format must be 'hdr', 'exr' or 'ultrahdr', got %r" % (what, output_format))
 
 
 def _exr_options(encoder, exr_options):
@@ -87,6 +88,26 @@ def _exr_options(encoder, exr_options):
     opts.update(exr_options or {})
     opts["reverse_channels"] = True
     return opts
+
+
+def _jpeg_base(data):
+    """the bytes of an input file if they can stand as the primary image of a gain-map file: a JPEG whose pixels are stored upright
+    (an EXIF Orientation other than 1 is applied by the readers, so the estimate would not lie on the coded pixels); None otherwise"""
+    try:
+        from . import jpeg, ultrahdr
+    except ImportError:
+        import jpeg
+        import ultrahdr
+    if data[:2] != b"\xff\xd8":
+        return None
+    try:
+        segs = ultrahdr._segments(data, "input")
+    except ValueError:
+        return None
+    for seg in segs:
+        if seg[0] == 0xE1 and jpeg._exif_orientation(data[seg[1] + 4:seg[2]]) not in (None, 1):
+            return None
+    return data
 
 
 def _write_scanlines(path, h, w, data):
@@ -335,8 +356,46 @@ class HdrReconstructor:
             return self.reconstruct_device(jpeg.read_ldr_device(ldr_path, unstuff="device" if decoder == "device_scan" else "host"))
         return self.reconstruct_device(read_ldr(ldr_path))
 
+    def _read_ultrahdr(self, ldr_path, decoder, what):
+        """(estimate, the input's pixels uint8 on the device, the input's bytes if they can be the primary image or None)"""
+        if decoder not in ("pil", "device", "device_scan"):
+            raise ValueError("%s: decoder must be 'pil', 'device' or 'device_scan', got %r" % (what, decoder))
+        with open(ldr_path, "rb") as f:
+            base = _jpeg_base(f.read())
+        if decoder != "pil":
+            try:
+                from . import jpeg
+            except ImportError:
+                import jpeg
+            u8 = jpeg.read_ldr_device(ldr_path, unstuff="device" if decoder == "device_scan" else "host")
+        else:
+            u8 = torch.from_numpy(read_ldr(ldr_path)).to(torch.device("cuda", torch.cuda.current_device()))
+        return self.reconstruct_device(u8), u8, base
+
+    def _write_ultrahdr(self, ldr_paths, hdr_paths, decoder, ultrahdr_options, what):
+        """the estimates of a list of files as gain-map JPEG files, ONE ultrahdr.encode call; returns the estimates"""
+        try:
+            from . import ultrahdr
+        except ImportError:
+            import ultrahdr
+        options = dict(ultrahdr_options or {})
+        for key in options:
+            if key not in ultrahdr.ENCODE_OPTIONS or key in ("base", "reverse_channels", "encoder"):
+                raise ValueError("%s: ultrahdr_options takes %s, got %r" % (what, ", ".join(
+                    k for k in ultrahdr.ENCODE_OPTIONS if k not in ("base", "reverse_channels", "encoder")), key))
+        ys, sdrs, bases = [], [], []
+        for src in ldr_paths:
+            y, u8, base = self._read_ultrahdr(src, decoder, what)
+            ys.append(y.contiguous())
+            sdrs.append(u8)
+            bases.append(base)
+        for dst, data in zip(hdr_paths, ultrahdr.encode(ys, sdrs, base=bases, reverse_channels=True, **options)):
+            with open(dst, "wb") as f:
+                f.write(data)
+        return ys
+
     def reconstruct_file(self, ldr_path, hdr_path, preview_path=None, decoder="pil", encoder="host", output_format="hdr",
-                         exr_options=None, preview_encoder="pil", preview_options=None):
+                         exr_options=None, preview_encoder="pil", preview_options=None, ultrahdr_options=None):
         """preview_path: also write an 8-bit tone-mapped PNG of the estimate (write_preview), for viewers without HDR support;
         preview_encoder, preview_options: write_preview's encoder and jpeg_options ("device": a .jpg preview coded on the device,
         "device_png": a .png preview coded on the device).
@@ -349,11 +408,19 @@ class HdrReconstructor:
         (exr.encode_exr with `exr_options`, a dict of its keyword arguments such as pixel_type or compression; `encoder` then says
         who deflates, and "device_lz", the device encoder with LZ77 matches, is a third choice that only this format has.
         exr_options=dict(compression="piz", piz="device") -- or piz="host" -- writes PIZ-compressed files, for which `encoder` plays
-        no part; the PIZ writer is unpinned against the OpenEXR library, see exr.encode_exr)"""
+        no part; the PIZ writer is unpinned against the OpenEXR library, see exr.encode_exr);
+        "ultrahdr" writes a gain-map JPEG file (ultrahdr.encode with `ultrahdr_options`: factor, hdr_scale, log2_range, base_options,
+        map_quality): the input file's own bytes are the primary image when it is a JPEG stored upright, otherwise the input's pixels are
+        coded with base_options (and the gains are taken against the coded pixels); `encoder` plays no part)"""
         _check_encoder(encoder, "reconstruct_file", output_format)
         _check_format(output_format, "reconstruct_file")
         if preview_path is not None:
             _check_preview_encoder(preview_encoder, preview_path, "reconstruct_file")
+        if output_format == "ultrahdr":
+            y = self._write_ultrahdr([ldr_path], [hdr_path], decoder, ultrahdr_options, "reconstruct_file")[0]
+            if preview_path is not None:
+                write_preview(preview_path, y, reverse_channels=True, encoder=preview_encoder, jpeg_options=preview_options)
+            return
         y = self._read_device(ldr_path, decoder, "reconstruct_file")
         if output_format == "exr":
             exr.write_exr(hdr_path, y, **_exr_options(encoder, exr_options))
@@ -376,13 +443,14 @@ class HdrReconstructor:
                 f.write(data)
 
     def reconstruct_files(self, ldr_paths, hdr_paths, decoder="pil", encoder="host", output_format="hdr", exr_options=None,
-                          preview_paths=None, preview_encoder="pil", preview_options=None):
+                          preview_paths=None, preview_encoder="pil", preview_options=None, ultrahdr_options=None):
         """reconstruct_file for a list of files: geometry and inference per image as there, then ALL results of the call coded in one
         batched scanline-RLE launch sequence and brought back in one copy (encoder="device"), then the files are written.
         encoder="host" (the default, as everywhere) is a loop over reconstruct_file.  The RGBE pixels of the whole list stay on the device until they are coded:
         4 B per pixel.  output_format="exr": the float estimates of the whole list go through ONE exr.encode_exr call, whatever the
         encoder (and whatever the compression: exr_options=dict(compression="piz", piz="device") codes every chunk of every file in
-        one K.piz_encode call).  preview_paths: one 8-bit preview per file as reconstruct_file writes it; with
+        one K.piz_encode call).  output_format="ultrahdr": the whole list goes through ONE ultrahdr.encode call (`ultrahdr_options`, see
+        reconstruct_file).  preview_paths: one 8-bit preview per file as reconstruct_file writes it; with
         preview_encoder="device_png" (.png paths) or "device" (.jpg paths) the previews of the whole list are coded in one call."""
         _check_encoder(encoder, "reconstruct_files", output_format)
         _check_format(output_format, "reconstruct_files")
@@ -398,6 +466,13 @@ class HdrReconstructor:
             previews = dict(preview_encoder=preview_encoder, preview_options=preview_options)
         if decoder not in ("pil", "device", "device_scan"):
             raise ValueError("reconstruct_files: decoder must be 'pil', 'device' or 'device_scan', got %r" % (decoder,))
+        if output_format == "ultrahdr":
+            if not ldr_paths:
+                return
+            ys = self._write_ultrahdr(ldr_paths, hdr_paths, decoder, ultrahdr_options, "reconstruct_files")
+            if preview_paths is not None:
+                self._write_previews(ys, preview_paths, **previews)
+            return
         if output_format == "exr":
             if not ldr_paths:
                 return
@@ -430,29 +505,37 @@ class HdrReconstructor:
             self._write_previews(ys, preview_paths, **previews)
 
     def reconstruct_dir(self, dataset_dir, output_dir, pattern="*.jpg", verbose=True, decoder="pil", encoder="host", group=16,
-                        output_format="hdr", exr_options=None, preview_dir=None, preview_encoder="pil", preview_options=None):
+                        output_format="hdr", exr_options=None, preview_dir=None, preview_encoder="pil", preview_options=None,
+                        ultrahdr_options=None):
         """the `for ldr_img_path in ldr_imgs` loop (:119-151); returns the written paths.  decoder, encoder: as reconstruct_file;
         with encoder="device" the files go through reconstruct_files in groups of `group`.  output_format="exr" names the outputs
-        *.exr.  preview_dir: also write an 8-bit preview per file there (*.png, or *.jpg with preview_encoder="device"), through
+        *.exr; output_format="ultrahdr" names them *.jpg, sends the files through reconstruct_files in groups of `group` whatever the
+        encoder, and refuses an output_dir that is dataset_dir: the outputs would overwrite the inputs.  preview_dir: also write an 8-bit preview per file there (*.png, or *.jpg with preview_encoder="device"), through
         reconstruct_files' preview_paths"""
         _check_encoder(encoder, "reconstruct_dir", output_format)
         _check_format(output_format, "reconstruct_dir")
         fmt = dict(output_format=output_format, exr_options=exr_options)
+        grouped = encoder != "host" or output_format == "ultrahdr"
+        if output_format == "ultrahdr":
+            if os.path.realpath(output_dir) == os.path.realpath(dataset_dir):
+                raise ValueError("reconstruct_dir: output_dir %r is dataset_dir: the gain-map files (*.jpg) would overwrite the inputs" % (output_dir,))
+            fmt["ultrahdr_options"] = ultrahdr_options
         os.makedirs(output_dir, exist_ok=True)
         if preview_dir is not None:
             os.makedirs(preview_dir, exist_ok=True)
             fmt.update(preview_encoder=preview_encoder, preview_options=preview_options)
         written = []
         paths = sorted(glob.glob(os.path.join(dataset_dir, pattern)))
-        step = max(int(group), 1) if encoder != "host" else 1
+        step = max(int(group), 1) if grouped else 1
         for i in range(0, len(paths), step):
             start = time.perf_counter()
             part = paths[i:i + step]
-            outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + "." + output_format) for path in part]        # :148-149
+            ext = "jpg" if output_format == "ultrahdr" else output_format
+            outs = [os.path.join(output_dir, os.path.split(path)[-1].split(".")[0] + "." + ext) for path in part]        # :148-149
             if preview_dir is not None:
                 ext = ".jpg" if preview_encoder == "device" else ".png"
                 fmt["preview_paths"] = [os.path.join(preview_dir, os.path.splitext(os.path.basename(out))[0] + ext) for out in outs]
-            if encoder != "host" or preview_dir is not None:
+            if grouped or preview_dir is not None:
                 self.reconstruct_files(part, outs, decoder=decoder, encoder=encoder, **fmt)
             else:
                 self.reconstruct_file(part[0], outs[0], decoder=decoder, **fmt)
