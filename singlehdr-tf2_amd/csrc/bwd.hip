@@ -3,15 +3,19 @@
 //
 // Replaces the GradientTape.gradient / Adam.apply_gradients call sites of
 // joint_training.py:185-186, train.py:175-176,195-196,242-243, finetune_real_dataset.py:177-178
-// for the ops of SURVEY.md section 2.2 rows T3, T5-T8, T12-T18.
+// for the ops of SURVEY.md section 2.2 rows T3, T5-T8, T12-T18.  The pooling / resize input gradients and the
+// BatchNorm finalisers are the fp32 instantiations of nhwc_vec.h.
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "nhwc_vec.h"
+
+using shdr::bn_bwd_finalize_kernel;
+using shdr::bn_finalize_kernel;
+using shdr::bn_fold_kernel;
+using shdr::check_nhwc;
+using shdr::launch_vec;
 
 namespace {
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -141,174 +145,6 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
   if (yr) shdr::range_out_block256(yr, ym);
 }
 
-// (e < 2^32 for every tensor below 64 GB: three 32-bit divisions -- about 25 instructions each -- instead of three emulated
-//  64-bit ones, which cost more than the whole rest of these HBM-bound kernels; wider indices keep the 64-bit path)
-#define SHDR_DECODE_QUAD(e, Q, Wd, Hd, q, w, h, n)                     \
-  int q, w, h;                                                          \
-  long n;                                                               \
-  if ((unsigned long)(e) <= 0xffffffffUL) {                             \
-    unsigned _t = (unsigned)(e);                                        \
-    q = (int)(_t % (unsigned)(Q)); _t /= (unsigned)(Q);                 \
-    w = (int)(_t % (unsigned)(Wd)); _t /= (unsigned)(Wd);               \
-    h = (int)(_t % (unsigned)(Hd)); n = (long)(_t / (unsigned)(Hd));    \
-  } else {                                                              \
-    long _t = (e);                                                      \
-    q = (int)(_t % (Q)); _t /= (Q);                                     \
-    w = (int)(_t % (Wd)); _t /= (Wd);                                   \
-    h = (int)(_t % (Hd)); n = _t / (Hd);                                \
-  }
-
-// ---- pooling / resize backward (gather form: one thread per INPUT quad) ------------------------
-__global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
-                                                           int N, int H, int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, Q = C >> 2;
-  const long total = (long)N * H * W * Q;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    SHDR_DECODE_QUAD(e, Q, W, H, q, w, h, n)
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((h >> 1) < Ho && (w >> 1) < Wo) {
-      g = ld4(dy + (((n * Ho + (h >> 1)) * Wo + (w >> 1)) * (long)C + 4 * q));
-      g.x *= 0.25f; g.y *= 0.25f; g.z *= 0.25f; g.w *= 0.25f;
-    }
-    st4(dx + e * 4, g);
-  }
-}
-
-// MaxPool 2x2/2: the gradient goes to the FIRST maximum of the window in row-major scan order
-__global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                           float* __restrict__ dx, int N, int H, int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, Q = C >> 2;
-  const long total = (long)N * Ho * Wo * Q;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    SHDR_DECODE_QUAD(e, Q, Wo, Ho, q, ow, oh, n)
-    const long base = ((n * H + 2 * oh) * W + 2 * ow) * (long)C + 4 * q;
-    const long off[4] = {0, (long)C, (long)W * C, (long)W * C + C};
-    float v[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float4 t = ld4(x + base + off[k]);
-      v[k][0] = t.x; v[k][1] = t.y; v[k][2] = t.z; v[k][3] = t.w;
-    }
-    const float4 g4 = ld4(dy + e * 4);
-    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-    float o[4][4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      int arg = 0;
-      float m = v[0][c];
-#pragma unroll
-      for (int k = 1; k < 4; ++k)
-        if (v[k][c] > m) { m = v[k][c]; arg = k; }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k][c] = (k == arg) ? g[c] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) st4(dx + base + off[k], make_float4(o[k][0], o[k][1], o[k][2], o[k][3]));
-  }
-}
-
-// MaxPool 3x3/2 SAME (overlapping windows): one thread per input quad gathers from every window
-// that contains it and whose first maximum it is.  With the pooled output at hand an element is a
-// candidate only where it equals the window's maximum (one load per window), and only the elements
-// BEFORE it in the window's scan order can still take the gradient from it (the tie rule).
-__global__ __launch_bounds__(256) void maxpool3s2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                             const float* __restrict__ dy, float* __restrict__ dx, int N, int H,
-                                                             int W, int C, int Ho, int Wo, int pt, int pl) {
-  const int Q = C >> 2;
-  const long total = (long)N * H * W * Q;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    SHDR_DECODE_QUAD(e, Q, W, H, q, w, h, n)
-    const float4 mine4 = ld4(x + e * 4);
-    const float mine[4] = {mine4.x, mine4.y, mine4.z, mine4.w};
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int oh = max(0, (h + pt - 1) / 2); oh <= min(Ho - 1, (h + pt) / 2); ++oh) {
-      for (int ow = max(0, (w + pl - 1) / 2); ow <= min(Wo - 1, (w + pl) / 2); ++ow) {
-        const int h0 = 2 * oh - pt, w0 = 2 * ow - pl;
-        if (h < h0 || h > h0 + 2 || w < w0 || w > w0 + 2) continue;
-        const long widx = ((n * Ho + oh) * Wo + ow) * (long)C + 4 * q;
-        const float4 m4 = ld4(y + widx);
-        bool win[4] = {mine[0] == m4.x, mine[1] == m4.y, mine[2] == m4.z, mine[3] == m4.w};
-        if (!(win[0] | win[1] | win[2] | win[3])) continue;
-        for (int ih = max(h0, 0); ih <= h; ++ih) {
-          const int wend = (ih == h) ? w : min(w0 + 3, W);
-          for (int iw = max(w0, 0); iw < wend; ++iw) {
-            const float4 o4 = ld4(x + (((n * H + ih) * W + iw) * (long)C + 4 * q));
-            win[0] &= o4.x != mine[0]; win[1] &= o4.y != mine[1]; win[2] &= o4.z != mine[2]; win[3] &= o4.w != mine[3];
-          }
-        }
-        if (!(win[0] | win[1] | win[2] | win[3])) continue;
-        const float4 g4 = ld4(dy + widx);
-        const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (win[c]) acc[c] += g[c];
-      }
-    }
-    st4(dx + e * 4, make_float4(acc[0], acc[1], acc[2], acc[3]));
-  }
-}
-
-// bilinear 2x backward: per axis, input m receives {.25,.75,.75,.25} from outputs {2m-1,2m,2m+1,2m+2};
-// the clamped borders fold the missing tap onto output 0 / 2H-1 (weight 1.0).
-__device__ __forceinline__ void resize_taps(int m, int n_in, int* idx, float* wt, int* cnt) {
-  int k = 0;
-  if (m > 0) { idx[k] = 2 * m - 1; wt[k] = 0.25f; ++k; }
-  idx[k] = 2 * m; wt[k] = (m == 0) ? 1.0f : 0.75f; ++k;
-  idx[k] = 2 * m + 1; wt[k] = (m == n_in - 1) ? 1.0f : 0.75f; ++k;
-  if (m < n_in - 1) { idx[k] = 2 * m + 2; wt[k] = 0.25f; ++k; }
-  *cnt = k;
-}
-__global__ __launch_bounds__(256) void resize2x_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
-                                                           int N, int H, int W, int C, unsigned* __restrict__ xr) {
-  const int Q = C >> 2, Ho = 2 * H, Wo = 2 * W;
-  const long total = (long)N * H * W * Q;
-  float dm = 0.f;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    SHDR_DECODE_QUAD(e, Q, W, H, q, w, h, n)
-    int yi[4], xi[4], ny, nx;
-    float yw[4], xw[4];
-    resize_taps(h, H, yi, yw, &ny);
-    resize_taps(w, W, xi, xw, &nx);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int a = 0; a < ny; ++a)
-      for (int b = 0; b < nx; ++b) {
-        const float4 g = ld4(dy + (((n * Ho + yi[a]) * Wo + xi[b]) * (long)C + 4 * q));
-        const float wgt = yw[a] * xw[b];
-        s.x += wgt * g.x; s.y += wgt * g.y; s.z += wgt * g.z; s.w += wgt * g.w;
-      }
-    st4(dx + e * 4, s);
-    dm = fmaxf(fmaxf(fmaxf(fmaxf(dm, fabsf(s.x)), fabsf(s.y)), fabsf(s.z)), fabsf(s.w));
-  }
-  if (xr) shdr::range_out_block256(xr, dm);                    // (a sum of up to nine weighted taps: not bounded by max |dy|)
-}
-
-__global__ __launch_bounds__(256) void gap_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
-                                                      long total_q, int HW, int C) {
-  const int Q = C >> 2;
-  const float hw = (float)HW;           // dy / HW, one rounding (dy * (1 / HW) rounds twice)
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total_q; e += (long)gridDim.x * 256) {
-    const int q = (int)(e % Q);
-    const long n = e / ((long)Q * HW);
-    float4 g = ld4(dy + n * C + 4 * q);
-    g.x /= hw; g.y /= hw; g.z /= hw; g.w /= hw;
-    st4(dx + e * 4, g);
-  }
-}
-
-// dx[n, 2*oh, 2*ow, :] = dy[n, oh, ow, :], zero elsewhere (input gradient of a 1x1 stride-2 conv
-// after the 1x1 dgrad has been evaluated on the coarse grid)
-__global__ __launch_bounds__(256) void upsample_zero2_kernel(const float* __restrict__ dy, float* __restrict__ dx,
-                                                             int N, int H, int W, int C) {
-  const int Q = C >> 2, Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
-  const long total = (long)N * H * W * Q;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    SHDR_DECODE_QUAD(e, Q, W, H, q, w, h, n)
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (((h | w) & 1) == 0) g = ld4(dy + (((n * Ho + (h >> 1)) * Wo + (w >> 1)) * (long)C + 4 * q));
-    st4(dx + e * 4, g);
-  }
-}
-
 // ---- BatchNormalization, training mode ----------------------------------------------------------
 // per-channel double-precision partial sums: ws[c] += sum v1, ws[C + c] += sum v2
 //   mode 0 (forward stats) : v1 = x,   v2 = x*x
@@ -427,35 +263,6 @@ __global__ __launch_bounds__(256) void bn_reduce4_kernel(const float* __restrict
     __syncthreads();
   }
 }
-// ws[col] = sum over the g partial rows ws[(1 + b) * 2C + col]: one wave per column, lanes stride over the rows
-__global__ __launch_bounds__(256) void bn_fold_kernel(double* __restrict__ ws, int C, int g) {
-  const int col = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (col >= 2 * C) return;
-  double t = 0.0;
-  for (int b = lane; b < g; b += 64) t += ws[(size_t)(1 + b) * 2 * C + col];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-  if (lane == 0) ws[col] = t;
-}
-
-// mean/var (biased) from the double sums; optional Keras moving-average update
-// (momentum m: moving = moving*m + batch*(1-m); the variance update uses the unbiased estimate)
-__global__ void bn_finalize_kernel(const double* __restrict__ ws, float* __restrict__ mean, float* __restrict__ var,
-                                   float* __restrict__ mov_mean, float* __restrict__ mov_var, long npix, int C,
-                                   float momentum) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double mu = ws[c] / (double)npix;
-  double v = ws[C + c] / (double)npix - mu * mu;
-  if (v < 0.0) v = 0.0;
-  mean[c] = (float)mu;
-  var[c] = (float)v;
-  if (mov_mean) {
-    const double unbiased = npix > 1 ? v * (double)npix / (double)(npix - 1) : v;
-    mov_mean[c] = mov_mean[c] * momentum + (float)mu * (1.0f - momentum);
-    mov_var[c] = mov_var[c] * momentum + (float)unbiased * (1.0f - momentum);
-  }
-}
 
 __global__ __launch_bounds__(256) void bn_train_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                              const float* __restrict__ var, const float* __restrict__ gamma,
@@ -470,14 +277,6 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const float* __rest
     ym = fmaxf(ym, fabsf(v));
   }
   if (yr) shdr::range_out_block256(yr, ym);                     // range slot of y: the consumer is usually a split-operand conv
-}
-
-__global__ void bn_bwd_finalize_kernel(const double* __restrict__ ws, const float* __restrict__ var,
-                                       float* __restrict__ dgamma, float* __restrict__ dbeta, int C, float eps) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  dbeta[c] += (float)ws[c];
-  dgamma[c] += (float)(ws[C + c] * (double)rsqrtf(var[c] + eps));
 }
 
 // dx = gamma*invstd * (dy' - mean(dy') - xhat * mean(dy'*xhat))
@@ -805,13 +604,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
-int nhwc4(const char* op, const void* a, const void* b, int N, int H, int W, int C) {
-  SHDR_REQUIRE(a && b, SHDR_E_NULL, "%s: null pointer", op);
-  SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "%s: non-positive dimension", op);
-  SHDR_REQUIRE((C & 3) == 0, SHDR_E_ALIGN, "%s: C=%d must be a multiple of 4", op, C);
-  SHDR_REQUIRE(shdr::aligned16(a) && shdr::aligned16(b), SHDR_E_ALIGN, "%s: tensors must be 16-byte aligned", op);
-  return SHDR_OK;
-}
 inline int reduce_grid(long npix, int C) {
   int CL = 1;
   while (CL < C && CL < 256) CL <<= 1;
@@ -895,52 +687,43 @@ extern "C" int shdr_add_f32(const float* a, const float* b, float* y, int64_t n,
   return shdr_add_ranged_f32(a, b, y, n, nullptr, stream);
 }
 extern "C" int shdr_avgpool2_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = nhwc4("avgpool2_bwd", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(avgpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
-                     dy, dx, N, H, W, C);
-  return shdr::check_launch("avgpool2_bwd");
+  if (int rc = check_nhwc<4>("avgpool2_bwd", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("avgpool2_bwd", shdr::avgpool2_bwd_kernel<float>, (long)N * H * W * (C / 4), stream, dy, dx, N, H, W, C);
 }
 extern "C" int shdr_maxpool2_bwd_f32(const float* x, const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = nhwc4("maxpool2_bwd", x, dx, N, H, W, C)) return rc;
+  if (int rc = check_nhwc<4>("maxpool2_bwd", x, dx, N, H, W, C)) return rc;
   SHDR_REQUIRE(dy, SHDR_E_NULL, "maxpool2_bwd: dy is null");
   SHDR_REQUIRE(shdr::aligned16(dy), SHDR_E_ALIGN, "maxpool2_bwd: dy must be 16-byte aligned");
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_bwd: H, W must be even");
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
-                     shdr::stream_of(stream), x, dy, dx, N, H, W, C);
-  return shdr::check_launch("maxpool2_bwd");
+  return launch_vec("maxpool2_bwd", shdr::maxpool2_bwd_kernel<float>, (long)N * (H / 2) * (W / 2) * (C / 4), stream, x, dy, dx, N, H, W, C);
 }
 extern "C" int shdr_maxpool3s2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int H, int W, int C,
                                        void* stream) {
-  if (int rc = nhwc4("maxpool3s2_bwd", x, dx, N, H, W, C)) return rc;
+  if (int rc = check_nhwc<4>("maxpool3s2_bwd", x, dx, N, H, W, C)) return rc;
   SHDR_REQUIRE(dy && y, SHDR_E_NULL, "maxpool3s2_bwd: dy or y (the pooled output) is null");
   SHDR_REQUIRE(shdr::aligned16(dy) && shdr::aligned16(y), SHDR_E_ALIGN, "maxpool3s2_bwd: dy and y must be 16-byte aligned");
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
-                     x, y, dy, dx, N, H, W, C, Ho, Wo, pt, pl);
-  return shdr::check_launch("maxpool3s2_bwd");
+  return launch_vec("maxpool3s2_bwd", shdr::maxpool3s2_bwd_kernel<float>, (long)N * H * W * (C / 4), stream, x, y, dy, dx, N, H, W, C, Ho,
+                    Wo, pt, pl);
 }
 extern "C" int shdr_resize2x_bwd_ranged_f32(const float* dy, float* dx, int N, int H, int W, int C, float* dx_range, void* stream) {
-  if (int rc = nhwc4("resize2x_bwd", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_bwd_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
-                     dy, dx, N, H, W, C, reinterpret_cast<unsigned*>(dx_range));
-  return shdr::check_launch("resize2x_bwd");
+  if (int rc = check_nhwc<4>("resize2x_bwd", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("resize2x_bwd", shdr::resize2x_bwd_kernel<float, true>, (long)N * H * W * (C / 4), stream, dy, dx, N, H, W, C,
+                    reinterpret_cast<unsigned*>(dx_range));
 }
 extern "C" int shdr_resize2x_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
   return shdr_resize2x_bwd_ranged_f32(dy, dx, N, H, W, C, nullptr, stream);
 }
 extern "C" int shdr_gap_bwd_f32(const float* dy, float* dx, int N, int HW, int C, void* stream) {
-  if (int rc = nhwc4("gap_bwd", dy, dx, N, HW, 1, C)) return rc;
+  if (int rc = check_nhwc<4>("gap_bwd", dy, dx, N, HW, 1, C)) return rc;
   const long tq = (long)N * HW * (C / 4);
-  hipLaunchKernelGGL(gap_bwd_kernel, dim3(shdr::stream_grid(tq)), dim3(256), 0, shdr::stream_of(stream), dy, dx, tq, HW, C);
-  return shdr::check_launch("gap_bwd");
+  return launch_vec("gap_bwd", shdr::gap_bwd_kernel<float>, tq, stream, dy, dx, tq, HW, C);
 }
 extern "C" int shdr_upsample_zero2_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = nhwc4("upsample_zero2", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(upsample_zero2_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 4))), dim3(256), 0, shdr::stream_of(stream),
-                     dy, dx, N, H, W, C);
-  return shdr::check_launch("upsample_zero2");
+  if (int rc = check_nhwc<4>("upsample_zero2", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("upsample_zero2", shdr::upsample_zero2_kernel<float>, (long)N * H * W * (C / 4), stream, dy, dx, N, H, W, C);
 }
 
 extern "C" int shdr_bn_stats_f32(const float* x, double* ws, float* mean, float* var, float* moving_mean,

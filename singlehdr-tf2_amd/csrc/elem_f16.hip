@@ -1,63 +1,24 @@
 // fp16 twins of the HBM-bound tape ops, for the native-fp16 activation layout of BASELINE configs[4] (csrc/conv_f16.hip): every
 // feature map of the fine-tuning chain is NHWC fp16 with C % 8 == 0, so one thread moves 16 bytes = 8 channels; all arithmetic
 // is fp32 in registers, reductions are fp32 / fp64, only the stored tensors are fp16 (half the bytes of the fp32 kernels in
-// bwd.hip / pool.hip / glue.hip / frontend.hip, whose semantics -- tie-breaking of the max-pools, border handling of the
-// bilinear resize, BatchNorm statistics in double -- they restate).  Image-like tensors (3 channels) stay fp32.
+// bwd.hip / glue.hip / frontend.hip, whose semantics -- BatchNorm statistics in double -- they restate).  Pooling, resize, global
+// average pooling and the BatchNorm finalisers are the fp16 instantiations of nhwc_vec.h.  Image-like tensors (3 channels) stay fp32.
 // Replaces the same TF op call sites as their _f32 counterparts (include/shdr.h).
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
-#include "shdr_internal.h"
+#include "nhwc_vec.h"
+
+using shdr::bn_bwd_finalize_kernel;
+using shdr::bn_finalize_kernel;
+using shdr::bn_fold_kernel;
+using shdr::launch_vec;
 
 namespace {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 typedef _Float16 hf;
-
-struct V8 {
-  float v[8];
-};
-__device__ __forceinline__ V8 ldh(const hf* p) {
-  const f16x8 t = *reinterpret_cast<const f16x8*>(p);
-  V8 r;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.v[i] = (float)t[i];
-  return r;
-}
-__device__ __forceinline__ void sth(hf* p, const V8& a) {
-  f16x8 t;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) t[i] = (hf)a.v[i];
-  *reinterpret_cast<f16x8*>(p) = t;
-}
-__device__ __forceinline__ V8 zero8() {
-  V8 r;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.v[i] = 0.f;
-  return r;
-}
-__device__ __forceinline__ V8 ld8f(const float* p) {          // 8 consecutive floats (32-byte aligned source)
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  V8 r;
-  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w; r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-  return r;
-}
-
-// e -> (n, h, w, o) of a [N, Hd, Wd, 8*O] tensor; 32-bit divisions while the index fits (see pool.hip)
-#define DECODE8(e, O, Wd, Hd, o, w, h, n)                              \
-  int o, w, h;                                                          \
-  long n;                                                               \
-  if ((unsigned long)(e) <= 0xffffffffUL) {                             \
-    unsigned _t = (unsigned)(e);                                        \
-    o = (int)(_t % (unsigned)(O)); _t /= (unsigned)(O);                 \
-    w = (int)(_t % (unsigned)(Wd)); _t /= (unsigned)(Wd);               \
-    h = (int)(_t % (unsigned)(Hd)); n = (long)(_t / (unsigned)(Hd));    \
-  } else {                                                              \
-    long _t = (e);                                                      \
-    o = (int)(_t % (O)); _t /= (O);                                     \
-    w = (int)(_t % (Wd)); _t /= (Wd);                                   \
-    h = (int)(_t % (Hd)); n = _t / (Hd);                                \
-  }
+using VH = shdr::Vec<hf>;            // a channel octet: 8 fp16 in 16 bytes, fp32 lanes in registers
+using V8 = VH::V;
 
 __device__ __forceinline__ float act_grad(float g, float y, int act) {
   switch (act) {
@@ -112,7 +73,7 @@ __global__ __launch_bounds__(256) void pack3_h_kernel(Src4 src, int nsrc, hf* __
       }
       r.v[j] = v;
     }
-    sth(y + e * 8, r);
+    VH::st(y + e * 8, r);
   }
 }
 struct Dst4 {
@@ -150,7 +111,7 @@ __global__ __launch_bounds__(256) void act_bwd_bias_h_kernel(const hf* __restric
     if (act != SHDR_ACT_NONE) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) d.v[j] = act_grad(g.v[j], yv.v[j], act);
-      sth(dz + 8 * i, d);
+      VH::st(dz + 8 * i, d);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] += d.v[j];
@@ -159,17 +120,17 @@ __global__ __launch_bounds__(256) void act_bwd_bias_h_kernel(const hf* __restric
     V8 g[4], yv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      g[u] = ldh(dy + 8 * (e + u * step));
+      g[u] = VH::ld(dy + 8 * (e + u * step));
       yv[u] = g[u];
-      if (act != SHDR_ACT_NONE) yv[u] = ldh(y + 8 * (e + u * step));
+      if (act != SHDR_ACT_NONE) yv[u] = VH::ld(y + 8 * (e + u * step));
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) one(e + u * step, g[u], yv[u]);
   }
   for (; e < nvec; e += step) {
-    const V8 g0 = ldh(dy + 8 * e);
+    const V8 g0 = VH::ld(dy + 8 * e);
     V8 y0 = g0;
-    if (act != SHDR_ACT_NONE) y0 = ldh(y + 8 * e);
+    if (act != SHDR_ACT_NONE) y0 = VH::ld(y + 8 * e);
     one(e, g0, y0);
   }
   if (db) {
@@ -188,260 +149,14 @@ __global__ __launch_bounds__(256) void act_bwd_bias_h_kernel(const hf* __restric
 __global__ __launch_bounds__(256) void add_h_kernel(const hf* __restrict__ a, const hf* __restrict__ b, hf* __restrict__ y, long nvec,
                                                     int relu) {
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nvec; e += (long)gridDim.x * 256) {
-    const V8 x0 = ldh(a + 8 * e), x1 = ldh(b + 8 * e);
+    const V8 x0 = VH::ld(a + 8 * e), x1 = VH::ld(b + 8 * e);
     V8 r;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       r.v[j] = x0.v[j] + x1.v[j];
       if (relu) r.v[j] = fmaxf(r.v[j], 0.f);
     }
-    sth(y + 8 * e, r);
-  }
-}
-
-// ---- pooling / resize ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pool2_h_kernel(const hf* __restrict__ x, hf* __restrict__ y, int N, int H, int W, int C, int is_max) {
-  const int Ho = H >> 1, Wo = W >> 1, O = C >> 3;
-  const long total = (long)N * Ho * Wo * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, Wo, Ho, o, ow, oh, n)
-    const hf* p = x + (((n * H + 2 * oh) * W + 2 * ow) * (long)C + 8 * o);
-    const V8 a = ldh(p), b = ldh(p + C), c = ldh(p + (long)W * C), d = ldh(p + (long)W * C + C);
-    V8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      r.v[j] = is_max ? fmaxf(fmaxf(a.v[j], b.v[j]), fmaxf(c.v[j], d.v[j])) : ((a.v[j] + b.v[j]) + (c.v[j] + d.v[j])) * 0.25f;
-    sth(y + e * 8, r);
-  }
-}
-__global__ __launch_bounds__(256) void avgpool2_bwd_h_kernel(const hf* __restrict__ dy, hf* __restrict__ dx, int N, int H, int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, O = C >> 3;
-  const long total = (long)N * H * W * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, W, H, o, w, h, n)
-    V8 g = zero8();
-    if ((h >> 1) < Ho && (w >> 1) < Wo) {
-      g = ldh(dy + (((n * Ho + (h >> 1)) * Wo + (w >> 1)) * (long)C + 8 * o));
-#pragma unroll
-      for (int j = 0; j < 8; ++j) g.v[j] *= 0.25f;
-    }
-    sth(dx + e * 8, g);
-  }
-}
-// the gradient goes to the FIRST maximum of the window in row-major scan order (as maxpool2_bwd_kernel)
-__global__ __launch_bounds__(256) void maxpool2_bwd_h_kernel(const hf* __restrict__ x, const hf* __restrict__ dy, hf* __restrict__ dx,
-                                                             int N, int H, int W, int C) {
-  const int Ho = H >> 1, Wo = W >> 1, O = C >> 3;
-  const long total = (long)N * Ho * Wo * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, Wo, Ho, o, ow, oh, n)
-    const long base = ((n * H + 2 * oh) * W + 2 * ow) * (long)C + 8 * o;
-    const long off[4] = {0, (long)C, (long)W * C, (long)W * C + C};
-    V8 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = ldh(x + base + off[k]);
-    const V8 g = ldh(dy + e * 8);
-    V8 r[4];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      int arg = 0;
-      float m = v[0].v[c];
-#pragma unroll
-      for (int k = 1; k < 4; ++k)
-        if (v[k].v[c] > m) { m = v[k].v[c]; arg = k; }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) r[k].v[c] = (k == arg) ? g.v[c] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sth(dx + base + off[k], r[k]);
-  }
-}
-__global__ __launch_bounds__(256) void maxpool3s2_h_kernel(const hf* __restrict__ x, hf* __restrict__ y, int N, int H, int W, int C, int Ho,
-                                                           int Wo, int pt, int pl) {
-  const int O = C >> 3;
-  const long total = (long)N * Ho * Wo * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, Wo, Ho, o, ow, oh, n)
-    V8 m;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m.v[j] = -__builtin_huge_valf();
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int ih = 2 * oh - pt + i;
-      if ((unsigned)ih >= (unsigned)H) continue;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int iw = 2 * ow - pl + k;
-        if ((unsigned)iw >= (unsigned)W) continue;
-        const V8 t = ldh(x + (((n * H + ih) * W + iw) * (long)C + 8 * o));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) m.v[j] = fmaxf(m.v[j], t.v[j]);
-      }
-    }
-    sth(y + e * 8, m);
-  }
-}
-// candidates are the elements equal to the window's maximum `y`; only earlier equals can take the gradient (maxpool3s2_bwd_kernel)
-__global__ __launch_bounds__(256) void maxpool3s2_bwd_h_kernel(const hf* __restrict__ x, const hf* __restrict__ y, const hf* __restrict__ dy,
-                                                               hf* __restrict__ dx, int N, int H, int W, int C, int Ho, int Wo, int pt,
-                                                               int pl) {
-  const int O = C >> 3;
-  const long total = (long)N * H * W * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, W, H, o, w, h, n)
-    const V8 mine = ldh(x + e * 8);
-    V8 acc = zero8();
-    for (int oh = max(0, (h + pt - 1) / 2); oh <= min(Ho - 1, (h + pt) / 2); ++oh) {
-      for (int ow = max(0, (w + pl - 1) / 2); ow <= min(Wo - 1, (w + pl) / 2); ++ow) {
-        const int h0 = 2 * oh - pt, w0 = 2 * ow - pl;
-        if (h < h0 || h > h0 + 2 || w < w0 || w > w0 + 2) continue;
-        const long widx = ((n * Ho + oh) * Wo + ow) * (long)C + 8 * o;
-        const V8 m = ldh(y + widx);
-        unsigned win = 0;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) win |= (unsigned)(mine.v[c] == m.v[c]) << c;
-        if (!win) continue;
-        for (int ih = max(h0, 0); ih <= h; ++ih) {
-          const int wend = (ih == h) ? w : min(w0 + 3, W);
-          for (int iw = max(w0, 0); iw < wend; ++iw) {
-            const V8 t = ldh(x + (((n * H + ih) * W + iw) * (long)C + 8 * o));
-#pragma unroll
-            for (int c = 0; c < 8; ++c) win &= ~((unsigned)(t.v[c] == mine.v[c]) << c);
-          }
-        }
-        if (!win) continue;
-        const V8 g = ldh(dy + widx);
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-          if (win >> c & 1) acc.v[c] += g.v[c];
-      }
-    }
-    sth(dx + e * 8, acc);
-  }
-}
-// tf.image.resize(2x, BILINEAR), half-pixel centres: one thread owns one INPUT octet and writes its 2x2 outputs (resize2x_kernel)
-__global__ __launch_bounds__(256) void resize2x_h_kernel(const hf* __restrict__ x, hf* __restrict__ y, int N, int H, int W, int C) {
-  const int O = C >> 3;
-  const long total = (long)N * H * W * O;
-  const long orow = (long)2 * W * C;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, W, H, o, w, h, n)
-    const int hm = max(h - 1, 0), hp = min(h + 1, H - 1), wm = max(w - 1, 0), wp = min(w + 1, W - 1);
-    const hf* b = x + (n * H * (long)W) * C + 8 * o;
-    const int rows[3] = {hm, h, hp};
-    V8 lo[3], hi[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const hf* rp = b + (long)rows[r] * W * C;
-      const V8 l = ldh(rp + (long)wm * C), c = ldh(rp + (long)w * C), rr = ldh(rp + (long)wp * C);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        lo[r].v[j] = l.v[j] + (c.v[j] - l.v[j]) * 0.75f;
-        hi[r].v[j] = c.v[j] + (rr.v[j] - c.v[j]) * 0.25f;
-      }
-    }
-    hf* op = y + ((n * 2 * H + 2 * h) * (long)(2 * W) + 2 * w) * C + 8 * o;
-    V8 t;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.v[j] = lo[0].v[j] + (lo[1].v[j] - lo[0].v[j]) * 0.75f;
-    sth(op, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.v[j] = hi[0].v[j] + (hi[1].v[j] - hi[0].v[j]) * 0.75f;
-    sth(op + C, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.v[j] = lo[1].v[j] + (lo[2].v[j] - lo[1].v[j]) * 0.25f;
-    sth(op + orow, t);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t.v[j] = hi[1].v[j] + (hi[2].v[j] - hi[1].v[j]) * 0.25f;
-    sth(op + orow + C, t);
-  }
-}
-__device__ __forceinline__ void resize_taps(int m, int n_in, int* idx, float* wt, int* cnt) {
-  int k = 0;
-  if (m > 0) { idx[k] = 2 * m - 1; wt[k] = 0.25f; ++k; }
-  idx[k] = 2 * m; wt[k] = (m == 0) ? 1.0f : 0.75f; ++k;
-  idx[k] = 2 * m + 1; wt[k] = (m == n_in - 1) ? 1.0f : 0.75f; ++k;
-  if (m < n_in - 1) { idx[k] = 2 * m + 2; wt[k] = 0.25f; ++k; }
-  *cnt = k;
-}
-__global__ __launch_bounds__(256) void resize2x_bwd_h_kernel(const hf* __restrict__ dy, hf* __restrict__ dx, int N, int H, int W, int C) {
-  const int O = C >> 3, Ho = 2 * H, Wo = 2 * W;
-  const long total = (long)N * H * W * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, W, H, o, w, h, n)
-    int yi[4], xi[4], ny, nx;
-    float yw[4], xw[4];
-    resize_taps(h, H, yi, yw, &ny);
-    resize_taps(w, W, xi, xw, &nx);
-    V8 s = zero8();
-    for (int a = 0; a < ny; ++a)
-      for (int b = 0; b < nx; ++b) {
-        const V8 g = ldh(dy + (((n * Ho + yi[a]) * Wo + xi[b]) * (long)C + 8 * o));
-        const float wgt = yw[a] * xw[b];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s.v[j] += wgt * g.v[j];
-      }
-    sth(dx + e * 8, s);
-  }
-}
-__global__ __launch_bounds__(256) void upsample_zero2_h_kernel(const hf* __restrict__ dy, hf* __restrict__ dx, int N, int H, int W, int C) {
-  const int O = C >> 3, Ho = (H + 1) >> 1, Wo = (W + 1) >> 1;
-  const long total = (long)N * H * W * O;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    DECODE8(e, O, W, H, o, w, h, n)
-    V8 g = zero8();
-    if (((h | w) & 1) == 0) g = ldh(dy + (((n * Ho + (h >> 1)) * Wo + (w >> 1)) * (long)C + 8 * o));
-    sth(dx + e * 8, g);
-  }
-}
-// tf.reduce_mean(x, [1,2]): fp16 [N, HW, C] -> fp32 [N, C]; grid (ceil(C / 128), N), thread = (octet 0..15, pixel lane 0..15)
-__global__ __launch_bounds__(256) void gap_h_kernel(const hf* __restrict__ x, float* __restrict__ y, int HW, int C) {
-  __shared__ float part[16][16][8];
-  const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int c0 = blockIdx.x * 128 + 8 * q;
-  const long n = blockIdx.y;
-  V8 s = zero8();
-  if (c0 < C) {
-    const hf* xb = x + n * HW * (long)C + c0;
-    V8 s1 = s, s2 = s, s3 = s;
-    int p = g;
-    for (; p + 48 < HW; p += 64) {
-      const V8 a = ldh(xb + (long)p * C), b = ldh(xb + (long)(p + 16) * C), c = ldh(xb + (long)(p + 32) * C), d = ldh(xb + (long)(p + 48) * C);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { s.v[j] += a.v[j]; s1.v[j] += b.v[j]; s2.v[j] += c.v[j]; s3.v[j] += d.v[j]; }
-    }
-    for (; p < HW; p += 16) {
-      const V8 a = ldh(xb + (long)p * C);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s.v[j] += a.v[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s.v[j] = (s.v[j] + s1.v[j]) + (s2.v[j] + s3.v[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) part[g][q][j] = s.v[j];
-  __syncthreads();
-  if (g == 0 && c0 < C) {
-    const float hw = (float)HW;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) t += part[i][q][j];
-      y[n * C + c0 + j] = t / hw;       // one correctly rounded division per output (sum * (1 / HW) rounds twice: up to 1.5 ulp, seen at HW = 63)
-    }
-  }
-}
-__global__ __launch_bounds__(256) void gap_bwd_h_kernel(const float* __restrict__ dy, hf* __restrict__ dx, long total_v, int HW, int C) {
-  const int O = C >> 3;
-  const float inv = 1.0f / (float)HW;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total_v; e += (long)gridDim.x * 256) {
-    const int o = (int)(e % O);
-    const long n = e / ((long)O * HW);
-    V8 g = ld8f(dy + n * C + 8 * o);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) g.v[j] *= inv;
-    sth(dx + e * 8, g);
+    VH::st(y + 8 * e, r);
   }
 }
 
@@ -462,8 +177,8 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
 #pragma unroll
     for (int j = 0; j < 8; ++j) { s1[j] = 0.0; s2[j] = 0.0; }
     if (o < O) {
-      V8 mu = zero8();
-      if (mode) mu = ld8f(mean + 8 * o);
+      V8 mu = VH::zero();
+      if (mode) mu = shdr::ldf<8>(mean + 8 * o);
       const long step = (long)gridDim.x * PL;
       // fp32 partial sums over short runs (<= 16 pixels: their rounding is 2^-24 relative, far below the fp16 input), folded into
       // the double accumulators once per run -- the double adds of every element made the kernel VALU-bound at ~2 TB/s
@@ -492,7 +207,7 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
         for (; p + 7 * step < npix; p += 8 * step) {         // statistics pass: eight 16-byte loads in flight per thread
           V8 av[8];
 #pragma unroll
-          for (int u = 0; u < 8; ++u) av[u] = ldh(a + (p + u * step) * C + 8 * o);
+          for (int u = 0; u < 8; ++u) av[u] = VH::ld(a + (p + u * step) * C + 8 * o);
 #pragma unroll
           for (int u = 0; u < 8; ++u) acc(av[u], av[u], av[u]);
           run += 8;
@@ -504,11 +219,11 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const long i = (p + u * step) * C + 8 * o;
-          av[u] = ldh(a + i);
+          av[u] = VH::ld(a + i);
           xv[u] = av[u]; yv[u] = av[u];
           if (mode) {
-            xv[u] = ldh(x + i);
-            if (y) yv[u] = ldh(y + i);
+            xv[u] = VH::ld(x + i);
+            if (y) yv[u] = VH::ld(y + i);
           }
         }
 #pragma unroll
@@ -518,11 +233,11 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
       }
       for (; p < npix; p += step) {
         const long i = p * C + 8 * o;
-        const V8 a0 = ldh(a + i);
+        const V8 a0 = VH::ld(a + i);
         V8 x0 = a0, y0 = a0;
         if (mode) {
-          x0 = ldh(x + i);
-          if (y) y0 = ldh(y + i);
+          x0 = VH::ld(x + i);
+          if (y) y0 = VH::ld(y + i);
         }
         acc(a0, x0, y0);
       }
@@ -532,7 +247,7 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
     for (int j = 0; j < 8; ++j) { part[j][threadIdx.x] = s1[j]; part[8 + j][threadIdx.x] = s2[j]; }
     __syncthreads();
     if (pl == 0 && o < O) {
-      double* wp = ws + (size_t)(1 + blockIdx.x) * 2 * C;       // this block's partial row; summed by bn_fold_h_kernel (no atomics, no memset)
+      double* wp = ws + (size_t)(1 + blockIdx.x) * 2 * C;       // this block's partial row; summed by bn_fold_kernel (no atomics, no memset)
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         double t1 = s1[j], t2 = s2[j];
@@ -543,38 +258,6 @@ __global__ __launch_bounds__(256) void bn_reduce_h_kernel(const hf* __restrict__
     }
     __syncthreads();
   }
-}
-// ws[col] = sum over the g partial rows ws[(1 + b) * 2C + col]: one wave per column, lanes stride over the rows
-__global__ __launch_bounds__(256) void bn_fold_h_kernel(double* __restrict__ ws, int C, int g) {
-  const int col = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (col >= 2 * C) return;
-  double t = 0.0;
-  for (int b = lane; b < g; b += 64) t += ws[(size_t)(1 + b) * 2 * C + col];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-  if (lane == 0) ws[col] = t;
-}
-__global__ void bn_finalize_h_kernel(const double* __restrict__ ws, float* __restrict__ mean, float* __restrict__ var,
-                                     float* __restrict__ mov_mean, float* __restrict__ mov_var, long npix, int C, float momentum) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double mu = ws[c] / (double)npix;
-  double v = ws[C + c] / (double)npix - mu * mu;
-  if (v < 0.0) v = 0.0;
-  mean[c] = (float)mu;
-  var[c] = (float)v;
-  if (mov_mean) {
-    const double unbiased = npix > 1 ? v * (double)npix / (double)(npix - 1) : v;
-    mov_mean[c] = mov_mean[c] * momentum + (float)mu * (1.0f - momentum);
-    mov_var[c] = mov_var[c] * momentum + (float)unbiased * (1.0f - momentum);
-  }
-}
-__global__ void bn_bwd_finalize_h_kernel(const double* __restrict__ ws, const float* __restrict__ var, float* __restrict__ dgamma,
-                                         float* __restrict__ dbeta, int C, float eps) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  dbeta[c] += (float)ws[c];
-  dgamma[c] += (float)(ws[C + c] * (double)rsqrtf(var[c] + eps));
 }
 // forward apply (mode 0): y = [relu]((x - mean) * rstd * gamma + beta);  backward apply (mode 1):
 // dx = gamma * rstd * (dy' - mean(dy') - xhat * mean(dy' * xhat)).  The launcher makes gridDim * 256 a multiple of O, so the
@@ -605,17 +288,17 @@ __global__ __launch_bounds__(256) void bn_apply_h_kernel(const hf* __restrict__ 
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nvec; e += (long)gridDim.x * 256) {
     V8 r;
     if (mode == 0) {
-      const V8 xv = ldh(a + 8 * e);
+      const V8 xv = VH::ld(a + 8 * e);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         r.v[j] = (xv.v[j] - mu[j]) * k0[j] + k1[j];
         if (relu) r.v[j] = fmaxf(r.v[j], 0.f);
       }
     } else {
-      V8 g = ldh(a + 8 * e);
-      const V8 xv = ldh(x + 8 * e);
+      V8 g = VH::ld(a + 8 * e);
+      const V8 xv = VH::ld(x + 8 * e);
       if (y) {
-        const V8 yv = ldh(y + 8 * e);
+        const V8 yv = VH::ld(y + 8 * e);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if (!(yv.v[j] > 0.f)) g.v[j] = 0.f;
@@ -626,7 +309,7 @@ __global__ __launch_bounds__(256) void bn_apply_h_kernel(const hf* __restrict__ 
         r.v[j] = k0[j] * (g.v[j] - k1[j] - xh * k2[j]);
       }
     }
-    sth(out + 8 * e, r);
+    VH::st(out + 8 * e, r);
   }
 }
 
@@ -690,7 +373,7 @@ __global__ __launch_bounds__(256) void lin_frontend_h_kernel(const float* __rest
         const float d = fabsf(xv - centre[j]);
         r.v[j] = (cj[j] >= 0 && d < wB[j]) ? 1.0f - d * fB[j] : 0.0f;
       }
-      sth(y + (p * O + o) * 8, r);
+      VH::st(y + (p * O + o) * 8, r);
     }
   } else {
     const long bid = blockIdx.x / 6, nb = (gridDim.x + 5) / 6;
@@ -704,7 +387,7 @@ __global__ __launch_bounds__(256) void lin_frontend_h_kernel(const float* __rest
       V8 r;
 #pragma unroll
       for (int j = 0; j < 8; ++j) r.v[j] = lin_feature(img, n, h, w, H, W, 8 * o + j);
-      sth(y + (p * O + o) * 8, r);
+      VH::st(y + (p * O + o) * 8, r);
     }
   }
 }
@@ -764,13 +447,6 @@ __global__ __launch_bounds__(256) void lin_frontend_bwd_h_kernel(const float* __
   }
 }
 
-int chk8(const char* op, const void* a, const void* b, int N, int H, int W, int C) {
-  SHDR_REQUIRE(a && b, SHDR_E_NULL, "%s: null pointer", op);
-  SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "%s: non-positive dimension", op);
-  SHDR_REQUIRE((C & 7) == 0, SHDR_E_ALIGN, "%s: C=%d must be a multiple of 8 (16-byte fp16 channel groups)", op, C);
-  SHDR_REQUIRE(shdr::aligned16(a) && shdr::aligned16(b), SHDR_E_ALIGN, "%s: tensors must be 16-byte aligned", op);
-  return SHDR_OK;
-}
 // grid whose thread count is a multiple of O (a thread keeps its channel octet), at most `cap` blocks
 inline int octet_grid(long nvec, int O, int cap) {
   long g = (nvec + 255) / 256;
@@ -855,76 +531,65 @@ extern "C" int shdr_add_f16(const void* a, const void* b, void* y, int64_t n, in
   hipLaunchKernelGGL(add_h_kernel, dim3(shdr::stream_grid(n / 8)), dim3(256), 0, shdr::stream_of(stream), H_(a), H_(b), HM_(y), (long)(n / 8), relu);
   return shdr::check_launch("add_f16");
 }
+// pooling / resize / global average pooling: nhwc_vec.h (launch_vec turns the ABI's void pointers into the kernel's)
 extern "C" int shdr_avgpool2_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("avgpool2_f16", x, y, N, H, W, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("avgpool2_f16", x, y, N, H, W, C)) return rc;
   SHDR_REQUIRE(H >= 2 && W >= 2, SHDR_E_SHAPE, "avgpool2_f16: H, W must be >= 2");
-  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C, 0);
-  return shdr::check_launch("avgpool2_f16");
+  return launch_vec("avgpool2_f16", shdr::pool2_kernel<hf, false>, (long)N * (H / 2) * (W / 2) * (C / 8), stream, x, y, N, H, W, C);
 }
 extern "C" int shdr_maxpool2_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("maxpool2_f16", x, y, N, H, W, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("maxpool2_f16", x, y, N, H, W, C)) return rc;
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_f16: H, W must be even");
-  hipLaunchKernelGGL(pool2_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C, 1);
-  return shdr::check_launch("maxpool2_f16");
+  return launch_vec("maxpool2_f16", shdr::pool2_kernel<hf, true>, (long)N * (H / 2) * (W / 2) * (C / 8), stream, x, y, N, H, W, C);
 }
 extern "C" int shdr_avgpool2_bwd_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("avgpool2_bwd_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(avgpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
-  return shdr::check_launch("avgpool2_bwd_f16");
+  if (int rc = shdr::check_nhwc<8>("avgpool2_bwd_f16", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("avgpool2_bwd_f16", shdr::avgpool2_bwd_kernel<hf>, (long)N * H * W * (C / 8), stream, dy, dx, N, H, W, C);
 }
 extern "C" int shdr_maxpool2_bwd_f16(const void* x, const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("maxpool2_bwd_f16", x, dx, N, H, W, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("maxpool2_bwd_f16", x, dx, N, H, W, C)) return rc;
   SHDR_REQUIRE(dy && shdr::aligned16(dy), SHDR_E_NULL, "maxpool2_bwd_f16: dy null or unaligned");
   SHDR_REQUIRE((H & 1) == 0 && (W & 1) == 0, SHDR_E_SHAPE, "maxpool2_bwd_f16: H, W must be even");
-  hipLaunchKernelGGL(maxpool2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x),
-                     H_(dy), HM_(dx), N, H, W, C);
-  return shdr::check_launch("maxpool2_bwd_f16");
+  return launch_vec("maxpool2_bwd_f16", shdr::maxpool2_bwd_kernel<hf>, (long)N * (H / 2) * (W / 2) * (C / 8), stream, x, dy, dx, N, H, W, C);
 }
 extern "C" int shdr_maxpool3s2_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("maxpool3s2_f16", x, y, N, H, W, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("maxpool3s2_f16", x, y, N, H, W, C)) return rc;
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_h_kernel, dim3(shdr::stream_grid((long)N * Ho * Wo * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H,
-                     W, C, Ho, Wo, pt, pl);
-  return shdr::check_launch("maxpool3s2_f16");
+  return launch_vec("maxpool3s2_f16", shdr::maxpool3s2_kernel<hf>, (long)N * Ho * Wo * (C / 8), stream, x, y, N, H, W, C, Ho, Wo, pt, pl);
 }
 extern "C" int shdr_maxpool3s2_bwd_f16(const void* x, const void* y, const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("maxpool3s2_bwd_f16", x, dx, N, H, W, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("maxpool3s2_bwd_f16", x, dx, N, H, W, C)) return rc;
   SHDR_REQUIRE(dy && shdr::aligned16(dy), SHDR_E_NULL, "maxpool3s2_bwd_f16: dy null or unaligned");
   SHDR_REQUIRE(y && shdr::aligned16(y), SHDR_E_NULL, "maxpool3s2_bwd_f16: y (the pooled output) null or unaligned");
   int Ho, Wo, pt, pl;
   shdr_same_pad(H, 3, 2, &Ho, &pt);
   shdr_same_pad(W, 3, 2, &Wo, &pl);
-  hipLaunchKernelGGL(maxpool3s2_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), H_(y),
-                     H_(dy), HM_(dx), N, H, W, C, Ho, Wo, pt, pl);
-  return shdr::check_launch("maxpool3s2_bwd_f16");
+  return launch_vec("maxpool3s2_bwd_f16", shdr::maxpool3s2_bwd_kernel<hf>, (long)N * H * W * (C / 8), stream, x, y, dy, dx, N, H, W, C, Ho,
+                    Wo, pt, pl);
 }
 extern "C" int shdr_resize2x_fwd_f16(const void* x, void* y, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("resize2x_f16", x, y, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(x), HM_(y), N, H, W, C);
-  return shdr::check_launch("resize2x_f16");
+  if (int rc = shdr::check_nhwc<8>("resize2x_f16", x, y, N, H, W, C)) return rc;
+  return launch_vec("resize2x_f16", shdr::resize2x_kernel<hf>, (long)N * H * W * (C / 8), stream, x, y, N, H, W, C);
 }
 extern "C" int shdr_resize2x_bwd_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("resize2x_bwd_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(resize2x_bwd_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
-  return shdr::check_launch("resize2x_bwd_f16");
+  if (int rc = shdr::check_nhwc<8>("resize2x_bwd_f16", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("resize2x_bwd_f16", shdr::resize2x_bwd_kernel<hf, false>, (long)N * H * W * (C / 8), stream, dy, dx, N, H, W, C, nullptr);
 }
 extern "C" int shdr_upsample_zero2_f16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
-  if (int rc = chk8("upsample_zero2_f16", dy, dx, N, H, W, C)) return rc;
-  hipLaunchKernelGGL(upsample_zero2_h_kernel, dim3(shdr::stream_grid((long)N * H * W * (C / 8))), dim3(256), 0, shdr::stream_of(stream), H_(dy), HM_(dx), N, H, W, C);
-  return shdr::check_launch("upsample_zero2_f16");
+  if (int rc = shdr::check_nhwc<8>("upsample_zero2_f16", dy, dx, N, H, W, C)) return rc;
+  return launch_vec("upsample_zero2_f16", shdr::upsample_zero2_kernel<hf>, (long)N * H * W * (C / 8), stream, dy, dx, N, H, W, C);
 }
 extern "C" int shdr_gap_fwd_f16(const void* x, float* y, int N, int HW, int C, void* stream) {
-  if (int rc = chk8("gap_f16", x, y, N, HW, 1, C)) return rc;
-  hipLaunchKernelGGL(gap_h_kernel, dim3((C + 127) / 128, N), dim3(256), 0, shdr::stream_of(stream), H_(x), y, HW, C);
+  if (int rc = shdr::check_nhwc<8>("gap_f16", x, y, N, HW, 1, C)) return rc;
+  hipLaunchKernelGGL(shdr::gap_kernel<hf>, dim3((C + 127) / 128, N), dim3(256), 0, shdr::stream_of(stream), H_(x), y, HW, C);
   return shdr::check_launch("gap_f16");
 }
 extern "C" int shdr_gap_bwd_f16(const float* dy, void* dx, int N, int HW, int C, void* stream) {
-  if (int rc = chk8("gap_bwd_f16", dy, dx, N, HW, 1, C)) return rc;
+  if (int rc = shdr::check_nhwc<8>("gap_bwd_f16", dy, dx, N, HW, 1, C)) return rc;
   const long tv = (long)N * HW * (C / 8);
-  hipLaunchKernelGGL(gap_bwd_h_kernel, dim3(shdr::stream_grid(tv)), dim3(256), 0, shdr::stream_of(stream), dy, HM_(dx), tv, HW, C);
-  return shdr::check_launch("gap_bwd_f16");
+  return launch_vec("gap_bwd_f16", shdr::gap_bwd_kernel<hf>, tv, stream, dy, dx, tv, HW, C);
 }
 namespace {
 inline void launch_bn_reduce_h(hipStream_t st, HP a, HP x, HP y, const float* mean, double* ws, long npix, int C, int mode) {
@@ -935,7 +600,7 @@ inline void launch_bn_reduce_h(hipStream_t st, HP a, HP x, HP y, const float* me
   long g = (npix + PL * 16 - 1) / (PL * 16);
   g = g < 1 ? 1 : (g > SHDR_BN_MAX_BLOCKS ? SHDR_BN_MAX_BLOCKS : g);       // every block owns a partial row of the workspace
   hipLaunchKernelGGL(bn_reduce_h_kernel, dim3((unsigned)g), dim3(256), 0, st, a, x, y, mean, ws, npix, C, mode);
-  hipLaunchKernelGGL(bn_fold_h_kernel, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, st, ws, C, (int)g);
+  hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, st, ws, C, (int)g);
 }
 }  // namespace
 extern "C" int shdr_bn_stats_f16(const void* x, double* ws, float* mean, float* var, float* moving_mean, float* moving_var, int64_t npix,
@@ -946,7 +611,7 @@ extern "C" int shdr_bn_stats_f16(const void* x, double* ws, float* mean, float* 
   SHDR_REQUIRE(shdr::aligned16(x), SHDR_E_ALIGN, "bn_stats_f16: x must be 16-byte aligned");
   hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce_h(st, H_(x), nullptr, nullptr, nullptr, ws, (long)npix, C, 0);
-  hipLaunchKernelGGL(bn_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var, (long)npix, C, momentum);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var, (long)npix, C, momentum);
   return shdr::check_launch("bn_stats_f16");
 }
 extern "C" int shdr_bn_train_apply_f16(const void* x, const float* mean, const float* var, const float* gamma, const float* beta, void* y,
@@ -967,7 +632,7 @@ extern "C" int shdr_bn_bwd_f16(const void* dy, const void* x, const void* y_relu
                SHDR_E_ALIGN, "bn_bwd_f16: dy, x, y_relu, dx and mean (read as float4) must be 16-byte aligned");
   hipStream_t st = shdr::stream_of(stream);
   launch_bn_reduce_h(st, H_(dy), H_(x), H_(y_relu), mean, ws, (long)npix, C, 1);
-  hipLaunchKernelGGL(bn_bwd_finalize_h_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
   const long nvec = (long)npix * (C / 8);
   hipLaunchKernelGGL(bn_apply_h_kernel, dim3(octet_grid(nvec, C / 8, 2048)), dim3(256), 0, st, H_(dy), H_(x), H_(y_relu), mean, var, gamma,
                      (const float*)nullptr, ws, HM_(dx), nvec, (long)npix, C, eps, 0, 1);

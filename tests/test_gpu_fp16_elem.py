@@ -1,4 +1,5 @@
-"""Every fp16 tape kernel of csrc/elem_f16.hip, element by element, against the float64 reference of tests/fp16_ref.py.
+"""Every fp16 tape kernel of csrc/elem_f16.hip (with its instantiations of csrc/nhwc_vec.h), element by element, against the float64
+reference of tests/fp16_ref.py.
 
 Two kinds of assertion, no tensor-scale bar ("fp16 tape ops"):
 

@@ -1,5 +1,5 @@
-"""Every fp32 tape kernel of csrc/bwd.hip, pool.hip, glue.hip, crf.hip, finetune.hip (+ soft_hist_bwd / lin_frontend_bwd), element by
-element, against the float64 reference of tests/tape_ref.py.
+"""Every fp32 tape kernel of csrc/bwd.hip, pool.hip (both with the channel-vector kernels of nhwc_vec.h), glue.hip, crf.hip, finetune.hip
+(+ soft_hist_bwd / lin_frontend_bwd), element by element, against the float64 reference of tests/tape_ref.py.
 
 Two kinds of assertion, no tensor-scale bar:
 
