@@ -1372,6 +1372,74 @@ int shdr_gainmap_apply(const uint8_t* sdr, int64_t arena_pixels, const uint8_t* 
                        const shdr_gainmap_apply_image* images, const shdr_gainmap_apply_image* images_dev, int n_images, float* out,
                        int64_t out_capacity, void* stream);
 
+/* ---- Deterministic mode: bit-reproducible forms of the fp32 training reductions -----------------------------------------------------------
+ * The default weight-gradient, bias-gradient, CRF-head and loss kernels end in floating-point atomics: several blocks add partial sums to
+ * the same address, in the order in which they happen to arrive, and two runs of one call differ in the last bits.  Each entry point
+ * below computes the same quantity as its namesake without the _det, with the same arguments plus a workspace, and returns the same bits
+ * for the same inputs on every run:
+ *   - every block STORES its partial result to a slab / row of its own in the caller's workspace (the kernel's address arithmetic plus
+ *     block * stride), and a second launch adds the slabs in block order, in double, and rounds once;
+ *   - where the namesake accumulates (dw, db, dwfc, dbfc, drf, dgamma, dbeta) the fold computes the sum S without reading the output and
+ *     then writes out = out + S, one thread per address and NO atomic: accumulating into g0 gives exactly g0 + (the result into zeros), and
+ *     the caller must order the call against every other writer of that output (two streams may not accumulate into one range unordered);
+ *   - the fold touches only what the call owns: shdr_conv2d_wgrad_det_f32 the rows [ci_off, ci_off + Cx) of every tap.
+ * The library allocates nothing and waits for nothing; everything is ordered on `stream`.  A workspace belongs to ONE call until that call
+ * has finished on its stream: concurrent calls on two streams need two workspaces.  Its size comes from shdr_det_workspace_bytes(op, d, n, c,
+ * k); it needs no initialisation; pointers must be 16-byte aligned.  The pixel slices of the deterministic weight gradients depend on the
+ * layer, not on the device (a constant 512 block slots, not the occupancy; SHDR_WGRAD_ROUNDS is ignored), so the query needs no GPU and the
+ * bits are the same on every device.  The kernel-family switches SHDR_NO_ALLTAPS and SHDR_NO_WGRAD96 still pick the kernel and its tile, and
+ * with them the slices: results are bit-identical from run to run under ONE setting of these two switches.
+ *   op                              n                     c          k      call
+ *   SHDR_DET_CONV2D_WGRAD           -                     which      -      shdr_conv2d_wgrad_det_f32 (d = the layer): slices x KH KW (C1+C2) Cout floats
+ *   SHDR_DET_CONV2D_WGRAD_WINOGRAD  -                     which      -      shdr_conv2d_wgrad_winograd_det_f32 (d: N, H, W, C1 / C2, Cout): slices x 16 Cx Cout floats
+ *   SHDR_DET_CONV2D_WGRAD_X3        -                     which      -      shdr_conv2d_wgrad_x3_det_f32 (d = the layer): slices x KH KW (C1+C2) Cout floats
+ *   SHDR_DET_BIAS_GRAD              npix                  C          -      shdr_bias_grad_det_f32: one row of C floats per block
+ *   SHDR_DET_ACT_BWD_BIAS           npix                  C          -      shdr_act_bwd_bias_det_f32 (never more than SHDR_OP_ACT_BWD_BIAS)
+ *   SHDR_DET_BATCHNORM              npix                  C          -      shdr_bn_stats_det_f32, shdr_bn_bwd_ranged_det_f32 (never more than SHDR_OP_BATCHNORM)
+ *   SHDR_DET_DIFF_LOSS              n_per_sample          B          -      shdr_diff_loss_det_f32
+ *   SHDR_DET_TV_LOSS                N H W C               -          -      shdr_tv_loss_det_f32
+ *   SHDR_DET_SAMPLE_DOT             n_per_sample          B          -      shdr_sample_dot_det_f32
+ *   SHDR_DET_INVCRF_DECODE_BWD      -                     B          F      shdr_invcrf_decode_bwd_det_f32: B rows of (F + 1) x 11 floats
+ *   SHDR_DET_APPLY_RF_BWD           n_per_batch           B          K      shdr_apply_rf_bwd_det_f32: one [B][K] slab per block column
+ * shdr_conv2d_wgrad_det_f32 runs the exact-fp32 kernels of shdr_conv2d_wgrad_f32 (algo AUTO, AUTO_EXACT, MFMA or DIRECT; the reduced-precision
+ * algos are refused).  shdr_conv2d_wgrad_winograd_det_f32 gives every unit slice its own slab of the dU scratch (16 x Cx x Cout), folds the
+ * slabs into `du` (every element written: no memset) and runs the dU -> dW transform as before (one thread per address, no atomic).
+ * shdr_conv2d_wgrad_x3_det_f32 is the slab form of the split-operand kernel.  A query answers -1 for a layer its family does not take.
+ * shdr_apply_rf_bwd_det_f32 fills the block's LDS table without atomics (every bin has one owning thread,
+ * which walks the staged pixels in order) and takes K <= 4096.  shdr_lin_frontend_bwd_det_f32 is the GATHER form of the front end's backward:
+ * one thread per pixel sums the transposed REFLECT Sobel stencil in a fixed order and writes dimg once (no memset, no workspace).  The BatchNorm
+ * _det entries differ from their namesakes only where C % 4 != 0 (the float4 reduction is deterministic already). */
+enum { SHDR_DET_CONV2D_WGRAD = 0, SHDR_DET_BIAS_GRAD = 1, SHDR_DET_ACT_BWD_BIAS = 2, SHDR_DET_BATCHNORM = 3, SHDR_DET_DIFF_LOSS = 4,
+       SHDR_DET_TV_LOSS = 5, SHDR_DET_SAMPLE_DOT = 6, SHDR_DET_INVCRF_DECODE_BWD = 7, SHDR_DET_APPLY_RF_BWD = 8,
+       SHDR_DET_CONV2D_WGRAD_WINOGRAD = 9, SHDR_DET_CONV2D_WGRAD_X3 = 10 };
+int64_t shdr_det_workspace_bytes(int op, const shdr_conv2d_desc* d, int64_t n, int c, int k);
+int shdr_conv2d_wgrad_winograd_det_f32(const float* x, const float* dz, float* du, float* dw, void* ws, int64_t ws_bytes, int N, int H, int W,
+                                       int Cx, int Cout, int Ct, int ci_off, float x_scale, void* stream);
+int shdr_conv2d_wgrad_x3_det_f32(const shdr_conv2d_desc* d, const void* xh, const void* xl, int which, const void* zh, const void* zl,
+                                 const float* x_range, const float* z_range, float* dw, void* ws, int64_t ws_bytes, void* stream);
+int shdr_conv2d_wgrad_det_f32(const shdr_conv2d_desc* d, const float* x, int which, const float* dz, float* dw, void* ws, int64_t ws_bytes,
+                              void* stream);
+int shdr_bias_grad_det_f32(const float* dz, float* db, void* ws, int64_t ws_bytes, int64_t npix, int C, void* stream);
+int shdr_act_bwd_bias_det_f32(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act, void* stream);
+int shdr_bn_stats_det_f32(const float* x, double* ws, float* mean, float* var, float* moving_mean, float* moving_var, int64_t npix, int C,
+                          float momentum, void* stream);
+int shdr_bn_bwd_ranged_det_f32(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var, const float* gamma,
+                               double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix, int C, float eps, float* dx_range,
+                               void* stream);
+int shdr_invcrf_decode_bwd_det_f32(const float* dinv, const float* feat, const float* wfc, const float* table, float* dfeat, float* dwfc,
+                                   float* dbfc, void* ws, int64_t ws_bytes, int B, int F, int K, void* stream);
+int shdr_apply_rf_bwd_det_f32(const float* x, const float* rf, const float* dy, float* drf, float* dx, void* ws, int64_t ws_bytes, int B,
+                              int64_t n_per_batch, int K, void* stream);
+int shdr_diff_loss_det_f32(const float* a, const float* b, float* out, void* ws, int64_t ws_bytes, int B, int64_t n_per_sample, int mode,
+                           void* stream);
+int shdr_tv_loss_det_f32(const float* y, float* out, void* ws, int64_t ws_bytes, int N, int H, int W, int C, void* stream);
+int shdr_sample_dot_det_f32(const float* a, const float* b, float* out, void* ws, int64_t ws_bytes, int B, int64_t n_per_sample, void* stream);
+int shdr_lin_frontend_bwd_det_f32(const float* img, const float* dF, float* dimg, int N, int H, int W, int y_channels, void* stream);
+/* Diagnostic: a process-wide count, kept on the host, of the launches whose RESULT depends on the order in which floating-point atomics
+ * reach memory -- the default forms of the entry points above (fp32 and fp16) whenever more than one block, or one block's LDS atomics, add
+ * to one address.  It does not move while a training step runs on the deterministic forms alone. */
+int64_t shdr_order_dependent_launches(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,50 @@ class precision:
         return False
 
 
+# Deterministic mode (fp32 training path): inside `deterministic(True)` every reduction of a training step that ends in floating-point
+# atomics by default -- weight / bias / BatchNorm / CRF-head gradients, the front end's backward, the loss sums -- runs its *_det_f32 form
+# (include/shdr.h "Deterministic mode"): per-block slabs in a workspace of the call plus a fold in a fixed order.  Same inputs, same bits,
+# run after run.  Not covered: the native-fp16 kernels (they raise here) and the collective across ranks.
+DETERMINISTIC = False
+
+
+class deterministic:
+    """with deterministic(True): ...   -- scoped switch of the bit-reproducible forms of the fp32 training reductions"""
+
+    def __init__(self, on=True):
+        self._on = bool(on)
+
+    def __enter__(self):
+        global DETERMINISTIC
+        self._prev, DETERMINISTIC = DETERMINISTIC, self._on
+        return self
+
+    def __exit__(self, *exc):
+        global DETERMINISTIC
+        DETERMINISTIC = self._prev
+        return False
+
+
+def order_dependent_launches():
+    """launches so far, in this process, whose result depends on the arrival order of floating-point atomics (diagnostic, kept on the
+    host by the library): it does not move over a step that ran on the deterministic forms alone"""
+    return int(_lib.load().shdr_order_dependent_launches())
+
+
+def _det_ws(op, device, d=None, n=0, c=0, k=0):
+    """(workspace tensor of ONE deterministic call, its bytes): a fresh torch allocation per call, so two streams never share one"""
+    nbytes = int(_lib.load().shdr_det_workspace_bytes(op, None if d is None else ctypes.byref(d), int(n), int(c), int(k)))
+    if nbytes < 0:
+        msg = _lib.load().shdr_last_error()
+        raise ValueError("deterministic mode: no workspace size for op %d (n=%d, c=%d, k=%d): %s" % (op, n, c, k, msg.decode() if msg else ""))
+    return torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8), nbytes
+
+
+def _no_det_h(what):
+    if DETERMINISTIC:
+        raise ValueError("%s: the deterministic mode does not cover the native-fp16 kernels yet" % what)
+
+
 def same_pad(in_size, k, stride):
     """TF 'SAME': out = ceil(in/s); pad_before = max((out-1)*s + k - in, 0) // 2."""
     out = -(-in_size // stride)
@@ -979,7 +1023,9 @@ def conv2d_wgrad(x, x2, dz, w_shape, stride=1, x2_scale=1.0, out=None):
     Channel counts that are not multiples of 16 (3/4-channel images, 3-channel heads) are zero-padded so
     that the layer runs on the MFMA weight-gradient tiles; the true rows / columns are sliced out.
     `out`: a gradient buffer of shape w_shape to ACCUMULATE into (the kernels add with atomics anyway): no zero fill and no
-    separate add -- used for variables whose .grad is a view of the flat gradient buffer (pipeline.FlatParams)."""
+    separate add -- used for variables whose .grad is a view of the flat gradient buffer (pipeline.FlatParams).
+    Under `deterministic(True)` every family runs its slab form and the fold writes out = out + S WITHOUT an atomic: the caller orders the
+    call against every other writer of `out` (one stream per gradient range: DESIGN.md "Deterministic mode")."""
     kh, kw, cin, cout = w_shape
     c1 = x.shape[3]
     c2 = 0 if x2 is None else x2.shape[3]
@@ -1000,6 +1046,8 @@ def conv2d_wgrad(x, x2, dz, w_shape, stride=1, x2_scale=1.0, out=None):
     x, dz = _chk(_d(x), "x"), _chk(_d(dz), "dz")
     if x2 is not None:
         _chk(_d(x2), "x2")
+    if DETERMINISTIC and PRECISION != "fp32":
+        raise ValueError("conv2d_wgrad: the deterministic mode covers precision 'fp32' only, not %r" % (PRECISION,))
     # Deep k x k layers (>= WGRAD_X3_MIN_CH channels on both sides): the split-operand weight gradient on the fp16 matrix pipe
     # (csrc/wgrad_x3.hip) -- one split pass per tensor, then three fp16 MFMAs per operand pair.  Measured at batch 32 (tools/wgrad_x3_bench.py,
     # split passes included) against the Winograd-domain fp32 kernel: 512 -> 512 at 32^2 0.85 -> 0.60 ms, 512 -> 256 at 64^2 1.61 -> 1.06,
@@ -1016,6 +1064,11 @@ def conv2d_wgrad(x, x2, dz, w_shape, stride=1, x2_scale=1.0, out=None):
             _set_range(dz_in, zr)           # the input gradient of the same layer (called next) takes the slot instead of measuring again
             for src, src_in, which in ((x, x_in, 0),) + (((_d(x2), x2_in, 1),) if x2 is not None else ()):
                 xh, xl, xr = _split_planes(lib, src, _range_of(src_in))
+                if DETERMINISTIC:
+                    ws, nws = _det_ws(_lib.DET_CONV2D_WGRAD_X3, x.device, d=d, c=which)
+                    _lib.check(lib.shdr_conv2d_wgrad_x3_det_f32(ctypes.byref(d), _ptr(xh), _ptr(xl), which, _ptr(zh), _ptr(zl), _ptr(xr), _ptr(zr),
+                                                                _ptr(dw), _ptr(ws), nws, _stream()), "shdr_conv2d_wgrad_x3_det_f32")
+                    continue
                 _lib.check(lib.shdr_conv2d_wgrad_x3_f32(ctypes.byref(d), _ptr(xh), _ptr(xl), which, _ptr(zh), _ptr(zl), _ptr(xr), _ptr(zr),
                                                         _ptr(dw), _stream()), "shdr_conv2d_wgrad_x3_f32")
             return dw
@@ -1028,6 +1081,12 @@ def conv2d_wgrad(x, x2, dz, w_shape, stride=1, x2_scale=1.0, out=None):
         dw = out if out is not None else torch.zeros(tuple(w_shape), device=x.device, dtype=torch.float32)
         for src, cx, off, sc in ((x, c1, 0, 1.0),) + (((_d(x2), c2, c1, float(x2_scale)),) if x2 is not None else ()):
             du = torch.empty((16, cx, cout), device=x.device, dtype=torch.float32)       # scratch, zeroed by the library call
+            if DETERMINISTIC:
+                dd = _conv_desc(x.shape, w_shape, stride, c2, x2_scale, None)
+                ws, nws = _det_ws(_lib.DET_CONV2D_WGRAD_WINOGRAD, x.device, d=dd, c=1 if off else 0)
+                _lib.check(lib.shdr_conv2d_wgrad_winograd_det_f32(_ptr(src), _ptr(dz), _ptr(du), _ptr(dw), _ptr(ws), nws, n, h, w, cx, cout, cin,
+                                                                  off, sc, _stream()), "shdr_conv2d_wgrad_winograd_det_f32")
+                continue
             _lib.check(lib.shdr_conv2d_wgrad_winograd_f32(_ptr(src), _ptr(dz), _ptr(du), _ptr(dw), n, h, w, cx, cout, cin, off, sc,
                                                           _stream()), "shdr_conv2d_wgrad_winograd_f32")
         return dw
@@ -1039,6 +1098,12 @@ def conv2d_wgrad(x, x2, dz, w_shape, stride=1, x2_scale=1.0, out=None):
     if tuple(dz.shape[:3]) != (x.shape[0], d.Ho, d.Wo):
         raise ValueError("conv2d_wgrad: dz spatial shape mismatch")
     dw = out if out is not None else torch.zeros(tuple(w_shape), device=x.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        for src, which in ((x, 0),) + (((_chk(_d(x2), "x2"), 1),) if x2 is not None else ()):
+            ws, nws = _det_ws(_lib.DET_CONV2D_WGRAD, x.device, d=d, c=which)
+            _lib.check(lib.shdr_conv2d_wgrad_det_f32(ctypes.byref(d), _ptr(src), which, _ptr(dz), _ptr(dw), _ptr(ws), nws, _stream()),
+                       "shdr_conv2d_wgrad_det_f32")
+        return dw
     _lib.check(lib.shdr_conv2d_wgrad_f32(ctypes.byref(d), _ptr(x), 0, _ptr(dz), _ptr(dw), _stream()), "shdr_conv2d_wgrad_f32")
     if x2 is not None:
         _lib.check(lib.shdr_conv2d_wgrad_f32(ctypes.byref(d), _ptr(_d(x2)), 1, _ptr(dz), _ptr(dw), _stream()),
@@ -1062,6 +1127,10 @@ def bias_grad(dz, out=None):
     dz = _chk(_d(dz), "dz")
     c = dz.shape[-1]
     db = out if out is not None else torch.zeros(c, device=dz.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_BIAS_GRAD, dz.device, n=dz.numel() // c, c=c)
+        _lib.check(lib.shdr_bias_grad_det_f32(_ptr(dz), _ptr(db), _ptr(ws), nws, dz.numel() // c, c, _stream()), "shdr_bias_grad_det_f32")
+        return db
     _lib.check(lib.shdr_bias_grad_f32(_ptr(dz), _ptr(db), dz.numel() // c, c, _stream()), "shdr_bias_grad_f32")
     return db
 
@@ -1091,8 +1160,8 @@ def act_bwd_bias(dy, y, act, out=None):
         y = _chk(_d(y), "y")
         dz = torch.empty_like(dy)
         yp, zp = _ptr(y), _ptr(dz)
-    _lib.check(lib.shdr_act_bwd_bias_f32(_ptr(dy), yp, zp, _ptr(db), _ptr(_bias_ws(c, dy.device)), dy.numel() // c, c, act, _stream()),
-               "shdr_act_bwd_bias_f32")
+    fn = "shdr_act_bwd_bias_det_f32" if DETERMINISTIC else "shdr_act_bwd_bias_f32"
+    _lib.check(getattr(lib, fn)(_ptr(dy), yp, zp, _ptr(db), _ptr(_bias_ws(c, dy.device)), dy.numel() // c, c, act, _stream()), fn)
     if dz is not dy_in:
         _carry_range(dz, dy_in)         # |act'(y)| <= 1
     return dz, db
@@ -1246,7 +1315,9 @@ def bn_stats(x, moving_mean=None, moving_var=None, momentum=0.99):
     mean = torch.empty(c, device=x.device, dtype=torch.float32)
     var = torch.empty(c, device=x.device, dtype=torch.float32)
     ws = _bn_ws(c, x.device)
-    fn = "shdr_bn_stats_f16" if h else "shdr_bn_stats_f32"
+    if h:
+        _no_det_h("bn_stats")
+    fn = "shdr_bn_stats_f16" if h else ("shdr_bn_stats_det_f32" if DETERMINISTIC else "shdr_bn_stats_f32")
     _lib.check(getattr(lib, fn)(_ptr(x), _ptr(ws), _ptr(mean), _ptr(var), _ptr(_d(moving_mean)), _ptr(_d(moving_var)),
                                 x.numel() // c, c, float(momentum), _stream()), fn)
     _mutated(moving_mean, moving_var)
@@ -1281,13 +1352,14 @@ def bn_bwd(dy, x, y_relu, mean, var, gamma, eps, dgamma_out=None, dbeta_out=None
     dx = torch.empty_like(x)
     ws = _bn_ws(c, x.device)
     if h:
+        _no_det_h("bn_bwd")
         _lib.check(lib.shdr_bn_bwd_f16(_ptr(dy), _ptr(x), _ptr(_d(y_relu)), _ptr(mean), _ptr(var), _ptr(_d(gamma)), _ptr(ws),
                                        _ptr(dgamma), _ptr(dbeta), _ptr(dx), x.numel() // c, c, float(eps), _stream()), "shdr_bn_bwd_f16")
         return dx, dgamma, dbeta
     xr = _new_slot(x.device)            # max |dx| out of the apply pass (the consumer is the input / weight gradient of the conv in front)
-    _lib.check(lib.shdr_bn_bwd_ranged_f32(_ptr(dy), _ptr(x), _ptr(_d(y_relu)), _ptr(mean), _ptr(var), _ptr(_d(gamma)), _ptr(ws),
-                                          _ptr(dgamma), _ptr(dbeta), _ptr(dx), x.numel() // c, c, float(eps), _ptr(xr), _stream()),
-               "shdr_bn_bwd_ranged_f32")
+    fn = "shdr_bn_bwd_ranged_det_f32" if DETERMINISTIC else "shdr_bn_bwd_ranged_f32"
+    _lib.check(getattr(lib, fn)(_ptr(dy), _ptr(x), _ptr(_d(y_relu)), _ptr(mean), _ptr(var), _ptr(_d(gamma)), _ptr(ws),
+                                _ptr(dgamma), _ptr(dbeta), _ptr(dx), x.numel() // c, c, float(eps), _ptr(xr), _stream()), fn)
     return _set_range(dx, xr), dgamma, dbeta
 
 
@@ -1299,6 +1371,11 @@ def invcrf_decode_bwd(dinv, feat, wfc, table):
     dfeat = torch.empty_like(feat)
     dwfc = torch.zeros_like(wfc)
     dbfc = torch.zeros(11, device=feat.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_INVCRF_DECODE_BWD, feat.device, c=b, k=f)
+        _lib.check(lib.shdr_invcrf_decode_bwd_det_f32(_ptr(dinv), _ptr(feat), _ptr(wfc), _ptr(table), _ptr(dfeat), _ptr(dwfc), _ptr(dbfc),
+                                                      _ptr(ws), nws, b, f, k, _stream()), "shdr_invcrf_decode_bwd_det_f32")
+        return dfeat, dwfc, dbfc
     _lib.check(lib.shdr_invcrf_decode_bwd_f32(_ptr(dinv), _ptr(feat), _ptr(wfc), _ptr(table), _ptr(dfeat), _ptr(dwfc),
                                               _ptr(dbfc), b, f, k, _stream()), "shdr_invcrf_decode_bwd_f32")
     return dfeat, dwfc, dbfc
@@ -1319,6 +1396,11 @@ def apply_rf_bwd(x, rf, dy, need_dx):
     b = x.shape[0]
     drf = torch.zeros_like(rf)
     dx = torch.empty_like(x) if need_dx else None
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_APPLY_RF_BWD, x.device, n=x.numel() // b, c=b, k=rf.shape[1])
+        _lib.check(lib.shdr_apply_rf_bwd_det_f32(_ptr(x), _ptr(rf), _ptr(dy), _ptr(drf), _ptr(dx), _ptr(ws), nws, b, x.numel() // b,
+                                                 rf.shape[1], _stream()), "shdr_apply_rf_bwd_det_f32")
+        return drf, dx
     _lib.check(lib.shdr_apply_rf_bwd_f32(_ptr(x), _ptr(rf), _ptr(dy), _ptr(drf), _ptr(dx), b, x.numel() // b, rf.shape[1],
                                          _stream()), "shdr_apply_rf_bwd_f32")
     return drf, dx
@@ -1334,6 +1416,11 @@ def diff_loss(a, b, mode):
         raise ValueError("diff_loss: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
     bs = a.shape[0]
     out = torch.empty(bs, device=a.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_DIFF_LOSS, a.device, n=a.numel() // bs, c=bs)
+        _lib.check(lib.shdr_diff_loss_det_f32(_ptr(a), _ptr(b), _ptr(out), _ptr(ws), nws, bs, a.numel() // bs, mode, _stream()),
+                   "shdr_diff_loss_det_f32")
+        return out
     _lib.check(lib.shdr_diff_loss_f32(_ptr(a), _ptr(b), _ptr(out), bs, a.numel() // bs, mode, _stream()), "shdr_diff_loss_f32")
     return out
 
@@ -1356,6 +1443,10 @@ def tv_loss(y):
     y = _chk(_d(y), "y")
     n, h, w, c = y.shape
     out = torch.empty(1, device=y.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_TV_LOSS, y.device, n=y.numel())
+        _lib.check(lib.shdr_tv_loss_det_f32(_ptr(y), _ptr(out), _ptr(ws), nws, n, h, w, c, _stream()), "shdr_tv_loss_det_f32")
+        return out
     _lib.check(lib.shdr_tv_loss_f32(_ptr(y), _ptr(out), n, h, w, c, _stream()), "shdr_tv_loss_f32")
     return out
 
@@ -1444,7 +1535,9 @@ def lin_frontend_bwd(img, dF):
     img, dF = _chk(_d(img), "img"), (_chkh(_d(dF), "dF") if h16 else _chk(_d(dF), "dF"))
     n, h, w, _ = img.shape
     dimg = torch.empty_like(img)
-    fn = "shdr_lin_frontend_bwd_f16" if h16 else "shdr_lin_frontend_bwd_f32"
+    if h16:
+        _no_det_h("lin_frontend_bwd")
+    fn = "shdr_lin_frontend_bwd_f16" if h16 else ("shdr_lin_frontend_bwd_det_f32" if DETERMINISTIC else "shdr_lin_frontend_bwd_f32")
     _lib.check(getattr(lib, fn)(_ptr(img), _ptr(dF), _ptr(dimg), n, h, w, dF.shape[3], _stream()), fn)
     return dimg
 
@@ -1482,6 +1575,11 @@ def sample_dot(a, b=None):
     a = _chk(_d(a), "a")
     bs = a.shape[0]
     out = torch.empty(bs, device=a.device, dtype=torch.float32)
+    if DETERMINISTIC:
+        ws, nws = _det_ws(_lib.DET_SAMPLE_DOT, a.device, n=a.numel() // bs, c=bs)
+        _lib.check(lib.shdr_sample_dot_det_f32(_ptr(a), _ptr(None if b is None else _chk(_d(b), "b")), _ptr(out), _ptr(ws), nws, bs,
+                                               a.numel() // bs, _stream()), "shdr_sample_dot_det_f32")
+        return out
     _lib.check(lib.shdr_sample_dot_f32(_ptr(a), _ptr(None if b is None else _chk(_d(b), "b")), _ptr(out), bs, a.numel() // bs, _stream()),
                "shdr_sample_dot_f32")
     return out
@@ -1632,6 +1730,7 @@ def conv2d_h(x, wp, bias, khw, cout_gemm, stride=1, x2=None, act1=ACT_NONE, cout
 def conv2d_wgrad_h(x, x2, dz, w_shape, stride=1, x2_scale=1.0, cout_valid=None, out=None):
     """dW [kh,kw,C1+C2,Cout] (fp32) of conv(concat[x, x2_scale*x2], W) from fp16 x / x2 / dz; columns >= cout_valid stay zero.
     `out`: gradient buffer of that shape to accumulate into."""
+    _no_det_h("conv2d_wgrad_h")
     lib = _lib.load()
     kh, kw, cin, cout = w_shape
     x, dz = _chkh(_d(x), "x"), _chkh(_d(dz), "dz")
@@ -1657,6 +1756,7 @@ def conv2d_wgrad_h(x, x2, dz, w_shape, stride=1, x2_scale=1.0, cout_valid=None, 
 def act_bwd_bias_h(dy, y, act, want_db, out=None):
     """(dz, db) on fp16 tensors: dz = dy * act'(y) (dy itself when act is NONE), db = sum over pixels of dz in fp32 (or None);
     `out`: gradient buffer to accumulate db into"""
+    _no_det_h("act_bwd_bias_h")
     lib = _lib.load()
     dy = _chkh(_d(dy), "dy")
     c = dy.shape[-1]

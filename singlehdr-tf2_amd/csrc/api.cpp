@@ -19,6 +19,10 @@ void set_error(const char* fmt, ...) {
 
 namespace shdr {
 int g_env_epoch = 0;
+int64_t g_order_dependent_launches = 0;
+}
+extern "C" int64_t shdr_order_dependent_launches(void) {
+  return __atomic_load_n(&shdr::g_order_dependent_launches, __ATOMIC_RELAXED);
 }
 extern "C" void shdr_config_reload(void) { __atomic_add_fetch(&shdr::g_env_epoch, 1, __ATOMIC_ACQ_REL); }
 

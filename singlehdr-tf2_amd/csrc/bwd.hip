@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
 //   mode 1 (backward)      : v1 = dy', v2 = dy' * (x - mean)   with dy' = dy masked by y > 0 when y != NULL
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ a, const float* __restrict__ x,
                                                         const float* __restrict__ y, const float* __restrict__ mean,
-                                                        double* __restrict__ ws, long npix, int C, int mode) {
+                                                        double* __restrict__ ws, long npix, int C, int mode, int rows) {
   __shared__ double p1[256], p2[256];
   int CL = 1;
   while (CL < C && CL < 256) CL <<= 1;
@@ -178,8 +178,14 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     __syncthreads();
     if (pl == 0 && c < C) {
       for (int j = 1; j < PL; ++j) { s1 += p1[j * CL + cl]; s2 += p2[j * CL + cl]; }
-      atomicAdd(ws + c, s1);
-      atomicAdd(ws + C + c, s2);
+      if (rows) {                                               // deterministic form: this block's partial row, as in bn_reduce4_kernel
+        double* wp = ws + (size_t)(1 + blockIdx.x) * 2 * C;
+        wp[c] = s1;
+        wp[C + c] = s2;
+      } else {
+        atomicAdd(ws + c, s1);
+        atomicAdd(ws + C + c, s2);
+      }
     }
     __syncthreads();
   }
@@ -351,7 +357,7 @@ constexpr int NPCA = 11;
 __global__ __launch_bounds__(256) void invcrf_decode_bwd_kernel(const float* __restrict__ dinv, const float* __restrict__ feat,
                                                                 const float* __restrict__ wfc, const float* __restrict__ table,
                                                                 float* __restrict__ dfeat, float* __restrict__ dwfc,
-                                                                float* __restrict__ dbfc, int F, int K) {
+                                                                float* __restrict__ dbfc, float* __restrict__ ws, int F, int K) {
   __shared__ float red[4][NPCA];
   __shared__ float dwv[NPCA];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -373,7 +379,8 @@ __global__ __launch_bounds__(256) void invcrf_decode_bwd_kernel(const float* __r
   if (tid < NPCA) {
     const float v = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
     dwv[tid] = v;
-    atomicAdd(dbfc + tid, v);
+    if (ws) ws[((size_t)b * (F + 1) + F) * NPCA + tid] = v;      // deterministic form: row b of ws = [dWfc terms F x 11 | dbfc terms 11]
+    else atomicAdd(dbfc + tid, v);
   }
   __syncthreads();
   for (int f = tid; f < F; f += 256) {
@@ -382,7 +389,8 @@ __global__ __launch_bounds__(256) void invcrf_decode_bwd_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < NPCA; ++j) {
       s = fmaf(wfc[f * NPCA + j], dwv[j], s);
-      atomicAdd(dwfc + f * NPCA + j, xv * dwv[j]);
+      if (ws) ws[((size_t)b * (F + 1) + f) * NPCA + j] = xv * dwv[j];
+      else atomicAdd(dwfc + f * NPCA + j, xv * dwv[j]);
     }
     dfeat[(long)b * F + f] = s;
   }
@@ -481,10 +489,57 @@ __global__ __launch_bounds__(256) void apply_rf_bwd_kernel(const float* __restri
     if (acc[k] != 0.f) atomicAdd(drf + (long)b * K + k, acc[k]);
 }
 
+// The deterministic form.  Same pixel-to-block assignment; the LDS table is filled WITHOUT atomics: a trip stages its 256 pixels' (bin,
+// two weights) in LDS, then thread t -- the only writer of the bins k = t (mod 256) -- walks the 256 staged pixels in order and adds what
+// falls into its bins.  So every bin sees its terms in pixel order of the trip, trips in loop order.  The block's table goes to its own
+// slab ws[blockIdx.x][b][K]; col_fold_det_kernel adds the slabs in block order.
+__global__ __launch_bounds__(256) void apply_rf_bwd_det_kernel(const float* __restrict__ x, const float* __restrict__ rf,
+                                                               const float* __restrict__ dy, float* __restrict__ ws,
+                                                               float* __restrict__ dx, long n_per_batch, int K) {
+  extern __shared__ float sm[];   // lut[K] | acc[K]
+  __shared__ int s_i0[256], s_i1[256];
+  __shared__ float s_w0[256], s_w1[256];
+  float* lut = sm;
+  float* acc = sm + K;
+  const int b = blockIdx.y, tid = threadIdx.x;
+  for (int k = tid; k < K; k += 256) { lut[k] = rf[(long)b * K + k]; acc[k] = 0.f; }
+  __syncthreads();
+  const float km1 = (float)(K - 1);
+  const float* xb = x + (long)b * n_per_batch;
+  const float* gb = dy + (long)b * n_per_batch;
+  const long step = (long)gridDim.x * 256;
+  for (long base = (long)blockIdx.x * 256; base < n_per_batch; base += step) {       // block-uniform trip count
+    const long i = base + tid;
+    int i0 = -1, i1 = -1;
+    float w0 = 0.f, w1 = 0.f;
+    if (i < n_per_batch) {
+#pragma clang fp contract(off)
+      const float yv = km1 * xb[i];                                                    // (the forward's weights: see apply_rf_bwd_kernel)
+      const float y0 = floorf(yv), y1 = y0 + 1.0f;
+      i0 = min(max((int)y0, 0), K - 1);
+      i1 = min(max((int)y1, 0), K - 1);
+      const float g = gb[i];
+      w0 = g * (y1 - yv);
+      w1 = g * (yv - y0);
+      if (dx) dx[(long)b * n_per_batch + i] = g * km1 * (lut[i1] - lut[i0]);
+    }
+    s_i0[tid] = i0; s_i1[tid] = i1; s_w0[tid] = w0; s_w1[tid] = w1;
+    __syncthreads();
+    for (int j = 0; j < 256; ++j) {                                                    // broadcast reads
+      const int j0 = s_i0[j], j1 = s_i1[j];
+      if (j0 >= 0 && (j0 & 255) == tid) acc[j0] += s_w0[j];
+      if (j1 >= 0 && (j1 & 255) == tid) acc[j1] += s_w1[j];
+    }
+    __syncthreads();
+  }
+  float* slab = ws + ((size_t)blockIdx.x * gridDim.y + b) * K;
+  for (int k = tid; k < K; k += 256) slab[k] = acc[k];
+}
+
 // ---- losses -------------------------------------------------------------------------------------
 // out[b] += mean over the sample of (a-b)^2 (mode 0) or |a-b| (mode 1); grid (blocks, B)
 __global__ __launch_bounds__(256) void diff_loss_kernel(const float* __restrict__ a, const float* __restrict__ bb,
-                                                        float* __restrict__ out, long n_per, int mode) {
+                                                        float* __restrict__ out, float* __restrict__ ws, long n_per, int mode) {
   __shared__ float sred[4];
   const int b = blockIdx.y;
   const float* pa = a + (long)b * n_per;
@@ -495,7 +550,10 @@ __global__ __launch_bounds__(256) void diff_loss_kernel(const float* __restrict_
     s += mode ? fabsf(d) : d * d;
   }
   const float t = block_sum(s, sred);
-  if (threadIdx.x == 0) atomicAdd(out + b, t / (float)n_per);
+  if (threadIdx.x == 0) {
+    if (ws) ws[(size_t)blockIdx.x * gridDim.y + b] = t / (float)n_per;    // deterministic form: row blockIdx.x of ws[gridDim.x][B]
+    else atomicAdd(out + b, t / (float)n_per);
+  }
 }
 
 // da = g[b] * d/da mean-loss: 2(a-b)/n (mode 0) or sign(a-b)/n (mode 1); `accumulate` adds into da
@@ -514,8 +572,8 @@ __global__ __launch_bounds__(256) void diff_loss_bwd_kernel(const float* __restr
 
 // TV loss (joint_training.py:175-179): out[0] += mean|y[h+1]-y[h]| (over N*H*W*C incl. the zero last row)
 //                                               + mean|y[w+1]-y[w]|
-__global__ __launch_bounds__(256) void tv_loss_kernel(const float* __restrict__ y, float* __restrict__ out, int N, int H,
-                                                      int W, int C) {
+__global__ __launch_bounds__(256) void tv_loss_kernel(const float* __restrict__ y, float* __restrict__ out, float* __restrict__ ws, int N,
+                                                      int H, int W, int C) {
   __shared__ float sred[4];
   const long total = (long)N * H * W * C;
   float s = 0.f;
@@ -528,7 +586,10 @@ __global__ __launch_bounds__(256) void tv_loss_kernel(const float* __restrict__ 
     if (w + 1 < W) s += fabsf(y[i + C] - v);
   }
   const float t = block_sum(s, sred);
-  if (threadIdx.x == 0) atomicAdd(out, t / (float)total);
+  if (threadIdx.x == 0) {
+    if (ws) ws[blockIdx.x] = t / (float)total;
+    else atomicAdd(out, t / (float)total);
+  }
 }
 
 // dy += g * d tv / d y
@@ -604,6 +665,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+inline int act_bwd_bias_cap(long nquads) { return nquads >= (1L << 24) ? 512 : (nquads >= (1L << 23) ? 384 : 256); }   // measured per tensor size
+// rows of the workspace form of act_bwd_bias
+inline int act_bwd_bias_rows(long nquads) {
+  const int grid = shdr::stream_grid(nquads);
+  const int rows = nquads >= (1L << 22) ? shdr::kBiasMaxBlocks : act_bwd_bias_cap(nquads);
+  return grid > rows ? rows : grid;
+}
 inline int reduce_grid(long npix, int C) {
   int CL = 1;
   while (CL < C && CL < 256) CL <<= 1;
@@ -612,8 +680,22 @@ inline int reduce_grid(long npix, int C) {
   return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
 }
 
+// rows of the BatchNorm reductions (launch_bn_reduce below).  C % 4 == 0: the float4 kernel's, or the scalar kernel's where the pointers
+// are not 16-byte aligned or SHDR_BN_SCALAR is set -- the larger of the two, so that a caller who sizes by the query is safe either way
+inline int bn_rows(long npix, int C) {
+  const int scalar = reduce_grid(npix, C);
+  if (C % 4) return scalar;
+  const int Q = C / 4;
+  int QL = 1;
+  while (QL < Q && QL < 256) QL <<= 1;
+  const long PL = 256 / QL;
+  long g = (npix + PL * 16 - 1) / (PL * 16);
+  g = g < 1 ? 1 : (g > SHDR_BN_MAX_BLOCKS ? SHDR_BN_MAX_BLOCKS : g);
+  return g > scalar ? (int)g : scalar;
+}
+
 inline void launch_bn_reduce(hipStream_t st, const float* a, const float* x, const float* y, const float* mean, double* ws,
-                             long npix, int C, int mode) {
+                             long npix, int C, int mode, bool det = false) {
   const bool vec = C % 4 == 0 && shdr::aligned16(a) && (!x || shdr::aligned16(x)) && (!y || shdr::aligned16(y)) &&
                    (!mean || shdr::aligned16(mean)) && SHDR_ENV("SHDR_BN_SCALAR") == nullptr;
   if (vec) {
@@ -627,9 +709,15 @@ inline void launch_bn_reduce(hipStream_t st, const float* a, const float* x, con
     g = g < 1 ? 1 : (g > SHDR_BN_MAX_BLOCKS ? SHDR_BN_MAX_BLOCKS : g);
     hipLaunchKernelGGL(bn_reduce4_kernel, dim3((unsigned)g), dim3(256), 0, st, a, x, y, mean, ws, npix, C, mode);
     hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, st, ws, C, (int)g);
+  } else if (det) {                                             // reduce_grid() <= SHDR_BN_MAX_BLOCKS rows
+    const int g = reduce_grid(npix, C);
+    hipLaunchKernelGGL(bn_reduce_kernel, dim3(g), dim3(256), 0, st, a, x, y, mean, ws, npix, C, mode, 1);
+    hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, st, ws, C, g);
   } else {
     (void)hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, st);
-    hipLaunchKernelGGL(bn_reduce_kernel, dim3(reduce_grid(npix, C)), dim3(256), 0, st, a, x, y, mean, ws, npix, C, mode);
+    const int g = reduce_grid(npix, C);
+    if (g > 1) shdr::count_order_dependent();
+    hipLaunchKernelGGL(bn_reduce_kernel, dim3(g), dim3(256), 0, st, a, x, y, mean, ws, npix, C, mode, 0);
   }
 }
 
@@ -641,9 +729,10 @@ extern "C" int shdr_act_bwd_f32(const float* dy, const float* y, float* dx, int6
   hipLaunchKernelGGL(act_bwd_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), dy, y, dx, (long)n, act);
   return shdr::check_launch("act_bwd");
 }
-extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act,
-                                     void* stream) {
+static int act_bwd_bias_run(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act, bool det,
+                            void* stream) {
   SHDR_REQUIRE(dy && db, SHDR_E_NULL, "act_bwd_bias: null pointer");
+  SHDR_REQUIRE(ws || !det, SHDR_E_NULL, "act_bwd_bias_det: null workspace");
   SHDR_REQUIRE(act == SHDR_ACT_NONE || (y && dz), SHDR_E_NULL, "act_bwd_bias: y and dz are needed with an activation");
   SHDR_REQUIRE(npix > 0 && act >= 0 && act <= 3, SHDR_E_SHAPE, "act_bwd_bias: bad arguments");
   const int Q = C / 4;
@@ -655,21 +744,30 @@ extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz,
   // <= 512 blocks: every block ends with one atomic per channel on the SAME C addresses (2048 blocks measured slower than
   // the unfused pair)
   int grid = shdr::stream_grid(nquads);
-  const int cap = nquads >= (1L << 24) ? 512 : (nquads >= (1L << 23) ? 384 : 256);     // measured per tensor size
+  const int cap = act_bwd_bias_cap(nquads);
   if (ws) {
     // partial rows + fold.  From ~64 MB on with the grid of a plain streaming kernel (that is where it pays in time); below that with
     // the capped grid, for the SUM: the blocks' sums are added in double by the fold instead of by fp32 atomics in arrival order, so
     // db carries one rounding per block sum and one of the total
     SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "act_bwd_bias: ws must be 16-byte aligned");
-    const int rows = nquads >= (1L << 22) ? shdr::kBiasMaxBlocks : cap;        // <= kBiasMaxBlocks rows of C floats: the workspace
-    if (grid > rows) grid = rows;
+    grid = act_bwd_bias_rows(nquads);                  // <= kBiasMaxBlocks rows of C floats: the workspace
     hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, shdr::stream_of(stream), dy, y, dz, db, ws, nquads, Q, act);
-    shdr::launch_col_fold(ws, db, grid, C, shdr::stream_of(stream));
+    if (det) shdr::launch_col_fold_det(ws, db, grid, C, shdr::stream_of(stream));
+    else shdr::launch_col_fold(ws, db, grid, C, shdr::stream_of(stream));
     return shdr::check_launch("act_bwd_bias");
   }
   if (grid > cap) grid = cap;
+  if (grid > 1) shdr::count_order_dependent();
   hipLaunchKernelGGL(act_bwd_bias_kernel, dim3(grid), dim3(256), 0, shdr::stream_of(stream), dy, y, dz, db, (float*)nullptr, nquads, Q, act);
   return shdr::check_launch("act_bwd_bias");
+}
+extern "C" int shdr_act_bwd_bias_f32(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act,
+                                     void* stream) {
+  return act_bwd_bias_run(dy, y, dz, db, ws, npix, C, act, false, stream);
+}
+extern "C" int shdr_act_bwd_bias_det_f32(const float* dy, const float* y, float* dz, float* db, float* ws, int64_t npix, int C, int act,
+                                         void* stream) {
+  return act_bwd_bias_run(dy, y, dz, db, ws, npix, C, act, true, stream);
 }
 extern "C" int shdr_clip_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, float lo, float hi, void* stream) {
   SHDR_REQUIRE(dy && x && dx, SHDR_E_NULL, "clip_bwd: null pointer");
@@ -726,16 +824,24 @@ extern "C" int shdr_upsample_zero2_f32(const float* dy, float* dx, int N, int H,
   return launch_vec("upsample_zero2", shdr::upsample_zero2_kernel<float>, (long)N * H * W * (C / 4), stream, dy, dx, N, H, W, C);
 }
 
-extern "C" int shdr_bn_stats_f32(const float* x, double* ws, float* mean, float* var, float* moving_mean,
-                                 float* moving_var, int64_t npix, int C, float momentum, void* stream) {
+static int bn_stats_run(const float* x, double* ws, float* mean, float* var, float* moving_mean,
+                        float* moving_var, int64_t npix, int C, float momentum, bool det, void* stream) {
   SHDR_REQUIRE(x && ws && mean && var, SHDR_E_NULL, "bn_stats: null pointer");
   SHDR_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), SHDR_E_NULL, "bn_stats: moving stats come in pairs");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bn_stats: bad shape");
   hipStream_t st = shdr::stream_of(stream);
-  launch_bn_reduce(st, x, nullptr, nullptr, nullptr, ws, (long)npix, C, 0);
+  launch_bn_reduce(st, x, nullptr, nullptr, nullptr, ws, (long)npix, C, 0, det);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, mean, var, moving_mean, moving_var,
                      (long)npix, C, momentum);
   return shdr::check_launch("bn_stats");
+}
+extern "C" int shdr_bn_stats_f32(const float* x, double* ws, float* mean, float* var, float* moving_mean,
+                                 float* moving_var, int64_t npix, int C, float momentum, void* stream) {
+  return bn_stats_run(x, ws, mean, var, moving_mean, moving_var, npix, C, momentum, false, stream);
+}
+extern "C" int shdr_bn_stats_det_f32(const float* x, double* ws, float* mean, float* var, float* moving_mean,
+                                     float* moving_var, int64_t npix, int C, float momentum, void* stream) {
+  return bn_stats_run(x, ws, mean, var, moving_mean, moving_var, npix, C, momentum, true, stream);
 }
 extern "C" int shdr_bn_train_apply_ranged_f32(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
                                               float* y, int64_t npix, int C, float eps, int relu, float* y_range, void* stream) {
@@ -749,13 +855,13 @@ extern "C" int shdr_bn_train_apply_f32(const float* x, const float* mean, const 
                                        const float* beta, float* y, int64_t npix, int C, float eps, int relu, void* stream) {
   return shdr_bn_train_apply_ranged_f32(x, mean, var, gamma, beta, y, npix, C, eps, relu, nullptr, stream);
 }
-extern "C" int shdr_bn_bwd_ranged_f32(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var,
-                                      const float* gamma, double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix,
-                                      int C, float eps, float* dx_range, void* stream) {
+static int bn_bwd_run(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var,
+                      const float* gamma, double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix,
+                      int C, float eps, float* dx_range, bool det, void* stream) {
   SHDR_REQUIRE(dy && x && mean && var && gamma && ws && dgamma && dbeta && dx, SHDR_E_NULL, "bn_bwd: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bn_bwd: bad shape");
   hipStream_t st = shdr::stream_of(stream);
-  launch_bn_reduce(st, dy, x, y_relu, mean, ws, (long)npix, C, 1);
+  launch_bn_reduce(st, dy, x, y_relu, mean, ws, (long)npix, C, 1, det);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, ws, var, dgamma, dbeta, C, eps);
   const int Q = C / 4;
   if (C % 4 == 0 && (Q & (Q - 1)) == 0 && Q <= 4096 && shdr::aligned16(dy) && shdr::aligned16(x) && shdr::aligned16(dx) &&
@@ -771,6 +877,16 @@ extern "C" int shdr_bn_bwd_ranged_f32(const float* dy, const float* x, const flo
   }
   return shdr::check_launch("bn_bwd");
 }
+extern "C" int shdr_bn_bwd_ranged_f32(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var,
+                                      const float* gamma, double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix,
+                                      int C, float eps, float* dx_range, void* stream) {
+  return bn_bwd_run(dy, x, y_relu, mean, var, gamma, ws, dgamma, dbeta, dx, npix, C, eps, dx_range, false, stream);
+}
+extern "C" int shdr_bn_bwd_ranged_det_f32(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var,
+                                          const float* gamma, double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix,
+                                          int C, float eps, float* dx_range, void* stream) {
+  return bn_bwd_run(dy, x, y_relu, mean, var, gamma, ws, dgamma, dbeta, dx, npix, C, eps, dx_range, true, stream);
+}
 extern "C" int shdr_bn_bwd_f32(const float* dy, const float* x, const float* y_relu, const float* mean, const float* var,
                                const float* gamma, double* ws, float* dgamma, float* dbeta, float* dx, int64_t npix,
                                int C, float eps, void* stream) {
@@ -781,9 +897,25 @@ extern "C" int shdr_invcrf_decode_bwd_f32(const float* dinv, const float* feat, 
                                           float* dfeat, float* dwfc, float* dbfc, int B, int F, int K, void* stream) {
   SHDR_REQUIRE(dinv && feat && wfc && table && dfeat && dwfc && dbfc, SHDR_E_NULL, "invcrf_decode_bwd: null pointer");
   SHDR_REQUIRE(B > 0 && F > 0 && K > 0, SHDR_E_SHAPE, "invcrf_decode_bwd: bad shape");
+  if (B > 1) shdr::count_order_dependent();
   hipLaunchKernelGGL(invcrf_decode_bwd_kernel, dim3(B), dim3(256), 0, shdr::stream_of(stream), dinv, feat, wfc, table, dfeat, dwfc,
-                     dbfc, F, K);
+                     dbfc, (float*)nullptr, F, K);
   return shdr::check_launch("invcrf_decode_bwd");
+}
+extern "C" int shdr_invcrf_decode_bwd_det_f32(const float* dinv, const float* feat, const float* wfc, const float* table,
+                                              float* dfeat, float* dwfc, float* dbfc, void* ws, int64_t ws_bytes, int B, int F, int K,
+                                              void* stream) {
+  SHDR_REQUIRE(dinv && feat && wfc && table && dfeat && dwfc && dbfc && ws, SHDR_E_NULL, "invcrf_decode_bwd_det: null pointer");
+  SHDR_REQUIRE(B > 0 && F > 0 && K > 0, SHDR_E_SHAPE, "invcrf_decode_bwd_det: bad shape");
+  const size_t row = (size_t)(F + 1) * NPCA;
+  SHDR_REQUIRE(ws_bytes >= (int64_t)(B * row * sizeof(float)), SHDR_E_SHAPE, "invcrf_decode_bwd_det: workspace of %lld bytes, %lld needed",
+               (long long)ws_bytes, (long long)(B * row * sizeof(float)));
+  hipStream_t st = shdr::stream_of(stream);
+  float* w = static_cast<float*>(ws);
+  hipLaunchKernelGGL(invcrf_decode_bwd_kernel, dim3(B), dim3(256), 0, st, dinv, feat, wfc, table, dfeat, dwfc, dbfc, w, F, K);
+  shdr::launch_col_fold_det(w, dwfc, B, F * NPCA, st, row);                    // the batch rows, in batch order
+  shdr::launch_col_fold_det(w + (size_t)F * NPCA, dbfc, B, NPCA, st, row);
+  return shdr::check_launch("invcrf_decode_bwd_det");
 }
 extern "C" int shdr_increase_bwd_f32(const float* rf, const float* dout, float* drf, int B, int K, void* stream) {
   SHDR_REQUIRE(rf && dout && drf, SHDR_E_NULL, "increase_bwd: null pointer");
@@ -798,9 +930,24 @@ extern "C" int shdr_apply_rf_bwd_f32(const float* x, const float* rf, const floa
   SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_batch > 0 && K >= 2 && K <= 8192, SHDR_E_SHAPE, "apply_rf_bwd: bad shape");
   int gx = shdr::stream_grid(n_per_batch);
   if (gx > 256) gx = 256;
+  shdr::count_order_dependent();                          // (LDS float atomics: the order inside one block already matters)
   hipLaunchKernelGGL(apply_rf_bwd_kernel, dim3(gx, B), dim3(256), (size_t)2 * K * sizeof(float), shdr::stream_of(stream), x, rf, dy,
                      drf, dx, (long)n_per_batch, K);
   return shdr::check_launch("apply_rf_bwd");
+}
+extern "C" int shdr_apply_rf_bwd_det_f32(const float* x, const float* rf, const float* dy, float* drf, float* dx, void* ws,
+                                         int64_t ws_bytes, int B, int64_t n_per_batch, int K, void* stream) {
+  SHDR_REQUIRE(x && rf && dy && drf && ws, SHDR_E_NULL, "apply_rf_bwd_det: null pointer");
+  SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_batch > 0 && K >= 2 && K <= 4096, SHDR_E_SHAPE, "apply_rf_bwd_det: bad shape (2 <= K <= 4096)");
+  const int gx = shdr::row_sum_grid(n_per_batch, shdr::kApplyRfMaxBlocks);
+  const int64_t need = (int64_t)gx * B * K * (int64_t)sizeof(float);
+  SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "apply_rf_bwd_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+  hipStream_t st = shdr::stream_of(stream);
+  float* w = static_cast<float*>(ws);
+  hipLaunchKernelGGL(apply_rf_bwd_det_kernel, dim3(gx, B), dim3(256), (size_t)2 * K * sizeof(float), st, x, rf, dy, w, dx,
+                     (long)n_per_batch, K);
+  shdr::launch_col_fold_det(w, drf, gx, B * K, st);
+  return shdr::check_launch("apply_rf_bwd_det");
 }
 
 extern "C" int shdr_diff_loss_f32(const float* a, const float* b, float* out, int B, int64_t n_per_sample, int mode, void* stream) {
@@ -810,8 +957,28 @@ extern "C" int shdr_diff_loss_f32(const float* a, const float* b, float* out, in
   if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "diff_loss: memset");
   int gx = shdr::stream_grid(n_per_sample);
   if (gx > 128) gx = 128;
-  hipLaunchKernelGGL(diff_loss_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, (long)n_per_sample, mode);
+  if (gx > 1) shdr::count_order_dependent();
+  hipLaunchKernelGGL(diff_loss_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, (float*)nullptr, (long)n_per_sample, mode);
   return shdr::check_launch("diff_loss");
+}
+// the deterministic forms of the forward sums: one partial per block in ws[blocks][B], added in block order by col_fold_det_kernel
+static int row_sum_ws_check(const char* who, const void* ws, int64_t ws_bytes, int gx, int B) {
+  SHDR_REQUIRE(ws, SHDR_E_NULL, "%s: null workspace", who);
+  const int64_t need = (int64_t)gx * B * (int64_t)sizeof(float);
+  SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes, (long long)need);
+  return SHDR_OK;
+}
+extern "C" int shdr_diff_loss_det_f32(const float* a, const float* b, float* out, void* ws, int64_t ws_bytes, int B, int64_t n_per_sample,
+                                      int mode, void* stream) {
+  SHDR_REQUIRE(a && b && out, SHDR_E_NULL, "diff_loss_det: null pointer");
+  SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_sample > 0 && (mode == 0 || mode == 1), SHDR_E_SHAPE, "diff_loss_det: bad arguments");
+  const int gx = shdr::row_sum_grid(n_per_sample, 128);
+  if (int e = row_sum_ws_check("diff_loss_det", ws, ws_bytes, gx, B)) return e;
+  hipStream_t st = shdr::stream_of(stream);
+  float* w = static_cast<float*>(ws);
+  hipLaunchKernelGGL(diff_loss_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, w, (long)n_per_sample, mode);
+  shdr::launch_col_fold_det(w, out, gx, B, st, 0, 0);
+  return shdr::check_launch("diff_loss_det");
 }
 extern "C" int shdr_diff_loss_bwd_f32(const float* a, const float* b, const float* g, float* da, int B,
                                       int64_t n_per_sample, int mode, int accumulate, void* stream) {
@@ -828,8 +995,20 @@ extern "C" int shdr_tv_loss_f32(const float* y, float* out, int N, int H, int W,
   if (hipMemsetAsync(out, 0, sizeof(float), st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "tv_loss: memset");
   int gx = shdr::stream_grid((long)N * H * W * C);
   if (gx > 512) gx = 512;
-  hipLaunchKernelGGL(tv_loss_kernel, dim3(gx), dim3(256), 0, st, y, out, N, H, W, C);
+  if (gx > 1) shdr::count_order_dependent();
+  hipLaunchKernelGGL(tv_loss_kernel, dim3(gx), dim3(256), 0, st, y, out, (float*)nullptr, N, H, W, C);
   return shdr::check_launch("tv_loss");
+}
+extern "C" int shdr_tv_loss_det_f32(const float* y, float* out, void* ws, int64_t ws_bytes, int N, int H, int W, int C, void* stream) {
+  SHDR_REQUIRE(y && out, SHDR_E_NULL, "tv_loss_det: null pointer");
+  SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, SHDR_E_SHAPE, "tv_loss_det: bad shape");
+  const int gx = shdr::row_sum_grid((long)N * H * W * C, 512);
+  if (int e = row_sum_ws_check("tv_loss_det", ws, ws_bytes, gx, 1)) return e;
+  hipStream_t st = shdr::stream_of(stream);
+  float* w = static_cast<float*>(ws);
+  hipLaunchKernelGGL(tv_loss_kernel, dim3(gx), dim3(256), 0, st, y, out, w, N, H, W, C);
+  shdr::launch_col_fold_det(w, out, gx, 1, st, 0, 0);
+  return shdr::check_launch("tv_loss_det");
 }
 extern "C" int shdr_tv_loss_bwd_f32(const float* y, const float* g, float* dy, int N, int H, int W, int C, int accumulate, void* stream) {
   SHDR_REQUIRE(y && g && dy, SHDR_E_NULL, "tv_loss_bwd: null pointer");
@@ -869,4 +1048,23 @@ extern "C" int shdr_adam_f32(float* p, const float* g, float* m, float* v, int64
   hipLaunchKernelGGL(adam_kernel, dim3(shdr::stream_grid(n)), dim3(256), 0, shdr::stream_of(stream), p, g, m, v, (long)n, lr_t, beta1,
                      beta2, eps, grad_scale);
   return shdr::check_launch("adam");
+}
+
+// bytes of the workspace that ONE call of a deterministic entry point uses (shdr.h "Deterministic mode"); -1: bad arguments
+extern "C" int64_t shdr_det_workspace_bytes(int op, const shdr_conv2d_desc* d, int64_t n, int c, int k) {
+  const int64_t f = (int64_t)sizeof(float);
+  switch (op) {
+    case SHDR_DET_CONV2D_WGRAD: return shdr::wgrad_det_bytes(d, c);
+    case SHDR_DET_CONV2D_WGRAD_WINOGRAD: return shdr::wgrad_winograd_det_bytes(d, c);
+    case SHDR_DET_CONV2D_WGRAD_X3: return shdr::wgrad_x3_det_bytes(d, c);
+    case SHDR_DET_BIAS_GRAD: return n > 0 && c > 0 ? (int64_t)shdr::bias_grad_grid(n, c) * c * f : -1;
+    case SHDR_DET_ACT_BWD_BIAS: return n > 0 && c > 0 && c % 4 == 0 ? (int64_t)act_bwd_bias_rows(n * (c / 4)) * c * f : -1;
+    case SHDR_DET_BATCHNORM: return n > 0 && c > 0 ? (int64_t)2 * c * (1 + bn_rows(n, c)) * (int64_t)sizeof(double) : -1;
+    case SHDR_DET_DIFF_LOSS:
+    case SHDR_DET_SAMPLE_DOT: return n > 0 && c > 0 ? (int64_t)shdr::row_sum_grid(n, 128) * c * f : -1;
+    case SHDR_DET_TV_LOSS: return n > 0 ? (int64_t)shdr::row_sum_grid(n, 512) * f : -1;
+    case SHDR_DET_INVCRF_DECODE_BWD: return c > 0 && k > 0 ? (int64_t)c * (k + 1) * NPCA * f : -1;
+    case SHDR_DET_APPLY_RF_BWD: return n > 0 && c > 0 && k >= 2 ? (int64_t)shdr::row_sum_grid(n, shdr::kApplyRfMaxBlocks) * c * k * f : -1;
+    default: return -1;
+  }
 }

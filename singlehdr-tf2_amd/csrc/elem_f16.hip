@@ -519,6 +519,7 @@ extern "C" int shdr_act_bwd_bias_f16(const void* dy, const void* y, void* dz, fl
   const int cap = db && !rows ? (nvec >= (1L << 23) ? 512 : 256) : 2048;
   int grid = octet_grid(nvec, O, cap);
   if (rows && grid > shdr::kBiasMaxBlocks) grid = octet_grid(nvec, O, shdr::kBiasMaxBlocks / 2);       // the rounding up to the octet unit stays below the row count
+  if (db) shdr::count_order_dependent();                  // (fp32 atomics into the block's LDS sums, then into db or through the fold)
   hipLaunchKernelGGL(act_bwd_bias_h_kernel, dim3(grid), dim3(256), db ? 8 * O * sizeof(float) : 0, shdr::stream_of(stream), H_(dy),
                      H_(y), HM_(dz), db, rows ? ws : (float*)nullptr, nvec, O, act);
   if (rows) shdr::launch_col_fold(ws, db, grid, C, shdr::stream_of(stream));

@@ -32,8 +32,8 @@ __device__ __forceinline__ float soft_bin_grad(float x, int i, int B) {
 // Backward of the fused front end: dimg (zeroed by the caller) += J^T dF.
 // one thread per pixel; identity + histogram terms are local, the REFLECT-padded sobel stencil is
 // scattered with fp32 atomics (36 per pixel on a 3-channel image).  They, not the reads, set the kernel's time: 1.8 ms at
-// 4 x 1024^2; a variant that stages the dF rows through LDS with coalesced float4 loads measured 2.05 ms.  A gather form
-// (transposed REFLECT stencil) is the way to the 0.4 ms of HBM time.
+// 4 x 1024^2; a variant that stages the dF rows through LDS with coalesced float4 loads measured 2.05 ms.  The gather form
+// (transposed REFLECT stencil) is lin_frontend_bwd_gather_kernel below, the deterministic entry point; README.md has both times.
 __global__ __launch_bounds__(256) void lin_frontend_bwd_kernel(const float* __restrict__ img, const float* __restrict__ dF,
                                                                float* __restrict__ dimg, int N, int H, int W, int YC) {
   const long npix = (long)N * H * W;
@@ -63,6 +63,57 @@ __global__ __launch_bounds__(256) void lin_frontend_bwd_kernel(const float* __re
         atomicAdd(dimg + (ibase + (long)hs[j] * W + wm) * 3 + c, -k[j] * gdx);
       }
     }
+  }
+}
+
+// The gather form (the deterministic entry point): one thread per pixel p and channel sums, in a FIXED order, what the scatter above adds
+// to p -- the transposed REFLECT stencil.  reflect() moves an index by at most one, so every source q that reaches p lies in p's 3 x 3
+// neighbourhood; each of q's twelve stencil terms is kept where its target is p (at H or W of 2 and 3 a border source folds both of its
+// neighbours onto one pixel and several terms of one source qualify).  Nothing is zeroed and nothing is atomic: dimg[p] is written once.
+__global__ __launch_bounds__(256) void lin_frontend_bwd_gather_kernel(const float* __restrict__ img, const float* __restrict__ dF,
+                                                                      float* __restrict__ dimg, int N, int H, int W, int YC) {
+  const long npix = (long)N * H * W;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long)gridDim.x * 256) {
+    const int w = (int)(p % W);
+    const long t = p / W;
+    const int h = (int)(t % H);
+    const long ibase = (t / H) * (long)H * W;
+    const float* g = dF + p * YC;
+    float acc[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float x = img[p * 3 + c];
+      float a = g[c];
+      for (int b = 0; b < 4; ++b) a += g[9 + 3 * b + c] * soft_bin_grad(x, b + 1, 4);
+      for (int b = 0; b < 8; ++b) a += g[21 + 3 * b + c] * soft_bin_grad(x, b + 1, 8);
+      for (int b = 0; b < 16; ++b) a += g[45 + 3 * b + c] * soft_bin_grad(x, b + 1, 16);
+      acc[c] = a;
+    }
+    const float k[3] = {1.f, 2.f, 1.f};
+    for (int sh = max(h - 1, 0); sh <= min(h + 1, H - 1); ++sh) {
+      const int hm = reflect(sh - 1, H), hp = reflect(sh + 1, H);
+      const int hs[3] = {hm, sh, hp};
+      for (int sw = max(w - 1, 0); sw <= min(w + 1, W - 1); ++sw) {
+        const int wm = reflect(sw - 1, W), wp = reflect(sw + 1, W);
+        const int ws[3] = {wm, sw, wp};
+        // coefficient of the source's gdy and gdx at p: the scatter's terms whose target is (h, w)
+        float cy = 0.f, cx = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          if (hp == h && ws[j] == w) cy += k[j];
+          if (hm == h && ws[j] == w) cy -= k[j];
+          if (hs[j] == h && wp == w) cx += k[j];
+          if (hs[j] == h && wm == w) cx -= k[j];
+        }
+        if (cy != 0.f || cx != 0.f) {
+          const float* gs = dF + (ibase + (long)sh * W + sw) * YC;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) acc[c] += cy * gs[3 + 2 * c] + cx * gs[4 + 2 * c];
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dimg[p * 3 + c] = acc[c];
   }
 }
 
@@ -107,7 +158,7 @@ __global__ __launch_bounds__(256) void unpack3_kernel(const float* __restrict__ 
 
 // per-sample sums: out[b] += sum_i a[b][i] * (b2 ? b2[b][i] : 1)
 __global__ __launch_bounds__(256) void sample_dot_kernel(const float* __restrict__ a, const float* __restrict__ b2,
-                                                         float* __restrict__ out, long n_per) {
+                                                         float* __restrict__ out, float* __restrict__ ws, long n_per) {
   __shared__ float sred[4];
   const int b = blockIdx.y;
   const float* pa = a + (long)b * n_per;
@@ -115,7 +166,10 @@ __global__ __launch_bounds__(256) void sample_dot_kernel(const float* __restrict
   float s = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_per; i += (long)gridDim.x * 256) s += pb ? pa[i] * pb[i] : pa[i];
   const float t = block_sum(s, sred);
-  if (threadIdx.x == 0) atomicAdd(out + b, t);
+  if (threadIdx.x == 0) {
+    if (ws) ws[(size_t)blockIdx.x * gridDim.y + b] = t;       // deterministic form: row blockIdx.x of ws[gridDim.x][B]
+    else atomicAdd(out + b, t);
+  }
 }
 
 // out = r / (eps + mean_b(r)) * target          (finetune_real_dataset.py:170)
@@ -148,8 +202,18 @@ extern "C" int shdr_lin_frontend_bwd_f32(const float* img, const float* dF, floa
   hipStream_t st = shdr::stream_of(stream);
   const long npix = (long)N * H * W;
   if (hipMemsetAsync(dimg, 0, sizeof(float) * 3 * npix, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "lin_frontend_bwd: memset");
+  shdr::count_order_dependent();
   hipLaunchKernelGGL(lin_frontend_bwd_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, st, img, dF, dimg, N, H, W, y_channels);
   return shdr::check_launch("lin_frontend_bwd");
+}
+extern "C" int shdr_lin_frontend_bwd_det_f32(const float* img, const float* dF, float* dimg, int N, int H, int W, int y_channels,
+                                             void* stream) {
+  SHDR_REQUIRE(img && dF && dimg, SHDR_E_NULL, "lin_frontend_bwd_det: null pointer");
+  SHDR_REQUIRE(N > 0 && H >= 2 && W >= 2 && y_channels >= 93, SHDR_E_SHAPE, "lin_frontend_bwd_det: bad shape");
+  const long npix = (long)N * H * W;
+  hipLaunchKernelGGL(lin_frontend_bwd_gather_kernel, dim3(shdr::stream_grid(npix)), dim3(256), 0, shdr::stream_of(stream), img, dF, dimg, N,
+                     H, W, y_channels);
+  return shdr::check_launch("lin_frontend_bwd_det");
 }
 
 extern "C" int shdr_alpha_blend_full_bwd_f32(const float* b, const float* hal, const float* dA, float* dB, float* dhal,
@@ -180,8 +244,22 @@ extern "C" int shdr_sample_dot_f32(const float* a, const float* b, float* out, i
   if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return shdr::fail(SHDR_E_LAUNCH, "sample_dot: memset");
   int gx = shdr::stream_grid(n_per_sample);
   if (gx > 128) gx = 128;
-  hipLaunchKernelGGL(sample_dot_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, (long)n_per_sample);
+  if (gx > 1) shdr::count_order_dependent();
+  hipLaunchKernelGGL(sample_dot_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, (float*)nullptr, (long)n_per_sample);
   return shdr::check_launch("sample_dot");
+}
+extern "C" int shdr_sample_dot_det_f32(const float* a, const float* b, float* out, void* ws, int64_t ws_bytes, int B, int64_t n_per_sample,
+                                       void* stream) {
+  SHDR_REQUIRE(a && out && ws, SHDR_E_NULL, "sample_dot_det: null pointer");
+  SHDR_REQUIRE(B > 0 && B <= 65535 && n_per_sample > 0, SHDR_E_SHAPE, "sample_dot_det: bad shape");
+  const int gx = shdr::row_sum_grid(n_per_sample, 128);
+  const int64_t need = (int64_t)gx * B * (int64_t)sizeof(float);
+  SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "sample_dot_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+  hipStream_t st = shdr::stream_of(stream);
+  float* w = static_cast<float*>(ws);
+  hipLaunchKernelGGL(sample_dot_kernel, dim3(gx, B), dim3(256), 0, st, a, b, out, w, (long)n_per_sample);
+  shdr::launch_col_fold_det(w, out, gx, B, st, 0, 0);
+  return shdr::check_launch("sample_dot_det");
 }
 
 extern "C" int shdr_mean_norm_fwd_f32(const float* r, const float* sum, float* out, int B, int64_t n_per_sample, float eps,

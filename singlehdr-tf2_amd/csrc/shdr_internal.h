@@ -78,6 +78,11 @@ inline const char* env_cached(EnvSlot& slot, const char* name) {
 }
 #define SHDR_ENV(name) ([]() -> const char* { static ::shdr::EnvSlot slot; return ::shdr::env_cached(slot, name); }())
 
+// shdr_order_dependent_launches(): bumped on the host by every launch whose RESULT depends on the order in which floating-point atomics
+// reach memory (more than one atomic add per address).  Nothing on the device.
+extern int64_t g_order_dependent_launches;
+inline void count_order_dependent() { __atomic_add_fetch(&g_order_dependent_launches, 1, __ATOMIC_RELAXED); }
+
 #define SHDR_REQUIRE(cond, code, ...) \
   do {                                \
     if (!(cond)) return ::shdr::fail((code), __VA_ARGS__); \
@@ -218,7 +223,43 @@ __global__ __launch_bounds__(256) static void col_fold_kernel(const float* __res
   }
 }
 inline void launch_col_fold(const float* ws, float* out, int g, int C, hipStream_t st) {
+  if (g > 256) count_order_dependent();                // more than one row slice: several atomics per address
   hipLaunchKernelGGL(col_fold_kernel, dim3((C + 15) / 16, (g + 255) / 256), dim3(256), 0, st, ws, out, g, C);
+}
+// The deterministic forms (shdr.h "Deterministic mode"): a fold that adds in a FIXED order and touches `out` once per address without an
+// atomic, so the caller must order it against every other writer of `out`.
+//   out[c] = out[c] + (float)(sum over the g rows of ws[r * rstride + c])     (accumulate = 0: out[c] = the sum)
+// col_fold_kernel's block (16 columns x 16 row lanes, double sums) over ALL rows: lane rl adds rows rl, rl + 16, ... in that order, thread
+// (0, cl) adds the 16 lane sums in lane order -- the order is a function of g alone.
+__global__ __launch_bounds__(256) static void col_fold_det_kernel(const float* __restrict__ ws, float* __restrict__ out, int g, int C,
+                                                                  size_t rstride, size_t ystride, int accumulate) {
+  __shared__ double part[16][17];
+  ws += blockIdx.y * ystride;                          // blockIdx.y: independent column ranges at the same offset of ws and out
+  out += blockIdx.y * ystride;
+  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const int c = blockIdx.x * 16 + cl;
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+  if (c < C) {
+    int r = rl;
+    for (; r + 48 < g; r += 64) {
+      t0 += ws[(size_t)r * rstride + c]; t1 += ws[(size_t)(r + 16) * rstride + c];
+      t2 += ws[(size_t)(r + 32) * rstride + c]; t3 += ws[(size_t)(r + 48) * rstride + c];
+    }
+    for (; r < g; r += 16) t0 += ws[(size_t)r * rstride + c];
+  }
+  part[rl][cl] = (t0 + t1) + (t2 + t3);
+  __syncthreads();
+  if (rl == 0 && c < C) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t += part[k][cl];
+    out[c] = accumulate ? out[c] + (float)t : (float)t;
+  }
+}
+inline void launch_col_fold_det(const float* ws, float* out, int g, int C, hipStream_t st, size_t rstride = 0, int accumulate = 1,
+                                int ny = 1, size_t ystride = 0) {
+  hipLaunchKernelGGL(col_fold_det_kernel, dim3((C + 15) / 16, ny), dim3(256), 0, st, ws, out, g, C, rstride ? rstride : (size_t)C, ystride,
+                     accumulate);
 }
 // Bijective XCD-aware remap of a 1-D grid: hardware block ids go round-robin over the 8 XCDs, so consecutive LOGICAL ids -- neighbouring
 // tiles, the cout slices of one tile, the taps of one slice -- share an XCD and its L2.
@@ -227,6 +268,24 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// grids of the reductions that have a deterministic form: ONE definition for the launch and for shdr_det_workspace_bytes()
+inline int bias_grad_grid(int64_t npix, int C) {
+  int CL = 1;
+  while (CL < C && CL < 256) CL <<= 1;
+  const long PL = 256 / CL;
+  long g = (npix + PL * 64 - 1) / (PL * 64);
+  return (int)(g < 1 ? 1 : (g > 1024 ? 1024 : g));
+}
+inline int row_sum_grid(int64_t n, int cap) {             // blocks per sample of diff_loss / sample_dot (cap 128), of tv_loss (cap 512)
+  const int g = stream_grid(n);
+  return g > cap ? cap : g;
+}
+constexpr long kDetSlots = 512;              // block slots the slices of a deterministic weight gradient aim at: a constant, not the device's
+// bytes of the deterministic weight gradients' workspaces (-1: the family does not take the layer); shdr_det_workspace_bytes()
+int64_t wgrad_det_bytes(const shdr_conv2d_desc* d, int which);
+int64_t wgrad_winograd_det_bytes(const shdr_conv2d_desc* d, int which);
+int64_t wgrad_x3_det_bytes(const shdr_conv2d_desc* d, int which);
+constexpr int kApplyRfMaxBlocks = 256;       // blocks per sample of apply_rf_bwd (one slab each in the deterministic form)
 constexpr int kBiasMaxBlocks = 2048;         // rows of the act_bwd_bias workspace (shdr_workspace_bytes(SHDR_OP_ACT_BWD_BIAS))
 
 __device__ __forceinline__ float act_apply(float v, int act) {

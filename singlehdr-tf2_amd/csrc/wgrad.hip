@@ -37,6 +37,8 @@ struct WgradArgs {
   int tiles_m, tiles_n;
   float x_scale;
   int prec;          // 0: exact fp32 MFMA, 1: fp16 operands, 2: bf16 operands
+  float* ws;         // deterministic form: pixel slice s STORES its partial dW at ws + s * slab (same address arithmetic as dw) ...
+  size_t slab;       // ... floats per slab; 0: the default form, fp32 atomics into dw
 };
 
 constexpr int PK = 32;  // pixels per chunk
@@ -203,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
 
   // D[row = ci][col = co]: lane holds rows 4*fg + r, column fi of each 16x16 tile
   if (!computing) return;
-  float* dwt = a.dw + (size_t)tap * a.Ct * a.Cout;
+  float* dwt = (a.slab ? a.ws + (size_t)blockIdx.y * a.slab : a.dw) + (size_t)tap * a.Ct * a.Cout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
@@ -212,8 +214,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ci = ci0 + wm * MT * 16 + mi * 16 + 4 * fg + r;
-        if (ci < a.Cx && co < a.Cout)
-          atomicAdd(dwt + (size_t)(a.ci_off + ci) * a.Cout + co, acc[mi][ni][r] * a.x_scale);
+        if (ci < a.Cx && co < a.Cout) {
+          float* o = dwt + (size_t)(a.ci_off + ci) * a.Cout + co;
+          if (a.slab) *o = acc[mi][ni][r] * a.x_scale;   // (uniform) this block is the only writer of its slab's tile
+          else atomicAdd(o, acc[mi][ni][r] * a.x_scale);
+        }
       }
     }
 }
@@ -345,14 +350,17 @@ __global__ __launch_bounds__(256) void wgrad_alltaps_kernel(const WgradArgs a) {
   for (int j = 0; j < TPW; ++j) {
     const int t = wave + 4 * j;
     if (t < NTAPS) {
-      float* dwt = a.dw + (size_t)t * a.Ct * a.Cout;
+      float* dwt = (a.slab ? a.ws + (size_t)blockIdx.x * a.slab : a.dw) + (size_t)t * a.Ct * a.Cout;
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni)
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            atomicAdd(dwt + (size_t)(a.ci_off + mi * 16 + 4 * fg + r) * a.Cout + ni * 16 + fi, acc[j][mi][ni][r] * a.x_scale);
+          for (int r = 0; r < 4; ++r) {
+            float* o = dwt + (size_t)(a.ci_off + mi * 16 + 4 * fg + r) * a.Cout + ni * 16 + fi;
+            if (a.slab) *o = acc[j][mi][ni][r] * a.x_scale;
+            else atomicAdd(o, acc[j][mi][ni][r] * a.x_scale);
+          }
     }
   }
 }
@@ -362,8 +370,13 @@ int launch_wgrad_alltaps(WgradArgs& a, hipStream_t st) {
   const long units = (long)a.N * a.Ho * ((a.Wo + 31) / 32);
   long blocks = 1024;                                     // 4 per CU; bounds the atomics (taps x 256 x MT x NT per block)
   if (blocks > units) blocks = units;
-  a.slice = (int)((units + blocks - 1) / blocks);
-  blocks = (units + a.slice - 1) / a.slice;
+  if (a.slab) {
+    blocks = a.nslices;                                   // deterministic form: det_plan() has cut the units, one slab per block
+  } else {
+    a.slice = (int)((units + blocks - 1) / blocks);
+    blocks = (units + a.slice - 1) / a.slice;
+    if (blocks > 1) shdr::count_order_dependent();
+  }
   hipLaunchKernelGGL((wgrad_alltaps_kernel<KK, MT, NT>), dim3((unsigned)blocks), dim3(256), 0, st, a);
   return shdr::check_launch("wgrad_alltaps_kernel");
 }
@@ -401,7 +414,9 @@ __global__ __launch_bounds__(256) void wgrad_direct_kernel(const WgradArgs a) {
       if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
         s = fmaf(a.x[(size_t)((n * a.H + ih) * a.W + iw) * a.Cx + ci], a.dz[(size_t)p * a.Cout + co], s);
     }
-    atomicAdd(a.dw + ((size_t)tap * a.Ct + a.ci_off + ci) * a.Cout + co, s * a.x_scale);
+    const size_t o = ((size_t)tap * a.Ct + a.ci_off + ci) * a.Cout + co;
+    if (a.slab) a.ws[(size_t)blockIdx.x * a.slab + o] = s * a.x_scale;
+    else atomicAdd(a.dw + o, s * a.x_scale);
   }
 }
 
@@ -422,7 +437,8 @@ __global__ __launch_bounds__(256) void filter_transform_kernel(const float* __re
 }
 
 // db[c] += sum over pixels of dz[p][c]; grid-stride over pixel blocks, one atomic per block and channel
-__global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict__ dz, float* __restrict__ db,
+// ws != NULL (deterministic form): the block's sums go to row blockIdx.x of ws instead, folded by col_fold_det_kernel
+__global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict__ dz, float* __restrict__ db, float* __restrict__ ws,
                                                         long npix, int C) {
   __shared__ float part[256];
   // thread = (channel lane, pixel lane): CL channels x PL pixel lanes, CL = min(C rounded to pow2, 256)
@@ -440,7 +456,8 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict_
     if (pl == 0 && c < C) {
       float tsum = s;
       for (int j = 1; j < PL; ++j) tsum += part[j * CL + cl];
-      atomicAdd(db + c, tsum);
+      if (ws) ws[(size_t)blockIdx.x * C + c] = tsum;
+      else atomicAdd(db + c, tsum);
     }
     __syncthreads();
   }
@@ -455,15 +472,18 @@ int launch_wgrad_prec(WgradArgs& a, hipStream_t st) {
   if (int e = shdr::dynamic_lds_slots<&wgrad_mfma_kernel<BMc, BNc, WM, WN, PREC>>(256, lds, "wgrad", slots)) return e;
   // pixel slices: one round of the chip's block slots, at least 1024 pixels per slice to bound the atomics
   const long tiles = (long)a.KH * a.KW * a.tiles_m * a.tiles_n;
-  long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
-  if (SHDR_ENV("SHDR_WGRAD_LEGACY_GRID")) {
-    const long want = (256L * 8 + tiles - 1) / tiles;
-    slice = (a.npix + want - 1) / want;
-    if (slice < 2048) slice = 2048;
+  if (!a.slab) {                                          // (deterministic form: det_plan() has cut the pixels)
+    long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
+    if (SHDR_ENV("SHDR_WGRAD_LEGACY_GRID")) {
+      const long want = (256L * 8 + tiles - 1) / tiles;
+      slice = (a.npix + want - 1) / want;
+      if (slice < 2048) slice = 2048;
+    }
+    slice = (slice + PK - 1) / PK * PK;
+    a.slice = (int)slice;
+    a.nslices = (int)((a.npix + slice - 1) / slice);
+    if (a.nslices > 1) shdr::count_order_dependent();
   }
-  slice = (slice + PK - 1) / PK * PK;
-  a.slice = (int)slice;
-  a.nslices = (int)((a.npix + slice - 1) / slice);
   if (a.nslices > 65535) return shdr::fail(SHDR_E_SHAPE, "wgrad: too many pixel slices");
   hipLaunchKernelGGL((wgrad_mfma_kernel<BMc, BNc, WM, WN, PREC>), dim3((unsigned)tiles, (unsigned)a.nslices), dim3(256),
                      lds, st, a);
@@ -494,11 +514,61 @@ int dispatch_n96(WgradArgs& a, hipStream_t st) {
   return launch_wgrad<96, 32, 2, 2>(a, st);
 }
 
-}  // namespace
+// slab size, the query's answer (returns 1: answered, nothing to launch), the workspace check
+int det_prepare(WgradArgs& a, float* ws, int64_t ws_bytes, int mode, int64_t* ws_need) {
+  a.slab = (size_t)a.KH * a.KW * a.Ct * a.Cout;
+  const int64_t need = (int64_t)a.nslices * (int64_t)a.slab * (int64_t)sizeof(float);
+  if (mode == 2) {
+    *ws_need = need;
+    return 1;
+  }
+  SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "wgrad_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+  a.ws = ws;
+  return SHDR_OK;
+}
+// dw = dw + (the slabs' sum in slice order), on the rows [ci_off, ci_off + Cx) of every tap and nowhere else: per tap these are Cx * Cout
+// contiguous floats
+int det_fold(const WgradArgs& a, hipStream_t st) {
+  const size_t off = (size_t)a.ci_off * a.Cout;
+  shdr::launch_col_fold_det(a.ws + off, a.dw + off, a.nslices, a.Cx * a.Cout, st, a.slab, 1, a.KH * a.KW, (size_t)a.Ct * a.Cout);
+  return shdr::check_launch("wgrad_det fold");
+}
 
-extern "C" int shdr_conv2d_wgrad_f32(const shdr_conv2d_desc* d, const float* x, int which, const float* dz,
-                                     float* dw, void* stream) {
-  SHDR_REQUIRE(d && x && dz && dw, SHDR_E_NULL, "wgrad: null pointer");
+// The deterministic form's pixel slices: a function of the layer alone (not of the device's occupancy), so that the workspace query and
+// the launch agree without a device.  family 0: all-taps, 1: MFMA tiles, 2: direct.
+using shdr::kDetSlots;                                    // blocks the slices of one MFMA layer aim at
+constexpr long kDetAlltapsBlocks = 256, kDetDirectBlocks = 1024;
+void det_plan(WgradArgs& a, int family) {
+  if (family == 0) {
+    const long units = (long)a.N * a.Ho * ((a.Wo + 31) / 32);
+    const long blocks = units < kDetAlltapsBlocks ? units : kDetAlltapsBlocks;
+    a.slice = (int)((units + blocks - 1) / blocks);
+    a.nslices = (int)((units + a.slice - 1) / a.slice);
+  } else if (family == 1) {
+    // the tiles of dispatch_n / dispatch_n96 below
+    const bool t96 = a.Cx % 128 && a.Cx % 64 && a.Cx % 96 == 0 && a.Cout % 32 == 0 && SHDR_ENV("SHDR_NO_WGRAD96") == nullptr;
+    const int bm = a.Cx % 128 == 0 ? 128 : (a.Cx % 64 == 0 ? 64 : (t96 ? 96 : (a.Cx % 32 == 0 ? 32 : 16)));
+    const int bn = a.Cout % 128 == 0 ? 128 : (a.Cout % 64 == 0 ? 64 : (a.Cout % 32 == 0 ? 32 : 16));
+    const long tiles = (long)a.KH * a.KW * ((a.Cx + bm - 1) / bm) * ((a.Cout + bn - 1) / bn);
+    long ns = kDetSlots / tiles;                           // (no SHDR_WGRAD_ROUNDS here: the slices, and with them the bits, are the layer's)
+    if (ns < 1) ns = 1;
+    long slice = (a.npix + ns - 1) / ns;
+    if (slice < 1024) slice = 1024;
+    slice = (slice + PK - 1) / PK * PK;
+    a.slice = (int)slice;
+    a.nslices = (int)((a.npix + slice - 1) / slice);
+  } else {
+    long slice = (a.npix + kDetDirectBlocks - 1) / kDetDirectBlocks;
+    if (slice < 1024) slice = 1024;
+    a.slice = (int)slice;
+    a.nslices = (int)((a.npix + slice - 1) / slice);
+  }
+}
+
+// mode 0: the default form (atomics into dw); 1: the deterministic form (slabs in ws, then the fold); 2: *ws_need = the bytes mode 1 needs
+int wgrad_run(const shdr_conv2d_desc* d, const float* x, int which, const float* dz, float* dw, float* ws, int64_t ws_bytes, int mode,
+              int64_t* ws_need, void* stream) {
+  SHDR_REQUIRE(d && (mode == 2 || (x && dz && dw)), SHDR_E_NULL, "wgrad: null pointer");
   SHDR_REQUIRE(which == 0 || which == 1, SHDR_E_SHAPE, "wgrad: which must be 0 (x1) or 1 (x2)");
   SHDR_REQUIRE(which == 0 || d->C2 > 0, SHDR_E_SHAPE, "wgrad: no second source");
   SHDR_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C1 > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 &&
@@ -518,6 +588,11 @@ extern "C" int shdr_conv2d_wgrad_f32(const shdr_conv2d_desc* d, const float* x, 
   a.x_scale = which ? d->x2_scale : 1.0f;
   hipStream_t st = shdr::stream_of(stream);
   const bool mfma_ok = (a.Cx % 16 == 0) && (a.Cout % 16 == 0) && shdr::aligned16(x) && shdr::aligned16(dz);
+  if (mode) {
+    SHDR_REQUIRE(d->algo == SHDR_ALGO_AUTO || d->algo == SHDR_ALGO_AUTO_EXACT || d->algo == SHDR_ALGO_MFMA || d->algo == SHDR_ALGO_DIRECT,
+                 SHDR_E_SHAPE, "wgrad_det: exact fp32 only (algo AUTO, AUTO_EXACT, MFMA or DIRECT)");
+    SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(dz), SHDR_E_ALIGN, "wgrad_det: x and dz must be 16-byte aligned");
+  }
   a.prec = (d->algo == SHDR_ALGO_MFMA_F16 || d->algo == SHDR_ALGO_AUTO_F16) ? 1
            : (d->algo == SHDR_ALGO_MFMA_BF16 || d->algo == SHDR_ALGO_AUTO_BF16) ? 2 : 0;
   // (also in the reduced-precision modes: the exact-fp32 all-taps kernel is 2x faster than the fp16-operand narrow kernel,
@@ -527,22 +602,60 @@ extern "C" int shdr_conv2d_wgrad_f32(const shdr_conv2d_desc* d, const float* x, 
       (a.Cout == 16 || a.Cout == 32) && a.KH == a.KW && (a.KH == 3 || a.KH == 5 || a.KH == 7) && a.Ho == a.H && a.Wo == a.W &&
       (a.KH == 3 || (a.KH == 5 && a.Cx * a.Cout <= 512) || (a.KH == 7 && a.Cx == 16 && a.Cout == 16)) &&   // <= 256 VGPRs
       SHDR_ENV("SHDR_NO_ALLTAPS") == nullptr) {
+    if (mode) {
+      det_plan(a, 0);
+      if (int e = det_prepare(a, ws, ws_bytes, mode, ws_need)) return e > 0 ? SHDR_OK : e;
+      const int e = a.Cx == 16 ? (a.Cout == 16 ? dispatch_alltaps<1, 1>(a, st) : dispatch_alltaps<1, 2>(a, st))
+                               : (a.Cout == 16 ? dispatch_alltaps<2, 1>(a, st) : dispatch_alltaps<2, 2>(a, st));
+      return e ? e : det_fold(a, st);
+    }
     if (a.Cx == 16) return a.Cout == 16 ? dispatch_alltaps<1, 1>(a, st) : dispatch_alltaps<1, 2>(a, st);
     return a.Cout == 16 ? dispatch_alltaps<2, 1>(a, st) : dispatch_alltaps<2, 2>(a, st);
   }
   if (mfma_ok && d->algo != SHDR_ALGO_DIRECT) {
-    if (a.Cx % 128 == 0) return dispatch_n<128>(a, st);
-    if (a.Cx % 64 == 0) return dispatch_n<64>(a, st);
-    if (a.Cx % 96 == 0 && a.Cout % 32 == 0 && SHDR_ENV("SHDR_NO_WGRAD96") == nullptr) return dispatch_n96(a, st);
-    if (a.Cx % 32 == 0) return dispatch_n<32>(a, st);
-    return dispatch_n<16>(a, st);
+    if (mode) {
+      det_plan(a, 1);
+      if (int e = det_prepare(a, ws, ws_bytes, mode, ws_need)) return e > 0 ? SHDR_OK : e;
+    }
+    int e;
+    if (a.Cx % 128 == 0) e = dispatch_n<128>(a, st);
+    else if (a.Cx % 64 == 0) e = dispatch_n<64>(a, st);
+    else if (a.Cx % 96 == 0 && a.Cout % 32 == 0 && SHDR_ENV("SHDR_NO_WGRAD96") == nullptr) e = dispatch_n96(a, st);
+    else if (a.Cx % 32 == 0) e = dispatch_n<32>(a, st);
+    else e = dispatch_n<16>(a, st);
+    return (e || !mode) ? e : det_fold(a, st);
   }
   SHDR_REQUIRE(d->algo != SHDR_ALGO_MFMA && d->algo != SHDR_ALGO_MFMA_F16 && d->algo != SHDR_ALGO_MFMA_BF16, SHDR_E_ALIGN,
                "wgrad: MFMA path needs Cin%%16==0 and Cout%%16==0");
-  a.slice = 1024;
-  a.nslices = (a.npix + a.slice - 1) / a.slice;
+  if (mode) {
+    det_plan(a, 2);
+    if (int e = det_prepare(a, ws, ws_bytes, mode, ws_need)) return e > 0 ? SHDR_OK : e;
+  } else {
+    a.slice = 1024;
+    a.nslices = (a.npix + a.slice - 1) / a.slice;
+    if (a.nslices > 1) shdr::count_order_dependent();
+  }
   hipLaunchKernelGGL(wgrad_direct_kernel, dim3((unsigned)a.nslices), dim3(256), 0, st, a);
-  return shdr::check_launch("wgrad_direct_kernel");
+  const int e = shdr::check_launch("wgrad_direct_kernel");
+  return (e || !mode) ? e : det_fold(a, st);
+}
+
+}  // namespace
+
+extern "C" int shdr_conv2d_wgrad_f32(const shdr_conv2d_desc* d, const float* x, int which, const float* dz,
+                                     float* dw, void* stream) {
+  return wgrad_run(d, x, which, dz, dw, nullptr, 0, 0, nullptr, stream);
+}
+int64_t shdr::wgrad_det_bytes(const shdr_conv2d_desc* d, int which) {
+  int64_t need = -1;
+  if (wgrad_run(d, nullptr, which, nullptr, nullptr, nullptr, 0, 2, &need, nullptr) != SHDR_OK) return -1;
+  return need;
+}
+extern "C" int shdr_conv2d_wgrad_det_f32(const shdr_conv2d_desc* d, const float* x, int which, const float* dz, float* dw, void* ws,
+                                         int64_t ws_bytes, void* stream) {
+  SHDR_REQUIRE(ws, SHDR_E_NULL, "wgrad_det: null workspace");
+  SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "wgrad_det: ws must be 16-byte aligned");
+  return wgrad_run(d, x, which, dz, dw, static_cast<float*>(ws), ws_bytes, 1, nullptr, stream);
 }
 
 extern "C" int shdr_filter_transform_f32(const float* w, float* wt, int KH, int KW, int Cin, int Cout,
@@ -556,16 +669,25 @@ extern "C" int shdr_filter_transform_f32(const float* w, float* wt, int KH, int 
   return shdr::check_launch("filter_transform");
 }
 
-extern "C" int shdr_bias_grad_f32(const float* dz, float* db, int64_t npix, int C, void* stream) {
+static int bias_grad_run(const float* dz, float* db, float* ws, int64_t ws_bytes, bool det, int64_t npix, int C, void* stream) {
   SHDR_REQUIRE(dz && db, SHDR_E_NULL, "bias_grad: null pointer");
   SHDR_REQUIRE(npix > 0 && C > 0, SHDR_E_SHAPE, "bias_grad: bad shape");
-  int CL = 1;
-  while (CL < C && CL < 256) CL <<= 1;
-  const int PL = 256 / CL;
-  long g = (npix + (long)PL * 64 - 1) / ((long)PL * 64);
-  if (g < 1) g = 1;
-  if (g > 1024) g = 1024;
+  const long g = shdr::bias_grad_grid(npix, C);
+  if (det) {
+    SHDR_REQUIRE(ws, SHDR_E_NULL, "bias_grad_det: null workspace");
+    SHDR_REQUIRE(ws_bytes >= (int64_t)g * C * (int64_t)sizeof(float), SHDR_E_SHAPE, "bias_grad_det: workspace of %lld bytes, %lld needed",
+                 (long long)ws_bytes, (long long)g * C * (long long)sizeof(float));
+  } else if (g > 1) {
+    shdr::count_order_dependent();
+  }
   hipLaunchKernelGGL(bias_grad_kernel, dim3((unsigned)g), dim3(256), 0, shdr::stream_of(stream), dz,
-                     db, (long)npix, C);
+                     db, ws, (long)npix, C);
+  if (det) shdr::launch_col_fold_det(ws, db, (int)g, C, shdr::stream_of(stream));
   return shdr::check_launch("bias_grad");
+}
+extern "C" int shdr_bias_grad_f32(const float* dz, float* db, int64_t npix, int C, void* stream) {
+  return bias_grad_run(dz, db, nullptr, 0, false, npix, C, stream);
+}
+extern "C" int shdr_bias_grad_det_f32(const float* dz, float* db, void* ws, int64_t ws_bytes, int64_t npix, int C, void* stream) {
+  return bias_grad_run(dz, db, static_cast<float*>(ws), ws_bytes, true, npix, C, stream);
 }

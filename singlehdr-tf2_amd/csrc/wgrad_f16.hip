@@ -274,6 +274,7 @@ int launch_wgrad_f16(WgradHArgs& a, hipStream_t st) {
   a.slice = (int)slice;
   const long nslices = (a.npix + slice - 1) / slice;
   if (tiles * nslices > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "wgrad_f16: grid too large");
+  if (nslices > 1) shdr::count_order_dependent();
   hipLaunchKernelGGL((wgrad_f16_kernel<CI_T, CO_T, KC, NWV, WM_>), dim3((unsigned)(tiles * nslices)), dim3(NWV * 64), lds, st, a);
   return shdr::check_launch("wgrad_f16_kernel");
 }

@@ -313,6 +313,7 @@ int launch_alltaps(WgradAArgs& a, hipStream_t st) {
   a.slice = (int)slice;
   const long nslices = (a.nsegs + slice - 1) / slice;
   if (nslices > 65535) return shdr::fail(SHDR_E_SHAPE, "wgrad_f16_alltaps: grid too large");
+  if (nslices > 1) shdr::count_order_dependent();
   hipLaunchKernelGGL((wgrad_f16_alltaps_kernel<KK, CI_T, CO_T, MODE>), dim3((unsigned)tiles, (unsigned)nslices), dim3(256), G::LDS_BYTES, st, a);
   return shdr::check_launch("wgrad_f16_alltaps_kernel");
 }

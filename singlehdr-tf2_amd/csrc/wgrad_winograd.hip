@@ -29,6 +29,7 @@ struct WinoWgradArgs {
   int N, H, W, Cx, Cout;
   int tiles_y, segs, units, slice;
   int tiles_m, tiles_n;
+  size_t slab;       // deterministic form: unit slice s STORES its partial dU at du + s * slab (floats); 0: fp32 atomics into du
 };
 
 constexpr int XP_PIX = 4 * 18, ZP_PIX = 2 * 16;
@@ -185,18 +186,24 @@ __global__ __launch_bounds__(256, 2) void wgrad_winograd_kernel(const WinoWgradA
   // ---- partial dU tiles: D[row = ci (4*fg + r)][col = co (fi)] --------------------------------------------------------------
 #pragma unroll
   for (int x2 = 0; x2 < 4; ++x2) {
-    float* dst = a.du + (size_t)(4 * wave + x2) * a.Cx * a.Cout;
+    float* dst = a.du + (size_t)blockIdx.y * a.slab + (size_t)(4 * wave + x2) * a.Cx * a.Cout;
 #pragma unroll
     for (int mt = 0; mt < MTC; ++mt)
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          atomicAdd(dst + (size_t)(ci0 + mt * 16 + 4 * fg + r) * a.Cout + co0 + nt * 16 + fi, acc[x2][mt][nt][r]);
+        for (int r = 0; r < 4; ++r) {
+          float* o = dst + (size_t)(ci0 + mt * 16 + 4 * fg + r) * a.Cout + co0 + nt * 16 + fi;
+          if (a.slab) *o = acc[x2][mt][nt][r];         // (uniform) the block is the only writer of its slab's tile
+          else atomicAdd(o, acc[x2][mt][nt][r]);
+        }
   }
 }
 
 // dW[a][b][ci_off + ci][co] += scale * sum_{i,j} G[i][a] dU[4i + j][ci][co] G[j][b],  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
+// DET (the deterministic form): the addend is rounded BEFORE it meets dw (contraction off: no FMA of the product with the add), so that
+// accumulating into g0 gives exactly g0 + (the result into zeros); the default form keeps its contracted multiply-add
+template <bool DET>
 __global__ __launch_bounds__(256) void winograd_dw_kernel(const float* __restrict__ du, float* __restrict__ dw, int Cx, int Cout,
                                                           int Ct, int ci_off, float scale) {
   const long cc = (long)Cx * Cout;
@@ -219,17 +226,58 @@ __global__ __launch_bounds__(256) void winograd_dw_kernel(const float* __restric
       const float w1 = 0.5f * (t[aa][1] - t[aa][2]);
       const float w2 = 0.5f * (t[aa][1] + t[aa][2]) + t[aa][3];
       float* o = dw + ((size_t)(aa * 3) * Ct + ci_off + ci) * Cout + co;
-      o[0] += scale * w0;
-      o[(size_t)Ct * Cout] += scale * w1;
-      o[(size_t)2 * Ct * Cout] += scale * w2;
+      if constexpr (DET) {
+#pragma clang fp contract(off)
+        const float v0 = scale * w0, v1 = scale * w1, v2 = scale * w2;
+        o[0] = o[0] + v0;
+        o[(size_t)Ct * Cout] = o[(size_t)Ct * Cout] + v1;
+        o[(size_t)2 * Ct * Cout] = o[(size_t)2 * Ct * Cout] + v2;
+      } else {
+        o[0] += scale * w0;
+        o[(size_t)Ct * Cout] += scale * w1;
+        o[(size_t)2 * Ct * Cout] += scale * w2;
+      }
     }
   }
 }
 
+// unit slices of the deterministic form: a function of the shape alone (512 block slots, >= 32 units per slice, no environment switch)
+long det_unit_slice(long tiles, long units) {
+  long ns = shdr::kDetSlots / tiles;
+  if (ns < 1) ns = 1;
+  const long slice = (units + ns - 1) / ns;
+  return slice < 32 ? 32 : slice;
+}
+long wino_units(int N, int H, int W) { return (long)N * ((H + 1) / 2) * ((W + 15) / 16); }
+
+int wgrad_winograd_run(const float* x, const float* dz, float* du, float* dw, float* ws, int64_t ws_bytes, bool det, int N, int H, int W, int Cx,
+                       int Cout, int Ct, int ci_off, float x_scale, void* stream);
+
 }  // namespace
+
+int64_t shdr::wgrad_winograd_det_bytes(const shdr_conv2d_desc* d, int which) {
+  if (!d || (which != 0 && !(which == 1 && d->C2 > 0))) return -1;
+  const int Cx = which ? d->C2 : d->C1;
+  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || Cx <= 0 || Cx % 32 || d->Cout <= 0 || d->Cout % 64) return -1;
+  const long tiles = (long)(Cx / 32) * (d->Cout / 64), units = wino_units(d->N, d->H, d->W);
+  const long slice = det_unit_slice(tiles, units);
+  return (int64_t)((units + slice - 1) / slice) * 16 * Cx * d->Cout * (int64_t)sizeof(float);
+}
 
 extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, float* du, float* dw, int N, int H, int W, int Cx,
                                               int Cout, int Ct, int ci_off, float x_scale, void* stream) {
+  return wgrad_winograd_run(x, dz, du, dw, nullptr, 0, false, N, H, W, Cx, Cout, Ct, ci_off, x_scale, stream);
+}
+extern "C" int shdr_conv2d_wgrad_winograd_det_f32(const float* x, const float* dz, float* du, float* dw, void* ws, int64_t ws_bytes, int N,
+                                                  int H, int W, int Cx, int Cout, int Ct, int ci_off, float x_scale, void* stream) {
+  SHDR_REQUIRE(ws, SHDR_E_NULL, "wgrad_winograd_det: null workspace");
+  SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "wgrad_winograd_det: ws must be 16-byte aligned");
+  return wgrad_winograd_run(x, dz, du, dw, static_cast<float*>(ws), ws_bytes, true, N, H, W, Cx, Cout, Ct, ci_off, x_scale, stream);
+}
+
+namespace {
+int wgrad_winograd_run(const float* x, const float* dz, float* du, float* dw, float* ws, int64_t ws_bytes, bool det, int N, int H, int W, int Cx,
+                       int Cout, int Ct, int ci_off, float x_scale, void* stream) {
   SHDR_REQUIRE(x && dz && du && dw, SHDR_E_NULL, "wgrad_winograd: null pointer");
   SHDR_REQUIRE(N > 0 && H > 0 && W > 0 && Cx > 0 && Cout > 0 && Ct >= Cx && ci_off >= 0 && ci_off + Cx <= Ct, SHDR_E_SHAPE,
                "wgrad_winograd: bad shape");
@@ -237,8 +285,9 @@ extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, f
   SHDR_REQUIRE(shdr::aligned16(x) && shdr::aligned16(dz), SHDR_E_ALIGN, "wgrad_winograd: x and dz must be 16-byte aligned");
   SHDR_REQUIRE((long)N * H * W * Cx < (1L << 32) && (long)N * H * W * Cout < (1L << 32), SHDR_E_SHAPE,
                "wgrad_winograd: tensor with more than 2^32 elements");
-  // du is scratch of this call: zeroed here, in stream order (the caller hands over uninitialised memory)
-  if (hipMemsetAsync(du, 0, sizeof(float) * 16 * (size_t)Cx * Cout, shdr::stream_of(stream)) != hipSuccess)
+  // du is scratch of this call: zeroed here, in stream order (the caller hands over uninitialised memory); the deterministic form
+  // writes every element of du in its fold
+  if (!det && hipMemsetAsync(du, 0, sizeof(float) * 16 * (size_t)Cx * Cout, shdr::stream_of(stream)) != hipSuccess)
     return shdr::fail(SHDR_E_LAUNCH, "wgrad_winograd: memset of the dU scratch failed");
   WinoWgradArgs a{};
   a.x = x; a.dz = dz; a.du = du;
@@ -251,10 +300,26 @@ extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, f
   a.tiles_m = Cx / 32;
   a.tiles_n = Cout / 64;
   hipStream_t st = shdr::stream_of(stream);
+  const long tiles = (long)a.tiles_m * a.tiles_n;
+  if (det) {
+    const long slice = det_unit_slice(tiles, a.units);
+    const long nslices = (a.units + slice - 1) / slice;
+    const size_t slab = (size_t)16 * Cx * Cout;
+    const int64_t need = (int64_t)nslices * (int64_t)slab * (int64_t)sizeof(float);
+    SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "wgrad_winograd_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    SHDR_REQUIRE(nslices <= 65535, SHDR_E_SHAPE, "wgrad_winograd_det: too many unit slices");
+    if (int e = shdr::dynamic_lds<&wgrad_winograd_kernel<2>>(WW<2>::LDS_BYTES)) return e;
+    a.du = ws; a.slab = slab; a.slice = (int)slice;
+    hipLaunchKernelGGL(wgrad_winograd_kernel<2>, dim3((unsigned)tiles, (unsigned)nslices), dim3(256), WW<2>::LDS_BYTES, st, a);
+    if (int rc = shdr::check_launch("wgrad_winograd_kernel")) return rc;
+    shdr::launch_col_fold_det(ws, du, (int)nslices, (int)slab, st, slab, 0);          // du = the slabs in slice order
+    hipLaunchKernelGGL(winograd_dw_kernel<true>, dim3(shdr::stream_grid((long)Cx * Cout)), dim3(256), 0, st, du, dw, Cx, Cout, Ct, ci_off,
+                       x_scale);
+    return shdr::check_launch("winograd_dw_kernel");
+  }
   long slots = 0;
   if (int e = shdr::dynamic_lds_slots<&wgrad_winograd_kernel<2>>(256, WW<2>::LDS_BYTES, "wgrad_winograd", slots)) return e;
   // unit slices: one round of the chip's block slots, >= 32 units (256 tiles) per block to bound the atomics
-  const long tiles = (long)a.tiles_m * a.tiles_n;
   long slice = shdr::slice_for_rounds(slots, tiles, a.units, 32);
   if (SHDR_ENV("SHDR_WGRAD_LEGACY_GRID")) {
     const long want = (768 + tiles - 1) / tiles;
@@ -264,9 +329,11 @@ extern "C" int shdr_conv2d_wgrad_winograd_f32(const float* x, const float* dz, f
   a.slice = (int)slice;
   const long nslices = (a.units + slice - 1) / slice;
   SHDR_REQUIRE(nslices <= 65535, SHDR_E_SHAPE, "wgrad_winograd: too many unit slices");
+  if (nslices > 1) shdr::count_order_dependent();
   hipLaunchKernelGGL(wgrad_winograd_kernel<2>, dim3((unsigned)tiles, (unsigned)nslices), dim3(256), WW<2>::LDS_BYTES, st, a);
   if (int rc = shdr::check_launch("wgrad_winograd_kernel")) return rc;
-  hipLaunchKernelGGL(winograd_dw_kernel, dim3(shdr::stream_grid((long)Cx * Cout)), dim3(256), 0, st, du, dw, Cx, Cout, Ct, ci_off,
+  hipLaunchKernelGGL(winograd_dw_kernel<false>, dim3(shdr::stream_grid((long)Cx * Cout)), dim3(256), 0, st, du, dw, Cx, Cout, Ct, ci_off,
                      x_scale);
   return shdr::check_launch("winograd_dw_kernel");
 }
+}  // namespace

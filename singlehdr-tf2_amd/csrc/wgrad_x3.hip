@@ -38,6 +38,9 @@ struct WgradXArgs {
   int npix, slice, tiles_m, tiles_n;
   int ci_valid, co_valid;
   float x_scale;
+  float* ws;           // deterministic form: pixel slice s STORES its partial dW at ws + s * slab (dw's address arithmetic) ...
+  size_t slab;         // ... floats per slab; 0: fp32 atomics into dw
+  int nslices;
 };
 
 constexpr int PK = 32;
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
   // (the loop of wgrad_f16.hip and wgrad_f16_alltaps.hip, kept apart on purpose: see the all-taps kernel)
   const float sc = a.x_scale * ldexpf(1.0f, -shdr::range_exponent(a.xr)) * ldexpf(1.0f, -shdr::range_exponent(a.zr));
   const int fi = lane & 15, fg = lane >> 4;
-  float* out = a.dw + ((size_t)tap * a.Ct + a.ci_off) * a.Cout;
+  float* out = (a.slab ? a.ws + (size_t)slice_id * a.slab : a.dw) + ((size_t)tap * a.Ct + a.ci_off) * a.Cout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
@@ -209,7 +212,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_kernel(const WgradXArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ci = ci0 + (wm * MT + mi) * 16 + 4 * fg + e;
-        if (ci < a.ci_valid && co < a.co_valid) atomicAdd(out + (size_t)ci * a.Cout + co, (hi[mi][ni][e] + lo[mi][ni][e] * (1.0f / 2048.0f)) * sc);
+        if (ci < a.ci_valid && co < a.co_valid) {
+          const float v = (hi[mi][ni][e] + lo[mi][ni][e] * (1.0f / 2048.0f)) * sc;
+          if (a.slab) out[(size_t)ci * a.Cout + co] = v;         // (uniform) one writer per address of the slab
+          else atomicAdd(out + (size_t)ci * a.Cout + co, v);
+        }
       }
     }
 }
@@ -222,17 +229,55 @@ int launch_wgrad_x3(WgradXArgs& a, hipStream_t st) {
   const long tiles = (long)a.KH * a.KW * a.tiles_m * a.tiles_n;
   long slots = 0;
   if (int e = shdr::dynamic_lds_slots<&wgrad_x3_kernel<CI_T, CO_T>>(256, lds, "wgrad_x3", slots)) return e;
-  // one round of the chip's block slots (wgrad_f16.hip: every block pays a DMA prologue and a tile of atomics)
-  long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
-  slice = (slice + PK - 1) / PK * PK;
-  a.slice = (int)slice;
-  const long nslices = (a.npix + slice - 1) / slice;
+  long nslices;
+  if (a.slab) {
+    nslices = a.nslices;                               // deterministic form: det_slices() has cut the pixels
+  } else {
+    // one round of the chip's block slots (wgrad_f16.hip: every block pays a DMA prologue and a tile of atomics)
+    long slice = shdr::slice_for_rounds(slots, tiles, a.npix, 1024);
+    slice = (slice + PK - 1) / PK * PK;
+    a.slice = (int)slice;
+    nslices = (a.npix + slice - 1) / slice;
+    if (nslices > 1) shdr::count_order_dependent();
+  }
   if (tiles * nslices > 0x7fffffffL) return shdr::fail(SHDR_E_SHAPE, "wgrad_x3: grid too large");
   hipLaunchKernelGGL((wgrad_x3_kernel<CI_T, CO_T>), dim3((unsigned)(tiles * nslices)), dim3(256), lds, st, a);
   return shdr::check_launch("wgrad_x3_kernel");
 }
 
+// the block tile of a layer: ONE choice for the dispatch, the deterministic slices and their workspace query
+void x3_tile(int Cx, int Cz, int& ci_t, int& co_t) {
+  // (96 channels -- the stem of the Linearization-Net: ONE 128-row tile with a quarter of its rows zero, 1.93 ms at 32 x 256^2 against 2.81
+  //  on two 64-row tiles and 3.0 on the exact fp32 kernel, split passes included)
+  ci_t = (Cx % 128 == 0 || Cx % 128 > 64) ? 128 : 64;
+  co_t = Cz % 128 == 0 ? 128 : 64;
+}
+// pixel slices of the deterministic form: a function of the layer alone (512 block slots, >= 1024 pixels per slice, no environment switch)
+void det_slices(const shdr_conv2d_desc* d, int which, long& slice, long& nslices) {
+  const int Cx = which ? d->C2 : d->C1;
+  int ci_t, co_t;
+  x3_tile(Cx, d->Cout, ci_t, co_t);
+  const long tiles = (long)d->KH * d->KW * ((Cx + ci_t - 1) / ci_t) * ((d->Cout + co_t - 1) / co_t);
+  const long npix = (long)d->N * d->Ho * d->Wo;
+  long ns = shdr::kDetSlots / tiles;
+  if (ns < 1) ns = 1;
+  slice = (npix + ns - 1) / ns;
+  if (slice < 1024) slice = 1024;
+  slice = (slice + PK - 1) / PK * PK;
+  nslices = (npix + slice - 1) / slice;
+}
+
+int wgrad_x3_run(const shdr_conv2d_desc* d, const void* xh, const void* xl, int which, const void* zh, const void* zl,
+                 const float* x_range, const float* z_range, float* dw, float* ws, int64_t ws_bytes, bool det, void* stream);
+
 }  // namespace
+
+int64_t shdr::wgrad_x3_det_bytes(const shdr_conv2d_desc* d, int which) {
+  if (!shdr_conv2d_wgrad_x3_ok_f32(d, which)) return -1;
+  long slice, nslices;
+  det_slices(d, which, slice, nslices);
+  return (int64_t)nslices * d->KH * d->KW * (d->C1 + d->C2) * d->Cout * (int64_t)sizeof(float);
+}
 
 // x [n] fp32 -> the two fp16 planes of x 2^T (T from the range slot: conv_x3.hip "Range"); n % 8 == 0, 16-byte aligned pointers
 extern "C" int shdr_x3_split_planes_f32(const float* x, int64_t n, const float* range, void* hi, void* lo, void* stream) {
@@ -258,6 +303,19 @@ extern "C" int shdr_conv2d_wgrad_x3_ok_f32(const shdr_conv2d_desc* d, int which)
 
 extern "C" int shdr_conv2d_wgrad_x3_f32(const shdr_conv2d_desc* d, const void* xh, const void* xl, int which, const void* zh, const void* zl,
                                         const float* x_range, const float* z_range, float* dw, void* stream) {
+  return wgrad_x3_run(d, xh, xl, which, zh, zl, x_range, z_range, dw, nullptr, 0, false, stream);
+}
+extern "C" int shdr_conv2d_wgrad_x3_det_f32(const shdr_conv2d_desc* d, const void* xh, const void* xl, int which, const void* zh,
+                                            const void* zl, const float* x_range, const float* z_range, float* dw, void* ws, int64_t ws_bytes,
+                                            void* stream) {
+  SHDR_REQUIRE(ws, SHDR_E_NULL, "wgrad_x3_det: null workspace");
+  SHDR_REQUIRE(shdr::aligned16(ws), SHDR_E_ALIGN, "wgrad_x3_det: ws must be 16-byte aligned");
+  return wgrad_x3_run(d, xh, xl, which, zh, zl, x_range, z_range, dw, static_cast<float*>(ws), ws_bytes, true, stream);
+}
+
+namespace {
+int wgrad_x3_run(const shdr_conv2d_desc* d, const void* xh, const void* xl, int which, const void* zh, const void* zl,
+                 const float* x_range, const float* z_range, float* dw, float* ws, int64_t ws_bytes, bool det, void* stream) {
   SHDR_REQUIRE(d && xh && xl && zh && zl && x_range && z_range && dw, SHDR_E_NULL, "wgrad_x3: null pointer");
   SHDR_REQUIRE(shdr_conv2d_wgrad_x3_ok_f32(d, which), SHDR_E_SHAPE, "wgrad_x3: layer not taken (64-channel tiles on both sides)");
   SHDR_REQUIRE(shdr::aligned16(xh) && shdr::aligned16(xl) && shdr::aligned16(zh) && shdr::aligned16(zl), SHDR_E_ALIGN, "wgrad_x3: planes must be 16-byte aligned");
@@ -275,10 +333,22 @@ extern "C" int shdr_conv2d_wgrad_x3_f32(const shdr_conv2d_desc* d, const void* x
   a.npix = d->N * d->Ho * d->Wo;
   a.x_scale = which ? d->x2_scale : 1.0f;
   hipStream_t st = shdr::stream_of(stream);
-  if ((a.Cx % 128 == 0 || a.Cx % 128 > 64) && a.Cz % 128 == 0) return launch_wgrad_x3<128, 128>(a, st);
-  // (96 channels -- the stem of the Linearization-Net: ONE 128-row tile with a quarter of its rows zero, 1.93 ms at 32 x 256^2 against 2.81
-  //  on two 64-row tiles and 3.0 on the exact fp32 kernel, split passes included)
-  if (a.Cx % 128 == 0 || a.Cx % 128 > 64) return launch_wgrad_x3<128, 64>(a, st);
-  if (a.Cz % 128 == 0) return launch_wgrad_x3<64, 128>(a, st);
-  return launch_wgrad_x3<64, 64>(a, st);
+  if (det) {
+    long slice, nslices;
+    det_slices(d, which, slice, nslices);
+    a.slab = (size_t)a.KH * a.KW * a.Ct * a.Cout;
+    const int64_t need = (int64_t)nslices * (int64_t)a.slab * (int64_t)sizeof(float);
+    SHDR_REQUIRE(ws_bytes >= need, SHDR_E_SHAPE, "wgrad_x3_det: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    a.ws = ws; a.slice = (int)slice; a.nslices = (int)nslices;
+  }
+  int ci_t, co_t;
+  x3_tile(a.Cx, a.Cz, ci_t, co_t);
+  const int e = ci_t == 128 ? (co_t == 128 ? launch_wgrad_x3<128, 128>(a, st) : launch_wgrad_x3<128, 64>(a, st))
+                            : (co_t == 128 ? launch_wgrad_x3<64, 128>(a, st) : launch_wgrad_x3<64, 64>(a, st));
+  if (e || !det) return e;
+  // dw = dw + (the slabs' sum in slice order) on the rows [ci_off, ci_off + Cx) of every tap: per tap Cx * Cout contiguous floats
+  const size_t off = (size_t)a.ci_off * a.Cout;
+  shdr::launch_col_fold_det(ws + off, dw + off, a.nslices, a.Cx * a.Cout, st, a.slab, 1, a.KH * a.KW, (size_t)a.Ct * a.Cout);
+  return shdr::check_launch("wgrad_x3_det fold");
 }
+}  // namespace

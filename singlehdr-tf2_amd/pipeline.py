@@ -3,6 +3,7 @@
 `inference` follows test_real_refinement.py:86-110 of the reference
 (deq -> clip -> lin -> apply_rf -> alpha -> hal -> blend -> ref).
 """
+import contextlib
 import math
 
 import torch
@@ -210,6 +211,12 @@ class KerasAdam:
             torch.autograd.graph.increment_version(v)
 
 
+def _det_scope(step):
+    """the scope of one call of a training step built with deterministic=True (K.deterministic: bit-reproducible fp32 reductions);
+    a step built without it leaves the ambient setting alone"""
+    return K.deterministic(True) if step.deterministic else contextlib.nullcontext()
+
+
 def _dp_scalars(step, mask):
     """(global batch size, global sum(loss_mask)) of a data-parallel step: the two batch-coupled scalars of the losses (the
     factor B of the broadcast loss, the crf weight, the batch-global TV mean).  One scalar all-reduce; equal shard sizes."""
@@ -243,13 +250,17 @@ class JointTrainStep:
     LEARNING_RATE = 1e-5   # joint_training.py:20
     THRESHOLD = 0.12       # joint_training.py:140
 
-    def __init__(self, deq, lin, hal, vgg, vgg2=None, lr=None, process_group=None, world_size=1, multi_stream=True, bucketed=True):
-        """bucketed (data parallel only): the flat gradient is reduced in FOUR collectives instead of one, each launched as async work
+    def __init__(self, deq, lin, hal, vgg, vgg2=None, lr=None, process_group=None, world_size=1, multi_stream=True, bucketed=True,
+                 deterministic=False):
+        """deterministic: run every call inside K.deterministic(True) -- losses, flat gradient, moving statistics and parameters are
+        bit-identical run to run on one GPU (DESIGN.md "Deterministic mode"; the collective across ranks is not covered).
+        bucketed (data parallel only): the flat gradient is reduced in FOUR collectives instead of one, each launched as async work
         as soon as its slice is complete and overlapped with the backward ops that remain (SURVEY.md section 8e "bucket per net, hal
         first"): hal's decoder half (from a tape mark at the bottleneck), hal's encoder half, lin, deq.  Same SUM per element as the
         one blocking all_reduce (bucketed=False); no rank-local code path issues a collective."""
         self._deq, self._lin, self._hal, self._vgg, self._vgg2 = deq, lin, hal, vgg, vgg2 or vgg
         self.bucketed = bucketed
+        self.deterministic = bool(deterministic)
         self.params = FlatParams([deq, lin, hal])
         self.optimizer = KerasAdam(self.params, self.LEARNING_RATE if lr is None else lr)
         self.pg, self.world = process_group, world_size
@@ -372,6 +383,10 @@ class JointTrainStep:
             w.wait()
 
     def __call__(self, ds, invcrf, apply=True):
+        with _det_scope(self):
+            return self._step(ds, invcrf, apply)
+
+    def _step(self, ds, invcrf, apply):
         self.params.zero_grad()
         dp = self.pg is not None and self.world > 1
         if dp and self.bucketed:
@@ -408,7 +423,9 @@ class TrainStep:
     LEARNING_RATE = 1e-4   # train.py:19
     THRESHOLD = 0.12       # train.py:209
 
-    def __init__(self, which, net, vgg=None, vgg2=None, lr=None, process_group=None, world_size=1):
+    def __init__(self, which, net, vgg=None, vgg2=None, lr=None, process_group=None, world_size=1, deterministic=False):
+        """deterministic: see JointTrainStep"""
+        self.deterministic = bool(deterministic)
         if which not in ("deq", "lin", "hal"):
             raise ValueError("TrainStep: which must be 'deq', 'lin' or 'hal'")
         if which == "hal" and vgg is None:
@@ -461,6 +478,10 @@ class TrainStep:
         return hal_loss, [pred_rgb, y_final, alpha]
 
     def __call__(self, ds, apply=True):
+        with _det_scope(self):
+            return self._step(ds, apply)
+
+    def _step(self, ds, apply):
         self.params.zero_grad()
         self._objective = None
         with K.range_scope():
@@ -486,12 +507,17 @@ class FinetuneStep:
     THRESHOLD = 0.12       # finetune_real_dataset.py:26
 
     def __init__(self, deq, lin, hal, ref, lr=None, process_group=None, world_size=1, precision="fp32",
-                 loss_scale=1.0):
-        """precision: "fp32" (parity path); "fp16" = BASELINE configs[4], the NATIVE fp16 conv path: fp16 feature maps in HBM
+                 loss_scale=1.0, deterministic=False):
+        """deterministic: see JointTrainStep; precision "fp32" only.
+        precision: "fp32" (parity path); "fp16" = BASELINE configs[4], the NATIVE fp16 conv path: fp16 feature maps in HBM
         for every conv forward / dgrad / wgrad, BatchNorm, pooling and resize pass, fp32 master weights, fp32 parameter gradients
         and fp32 accumulation (_ops.PRECISION); "fp16op" / "bf16" = the round-1 operand-rounding modes (fp32 tensors in HBM).  loss_scale: static scale applied to the seed gradient
         and divided out of the flat gradient before the collective.  The loss here is a SUM over pixels, so output
         gradients are O(1)..O(1e3) and need no up-scaling; 256 overflows fp16 at 512x512 tiles (measured)."""
+        if deterministic and precision != "fp32":
+            raise ValueError("FinetuneStep: deterministic=True needs precision='fp32'; the native-fp16 path (and the operand-rounding "
+                             "modes) are not covered by the deterministic mode yet, got precision=%r" % (precision,))
+        self.deterministic = bool(deterministic)
         self._deq, self._lin, self._hal, self._ref = deq, lin, hal, ref
         self.params = FlatParams([deq, lin, hal, ref])
         self.optimizer = KerasAdam(self.params, self.LEARNING_RATE if lr is None else lr)
@@ -520,6 +546,10 @@ class FinetuneStep:
         return dict(loss_sum=loss_sum, C_pred=C_pred, B_pred=B_pred, A_pred=A_pred, refinement_output=refinement_output)
 
     def __call__(self, ldr, hdr, apply=True):
+        with _det_scope(self):
+            return self._step(ldr, hdr, apply)
+
+    def _step(self, ldr, hdr, apply):
         self.params.zero_grad()
         with K.precision(self.precision), K.range_scope():
             out = self.forward(ldr, hdr)
